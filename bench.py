@@ -8,7 +8,8 @@ max over ranks; rank 0 prints ONE JSON line.
 Workload (BASELINE.json configs[2], the one `metric` is quoted on): X3D-M, clips of 16x224x224, batch
 64 per GPU, bf16 activation storage (fp32 accumulation; matrix-core operands -- the pointwise convs and the depthwise
 planes dw_mx.hip covers -- rounded to bf16), synthetic N(0,1) clips (NTHWC at the module
-boundary, already resident in HBM), random-init weights; weak scaling (per-GPU batch fixed).
+boundary, already resident in HBM), random-init weights; weak scaling (per-GPU batch fixed).  Every step starts from the
+same seeded weights, BN moving statistics and momentum (restored by two device copies inside the step).
 
 Extra objects on the JSON line:
   roofline      dominant depthwise kernel instantiation: algorithmic bytes per launch (SURVEY 8d:
@@ -23,6 +24,14 @@ Extra objects on the JSON line:
                 time in three extra steps after the timed region, against the dense 16-bit matrix-core peak.
   cpu_baseline  the CPU oracle (a PyTorch-CPU restatement of the reference graph; TensorFlow is not
                 available) timed on the host cores over a bounded sample of the same workload.
+
+--dump-outputs DIR: rank 0 writes what the LAST timed step computed as DIR/<name>.npy (float32), copied off the device
+after the timed region and before any untimed step runs: probs, loss_rows, loss, and the model state the step left behind
+(params with the moving statistics, grads, velocity).  Clips, labels, initial weights and the dropout draws are seeded, so
+two builds run with the same arguments get the same inputs.  Past DUMP_BYTES every array keeps the same fixed, seeded
+sample share.
+The device reduces gradients with floating-point atomics, so two runs agree up to that rounding (gradients ~1e-7 rel-L2),
+not bit for bit.
 """
 import argparse
 import json
@@ -45,6 +54,30 @@ from x3d_tf_amd import dist as xdist  # noqa: E402
 CLIP = {"XS": (4, 160), "S": (13, 160), "M": (16, 224), "L": (16, 312), "XL": (16, 312)}
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6290 measured copy ceiling
 MFMA_PEAK_TFLOPS = 2500.0   # dense bf16 / fp16 matrix-core peak (MI355X_MICROARCH.md; the sparse headline figure is 2x this)
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs data budget: the files with their .npy headers stay under 64 MB
+
+
+def step_outputs(model, pl, loss):
+    """What a caller of the timed step receives, as float32 host tensors: the plan's outputs and the updated model state."""
+    out = {"probs": pl.probs, "loss_rows": pl.loss_rows, "loss": loss.reshape(1),
+           "params": model.flat_params, "grads": model.flat_grads, "velocity": model.flat_velocity}
+    return {k: v.detach().float().cpu().clone() for k, v in out.items()}
+
+
+def dump_outputs(arrays, outdir):
+    """Writes every array as outdir/<name>.npy.  Over DUMP_BYTES each array keeps the same share of its elements, at indices
+    drawn from a fixed seed, so the sample depends on the array sizes only."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(v.numel() for v in arrays.values())
+    keep = DUMP_BYTES // 4
+    for name, v in arrays.items():
+        if total > keep:
+            v = v.reshape(-1)
+            k = max(1, v.numel() * keep // total)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            v = v[idx]
+        np.save(os.path.join(outdir, name + ".npy"), v.numpy())
 
 
 def dw_key(pl, lst, i):
@@ -131,7 +164,7 @@ class KernelTimer:
 PW_ENTRIES = ("x3d_pw_fwd", "x3d_pw_dgrad", "x3d_pw_wgrad", "x3d_pw_bwd")
 
 
-def mfma_utilisation(model, pl, trainer, clips, labels, lr, steps=3):
+def mfma_utilisation(model, pl, train_step, steps=3):
     """north_star's second figure: MFMA utilisation of the pointwise convs.  Every pointwise launch of `steps` extra steps
     (AFTER the timed region) is bracketed by HIP events on the launch stream; FLOPs = 2 * Cin * Cout * output points per
     GEMM (the fused backward x3d_pw_bwd is two GEMMs), over the dense 16-bit matrix-core peak."""
@@ -171,7 +204,7 @@ def mfma_utilisation(model, pl, trainer, clips, labels, lr, steps=3):
     pl.run = run
     try:
         for _ in range(steps):
-            trainer.step(clips, labels, lr)
+            train_step()
         torch.cuda.synchronize()
     finally:
         pl.run = prev_run
@@ -228,7 +261,10 @@ def main():
                     help="activation storage: bf16 (the headline), fp16 (the reference's mixed_float16 mode; dynamic loss scale), fp32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # Invoked directly with --gpus N: start the N ranks as CHILD processes (torchrun, one rank per GPU) and exit with
@@ -256,6 +292,7 @@ def main():
         raise SystemExit("bench.py needs one MI355X GPU per rank and none is visible (no CPU fallback for the hot path)")
     device = torch.device(f"cuda:{xdist.local_device(local_rank)}")
     torch.cuda.set_device(device)
+    torch.manual_seed(2000 + rank)    # the per-step dropout draw: the same arguments give the same inputs run to run
 
     from x3d_tf_amd.model import X3D
     from x3d_tf_amd.train import Trainer
@@ -270,20 +307,31 @@ def main():
     clips = torch.randn((B, t, s, s, 3), generator=g, device=device, dtype=torch.float32).to(dtype)
     labels = torch.randint(0, model.num_classes, (B,), generator=g, device=device)
     lr = cfg.TRAIN.WARMUP_LR
+    # Every step trains from the same seeded state.  The fp32 atomic reductions make one step's gradients differ run to run
+    # in the last bits (~1e-7), and the forward of the random-init network is chaotic in its weights (every weight one ulp
+    # off moves probs by ~1e-2), so along a training trajectory the outputs of later steps stop matching between runs.
+    # Restoring weights, BN moving statistics and momentum (two device copies, ~0.1 % of a step) gives every step the same
+    # inputs, so what a step computes is the same in every run up to that rounding.
+    state0 = (model.flat_params.clone(), model.flat_velocity.clone())
+
+    def train_step():
+        model.flat_params.copy_(state0[0])
+        model.flat_velocity.copy_(state0[1])
+        return trainer.step(clips, labels, lr)
 
     def barrier():
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
 
     for _ in range(max(args.warmup, 1)):
-        pl = trainer.step(clips, labels, lr)
+        pl = train_step()
     torch.cuda.synchronize()
     trainer.reducer.exposed_ms()      # (drop the warm-up steps' measurements)
     timer = KernelTimer(model, pl, 4 if dtype == torch.float32 else 2)
     timer.wrap(pl)
     timer.enabled = True
     for _ in range(2):                # untimed probe: which depthwise instantiation has the largest total
-        pl = trainer.step(clips, labels, lr)
+        pl = train_step()
     torch.cuda.synchronize()
     probe = timer.summary()
     timer.reset()
@@ -294,33 +342,35 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        pl = trainer.step(clips, labels, lr)
+        pl = train_step()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     per_rank = xdist.gather_over_ranks(elapsed, device)      # every rank's own clock around the same K steps
     elapsed = max(per_rank)
-    loss = float(trainer.loss(pl).item())
+    loss_t = trainer.loss(pl)         # (an all-reduce over ranks: every rank computes it)
+    outputs = step_outputs(model, pl, loss_t) if args.dump_outputs and rank == 0 else None
+    loss = float(loss_t.item())
     coll = trainer.collective_stats()     # (exposed_ms over the timed steps only)
     dominant = timer.summary()        # the dominant instantiation, HIP events inside the timed region
     timer.reset()
     timer.only = None
     for _ in range(2):                # every depthwise instantiation, after the timed region
-        trainer.step(clips, labels, lr)
+        train_step()
     torch.cuda.synchronize()
     timer.enabled = False
-    mfma = mfma_utilisation(model, pl, trainer, clips, labels, lr) if (world == 1 and rank == 0) else None
+    mfma = mfma_utilisation(model, pl, train_step) if (world == 1 and rank == 0) else None
     if world == 1 and trainer.collectives:
         # one-rank rehearsal (X3D_DIST_REHEARSE=1): the same K steps again WITHOUT hooks and collectives -- what the data-parallel
         # machinery costs a step before a byte crosses xGMI (profiles/r06_collective_overhead.txt: it is the first cross-queue
         # dependency of the step in the HIP runtime, ~0.2 ms, not RCCL work)
         trainer.collectives = trainer.reducer.active = trainer.sync_moving_stats = False
         for _ in range(2):
-            trainer.step(clips, labels, lr)
+            train_step()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            trainer.step(clips, labels, lr)
+            train_step()
         torch.cuda.synchronize()
         coll["overhead_ms_vs_no_collectives"] = 1e3 * (elapsed - (time.perf_counter() - t1)) / args.steps
 
@@ -370,6 +420,8 @@ def main():
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.variant, args.cpu_seconds)
+        if outputs is not None:
+            dump_outputs(outputs, args.dump_outputs)
         print(json.dumps(out))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

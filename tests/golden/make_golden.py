@@ -1,5 +1,5 @@
-"""Regenerates the fixtures under tests/golden/.  Run in the BUILD container only (it reads the reference
-checkout at /root/reference, which does not exist on the GPU box); the outputs are committed.
+"""Regenerates the fixtures under tests/golden/ from a checkout of the reference project; the outputs are committed,
+so the tests never read the reference.   python tests/golden/make_golden.py <reference checkout>
 
   summaries.json             rows + totals of reference models/X3D-*/X3D_*.txt (Keras `summary()` dumps)
   model_index_manifest.json  key / dtype / shape / offset / size of every entry of reference
@@ -18,7 +18,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
+REF = None   # the reference checkout, from the command line
 
 
 def summaries():
@@ -84,6 +84,7 @@ def oracle_vectors():
 
 
 if __name__ == "__main__":
+    REF = sys.argv[1]
     json.dump(summaries(), open(f"{HERE}/summaries.json", "w"), indent=1)
     json.dump(manifest(), open(f"{HERE}/model_index_manifest.json", "w"))
     fwd, train = oracle_vectors()
