@@ -7,6 +7,11 @@ sums, fp32 atomics), one of them -- the recomputed-output `a` backward, pw_bwd_r
 part of the first).  "Finite and linear in the upstream gradient" (test_full_size_plan_properties) passes for any amount of
 cancellation error, so here the same launches are compared with the fp64 definition at the real reduction length.
 
+The stem (conv_s -> conv_t, one launch each way for 16-bit clips: stem_fused.hip) reduces its weight gradients over the
+same 12.8 M points, from inputs with the non-zero channel means of a normalised clip, so that sum dY = 0 cancels their mean
+part as in a real step; its BatchNorm sums go through replicated fp64 atomics.  Those cases run here as well, with the
+two-kernel plans (stem.hip) that the fp32 model and X3D-XL training use.
+
 The fp64 side is torch on the GPU (einsum / shifted slices), TEST SIDE ONLY, chunked over samples; it restates the same
 definitions the small cases check against the CPU oracle (test_pw_bwd_rc, test_pw_wgrad, test_dw3d_bwd), with the
 BatchNorm-backward coefficients DERIVED from the data (sum dY = 0 and sum dY * yhat = 0 per channel, as in a real step) instead
@@ -15,7 +20,7 @@ of drawn at random -- that is what makes the moment sums cancel.
 import pytest
 import torch
 
-from tests.util import round_to, tol_gemm, tol_store
+from tests.util import round_to, tie_slack_t, tol_gemm, tol_store
 
 pytestmark = pytest.mark.gpu
 HALF = [torch.bfloat16, torch.float16]
@@ -29,11 +34,16 @@ def _bn_bwd_coef(g, y, gamma):
     """[C][4] fp32 coefficients (A, B, C, 0) of dY = A g + B y + C for training-mode BatchNorm over (N, T, H, W), from the
     tensors themselves: fp64 statistics, as x3d_bn_finalize / x3d_bn_bwd_finalize produce them."""
     m = y.shape[0] * y.shape[2] * y.shape[3] * y.shape[4]
-    mean = y.mean((0, 2, 3, 4))
-    var = (y * y).mean((0, 2, 3, 4)) - mean * mean
+    return _bn_bwd_coef_sums(m, y.sum((0, 2, 3, 4)), (y * y).sum((0, 2, 3, 4)), g.sum((0, 2, 3, 4)), (g * y).sum((0, 2, 3, 4)), gamma)
+
+
+def _bn_bwd_coef_sums(m, sy, syy, sg, sgy, gamma):
+    """_bn_bwd_coef from the fp64 per-channel sums of y, y^2, g, g y over m points (tensors too large for one expression)."""
+    mean = sy / m
+    var = syy / m - mean * mean
     invstd = 1.0 / torch.sqrt(var + 1e-5)
-    dbe = g.sum((0, 2, 3, 4))
-    dga = ((g * y).sum((0, 2, 3, 4)) - mean * dbe) * invstd
+    dbe = sg
+    dga = (sgy - mean * dbe) * invstd
     k1 = gamma * invstd
     b = -k1 * invstd * dga / m
     c = -k1 * dbe / m - b * mean
@@ -293,3 +303,306 @@ def test_depthwise_112_stride2_backward_full_size(gpu, dtype):
     sref = torch.stack([s1, s2], 1)
     _check("a_sums", a_sums, sref, 10 * st, 10 * st * max(1.0, sref.abs().max().item()))
     print(f"full-size 112^2 -> 56^2 depthwise backward {dtype} ({name}): ga err {worst:.2e} of max, dW err {e:.2e} of max (limit 2e-05)")
+
+
+# ---- the stem: conv_s (1 x 3 x 3, stride 2, 3 -> C1 channels) then conv_t (KT x 1 x 1 depthwise), reference model.py:202-206 ----
+# Shapes and channel counts come from the named variant's config; the clip counts are BASELINE's (configs 2 - 5).
+STEM_MU = (0.5, 0.4, 0.3)        # per-channel means of the normalised clip: every RGB channel of a real one has one
+
+
+def _stol(dtype):
+    return 1e-5 if dtype == torch.float32 else (3e-3 if dtype == torch.bfloat16 else 5e-4)     # as tests/test_kernels_gpu.py::_stol
+
+
+def _stem_inputs(gpu, variant, n, dtype, seed):
+    """(x [n, T, S, S, 3] channels-last in `dtype`, w_s [C1, 3, 3, 3], w_t [C1, KT], generator): x = randn * 0.5 + mu_c."""
+    import x3d_tf_amd as x3d
+    cfg = x3d.get_config(variant)
+    arch = x3d.build_arch(cfg)
+    c1, kt, t, s = arch.c1, arch.c1_temp_filter, cfg.DATA.TEMP_DURATION, cfg.DATA.TRAIN_CROP_SIZE
+    g_ = torch.Generator(device=gpu)
+    g_.manual_seed(seed)
+    rn = lambda *sh: torch.randn(*sh, generator=g_, device=gpu, dtype=torch.float32)
+    x = (rn(n, t, s, s, 3) * 0.5 + torch.tensor(STEM_MU, device=gpu)).to(dtype)
+    return x, rn(c1, 3, 3, 3) * 0.3, rn(c1, kt) * 0.4, rn
+
+
+def _im2col_taps(xc):
+    """The nine (kh, kw) taps of conv_s over a channels-last fp64 chunk [n, T, H, W, 3]: tap[..., ho, wo, ci] =
+    x[..., 2 ho + kh - 1, 2 wo + kw - 1, ci], zero outside the image."""
+    n, t, h, w, _ = xc.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    xp = torch.nn.functional.pad(xc, (0, 0, 1, 2 * wo - w, 1, 2 * ho - h))
+    return [((kh, kw), xp[:, :, kh:kh + 2 * ho:2, kw:kw + 2 * wo:2, :]) for kh in range(3) for kw in range(3)]
+
+
+def _conv_s64(taps, ws):
+    return sum(torch.einsum("oc,nthwc->nothw", ws[:, :, kh, kw], tap) for (kh, kw), tap in taps)
+
+
+def _conv_t64(s, wt):
+    """out[t] = sum_k w[c, k] s[t + k - KT // 2], zero outside [0, T)."""
+    kt, t = wt.shape[1], s.shape[2]
+    sp = torch.nn.functional.pad(s, (0, 0, 0, 0, kt // 2, kt // 2))
+    out = torch.zeros_like(s)
+    for k in range(kt):
+        out += wt[:, k].view(1, -1, 1, 1, 1) * sp[:, :, k:k + t]
+    return out
+
+
+def _check_slack(name, got, ref, rtol, atol, slack):
+    """_check with a per-element tie slack on top of atol + rtol |ref|: returns (worst err / its limit, elements that needed
+    the slack)."""
+    got, ref = got.double(), ref.double()
+    err = (got - ref).abs()
+    base = atol + rtol * ref.abs()
+    lim = base + slack
+    bad = err > lim
+    assert torch.isfinite(got).all(), f"{name}: non-finite values"
+    assert not bad.any(), (f"{name}: {int(bad.sum())}/{bad.numel()} out of tolerance (rtol {rtol}, atol {atol:.3e} + tie slack); "
+                           f"max err {err.max().item():.3e}, max |ref| {ref.abs().max().item():.3e}")
+    return (err / lim).max().item(), int((err > base).sum())
+
+
+STEM_FWD = [("M", 64, torch.bfloat16), ("M", 64, torch.float16),    # config 3: Wo = 112 = 64 + 48 columns
+            ("L", 16, torch.bfloat16),                               # config 4: Wo = 156, the third segment 28 of 64 columns
+            ("XL", 30, torch.float16)]                               # config 5 (30 views of one video): 32 channels, inference
+
+
+@pytest.mark.parametrize("variant,n,dtype", STEM_FWD, ids=[f"{v}-{str(d)[6:]}" for v, _, d in STEM_FWD])
+def test_stem_fused_forward_full_size(gpu, variant, n, dtype):
+    """x3d_stem_fwd at full size against fp64: t_raw = conv_t(s) with s = conv_s over the weights rounded to storage, then
+    rounded to storage as the kernel does on chip (tol_store plus the conv_t tie slack, tests.util.tie_slack_t; fewer than
+    1e-4 of the elements may need that slack); the BatchNorm sums (replicated fp64 atomics) against an fp64 reduction of
+    the stored t_raw; for X3D-XL the inference epilogue act(s * conv + b) as well, act in {none, ReLU}.  (Measured: worst
+    err / limit 0.61 - 0.99, the store's half ulp against tol_store's rtol; 3e-8 - 7e-7 of the outputs needed the slack;
+    the sums 1.1e-8 - 1.6e-8 of their maximum.)"""
+    from x3d_tf_amd import ops
+    x, ws, wt, rn = _stem_inputs(gpu, variant, n, dtype, 61)
+    c1 = ws.shape[0]
+    infer = c1 > 24
+    assert ops.stem_fused_supported(x, c1) == (1 if infer else 3)       # (forward only with 32 channels)
+    st = torch.zeros((c1, 2), dtype=torch.float64, device=gpu)
+    y = ops.stem_fwd(x, ws, wt, stats=st)
+    outs = [("t_raw", y, None)]
+    if infer:
+        oss = torch.stack([1 + 0.3 * rn(c1), 0.3 * rn(c1)], 1)
+        outs += [(f"inference epilogue act {act}", ops.stem_fwd(x, ws, wt, out_ss=oss, out_act=act), act) for act in (0, 1)]
+    torch.cuda.synchronize()
+    wsr, wt64, wabs = round_to(ws, dtype), wt.double(), wt.abs()
+    rt, at = tol_store(dtype)
+    worst = {name: 0.0 for name, _, _ in outs}
+    needed = 0
+    s1 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    s2 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    CH = 8
+    for i in range(0, n, CH):
+        s64 = _conv_s64(_im2col_taps(x[i:i + CH].double()), wsr)
+        slack = tie_slack_t(s64, dtype, wabs)
+        tref = _conv_t64(round_to(s64, dtype), wt64)
+        del s64
+        for name, got, act in outs:
+            ref, sl = tref, slack
+            if act is not None:
+                ref = oss[:, 0].double().view(1, -1, 1, 1, 1) * tref + oss[:, 1].double().view(1, -1, 1, 1, 1)
+                ref = torch.relu(ref) if act == 1 else ref
+                sl = slack * oss[:, 0].double().abs().view(1, -1, 1, 1, 1)
+            e, nd = _check_slack(f"{name}[{i}:{i + CH}]", got[i:i + CH], ref, rt, at * ref.abs().max().item(), sl)
+            worst[name] = max(worst[name], e)
+            needed += nd
+            del ref, sl
+        yd = y[i:i + CH].double()
+        s1 += yd.sum((0, 2, 3, 4))
+        s2 += (yd * yd).sum((0, 2, 3, 4))
+        del slack, tref, yd
+    frac = needed / (y.numel() * len(outs))
+    assert frac < 1e-4, f"{frac:.2e} of the outputs needed the tie slack: a systematic error, not ties"
+    sref = torch.stack([s1, s2], 1)
+    stol = _stol(dtype)
+    e_st = _check("stats", st, sref, stol, stol * max(1.0, sref.abs().max().item()))
+    print(f"full-size stem forward X3D-{variant} {dtype} {tuple(y.shape)}: worst err / limit "
+          + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()) + f"; {frac:.1e} needed the tie slack; stats err {e_st:.2e} of max "
+          f"(limit {stol:.0e})")
+
+
+def _stem_backward_case(gpu, variant, n, dtype, seed, fused):
+    """Shared body of the full-size stem backward tests.  A training step's inputs: the stored t_raw of the forward pass, a
+    random upstream gradient g (unmasked: the ReLU behind conv1/bn is applied inside the kernels), relu_ss from the actual
+    BatchNorm of t_raw (random gamma / beta), and coef derived from the masked g and t_raw (sum dY = 0 per channel, so both
+    weight gradients lose the mean part of s and x to cancellation).  Runs x3d_stem_bwd when `fused`, and always the
+    two-kernel plan (x3d_dwt_bwd, then x3d_stem_s_wgrad on the conv_t input gradient ds); returns the launches' results with
+    the fp64 definitions: dW_t[c, k] = sum dY[t + 2 - k] s[t], ds = conv_t^T dY, dW_s = sum round_to(ds) im2col(x); for fp32
+    also sum |terms| of both (what an fp32 summation bound scales with)."""
+    from x3d_tf_amd import ops
+    x, ws, wt, rn = _stem_inputs(gpu, variant, n, dtype, seed)
+    c1 = ws.shape[0]
+    cl = dtype != torch.float32             # fp32 storage: the planar batch and the scalar kernels (config 2's plan)
+    xk = x if cl else x.permute(0, 4, 1, 2, 3).contiguous()
+    if cl:
+        assert ops.stem_fused_supported(x, c1) == (3 if fused else 1)
+        assert x.shape[3] % 8 == 0       # x3d_stem_s_wgrad takes stem_s_wgrad_bf16_kernel (16-bit, W % 8 == 0)
+    s = ops.stem_s_fwd(xk, ws, channels_last=cl)
+    t_raw = ops.dwt_fwd(s, wt)
+    torch.cuda.synchronize()
+    CH = 8
+    m = t_raw.numel() // c1
+    s1 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    s2 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    for i in range(0, n, CH):
+        yd = t_raw[i:i + CH].double()
+        s1 += yd.sum((0, 2, 3, 4))
+        s2 += (yd * yd).sum((0, 2, 3, 4))
+        del yd
+    gamma = (1 + 0.3 * rn(c1)).double()
+    beta = (0.3 * rn(c1)).double()
+    mean = s1 / m
+    k1 = gamma / torch.sqrt(s2 / m - mean * mean + 1e-5)
+    rss = torch.stack([k1, beta - mean * k1], 1).float()
+    g = rn(*t_raw.shape).to(dtype)
+    v = lambda a: a.double().view(1, -1, 1, 1, 1)
+    mask = lambda i: (v(rss[:, 0]) * t_raw[i:i + CH].double() + v(rss[:, 1])) > 0       # (exact sign, as the kernels' fma)
+    sg = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    sgy = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    for i in range(0, n, CH):
+        gm = g[i:i + CH].double() * mask(i)
+        sg += gm.sum((0, 2, 3, 4))
+        sgy += (gm * t_raw[i:i + CH].double()).sum((0, 2, 3, 4))
+        del gm
+    coef = _bn_bwd_coef_sums(m, s1, s2, sg, sgy, gamma)
+    res = {}
+    if fused:
+        dwt = torch.full((c1, wt.shape[1]), 0.5, dtype=torch.float32, device=gpu)      # += on what is there
+        dws = torch.full((c1, 3, 3, 3), -0.25, dtype=torch.float32, device=gpu)
+        ops.stem_bwd(g, t_raw, coef, x, ws, wt, dws, dwt, relu_ss=rss)
+        res["fused"] = (dwt, 0.5, dws, -0.25)
+    ds = torch.empty_like(s)
+    dwt2 = torch.full((c1, wt.shape[1]), 0.5, dtype=torch.float32, device=gpu)
+    dws2 = torch.full((c1, 3, 3, 3), -0.25, dtype=torch.float32, device=gpu)
+    ops.dwt_bwd(g, t_raw, coef, s, wt, ds, dwt2, relu_ss=rss)
+    ops.stem_s_wgrad(xk, ds, dws2, channels_last=cl)
+    res["two-kernel"] = (dwt2, 0.5, dws2, -0.25)
+    torch.cuda.synchronize()
+    # ---- fp64 definitions, chunked
+    wsr, wt64, cf = round_to(ws, dtype), wt.double(), coef.double()
+    kt, t = wt.shape[1], t_raw.shape[2]
+    dwt_ref = torch.zeros((c1, kt), dtype=torch.float64, device=gpu)
+    dws_ref = torch.zeros((c1, 3, 3, 3), dtype=torch.float64, device=gpu)
+    abs_t = torch.zeros_like(dwt_ref)
+    abs_s = torch.zeros_like(dws_ref)
+    rt, at = tol_store(dtype)
+    e_ds = 0.0
+    for i in range(0, n, CH):
+        taps = _im2col_taps(x[i:i + CH].double())
+        sp = torch.nn.functional.pad(round_to(_conv_s64(taps, wsr), dtype), (0, 0, 0, 0, kt // 2, kt // 2))
+        yd = t_raw[i:i + CH].double()
+        gm = g[i:i + CH].double() * mask(i)
+        dy = v(cf[:, 0]) * gm + v(cf[:, 1]) * yd + v(cf[:, 2])
+        dyp = torch.nn.functional.pad(dy, (0, 0, 0, 0, kt // 2, kt // 2))
+        dsr = torch.zeros_like(dy)
+        for k in range(kt):
+            dwt_ref[:, k] += (dy * sp[:, :, k:k + t]).sum((0, 2, 3, 4))
+            dsr += v(wt64[:, k]) * dyp[:, :, kt - 1 - k:kt - 1 - k + t]          # ds[t] = sum_k w[k] dY[t + 2 - k]
+        e_ds = max(e_ds, _check(f"ds[{i}:{i + CH}]", ds[i:i + CH], dsr, rt, at * dsr.abs().max().item()))
+        dsr = round_to(dsr, dtype)
+        for (kh, kw), tap in taps:
+            dws_ref[:, :, kh, kw] += torch.einsum("nothw,nthwc->oc", dsr, tap)
+        if dtype == torch.float32:       # |terms|, with |dY| bounded by |A g| + |B y| + |C| (its own fp32 rounding scales with those)
+            mag = v(cf[:, 0].abs()) * gm.abs() + v(cf[:, 1].abs()) * yd.abs() + v(cf[:, 2].abs())
+            magp = torch.nn.functional.pad(mag, (0, 0, 0, 0, kt // 2, kt // 2))
+            mds = torch.zeros_like(mag)
+            for k in range(kt):
+                abs_t[:, k] += (mag * sp[:, :, k:k + t].abs()).sum((0, 2, 3, 4))
+                mds += v(wt64[:, k].abs()) * magp[:, :, kt - 1 - k:kt - 1 - k + t]
+            for (kh, kw), tap in taps:
+                abs_s[:, :, kh, kw] += torch.einsum("nothw,nthwc->oc", mds, tap.abs())
+            del mag, magp, mds
+        del taps, sp, yd, gm, dy, dyp, dsr
+    return res, dwt_ref, dws_ref, abs_t, abs_s, e_ds, tuple(x.shape)
+
+
+@pytest.mark.parametrize("dtype", HALF)
+def test_stem_backward_full_size(gpu, dtype):
+    """Config 3's stem backward at full size (X3D-M, 64 x 16 x 224^2: 14 336 row segments, 12.8 M points per channel):
+    x3d_stem_bwd, and the two-kernel plan of X3D_NO_STEM_FUSED (x3d_dwt_bwd + the 16-bit stem_s_wgrad_bf16_kernel),
+    against the fp64 definitions (_stem_backward_case) at _wtol (1e-3 / 4e-4 of the maximum), accumulators pre-filled;
+    the two-kernel plan's ds against fp64 at tol_store.  (Measured: 1.3e-2 - 1.5e-2 of the limit for bf16, 4.0e-2 - 5.4e-2
+    for fp16, both plans.)"""
+    res, dwt_ref, dws_ref, _, _, e_ds, shape = _stem_backward_case(gpu, "M", 64, dtype, 67, fused=True)
+    tol = _wtol(dtype)
+    msg = []
+    for name, (dwt, ft, dws, fs) in res.items():
+        e_t = _check(f"{name} dW_t", dwt.double() - ft, dwt_ref, tol, tol * dwt_ref.abs().max().item())
+        e_s = _check(f"{name} dW_s", dws.double() - fs, dws_ref, tol, tol * dws_ref.abs().max().item())
+        msg.append(f"{name}: dW_t {e_t / tol:.2e}, dW_s {e_s / tol:.2e}")
+    print(f"full-size stem backward X3D-M {dtype} {shape}: worst err / limit " + "; ".join(msg) + f"; ds err {e_ds:.2e} of max")
+
+
+def test_stem_two_kernel_backward_xl_full_rows(gpu):
+    """The stem backward X3D-XL training runs (x3d_stem_fused_supported refuses its 32 channels for the backward pass):
+    x3d_dwt_bwd + stem_s_wgrad_bf16_kernel on full 312^2 rows of 16 frames, fp16, a reduced batch of 4 clips; fp64
+    definitions at _wtol.  (Measured: dW_t 3.8e-2, dW_s 2.7e-2 of the limit.)"""
+    res, dwt_ref, dws_ref, _, _, e_ds, shape = _stem_backward_case(gpu, "XL", 4, torch.float16, 71, fused=False)
+    tol = _wtol(torch.float16)
+    dwt, ft, dws, fs = res["two-kernel"]
+    e_t = _check("dW_t", dwt.double() - ft, dwt_ref, tol, tol * dwt_ref.abs().max().item())
+    e_s = _check("dW_s", dws.double() - fs, dws_ref, tol, tol * dws_ref.abs().max().item())
+    print(f"full-row stem backward X3D-XL fp16 {shape}: worst err / limit dW_t {e_t / tol:.2e}, dW_s {e_s / tol:.2e}; ds err {e_ds:.2e} of max")
+
+
+def test_stem_fp32_full_size(gpu):
+    """Config 2's stem at full size (X3D-S, 32 x 13 x 160^2, fp32 storage, planar batch: two kernels each way, the only
+    full-size case of stem_s_wgrad_rows_kernel).  Forward: s_raw and t_raw against fp64 at tol_store(float32), the
+    BatchNorm sums at _stol.  Backward (_stem_backward_case): ds at tol_store(float32); the two weight gradients against an
+    fp32 summation bound.  A sum of L fp32 roundings over terms a_i is off by at most lambda sqrt(L) u sum |a_i| with
+    probability >= 1 - 2 exp(-lambda^2 / 2) when the rounding errors are independent (Higham & Mary, SIAM J. Sci. Comput.
+    41 (2019), the probabilistic form of gamma_L); u = 2^-24, lambda = 6 (1.5e-8 per element).  L is the longest chain a
+    term passes through in the launch:
+      dW_t (x3d_dwt_bwd, <= 2 points per thread): 2 T products per thread, <= 8 levels of the workgroup sum, one atomic per
+           workgroup of the channel (N ceil(HW / 256)), and the 3 roundings of dY = A g + B y + C;
+      dW_s (stem_s_wgrad_rows_kernel): 16 points per wave and segment over the workgroup's spb segments, 3 adds across the
+           four waves, one atomic per workgroup (gx), and the 8 roundings of ds (dY, then 5 taps);
+    spb / gx as the launcher sets them (ceil(segments / (3 CUs)), at least 8).  |a_i| uses |A g| + |B y| + |C| for |dY|.
+    (Measured on 256 CUs: dW_t 2.4e-3 and dW_s 5.6e-4 of these limits, which are 6e-3 and 1.1e-2 of the maxima.)"""
+    import math
+    from x3d_tf_amd import ops
+    n, dtype = 32, torch.float32
+    x, ws, wt, _ = _stem_inputs(gpu, "S", n, dtype, 73)
+    c1 = ws.shape[0]
+    xp = x.permute(0, 4, 1, 2, 3).contiguous()
+    s = ops.stem_s_fwd(xp, ws)
+    st = torch.zeros((c1, 2), dtype=torch.float64, device=gpu)
+    y = ops.dwt_fwd(s, wt, stats=st)
+    torch.cuda.synchronize()
+    rt, at = tol_store(dtype)
+    e_s = e_y = 0.0
+    s1 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    s2 = torch.zeros(c1, dtype=torch.float64, device=gpu)
+    CH = 8
+    for i in range(0, n, CH):
+        s64 = _conv_s64(_im2col_taps(x[i:i + CH].double()), ws.double())
+        e_s = max(e_s, _check(f"s_raw[{i}:{i + CH}]", s[i:i + CH], s64, rt, at * s64.abs().max().item()))
+        t64 = _conv_t64(s64, wt.double())
+        e_y = max(e_y, _check(f"t_raw[{i}:{i + CH}]", y[i:i + CH], t64, rt, at * t64.abs().max().item()))
+        yd = y[i:i + CH].double()
+        s1 += yd.sum((0, 2, 3, 4))
+        s2 += (yd * yd).sum((0, 2, 3, 4))
+        del s64, t64, yd
+    sref = torch.stack([s1, s2], 1)
+    e_st = _check("stats", st, sref, _stol(dtype), _stol(dtype) * max(1.0, sref.abs().max().item()))
+    res, dwt_ref, dws_ref, abs_t, abs_s, e_ds, shape = _stem_backward_case(gpu, "S", n, dtype, 73, fused=False)
+    _, t, h, w, _ = shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    segs = n * t * ho * -(-wo // 64)
+    spb = max(8, -(-segs // (3 * torch.cuda.get_device_properties(gpu).multi_processor_count)))
+    l_t = 2 * t + 8 + n * -(-(ho * wo) // 256) + 3
+    l_s = 16 * spb + 3 + -(-segs // spb) + 8
+    lam, u = 6.0, 2.0 ** -24
+    dwt, ft, dws, fs = res["two-kernel"]
+    got_t, got_s = dwt.double() - ft, dws.double() - fs
+    lim_t = lam * math.sqrt(l_t) * u * abs_t + 2 * u * abs(ft)           # (+ the rounding of the pre-filled accumulator)
+    lim_s = lam * math.sqrt(l_s) * u * abs_s + 2 * u * abs(fs)
+    e_t, _ = _check_slack("dW_t", got_t, dwt_ref, 0.0, 0.0, lim_t)
+    e_w, _ = _check_slack("dW_s", got_s, dws_ref, 0.0, 0.0, lim_s)
+    print(f"full-size stem X3D-S fp32 {shape}: s_raw err {e_s:.2e}, t_raw err {e_y:.2e} of max (limit {at:.0e}), stats "
+          f"{e_st:.2e}, ds {e_ds:.2e}; dW_t err / limit {e_t:.2e} (L {l_t}, limit {(lim_t / dwt_ref.abs().max()).max().item():.1e} "
+          f"of max), dW_s err / limit {e_w:.2e} (L {l_s}, limit {(lim_s / dws_ref.abs().max()).max().item():.1e} of max)")

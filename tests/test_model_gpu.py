@@ -703,19 +703,23 @@ def test_full_size_plan_properties(gpu, name, n, t, s, dtype, part):
     assert torch.isfinite(pl.loss_rows).all() and torch.isfinite(m.flat_grads).all()
     assert 4.0 < pl.loss_rows.mean().item() < 9.0           # ~ln(400) = 5.99 for a random-init classifier
     g1 = m.flat_grads.clone()
-    # batch statistics: first two blocks (the widest planes), a mid-network block, the last block
+    # batch statistics: the stem (x3d_stem_fwd's replicated sums for configs 3 / 4, x3d_dwt_fwd for config 2), the first two
+    # blocks (the widest planes), a mid-network block, the last block
     nb = len(pl.blocks)
+    assert pl.stem_fused == (dtype != torch.float32)          # (so the stem's sums below are x3d_stem_fwd's for configs 3 / 4)
+    checked = [("stem", pl.t_raw, pl.bn1)]
     for bi in (0, 1, nb // 2, nb - 1):
         B = pl.blocks[bi]
-        for raw, bn in ((B.a_raw, B.bn_a), (B.b_raw, B.bn_b), (B.c_raw, B.bn_c)):
-            d = raw.double()
-            mean = d.mean((0, 2, 3, 4))
-            var = d.var((0, 2, 3, 4), unbiased=False)
-            del d
-            mi = bn.mi.double()
-            scale = max(mean.abs().max().item(), var.sqrt().max().item())
-            report(f"block {bi} {bn.prefix} mean", mi[:, 0], mean, 0, 2e-4 * scale)
-            report(f"block {bi} {bn.prefix} invstd", mi[:, 1], 1 / torch.sqrt(var + arch.bn_eps), 5e-4, 0)
+        checked += [(f"block {bi}", raw, bn) for raw, bn in ((B.a_raw, B.bn_a), (B.b_raw, B.bn_b), (B.c_raw, B.bn_c))]
+    for where, raw, bn in checked:
+        d = raw.double()
+        mean = d.mean((0, 2, 3, 4))
+        var = d.var((0, 2, 3, 4), unbiased=False)
+        del d
+        mi = bn.mi.double()
+        scale = max(mean.abs().max().item(), var.sqrt().max().item())
+        report(f"{where} {bn.prefix} mean", mi[:, 0], mean, 0, 2e-4 * scale)
+        report(f"{where} {bn.prefix} invstd", mi[:, 1], 1 / torch.sqrt(var + arch.bn_eps), 5e-4, 0)
     # linearity
     m.moving_stats_flat().copy_(moving0)
     pl = m.forward_backward(clips, labels, loss_scale=2.0)

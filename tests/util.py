@@ -24,13 +24,36 @@ def tie_slack(v, dtype, w_abs, eps_ulps=2e-4):
     the other neighbour: one ulp of the operand, so every output at that point may move by ulp * |w[m, k]|.  Zero almost
     everywhere.  (Found by the fuzz sweep, seed 20261004: a prologue value 2.1e-6 bf16-ulps off a midpoint under a weight
     of 0.66 moved 15 outputs of one point by up to 1.2e-2, five times the flat atol.)"""
-    v64 = v.detach().double().cpu()
+    amb = _tie_ulps(v.detach().double().cpu(), dtype, eps_ulps)      # [N, K, T, H, W]
+    return torch.einsum("mk,nkthw->nmthw", w_abs.detach().double().cpu(), amb)
+
+
+def _tie_ulps(v64, dtype, eps_ulps):
+    """ulp(v) in `dtype` where the fp64 value v sits within `eps_ulps` of a rounding midpoint, 0 elsewhere (on v's device)."""
     r = v64.float().to(dtype).double()
     mant = 7 if dtype == torch.bfloat16 else 10
     ulp = torch.exp2(torch.floor(torch.log2(r.abs().clamp_min(1e-30))) - mant)
+    if dtype == torch.float16:
+        ulp = ulp.clamp_min(2.0 ** -24)               # (subnormals: a fixed spacing)
     d = (v64 - r).abs() / ulp                         # 0 .. 0.5 (0.5 = a tie)
-    amb = ((0.5 - d) < eps_ulps).double() * ulp       # [N, K, T, H, W]
-    return torch.einsum("mk,nkthw->nmthw", w_abs.detach().double().cpu(), amb)
+    return ((0.5 - d) < eps_ulps).double() * ulp
+
+
+def tie_slack_t(v, dtype, w_abs, eps_ulps=2e-4):
+    """The temporal analogue of tie_slack, for a depthwise conv along T (the stem's conv_t, "same" padding KT // 2) whose
+    input `v` ([N, C, T, H, W], fp64: the conv_s output before the kernel rounds it to the 16-bit `dtype` on chip) is such a
+    rounded operand: where v sits within `eps_ulps` of a midpoint, the kernel's fp32 sum may round to the other neighbour
+    than the fp64 reference did, and every output that reads that point, out[t] = sum_k w[c, k] v[t + k - KT // 2], may move
+    by |w[c, k]| * ulp.  Returns that extra absolute tolerance [N, C, T, H, W] on v's device (the full-size tests stay on the
+    GPU).  w_abs: [C, KT]."""
+    kt = w_abs.shape[1]
+    amb = torch.nn.functional.pad(_tie_ulps(v.detach().double(), dtype, eps_ulps), (0, 0, 0, 0, kt // 2, kt // 2))
+    t = v.shape[2]
+    wa = w_abs.detach().double().to(v.device)
+    out = torch.zeros(v.shape, dtype=torch.float64, device=v.device)
+    for k in range(kt):
+        out += wa[:, k].view(1, -1, 1, 1, 1) * amb[:, :, k:k + t]
+    return out
 
 
 def relu_mask_mismatch(masks, oracle_taps_masks):

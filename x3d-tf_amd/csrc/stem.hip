@@ -647,10 +647,12 @@ extern "C" int x3d_stem_s_wgrad(const void* x, const void* dy, float* dw, int N,
     // row segments (round 6): 2-3 workgroups per CU, an equal share of the segments each
     const int nws = ceil_div(Wo, 64);
     const long long total_segs = (long long)N * T * Ho * nws;
-    if (total_segs < (1ll << 31) && x3d_env_int("X3D_STEM_WGRAD_ROWS", 1) != 0) {      // X3D_STEM_WGRAD_ROWS=0: A/B hook (the flattened-point kernel)
-      long long spb2 = ceil_div_ll(total_segs, 3ll * x3d_device_cus());
-      if (spb2 < 8) spb2 = 8;
-      const long long gx2 = ceil_div_ll(total_segs, spb2);
+    long long spb2 = ceil_div_ll(total_segs, 3ll * x3d_device_cus());
+    if (spb2 < 8) spb2 = 8;
+    const long long gx2 = ceil_div_ll(total_segs, spb2);
+    // the kernel forms blockIdx.x * spb2 + spb2 and reads ahead to seg + 1 in int: the sum must stay below 2^31 (as in the
+    // 16-bit path above); past that, the flattened-point kernel below
+    if (total_segs + spb2 < (1ll << 31) && gx2 < (1ll << 31) && x3d_env_int("X3D_STEM_WGRAD_ROWS", 1) != 0) {      // X3D_STEM_WGRAD_ROWS=0: A/B hook (the flattened-point kernel)
 #define STEM_WGR(TT) hipLaunchKernelGGL((stem_s_wgrad_rows_kernel<TT>), dim3((unsigned)gx2), dim3(256), 0, st, (const TT*)x, (const TT*)dy, dw, \
                                         Cin, Cout, T, H, W, Ho, Wo, nws, (int)total_segs, (int)spb2)
       if (dtype == X3D_F32) STEM_WGR(float); else if (dtype == X3D_F16) STEM_WGR(f16); else STEM_WGR(bf16);
