@@ -47,8 +47,9 @@ extern "C" {
 
 /* Version of THIS header: bumped with every incompatible change of a signature or struct.  x3d_version() returns the value
  * the library was built with; a binding must refuse a library whose version differs from the header it was written against
- * (x3d_tf_amd/hip.py does): a stale libx3d_hip.so would otherwise take shifted arguments silently. */
-#define X3D_ABI_VERSION 133
+ * (x3d_tf_amd/hip.py does): a stale libx3d_hip.so would otherwise take shifted arguments silently.
+ * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit). */
+#define X3D_ABI_VERSION 134
 int x3d_version(void);
 const char* x3d_last_error(void);
 
@@ -500,6 +501,16 @@ int x3d_softmax_xent(const float* logits, const int* labels, float* probs, float
                      float* dlogits, float grad_scale, int N, int M, void* stream);
 /* out[v][m] = mean over `views` consecutive rows (model.py:123-126) */
 int x3d_view_mean(const float* probs, float* out, int videos, int views, int M, void* stream);
+/* Keras metrics of a batch of probabilities (ABI 134; reference train.py:102-108 compile(metrics=[acc, top_5_acc]),
+ * eval.py:48-66), added into four fp64 device counters:
+ *   acc[0] += sum of loss rows, acc[1] += top-1 hits, acc[2] += top-k hits, acc[3] += N.
+ * probs [N][M] fp32; labels [N] int32 (label_bytes 4) or int64 (label_bytes 8).  Per row, with q = clamp(p, 1e-7, 1-1e-7)
+ * in fp64: loss = -log q_y + log sum_j q_j (NaN for a label outside [0, M), which is never used as an index);
+ * top-k hit = label in range, every p_j finite and #{j : p_j > p_y} < k (tf.math.in_top_k: ties at the boundary hit);
+ * top-1 hit = the same with no p_j > p_y and no j < y with p_j == p_y (first-index argmax).  One workgroup, no
+ * floating-point atomics: the same inputs give bit-identical counters.  N * M < 2^31, k >= 1; N = 0 is a no-op. */
+int x3d_topk_metrics(const float* probs, const void* labels, int label_bytes, double* acc, int N, int M, int k,
+                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K12  SGD with Nesterov momentum + L2 (train.py:89-92, model.py:47):

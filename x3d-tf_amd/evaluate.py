@@ -51,6 +51,51 @@ class Metrics:
         return {"loss": self.loss / n + self.reg_loss, "acc": self.top1 / n, "top_5_acc": self.top5 / n, "videos": self.n}
 
 
+class DeviceMetrics:
+    """`Metrics` with the counters on the device: `update` launches one x3d_topk_metrics (no host read, no ATen op), the
+    host reads the four fp64 counters once, in `result()`.  For the training loop, where a per-batch `int(...)` would
+    synchronise every step.  Top-1 is the first-index argmax and top-5 is tf.math.in_top_k, ties at the 5th place
+    counting as hits (include/x3d_hip.h); on tie-free rows both equal `Metrics`."""
+
+    def __init__(self, reg_loss=0.0, k: int = 5):
+        self.reg_loss = reg_loss      # float, or a device tensor (model.regularization_loss()): read in result()
+        self.k = int(k)
+        self.acc = None               # [loss sum, top-1 hits, top-k hits, rows] fp64, on the device of the first batch
+
+    def _counters(self, device):
+        if self.acc is None:
+            self.acc = torch.zeros(4, dtype=torch.float64, device=device)
+        return self.acc
+
+    def update(self, probs: torch.Tensor, labels: torch.Tensor):
+        """probs [videos, classes] fp32 on the GPU; labels [videos] int32 / int64 (moved to probs' device if elsewhere)."""
+        from . import ops
+        if labels.device != probs.device:
+            labels = labels.to(probs.device, non_blocking=True)
+        ops.topk_metrics(probs, labels, self._counters(probs.device), self.k)
+
+    def all_reduce_(self, group=None, device=None):
+        """Sums the four counters over the replicas, as `Metrics.all_reduce_` does (no-op without a multi-rank process
+        group; the exchange runs on the CPU for gloo, on the GPU for RCCL)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        if device is None:
+            device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+        acc = self._counters(device)
+        t = acc.to(device)
+        dist.all_reduce(t, group=group)
+        if t is not acc:
+            acc.copy_(t)
+        return self
+
+    def result(self) -> Dict[str, float]:
+        loss, top1, topk, n = self.acc.tolist() if self.acc is not None else (0.0, 0.0, 0.0, 0.0)
+        reg = float(self.reg_loss.item()) if torch.is_tensor(self.reg_loss) else float(self.reg_loss)
+        d = max(n, 1.0)
+        return {"loss": loss / d + reg, "acc": top1 / d, "top_5_acc": topk / d, "videos": int(round(n))}
+
+
 def evaluate(model, cfg, videos: Iterable[Tuple[torch.Tensor, int]], batch_videos: int = None) -> Dict[str, float]:
     """videos: iterable of (uint8 [F, H, W, 3] GPU tensor, label).  Batches `batch_videos` videos
     (default cfg.TEST.BATCH_SIZE) of views x crops clips each through `model(clips, training=False)`."""

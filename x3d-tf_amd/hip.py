@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X3D_HIP_LIB") or os.path.join(_HERE, "libx3d_hip.so")   # X3D_HIP_LIB: A/B builds (tools/build_variant.sh)
 
-ABI_VERSION = 133   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
+ABI_VERSION = 134   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = 0, 1, 2, 3
@@ -174,6 +174,7 @@ _SIGS = {
     "x3d_dense_bwd": ([_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "x3d_softmax_xent": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
     "x3d_view_mean": ([_vp, _vp, _i, _i, _i, _vp], _i),
+    "x3d_topk_metrics": ([_vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
     "x3d_sgd_nesterov": ([_vp, _vp, _vp, _vp, _f, _f, _f, _f, _ll, _vp], _i),
     "x3d_adam": ([_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _ll, _ll, _vp], _i),
     "x3d_all_finite": ([_vp, _ll, _vp, _vp], _i),

@@ -473,6 +473,26 @@ def view_mean(probs, out, views):
     return out
 
 
+def topk_metrics(probs, labels, acc, k=5):
+    """acc [4] fp64 += (sum of loss rows, top-1 hits, top-k hits, rows) of probs [N, M] fp32 against labels [N] int32 |
+    int64 (x3d_topk_metrics: the rules are in include/x3d_hip.h).  Launches one kernel, does not synchronise."""
+    _chk(probs, labels, acc)
+    if probs.dtype != torch.float32 or probs.dim() != 2:
+        raise ValueError(f"topk_metrics: probs must be [N, M] float32, got {tuple(probs.shape)} {probs.dtype}")
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != probs.shape[0]:
+        raise ValueError(f"topk_metrics: labels must be [{probs.shape[0]}] int32 or int64, got {tuple(labels.shape)} "
+                         f"{labels.dtype}")
+    if acc.dtype != torch.float64 or acc.numel() != 4:
+        raise ValueError(f"topk_metrics: acc must be 4 float64 counters, got {acc.numel()} {acc.dtype}")
+    if not probs.device == labels.device == acc.device:
+        raise ValueError("topk_metrics: probs, labels and acc must be on one device")
+    if int(k) < 1:
+        raise ValueError(f"topk_metrics: k = {k} (k >= 1)")
+    hip.call("x3d_topk_metrics", ptr(probs), ptr(labels), labels.element_size(), ptr(acc), probs.shape[0],
+             probs.shape[1], int(k))
+    return acc
+
+
 def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
     _chk(w, v, g, l2_mask)
     hip.call("x3d_sgd_nesterov", ptr(w), ptr(v), ptr(g), ptr(l2_mask), float(lr), float(momentum),

@@ -20,6 +20,51 @@ def lr_schedule(epoch, cfg):
     return tr.WARMUP_LR + epoch * (tr.BASE_LR - tr.WARMUP_LR) / tr.WARMUP_EPOCHS
 
 
+class SaveSchedule:
+    """When Keras' `ModelCheckpoint(save_freq=...)` writes (reference utils.py:128-132, train.py:110-112).
+
+    save_freq="epoch": `ckpt-{epoch + 1}` after every epoch.  save_freq=n (a positive int): a batch counter runs from the
+    start of the `fit` call across epoch boundaries; when it reaches n the checkpoint of the RUNNING epoch is written --
+    `ckpt-{epoch index + 1}`, so a save in the middle of epoch index e is named as if e had finished and `resume` continues
+    at epoch e + 1, as the reference's does -- the counter resets, and nothing is written at epoch end."""
+
+    def __init__(self, save_freq="epoch"):
+        if save_freq != "epoch" and not (isinstance(save_freq, int) and not isinstance(save_freq, bool) and save_freq > 0):
+            raise ValueError(f"save_freq must be 'epoch' or a positive int, got {save_freq!r}")
+        self.save_freq = save_freq
+        self.batches = 0
+
+    def after_batch(self, epoch: int) -> Optional[int]:
+        """Called after every batch of epoch index `epoch`; the checkpoint number to write now, or None."""
+        if self.save_freq == "epoch":
+            return None
+        self.batches += 1
+        if self.batches < self.save_freq:
+            return None
+        self.batches = 0
+        return epoch + 1
+
+    def after_epoch(self, epoch: int) -> Optional[int]:
+        """Called when epoch index `epoch` has finished; the checkpoint number to write now, or None."""
+        return epoch + 1 if self.save_freq == "epoch" else None
+
+
+TRAIN_METRICS = ("acc", "top_5_acc")
+
+
+def _validation_source(validation_data, epochs_to_run: int):
+    """validation_data -> a zero-argument callable returning a fresh iterable of (clips, labels) batches."""
+    if validation_data is None:
+        return None
+    if callable(validation_data) and not hasattr(validation_data, "__iter__"):
+        return validation_data
+    if iter(validation_data) is validation_data and epochs_to_run > 1:
+        raise ValueError("validation_data is a one-shot iterator and would be exhausted after the first epoch: pass a "
+                         "callable that returns a fresh one, e.g. validation_data=lambda: InputReader(cfg, False, True)"
+                         "(pattern, cfg.TEST.BATCH_SIZE)")
+    return lambda: validation_data
+
+
 class Trainer:
     """fwd + bwd + gradient all-reduce + optimizer for one replica.
 
@@ -94,38 +139,99 @@ class Trainer:
         return pl
 
     def fit(self, dataset, epochs: Optional[int] = None, steps_per_epoch: Optional[int] = None, model_dir: Optional[str] = None,
-            initial_epoch: Optional[int] = None, on_step=None):
-        """The loop `model.fit(dataset, epochs, steps_per_epoch, initial_epoch, callbacks)` runs in reference train.py:145-152
-        with its LearningRateScheduler (per-epoch `lr_schedule`, train.py:114-125) and ModelCheckpoint (`ckpt-{epoch}`
-        after every epoch, utils.py:128-132) callbacks -- nothing else of the Keras harness (TensorBoard / wandb callbacks
-        are out of scope).  `dataset`: an iterator of (clips, labels) batches, e.g. `dataloader.InputReader(cfg, True,
-        True)(pattern, cfg.TRAIN.BATCH_SIZE)` (infinite in training mode, like `dataset.repeat()`; under torchrun the reader
-        shards the records by rank and yields BATCH_SIZE // world clips per step, so `steps_per_epoch` = DATASET_SIZE //
-        BATCH_SIZE is one pass over the data on every world size, as with MirroredStrategy).  Returns the per-epoch mean
-        losses."""
+            initial_epoch: Optional[int] = None, on_step=None, validation_data=None, validation_steps: Optional[int] = None,
+            metrics=TRAIN_METRICS, save_freq="epoch"):
+        """The loop `model.fit(dataset, epochs, steps_per_epoch, initial_epoch, validation_data, callbacks)` runs in reference
+        train.py:145-152, with the metrics it was compiled with (train.py:102-108), its LearningRateScheduler (per-epoch
+        `lr_schedule`, train.py:114-125) and ModelCheckpoint (utils.py:128-132) callbacks -- nothing else of the Keras harness
+        (TensorBoard / wandb callbacks are out of scope).  `dataset`: an iterator of (clips, labels) batches, e.g.
+        `dataloader.InputReader(cfg, True, True)(pattern, cfg.TRAIN.BATCH_SIZE)` (infinite in training mode, like
+        `dataset.repeat()`; under torchrun the reader shards the records by rank and yields BATCH_SIZE // world clips per
+        step, so `steps_per_epoch` = DATASET_SIZE // BATCH_SIZE is one pass over the data on every world size, as with
+        MirroredStrategy).  Returns the per-epoch mean losses.
+
+        validation_data: None, a zero-argument callable returning a fresh iterable of (clips [B * views * crops, T, S, S, 3],
+            labels [B]) -- e.g. `lambda: InputReader(cfg, False, True)(val_pattern, cfg.TEST.BATCH_SIZE)` -- or an iterable
+            `iter()` can walk again every epoch.  After every epoch `model(clips, training=False)` runs over the whole stream
+            (or its first `validation_steps` batches) into `evaluate.DeviceMetrics`; under data parallelism every rank
+            validates its shard and the counters are summed once.  The training plan stays cached across it.
+        metrics: any of "acc", "top_5_acc": the hits of the training batches' probabilities, one x3d_topk_metrics launch
+            after every step (skipped fp16 steps too, as Keras updates compiled metrics), read once per epoch.
+        save_freq: "epoch" or a positive int (`SaveSchedule`); rank 0 writes the checkpoints into `model_dir`.
+
+        self.history: per-epoch lists like keras.callbacks.History.history -- `loss` (= the returned list), `lr`, the
+        requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating."""
+        from .evaluate import DeviceMetrics
         tr = self.cfg.TRAIN
         epochs = int(tr.EPOCHS if epochs is None else epochs)
         steps = int(steps_per_epoch if steps_per_epoch is not None else tr.DATASET_SIZE // tr.BATCH_SIZE)
         if steps <= 0:
             raise ValueError("steps_per_epoch must be positive (cfg.TRAIN.DATASET_SIZE // cfg.TRAIN.BATCH_SIZE)")
+        metrics = tuple(metrics or ())
+        unknown = [k for k in metrics if k not in TRAIN_METRICS]
+        if unknown:
+            raise ValueError(f"unknown metrics {unknown}: fit computes {TRAIN_METRICS}")
+        schedule = SaveSchedule(save_freq)
         if initial_epoch is not None:
             self.epoch = int(initial_epoch)
+        val_source = _validation_source(validation_data, epochs - self.epoch)
         it = iter(dataset)
         history = []
+        self.history = {"loss": [], "lr": []}
+        self.history.update({k: [] for k in metrics})
+        if val_source is not None:
+            self.history.update({"val_loss": [], "val_acc": [], "val_top_5_acc": []})
+        writer = model_dir is not None and xdist.env_world()[0] == 0
         while self.epoch < epochs:
             lr = lr_schedule(self.epoch, self.cfg)
             tot = torch.zeros((), dtype=torch.float64, device=self.model.device)
+            train_m = DeviceMetrics() if metrics else None
             for _ in range(steps):
                 clips, labels = next(it)
                 pl = self.step(clips, labels, lr)
                 tot += self.loss(pl).double()
+                if train_m is not None:
+                    train_m.update(pl.probs, pl.labels)
                 if on_step is not None:
                     on_step(self, pl)
+                ckpt = schedule.after_batch(self.epoch)
+                if ckpt is not None and writer:
+                    self.save_checkpoint(model_dir, ckpt)
+            ckpt = schedule.after_epoch(self.epoch)
             self.epoch += 1
             history.append(float(tot.item()) / steps)
-            if model_dir is not None and xdist.env_world()[0] == 0:
-                self.save_checkpoint(model_dir, self.epoch)
+            self.history["loss"].append(history[-1])
+            self.history["lr"].append(lr)
+            if train_m is not None:
+                r = train_m.all_reduce_(self.group).result()
+                for k in metrics:
+                    self.history[k].append(r[k])
+            if val_source is not None:
+                r = self.validate(val_source(), validation_steps)
+                for k in ("loss", "acc", "top_5_acc"):
+                    self.history["val_" + k].append(r[k])
+            if ckpt is not None and writer:
+                self.save_checkpoint(model_dir, ckpt)
         return history
+
+    def validate(self, batches, steps: Optional[int] = None):
+        """`model.evaluate` inside `fit` (reference train.py:148-151): `model(clips, training=False)` over `batches` (the
+        first `steps` of them when given) into a DeviceMetrics, counters summed over the ranks once.  Unlike
+        `evaluate_dataset` this releases no plan, so the training plan is still cached in the next epoch.  Returns
+        {"loss", "acc", "top_5_acc", "videos"}."""
+        import itertools
+        from .evaluate import DeviceMetrics
+        m = self.model
+        dm = DeviceMetrics(m.regularization_loss())
+        it = iter(batches)
+        try:
+            for clips, labels in itertools.islice(it, None if steps is None else int(steps)):
+                dm.update(m(clips, training=False), labels)
+        finally:
+            close = getattr(it, "close", None)
+            if close is not None:
+                close()       # a reader's generator: stops its prefetch thread
+        return dm.all_reduce_(self.group).result()
 
     def collective_stats(self):
         """What the exchange step of this replica did so far (bench.py's `collectives` block)."""
@@ -171,14 +277,33 @@ class Trainer:
         self.model.save_weights(prefix, optimizer_hyper=hyper, optimizer=self.optimizer)
         return prefix
 
-    def resume(self, model_dir: str) -> int:
-        """train.py:131-136: load the latest `ckpt-<epoch>` of `model_dir` if there is one; returns the epoch to
-        continue from (0 without a checkpoint) and sets `self.epoch`."""
+    def resume(self, model_dir: str, pretrained_ckpt: Optional[str] = None) -> int:
+        """train.py:131-143: load the latest `ckpt-<epoch>` of `model_dir` if there is one; returns the epoch to
+        continue from (0 without a checkpoint) and sets `self.epoch`.  Without one, `pretrained_ckpt` (the reference's
+        --pretrained_ckpt) is loaded when given -- a directory through its latest checkpoint (FileNotFoundError when it
+        holds none), anything else as a checkpoint prefix -- with the same optimizer-slot and `iter` rules, and training
+        starts at epoch 0."""
         import os
         from .checkpoint import latest_checkpoint
         path = latest_checkpoint(model_dir)
+        if not path and pretrained_ckpt is not None:
+            pre = str(pretrained_ckpt)
+            if os.path.isdir(pre):
+                found = latest_checkpoint(pre)
+                if not found:
+                    raise FileNotFoundError(f"pretrained_ckpt {pre}: the directory holds no checkpoint")
+                pre = found
+            self._load(pre)
+            self.epoch = 0
+            return 0
         if not path:
             return 0
+        self._load(path)
+        self.epoch = int(os.path.basename(path).split("-")[1])
+        return self.epoch
+
+    def _load(self, path: str):
+        """Weights + this optimizer branch's slots from the checkpoint prefix `path`; sets `opt_step` from its `iter`."""
         m = self.model
         m.load_weights(path, optimizer=self.optimizer)   # weights + this branch's optimizer slots; unknown keys tolerated as Keras does
         st = getattr(m, "optimizer_state", None) or {}
@@ -196,8 +321,6 @@ class Trainer:
             if self.optimizer == "adam" and kind is None:
                 m.flat_velocity.zero_()
                 self.opt_step = 0
-        self.epoch = int(os.path.basename(path).split("-")[1])
-        return self.epoch
 
     def loss(self, pl):
         """global-batch mean cross-entropy + L2 term (what Keras reports as `loss`)."""
