@@ -226,6 +226,42 @@ DW = [
     (2, 2, 3, 13, 13, 2), (1, 2, 3, 6, 21, 1), (1, 1, 3, 30, 11, 1), (1, 2, 2, 3, 37, 1),
 ]
 
+# ---- every depthwise launch of the full-size plans of BASELINE configs 2 - 5 (and config 3 with fp16 storage), for the fp64
+# checks of tests/test_full_size_gpu.py.  Keyed by shape and launch form, not by kernel: after a rewrite the same case runs
+# whatever the dispatch picks.  tests/test_dispatch_coverage.py asserts that every x3d_dw3d_fwd / x3d_dw3d_bwd launch of
+# those dry plans has its entry here.
+#   entry, dtype, N, C, T, H, W, stride, prologue, stats, pool
+# prologue: "ss" (BN_a as a scale / shift table) or "bn" (its finalize folded into the launch, ops.bn_fold); stats: the BN_b
+# sums are written (training); pool: the SE squeeze sums are written.  The stride-1 layers of every stage launch with and
+# without pool (SE on every second block): one case with pool stands for both where the coverage test finds that the two
+# dispatch the same kernel.  Backward launches have no form of their own (None, None, None).
+def _dw_full(dtype, n, t, chans, s, pools, training):
+    """The launches of one plan, stage by stage: the first block's stride-2 layer (with the SE pool where `pools` says so),
+    then the stride-1 layer of the other blocks (pool on and off)."""
+    out = []
+    for i, (c, pool2) in enumerate(zip(chans, pools)):
+        h = -(-s // 2 ** (i + 1))            # the stage's input extent (the stem halves S)
+        for stride, hh, pool in ((2, h, pool2), (1, -(-h // 2), True)):
+            out.append(("fwd", dtype, n, c, t, hh, hh, stride, "ss", training, pool))
+            if training:
+                out.append(("bwd", dtype, n, c, t, hh, hh, stride, None, None, None))
+    return out
+
+
+_W, _SM, _SL = (54, 108, 216, 432), (True, False, True, False), (True, False, False, True)
+DW_FULL = (_dw_full(F32, 32, 13, _W, 160, _SM, True)                                   # config 2: X3D-S, fp32
+           + _dw_full(BF16, 64, 16, _W, 224, _SM, True)                                # config 3: X3D-M (bench.py's workload)
+           + _dw_full(F16, 64, 16, _W, 224, _SM, True)                                 # ... with fp16 storage (bench.py --dtype fp16)
+           + _dw_full(BF16, 16, 16, _W, 312, _SL, True)                                # config 4: X3D-L
+           + _dw_full(F16, 30, 16, (72, 162, 306, 630), 312, _SL, False))           # config 5: X3D-XL inference, 30 views
+
+
+def dw_full_id(case):
+    e, dt, n, c, t, h, w, s, pro, st, pool = case
+    form = "" if e == "bwd" else f"-{pro}" + ("-stats" if st else "") + ("-pool" if pool else "")
+    return f"{e}-{str(dt)[6:]}-N{n}-C{c}-T{t}-{h}x{w}-s{s}{form}"
+
+
 # ---- whole-model cases (tests/test_model_gpu.py): variant, N, T, S --------------------------------------------------------
 MODEL_TRAIN_FP32 = [
     ("XS", 4, 4, 64), ("S", 2, 13, 64), ("M", 2, 4, 64), ("S", 3, 5, 96),
@@ -343,6 +379,20 @@ def dw_fwd_struct(shape, dtype):
     n, c, t, h, w, stride = shape
     A = _Addr.new
     return hip.Dw3dFwdArgs(A(), A(), A(), A(), 1, A(), A(), n, c, t, h, w, stride, _code(dtype))
+
+
+def dw_full_struct(case):
+    """The argument struct of a DW_FULL case over address-only operands, in the case's launch form."""
+    from x3d_tf_amd import hip
+    e, dtype, n, c, t, h, w, stride, pro, st, pool = case
+    A = _Addr.new
+    if e == "bwd":
+        return dw_bwd_struct((n, c, t, h, w, stride), dtype)
+    fold = hip.BnFold(A(), 1.0, A(), A(), A(), A(), 1e-5, 0.9, 1, A(), A()) if pro == "bn" else None
+    a = hip.Dw3dFwdArgs(A(), A(), A(), None if fold else A(), 1, A() if st else None, A() if pool else None, n, c, t, h, w,
+                        stride, _code(dtype), None if fold is None else __import__("ctypes").pointer(fold))
+    a._fold = fold           # (the struct holds a raw pointer to it)
+    return a
 
 
 def dw_bwd_struct(shape, dtype):

@@ -150,3 +150,80 @@ def test_inference_plan_is_inference_shaped(index):
     assert len(ys) == 2 and len({B.a_raw.data_ptr() for B in pl.blocks}) == 1
     for prev, cur in zip(pl.blocks, pl.blocks[1:]):
         assert cur.x.data_ptr() == prev.y.data_ptr() and cur.y.data_ptr() != cur.x.data_ptr()
+
+
+
+# the plans whose depthwise launches tests/test_full_size_gpu.py checks against fp64 at their real size (shapes.DW_FULL):
+# BASELINE configs 2 - 5 and config 3 with fp16 storage (bench.py --dtype fp16)
+DW_FULL_PLANS = {"2": 2, "3": 3, "3-fp16": ("M", 64, 16, 224, torch.float16, True), "4": 4, "5": 5}
+
+
+def _dw_launches(plan):
+    """(entry, kernel instantiation, argument struct) of every x3d_dw3d_fwd / x3d_dw3d_bwd launch of a full-size dry plan."""
+    from x3d_tf_amd import hip
+    from x3d_tf_amd.config import get_config
+    from x3d_tf_amd.dispatch import BASELINE_CONFIGS
+    from x3d_tf_amd.model import X3D
+    variant, n, t, s, dtype, training, over = BASELINE_CONFIGS[plan] if isinstance(plan, int) else plan + ({},)
+    flat = [x for kv in over.items() for x in kv]
+    m = X3D(get_config(variant, flat or None), dtype=dtype, device="dry")
+    pl = m._plan(n, t, s, s, training)
+    out = []
+    for lst in (pl.fwd, pl.bwd):
+        for i, item in enumerate(lst):
+            if item is not None and item[0] in ("x3d_dw3d_fwd", "x3d_dw3d_bwd"):
+                st = pl.structs[(id(lst), i)]
+                out.append((item[0], hip.kernel_name(st), st))
+    m.release_plans()
+    return out
+
+
+def _dw_launch_key(entry, st):
+    """shapes.DW_FULL's key (entry, dtype, N, C, T, H, W, stride, prologue, stats, pool) of a recorded depthwise launch."""
+    from x3d_tf_amd import hip
+    dtype = [d for d in S.DTYPES if hip.dtype_code(d) == st.dtype][0]
+    head = ("fwd" if entry == "x3d_dw3d_fwd" else "bwd", dtype, st.N, st.C, st.T, st.H, st.W, st.stride)
+    if entry == "x3d_dw3d_bwd":
+        return head + (None, None, None)
+    return head + ("bn" if st.in_bn else "ss", bool(st.stats), bool(st.pool))
+
+
+def _dw_full_cover(launches):
+    """{launch key: message} of the launches without a full-size fp64 case.  A forward launch is covered by the DW_FULL entry
+    of its own key, or by the entry of its shape and prologue with the OTHER pool / stats setting if both dispatch the same
+    kernel instantiation (asserted here through hip.kernel_name, not assumed); a case must run the plan's kernel."""
+    from x3d_tf_amd import hip
+    cases = set(S.DW_FULL)
+    missing = {}
+    for entry, kern, st in launches:
+        key = _dw_launch_key(entry, st)
+        alts = [key] if key[0] == "bwd" else [key[:9] + (sts, pool) for sts in (key[9], not key[9]) for pool in (key[10], not key[10])]
+        got = [a for a in alts if a in cases]
+        why = "no DW_FULL entry of this shape and form"
+        for a in got:
+            case_kern = hip.kernel_name(S.dw_full_struct(a))
+            if case_kern == kern:
+                break
+            why = f"the DW_FULL case {S.dw_full_id(a)} runs {case_kern}"
+        else:
+            missing[key] = f"{S.dw_full_id(key)} ({kern}): {why}"
+    return missing
+
+
+@pytest.mark.parametrize("plan", list(DW_FULL_PLANS))
+def test_every_depthwise_launch_of_a_full_size_plan_has_a_full_size_case(plan):
+    """Every x3d_dw3d_fwd / x3d_dw3d_bwd launch of the plan has a shapes.DW_FULL case (tests/test_full_size_gpu.py:
+    test_depthwise_full_size) at its real size and in its launch form, which dispatches the same kernel as the plan."""
+    launches = _dw_launches(DW_FULL_PLANS[plan])
+    assert launches, "the dry plan recorded no depthwise launches"
+    missing = _dw_full_cover(launches)
+    assert not missing, (f"plan {plan}: depthwise launches without a full-size fp64 case (tests/shapes.py DW_FULL):\n"
+                         + "\n".join(f"  {v}" for v in sorted(set(missing.values()))))
+
+
+def test_every_dw_full_case_is_a_launch_of_a_full_size_plan():
+    """... and no DW_FULL case is left over from a plan that no longer launches it (a case that stands for a launch form
+    only through the kernel-sameness rule still has the shape of a real launch)."""
+    keys = {_dw_launch_key(e, st)[:9] for plan in DW_FULL_PLANS.values() for e, _, st in _dw_launches(plan)}
+    stale = [S.dw_full_id(c) for c in S.DW_FULL if c[:9] not in keys]
+    assert not stale, "DW_FULL cases that no full-size plan launches: " + ", ".join(stale)

@@ -20,6 +20,7 @@ of drawn at random -- that is what makes the moment sums cancel.
 import pytest
 import torch
 
+from tests import shapes as S
 from tests.util import round_to, tie_slack_t, tol_gemm, tol_store
 
 pytestmark = pytest.mark.gpu
@@ -606,3 +607,223 @@ def test_stem_fp32_full_size(gpu):
     print(f"full-size stem X3D-S fp32 {shape}: s_raw err {e_s:.2e}, t_raw err {e_y:.2e} of max (limit {at:.0e}), stats "
           f"{e_st:.2e}, ds {e_ds:.2e}; dW_t err / limit {e_t:.2e} (L {l_t}, limit {(lim_t / dwt_ref.abs().max()).max().item():.1e} "
           f"of max), dW_s err / limit {e_w:.2e} (L {l_s}, limit {(lim_s / dws_ref.abs().max()).max().item():.1e} of max)")
+
+
+# ---- every depthwise launch of the full-size plans (tests/shapes.py DW_FULL: BASELINE configs 2 - 5, config 3 in fp16 too) ----
+def _frac(name, got, ref, rtol, atol):
+    """_check, returning the worst error as a fraction of its limit atol + rtol |ref|."""
+    _check(name, got, ref, rtol, atol)
+    got, ref = got.double(), ref.double()
+    return ((got - ref).abs() / (atol + rtol * ref.abs()).clamp_min(1e-300)).max().item()
+
+
+def _dw_chunk(case):
+    """Samples per fp64 chunk: about 48 M input elements (0.4 GB in fp64) at a time."""
+    _, _, n, c, t, h, w = case[:7]
+    return max(1, min(n, 48_000_000 // (c * t * h * w)))
+
+
+def _dw_fp32_chain(name, n, t, h, w, stride):
+    """L, the longest chain of fp32 roundings a product of the fp32 weight gradient passes through in the vector kernels of
+    config 2 (one thread owns a strip of SW outputs of one row: T SW products per tap; the wave's DPP tree, 6 levels; the
+    sum over the workgroup's waves; one atomic per workgroup of the channel; the 4 roundings of dB = A dv + B b + C and of
+    the prologue).  dw3d_bwd_kernel / dw3d_bwd_pd_kernel: dw_geom's partition (workgroups of 64 / 128 / 256 threads, one
+    per (n, c, H-tile)); dw3d_bwd_pk_kernel: one plane per strip set, at most 8 waves and N workgroups per channel."""
+    args = name[name.index("<") + 1:-1].split(", ")
+    ho, wo = -(-h // stride), -(-w // stride)
+    if name.startswith("dw3d_bwd_pk_kernel<"):
+        sw, waves, atomics = int(args[1]), 8, n
+    elif name.startswith(("dw3d_bwd_kernel<", "dw3d_bwd_pd_kernel<")):
+        sw = int(args[2])
+        nstrips = -(-wo // sw)
+        items = ho * nstrips
+        bd = 64 if items <= 64 else (128 if items <= 128 else 256)
+        th = min(bd // nstrips, ho)
+        waves, atomics = bd // 64, n * -(-ho // th)
+    else:
+        raise AssertionError(f"no fp32 summation bound for {name}")
+    return t * sw + 6 + waves + atomics + 4
+
+
+def _dw_inputs(gpu, case, seed):
+    """a_raw (the `a` conv's raw output, [N, C, T, H, W] in the storage type) with non-zero channel means, the depthwise
+    weights, and BN_a over the whole batch as the prologue sees it: (gamma, beta, fp64 sums of a_raw, scale / shift)."""
+    _, dtype, n, c, t, h, w = case[:7]
+    g_ = torch.Generator(device=gpu)
+    g_.manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g_, device=gpu, dtype=torch.float32)
+    mu, sd = 1.0 + rn(c), 0.5 + rn(c).abs()
+    araw = torch.empty((n, c, t, h, w), dtype=dtype, device=gpu)
+    for i in range(n):
+        araw[i] = (rn(c, t, h, w) * sd.view(-1, 1, 1, 1) + mu.view(-1, 1, 1, 1)).to(dtype)
+    wt = rn(c, 3, 3, 3) * 0.3
+    gamma, beta = 1 + 0.3 * rn(c), 0.3 * rn(c)
+    s1 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    s2 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    for i in range(n):
+        ad = araw[i].double()
+        s1 += ad.sum((1, 2, 3))
+        s2 += (ad * ad).sum((1, 2, 3))
+    m = n * t * h * w
+    mean = s1 / m
+    k = gamma.double() / torch.sqrt(s2 / m - mean * mean + 1e-5)
+    ss = torch.stack([k, beta.double() - mean * k], 1).float()
+    return araw, wt, gamma, beta, torch.stack([s1, s2], 1), ss, rn, g_
+
+
+def _dw_forward_case(gpu, case, seed):
+    """x3d_dw3d_fwd in the plan's form: y against the fp64 stencil of act = relu(s a_raw + t) at tol_store, or -- matrix-core
+    kernels, which round act and the weights to the storage type -- over those rounded operands at tol_gemm plus a tie slack:
+    where act sits within 2e-4 ulps of a rounding midpoint the kernel's fp32 prologue may round it to the other neighbour, so
+    every output reading it may move by ulp |w| per such tap (at most 1e-4 of the outputs may need that); stats and pool
+    against fp64 sums of the stored y at _stol."""
+    from x3d_tf_amd import hip, ops
+    from tests import shapes as S
+    from tests.util import _tie_ulps, dw_stencil64
+    _, dtype, n, c, t, h, w, stride, pro, want_stats, want_pool = case
+    araw, wt, gamma, beta, sums, ss, _, _ = _dw_inputs(gpu, case, seed)
+    stats = torch.zeros((c, 2), dtype=torch.float64, device=gpu) if want_stats else None
+    pool = torch.zeros((n, c), dtype=torch.float64, device=gpu) if want_pool else None
+    fold = None
+    if pro == "bn":        # the prologue's finalize inside the launch: it writes the scale / shift the reference then reads
+        ss = torch.zeros((c, 2), dtype=torch.float32, device=gpu)
+        fold = ops.bn_fold(sums, n * t * h * w, gamma, beta, torch.zeros(c, device=gpu), torch.ones(c, device=gpu), 1e-5, 0.9,
+                           1, ss, torch.zeros((c, 2), device=gpu))
+    y = ops.dw3d_fwd(araw, wt, stride, in_ss=ss if fold is None else None, in_act=1, stats=stats, pool=pool, in_bn=fold)
+    torch.cuda.synchronize()
+    name = hip.kernel_name(S.dw_full_struct(case))
+    mx = "_mx" in name
+    rt, at = tol_gemm(dtype) if mx else tol_store(dtype)
+    wd = round_to(wt, dtype) if mx else wt.double()
+    sc, sh = ss[:, 0].double().view(1, -1, 1, 1, 1), ss[:, 1].double().view(1, -1, 1, 1, 1)
+    worst, needed, CH = 0.0, 0, _dw_chunk(case)
+    y1 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    y2 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    pref = torch.zeros((n, c), dtype=torch.float64, device=gpu)
+    for i in range(0, n, CH):
+        act = torch.relu(araw[i:i + CH].double() * sc + sh)
+        slack = 0.0
+        if mx:
+            slack = dw_stencil64(_tie_ulps(act, dtype, 2e-4), wd.abs(), stride)
+            act = round_to(act, dtype)
+        ref = dw_stencil64(act, wd, stride)
+        del act
+        e, nd = _check_slack(f"y[{i}:{i + CH}]", y[i:i + CH], ref, rt, at * ref.abs().max().item(), slack)
+        worst, needed = max(worst, e), needed + nd
+        del ref, slack
+        yd = y[i:i + CH].double()
+        y1 += yd.sum((0, 2, 3, 4))
+        y2 += (yd * yd).sum((0, 2, 3, 4))
+        pref[i:i + CH] = yd.sum((2, 3, 4))
+        del yd
+    frac = needed / y.numel()
+    assert frac < 1e-4, f"{frac:.2e} of the outputs needed the tie slack: a systematic error, not ties"
+    stol = _stol(dtype)
+    msg = f"y {worst:.2e}"
+    if want_stats:
+        sref = torch.stack([y1, y2], 1)
+        msg += f", stats {_frac('stats', stats, sref, stol, stol * max(1.0, sref.abs().max().item())):.2e}"
+    if want_pool:
+        msg += f", pool {_frac('pool', pool, pref, stol, stol * max(1.0, pref.abs().max().item())):.2e}"
+    return name, msg + (f" ({frac:.1e} needed the tie slack)" if mx else "")
+
+
+def _dw_backward_case(gpu, case, seed):
+    """x3d_dw3d_bwd with the coefficients of a real step: dB = A[n, c] dv + B[c] b_raw + C[c], A = k1[c] times a positive
+    per-sample SE gate, and B, C solved so that sum dB = 0 and sum dB b_raw = 0 per channel over the whole batch (what BN_b's
+    backward guarantees).  dW = sum dB shift(relu(z)) then cancels the positive mean of the post-ReLU activation at the real
+    reduction length.  ga against the fp64 stencil (tol_gemm on matrix-core kernels, over operands rounded as they round them;
+    tol_store on vector kernels), a_sums at 10 _stol, dW (accumulator pre-filled with 0.25) at _wtol on matrix-core kernels,
+    2e-5 of its maximum on vector kernels with 16-bit storage, and for fp32 (config 2) at the probabilistic fp32 summation
+    bound of test_stem_fp32_full_size, lambda sqrt(L) u sum |dB act| with lambda = 6, L from the launcher's partition
+    (_dw_fp32_chain)."""
+    import math
+    from x3d_tf_amd import hip, ops
+    from tests import shapes as S
+    from tests.util import dw_stencil64
+    _, dtype, n, c, t, h, w, stride = case[:8]
+    araw, wt, _, _, _, ss, rn, g_ = _dw_inputs(gpu, case, seed)
+    ho, wo = -(-h // stride), -(-w // stride)
+    dv = rn(n, c, t, ho, wo).to(dtype)
+    braw = (rn(n, c, t, ho, wo) * 0.8 + 0.5 * rn(c).view(1, -1, 1, 1, 1)).to(dtype)
+    gate = 0.2 + 0.8 * torch.rand((n, c), generator=g_, device=gpu)
+    m = n * t * ho * wo
+    red = lambda v: v.sum((2, 3, 4))                         # [n, c]
+    bd, dvd = braw.double(), dv.double()
+    sb, sbb = red(bd).sum(0), red(bd * bd).sum(0)
+    mean_b = sb / m
+    k1 = (1 + 0.3 * rn(c)).double() / torch.sqrt(sbb / m - mean_b * mean_b + 1e-5)
+    cA = (k1.view(1, -1) * gate.double()).float()
+    sa, sab = (cA.double() * red(dvd)).sum(0), (cA.double() * red(dvd * bd)).sum(0)
+    det = sb * sb - m * sbb
+    cB, cC = ((m * sab - sa * sb) / det).float(), ((sbb * sa - sb * sab) / det).float()
+    del bd, dvd
+    coef = torch.stack([cA, cB.expand(n, c), cC.expand(n, c), torch.zeros_like(cA)], 2).contiguous()
+    ga = torch.empty_like(araw)
+    a_sums = torch.zeros((c, 2), dtype=torch.float64, device=gpu)
+    dw = torch.full((c, 27), 0.25, dtype=torch.float32, device=gpu)
+    ops.dw3d_bwd(dv, braw, coef, araw, ss, wt.view(c, 27), ga, a_sums, dw, stride)
+    torch.cuda.synchronize()
+    name = hip.kernel_name(S.dw_full_struct(case))
+    mx = "_mx" in name
+    fp32 = dtype == torch.float32
+    wd = round_to(wt, dtype) if mx else wt.double()
+    rt, at = tol_gemm(dtype) if mx else tol_store(dtype)
+    sc, sh = ss[:, 0].double().view(1, -1, 1, 1, 1), ss[:, 1].double().view(1, -1, 1, 1, 1)
+    dw_ref = torch.zeros((c, 3, 3, 3), dtype=torch.float64, device=gpu)
+    dw_abs = torch.zeros_like(dw_ref)
+    s1 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    s2 = torch.zeros(c, dtype=torch.float64, device=gpu)
+    worst, CH = 0.0, _dw_chunk(case)
+    for i in range(0, n, CH):
+        cd = coef[i:i + CH].double()
+        terms = [cd[:, :, j, None, None, None] * v for j, v in ((0, dv[i:i + CH].double()), (1, braw[i:i + CH].double()))]
+        dB = terms[0] + terms[1] + cd[:, :, 2, None, None, None]
+        ad = araw[i:i + CH].double()
+        z = ad * sc + sh
+        act = torch.relu(z)
+        if fp32:        # sum |terms| of dW, with |dB| bounded by |A dv| + |B b| + |C|
+            mag = terms[0].abs() + terms[1].abs() + cd[:, :, 2, None, None, None].abs()
+            dw_abs += dw_stencil64(act, wd.abs(), stride, dy=mag)[1]
+            del mag
+        del terms
+        if mx:
+            dB, act = round_to(dB, dtype), round_to(act, dtype)
+        dA, dwc = dw_stencil64(act, wd, stride, dy=dB)
+        dw_ref += dwc
+        del dB, act
+        ref = dA * (z > 0)
+        del dA, z
+        worst = max(worst, _frac(f"ga[{i}:{i + CH}]", ga[i:i + CH], ref, rt, at * ref.abs().max().item()))
+        del ref
+        gs = ga[i:i + CH].double()
+        s1 += gs.sum((0, 2, 3, 4))
+        s2 += (gs * ad).sum((0, 2, 3, 4))
+        del gs, ad
+    stol = _stol(dtype)
+    sref = torch.stack([s1, s2], 1)
+    e_s = _frac("a_sums", a_sums, sref, 10 * stol, 10 * stol * max(1.0, sref.abs().max().item()))
+    got = dw.double().view(c, 3, 3, 3) - 0.25
+    if fp32:
+        L = _dw_fp32_chain(name, n, t, h, w, stride)
+        lim = 6.0 * math.sqrt(L) * 2.0 ** -24 * dw_abs + 2 * 2.0 ** -24 * 0.25
+        e_w, _ = _check_slack("dw", got, dw_ref, 0.0, 0.0, lim)
+        wmsg = f"dW {e_w:.2e} (L {L}, limit {(lim / dw_ref.abs().max()).max().item():.1e} of max)"
+    else:
+        wtol = _wtol(dtype) if mx else 2e-5
+        e_w = _frac("dw", got, dw_ref, wtol, wtol * dw_ref.abs().max().item())
+        wmsg = f"dW {e_w:.2e} (limit {wtol:.0e} of max)"
+    return name, f"ga {worst:.2e}, a_sums {e_s:.2e}, {wmsg}"
+
+
+@pytest.mark.parametrize("case", S.DW_FULL, ids=[S.dw_full_id(c) for c in S.DW_FULL])
+def test_depthwise_full_size(gpu, case):
+    """One depthwise launch of a full-size plan (tests/shapes.py DW_FULL; tests/test_dispatch_coverage.py keeps the list
+    complete), in its launch form, against the fp64 stencil (tests.util.dw_stencil64) on the GPU, sample chunk by sample
+    chunk: _dw_forward_case / _dw_backward_case.  Prints the kernel and each check's worst error as a fraction of its limit."""
+    import time
+    t0 = time.time()
+    seed = 1000 + S.DW_FULL.index(case)
+    name, msg = (_dw_forward_case if case[0] == "fwd" else _dw_backward_case)(gpu, case, seed)
+    torch.cuda.synchronize()
+    print(f"full-size depthwise {S.dw_full_id(case)} {name}: worst err / limit {msg}; {time.time() - t0:.1f} s")

@@ -49,6 +49,27 @@ def test_depthwise_against_naive_numpy(h, w, stride):
     assert got.shape == ref.shape and np.allclose(got, ref, atol=1e-12)
 
 
+@pytest.mark.parametrize("t,h,w,stride", [(4, 8, 8, 1), (4, 8, 8, 2), (3, 7, 7, 1), (3, 9, 9, 2), (2, 7, 9, 2), (3, 6, 11, 1),
+                                         (1, 10, 10, 1), (1, 13, 12, 2), (2, 12, 10, 2), (2, 39, 5, 2)])
+def test_dw_stencil64_matches_the_oracle(t, h, w, stride):
+    """tests.util.dw_stencil64 (the fp64 reference of the full-size depthwise tests, which runs on the GPU) against the oracle's
+    depthwise3x3x3 and its autograd gradients: even, odd, non-square extents, T = 1, TF-SAME pads 0/1 (even at stride 2) and
+    1/1 (odd)."""
+    from tests.util import dw_same_pads, dw_stencil64
+    assert dw_same_pads(156, 2) == (78, 0, 1) and dw_same_pads(39, 2) == (20, 1, 1) and dw_same_pads(56, 1) == (56, 1, 1)
+    g = torch.Generator().manual_seed(7)
+    a = torch.randn(2, 3, t, h, w, generator=g, dtype=torch.float64, requires_grad=True)
+    wt = torch.randn(3, 3, 3, 3, generator=g, dtype=torch.float64, requires_grad=True)
+    ref = O.depthwise3x3x3(a, wt, stride)
+    got = dw_stencil64(a.detach(), wt.detach(), stride)
+    assert got.shape == ref.shape and torch.allclose(got, ref.detach(), rtol=0, atol=1e-12)
+    dy = torch.randn(ref.shape, generator=g, dtype=torch.float64)
+    da_ref, dw_ref = torch.autograd.grad((ref * dy).sum(), [a, wt])
+    da, dw = dw_stencil64(a.detach(), wt.detach(), stride, dy=dy)
+    assert da.shape == da_ref.shape and torch.allclose(da, da_ref, rtol=0, atol=1e-12)
+    assert torch.allclose(dw, dw_ref, rtol=0, atol=1e-11)
+
+
 def test_pointwise_bn_stem_against_numpy():
     g = torch.Generator().manual_seed(1)
     xt = torch.randn(2, 5, 3, 6, 7, generator=g, dtype=torch.float64)

@@ -56,6 +56,40 @@ def tie_slack_t(v, dtype, w_abs, eps_ulps=2e-4):
     return out
 
 
+def dw_same_pads(n, stride):
+    """(output extent, pad before, pad after) of a 3-tap TF-SAME window along an extent of n at `stride` (156 -> 78: 0 / 1,
+    39 -> 20: 1 / 1, 56 -> 56: 1 / 1)."""
+    out = -(-n // stride)
+    tot = max((out - 1) * stride + 3 - n, 0)
+    return out, tot // 2, tot - tot // 2
+
+
+def dw_stencil64(a, w, stride, dy=None):
+    """The channelwise 3x3x3 convolution (strides (1, s, s), TF-SAME padding: oracle.x3d_oracle.depthwise3x3x3) as 27
+    shifted-slice products in the dtype and on the device of `a` [N, C, T, H, W]; w [C, 3, 3, 3].  Without `dy`: the output
+    [N, C, T, Ho, Wo].  With `dy` (an output gradient): (dA, dW), the gradients with respect to `a` and `w`.  Test side only:
+    the full-size tests run it in fp64 on the GPU, sample chunk by sample chunk."""
+    n, c, t, h, wd = a.shape
+    ho, hb, ha = dw_same_pads(h, stride)
+    wo, wb, wa = dw_same_pads(wd, stride)
+    ap = torch.nn.functional.pad(a, (wb, wa, hb, ha, 1, 1))
+    wv = lambda k: w[:, k[0], k[1], k[2]].view(1, -1, 1, 1, 1)
+    sl = lambda kt, kh, kw: (slice(None), slice(None), slice(kt, kt + t), slice(kh, kh + stride * (ho - 1) + 1, stride),
+                             slice(kw, kw + stride * (wo - 1) + 1, stride))
+    taps = [(kt, kh, kw) for kt in range(3) for kh in range(3) for kw in range(3)]
+    if dy is None:
+        out = torch.zeros((n, c, t, ho, wo), dtype=a.dtype, device=a.device)
+        for k in taps:
+            out += wv(k) * ap[sl(*k)]
+        return out
+    dap = torch.zeros_like(ap)
+    dw = torch.zeros((c, 3, 3, 3), dtype=a.dtype, device=a.device)
+    for k in taps:
+        dap[sl(*k)] += wv(k) * dy
+        dw[:, k[0], k[1], k[2]] = (dy * ap[sl(*k)]).sum((0, 2, 3, 4))
+    return dap[:, :, 1:1 + t, hb:hb + h, wb:wb + wd], dw
+
+
 def relu_mask_mismatch(masks, oracle_taps_masks):
     """Fraction of ReLU sites whose sign differs between the device (hip_relu_masks) and a free-running oracle forward."""
     bad = tot = 0
