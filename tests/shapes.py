@@ -262,6 +262,287 @@ def dw_full_id(case):
     return f"{e}-{str(dt)[6:]}-N{n}-C{c}-T{t}-{h}x{w}-s{s}{form}"
 
 
+# ---- every pointwise launch (x3d_pw_fwd / _dgrad / _wgrad / _bwd) of the same full-size plans, for the fp64 checks of
+# tests/test_full_size_gpu.py; tests/test_dispatch_coverage.py keeps it complete and free of stale entries.  Keyed by shape
+# and launch form, read from the argument struct, not by kernel.
+#   entry, dtype, N, Cin, Cout, T, H, W, stride, epi, in_act, out_act, form
+# H, W: the input extents of fwd / wgrad and of a bwd launch with x_stride = 2 (the strided recomputed-output shortcut),
+# else the output points.  stride: fwd / wgrad stride, bwd x_stride (0 dense, 2 strided), None for dgrad.  epi: X3D_EPI_* of
+# dgrad / bwd.  in_act: fwd / wgrad prologue activation; out_act: fwd.  form, in PW_FLAGS order:
+#   fwd: stats; prologue ss (in_scale_shift) / gate (in_gate); tail fold add (in_add) / add_ss / store (in_store); inference
+#        epilogue oss (out_scale_shift) / oadd (out_add) / oadd_ss (out_add_scale_shift)
+#   dgrad / bwd: gate (SE gate of EPI_SWISH_BWD); tail_c / tail_r (folded residual-tail backward); rc (rc_panel: recomputed
+#        conv output); slab (dw_slab); fold (coef_fold); pub (the fold publishes dgamma / dbeta / coef_out)
+#   wgrad: ss / gate (prologue replayed); slab; fold
+# A case with gate or pub stands for the launch of its shape without them only where the coverage test finds that both
+# dispatch the same kernel instantiation (never the reverse).  16-bit fwd / dgrad / bwd launches pass the weight panel, as
+# the plans do (rc launches need none).
+PW_FLAGS = ("stats", "ss", "gate", "add", "add_ss", "store", "oss", "oadd", "oadd_ss", "tail_c", "tail_r", "rc", "slab", "fold",
+            "pub")
+PW_FULL = [
+    # config 2: X3D-S, fp32
+    ('fwd', F32, 32, 24, 54, 13, 80, 80, 1, None, 1, 0, ('stats', 'ss', 'store')),
+    ('fwd', F32, 32, 54, 24, 13, 40, 40, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F32, 32, 24, 24, 13, 80, 80, 2, None, 0, 0, ('stats',)),
+    ('fwd', F32, 32, 24, 54, 13, 40, 40, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F32, 32, 24, 54, 13, 40, 40, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 24, 108, 13, 40, 40, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 108, 48, 13, 20, 20, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F32, 32, 24, 48, 13, 40, 40, 2, None, 0, 0, ('stats',)),
+    ('fwd', F32, 32, 48, 108, 13, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F32, 32, 48, 108, 13, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 48, 216, 13, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 216, 96, 13, 10, 10, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F32, 32, 48, 96, 13, 20, 20, 2, None, 0, 0, ('stats',)),
+    ('fwd', F32, 32, 96, 216, 13, 10, 10, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F32, 32, 96, 216, 13, 10, 10, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 96, 432, 13, 10, 10, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F32, 32, 432, 192, 13, 5, 5, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F32, 32, 96, 192, 13, 5, 5, 1, None, 0, 0, ('stats',)),
+    ('fwd', F32, 32, 192, 432, 13, 5, 5, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F32, 32, 192, 432, 13, 5, 5, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('wgrad', F32, 32, 192, 432, 13, 5, 5, 1, None, 0, None, ('fold',)),
+    ('dgrad', F32, 32, 192, 432, 13, 5, 5, None, 0, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 432, 192, 13, 5, 5, 1, None, 2, None, ('ss', 'gate', 'slab', 'fold')),
+    ('dgrad', F32, 32, 432, 192, 13, 5, 5, None, 3, None, None, ('gate', 'fold', 'pub')),
+    ('wgrad', F32, 32, 192, 432, 13, 5, 5, 1, None, 0, None, ('slab', 'fold')),
+    ('dgrad', F32, 32, 192, 432, 13, 5, 5, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 96, 192, 13, 5, 5, 1, None, 0, None, ('fold',)),
+    ('dgrad', F32, 32, 96, 192, 13, 5, 5, None, 0, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 96, 432, 13, 10, 10, 1, None, 0, None, ()),
+    ('dgrad', F32, 32, 96, 432, 13, 10, 10, None, 2, None, None, ()),
+    ('wgrad', F32, 32, 216, 96, 13, 10, 10, 1, None, 2, None, ('ss', 'gate', 'slab', 'fold')),
+    ('dgrad', F32, 32, 216, 96, 13, 10, 10, None, 3, None, None, ('gate', 'fold', 'pub')),
+    ('wgrad', F32, 32, 96, 216, 13, 10, 10, 1, None, 0, None, ('slab', 'fold')),
+    ('dgrad', F32, 32, 96, 216, 13, 10, 10, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 48, 96, 13, 20, 20, 2, None, 0, None, ()),
+    ('dgrad', F32, 32, 48, 96, 13, 10, 10, None, 0, None, None, ()),
+    ('wgrad', F32, 32, 48, 216, 13, 20, 20, 1, None, 0, None, ()),
+    ('dgrad', F32, 32, 48, 216, 13, 20, 20, None, 2, None, None, ()),
+    ('wgrad', F32, 32, 108, 48, 13, 20, 20, 1, None, 2, None, ('ss', 'gate', 'fold')),
+    ('dgrad', F32, 32, 108, 48, 13, 20, 20, None, 3, None, None, ('gate', 'fold', 'pub')),
+    ('wgrad', F32, 32, 48, 108, 13, 20, 20, 1, None, 0, None, ('fold',)),
+    ('dgrad', F32, 32, 48, 108, 13, 20, 20, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 24, 48, 13, 40, 40, 2, None, 0, None, ()),
+    ('dgrad', F32, 32, 24, 48, 13, 20, 20, None, 0, None, None, ()),
+    ('wgrad', F32, 32, 24, 108, 13, 40, 40, 1, None, 0, None, ()),
+    ('dgrad', F32, 32, 24, 108, 13, 40, 40, None, 2, None, None, ()),
+    ('wgrad', F32, 32, 54, 24, 13, 40, 40, 1, None, 2, None, ('ss', 'gate', 'fold')),
+    ('dgrad', F32, 32, 54, 24, 13, 40, 40, None, 3, None, None, ('gate', 'fold', 'pub')),
+    ('wgrad', F32, 32, 24, 54, 13, 40, 40, 1, None, 0, None, ('fold',)),
+    ('dgrad', F32, 32, 24, 54, 13, 40, 40, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', F32, 32, 24, 24, 13, 80, 80, 2, None, 0, None, ()),
+    ('dgrad', F32, 32, 24, 24, 13, 40, 40, None, 0, None, None, ()),
+    ('wgrad', F32, 32, 24, 54, 13, 80, 80, 1, None, 0, None, ()),
+    ('dgrad', F32, 32, 24, 54, 13, 80, 80, None, 2, None, None, ()),
+    # config 3: X3D-M (bench.py's workload)
+    ('fwd', BF16, 64, 24, 54, 16, 112, 112, 1, None, 1, 0, ('stats', 'ss', 'store')),
+    ('fwd', BF16, 64, 54, 24, 16, 56, 56, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 64, 24, 24, 16, 112, 112, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 64, 24, 54, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 64, 24, 54, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 24, 108, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 108, 48, 16, 28, 28, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 64, 24, 48, 16, 56, 56, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 64, 48, 108, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 64, 48, 108, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 48, 216, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 216, 96, 16, 14, 14, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 64, 48, 96, 16, 28, 28, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 64, 96, 216, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 64, 96, 216, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 96, 432, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 64, 432, 192, 16, 7, 7, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 64, 96, 192, 16, 7, 7, 1, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 64, 192, 432, 16, 7, 7, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 64, 192, 432, 16, 7, 7, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('wgrad', BF16, 64, 192, 432, 16, 7, 7, 1, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 64, 192, 432, 16, 7, 7, None, 0, None, None, ('fold', 'pub')),
+    ('bwd', BF16, 64, 432, 192, 16, 7, 7, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('wgrad', BF16, 64, 192, 432, 16, 7, 7, 1, None, 0, None, ('slab', 'fold')),
+    ('dgrad', BF16, 64, 192, 432, 16, 7, 7, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', BF16, 64, 96, 192, 16, 7, 7, 1, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 64, 96, 192, 16, 7, 7, None, 0, None, None, ('fold', 'pub')),
+    ('wgrad', BF16, 64, 96, 432, 16, 14, 14, 1, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 64, 96, 432, 16, 14, 14, None, 2, None, None, ('fold', 'pub')),
+    ('bwd', BF16, 64, 216, 96, 16, 14, 14, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('bwd', BF16, 64, 96, 216, 16, 14, 14, 0, 1, None, None, ('tail_c', 'slab', 'fold', 'pub')),
+    ('bwd', BF16, 64, 96, 216, 16, 14, 14, 0, 1, None, None, ('slab', 'fold', 'pub')),
+    ('bwd', BF16, 64, 48, 96, 16, 28, 28, 2, 0, None, None, ('rc',)),
+    ('bwd', BF16, 64, 48, 216, 16, 28, 28, 0, 2, None, None, ('rc',)),
+    ('bwd', BF16, 64, 108, 48, 16, 28, 28, 0, 3, None, None, ('gate',)),
+    ('bwd', BF16, 64, 48, 108, 16, 28, 28, 0, 1, None, None, ('rc',)),
+    ('bwd', BF16, 64, 24, 48, 16, 56, 56, 2, 0, None, None, ('rc',)),
+    ('bwd', BF16, 64, 24, 108, 16, 56, 56, 0, 2, None, None, ('tail_c', 'rc')),
+    ('bwd', BF16, 64, 54, 24, 16, 56, 56, 0, 3, None, None, ('gate',)),
+    ('bwd', BF16, 64, 24, 54, 16, 56, 56, 0, 1, None, None, ('tail_c', 'rc')),
+    ('bwd', BF16, 64, 24, 54, 16, 56, 56, 0, 1, None, None, ('tail_c', 'tail_r', 'rc')),
+    ('bwd', BF16, 64, 24, 24, 16, 112, 112, 2, 0, None, None, ('rc',)),
+    ('bwd', BF16, 64, 24, 54, 16, 112, 112, 0, 2, None, None, ('tail_c', 'rc')),
+    # config 3 with fp16 storage
+    ('fwd', F16, 64, 24, 54, 16, 112, 112, 1, None, 1, 0, ('stats', 'ss', 'store')),
+    ('fwd', F16, 64, 54, 24, 16, 56, 56, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F16, 64, 24, 24, 16, 112, 112, 2, None, 0, 0, ('stats',)),
+    ('fwd', F16, 64, 24, 54, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F16, 64, 24, 54, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 24, 108, 16, 56, 56, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 108, 48, 16, 28, 28, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F16, 64, 24, 48, 16, 56, 56, 2, None, 0, 0, ('stats',)),
+    ('fwd', F16, 64, 48, 108, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F16, 64, 48, 108, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 48, 216, 16, 28, 28, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 216, 96, 16, 14, 14, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F16, 64, 48, 96, 16, 28, 28, 2, None, 0, 0, ('stats',)),
+    ('fwd', F16, 64, 96, 216, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F16, 64, 96, 216, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 96, 432, 16, 14, 14, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', F16, 64, 432, 192, 16, 7, 7, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', F16, 64, 96, 192, 16, 7, 7, 1, None, 0, 0, ('stats',)),
+    ('fwd', F16, 64, 192, 432, 16, 7, 7, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', F16, 64, 192, 432, 16, 7, 7, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('wgrad', F16, 64, 192, 432, 16, 7, 7, 1, None, 0, None, ('fold',)),
+    ('dgrad', F16, 64, 192, 432, 16, 7, 7, None, 0, None, None, ('fold', 'pub')),
+    ('bwd', F16, 64, 432, 192, 16, 7, 7, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('wgrad', F16, 64, 192, 432, 16, 7, 7, 1, None, 0, None, ('slab', 'fold')),
+    ('dgrad', F16, 64, 192, 432, 16, 7, 7, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', F16, 64, 96, 192, 16, 7, 7, 1, None, 0, None, ('fold',)),
+    ('dgrad', F16, 64, 96, 192, 16, 7, 7, None, 0, None, None, ('fold', 'pub')),
+    ('wgrad', F16, 64, 96, 432, 16, 14, 14, 1, None, 0, None, ('fold',)),
+    ('dgrad', F16, 64, 96, 432, 16, 14, 14, None, 2, None, None, ('fold', 'pub')),
+    ('bwd', F16, 64, 216, 96, 16, 14, 14, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('bwd', F16, 64, 96, 216, 16, 14, 14, 0, 1, None, None, ('tail_c', 'slab', 'fold', 'pub')),
+    ('bwd', F16, 64, 96, 216, 16, 14, 14, 0, 1, None, None, ('slab', 'fold', 'pub')),
+    ('bwd', F16, 64, 48, 96, 16, 28, 28, 2, 0, None, None, ('rc',)),
+    ('bwd', F16, 64, 48, 216, 16, 28, 28, 0, 2, None, None, ('rc',)),
+    ('bwd', F16, 64, 108, 48, 16, 28, 28, 0, 3, None, None, ('gate',)),
+    ('bwd', F16, 64, 48, 108, 16, 28, 28, 0, 1, None, None, ('rc',)),
+    ('bwd', F16, 64, 24, 48, 16, 56, 56, 2, 0, None, None, ('rc',)),
+    ('bwd', F16, 64, 24, 108, 16, 56, 56, 0, 2, None, None, ('tail_c', 'rc')),
+    ('bwd', F16, 64, 54, 24, 16, 56, 56, 0, 3, None, None, ('gate',)),
+    ('bwd', F16, 64, 24, 54, 16, 56, 56, 0, 1, None, None, ('tail_c', 'rc')),
+    ('bwd', F16, 64, 24, 54, 16, 56, 56, 0, 1, None, None, ('tail_c', 'tail_r', 'rc')),
+    ('bwd', F16, 64, 24, 24, 16, 112, 112, 2, 0, None, None, ('rc',)),
+    ('bwd', F16, 64, 24, 54, 16, 112, 112, 0, 2, None, None, ('tail_c', 'rc')),
+    # config 4: X3D-L
+    ('fwd', BF16, 16, 24, 54, 16, 156, 156, 1, None, 1, 0, ('stats', 'ss', 'store')),
+    ('fwd', BF16, 16, 54, 24, 16, 78, 78, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 16, 24, 24, 16, 156, 156, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 16, 24, 54, 16, 78, 78, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 16, 24, 54, 16, 78, 78, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 24, 108, 16, 78, 78, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 108, 48, 16, 39, 39, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 16, 24, 48, 16, 39, 39, 1, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 16, 48, 108, 16, 39, 39, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 16, 48, 108, 16, 39, 39, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 48, 216, 16, 39, 39, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 216, 96, 16, 20, 20, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 16, 48, 96, 16, 39, 39, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 16, 96, 216, 16, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 16, 96, 216, 16, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 96, 432, 16, 20, 20, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('fwd', BF16, 16, 432, 192, 16, 10, 10, 1, None, 2, 0, ('stats', 'ss', 'gate')),
+    ('fwd', BF16, 16, 96, 192, 16, 20, 20, 2, None, 0, 0, ('stats',)),
+    ('fwd', BF16, 16, 192, 432, 16, 10, 10, 1, None, 1, 0, ('stats', 'ss', 'add', 'add_ss', 'store')),
+    ('fwd', BF16, 16, 192, 432, 16, 10, 10, 1, None, 1, 0, ('stats', 'ss', 'add', 'store')),
+    ('wgrad', BF16, 16, 192, 432, 16, 10, 10, 1, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 16, 192, 432, 16, 10, 10, None, 0, None, None, ('fold', 'pub')),
+    ('bwd', BF16, 16, 432, 192, 16, 10, 10, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('wgrad', BF16, 16, 192, 432, 16, 10, 10, 1, None, 0, None, ('slab', 'fold')),
+    ('dgrad', BF16, 16, 192, 432, 16, 10, 10, None, 1, None, None, ('fold', 'pub')),
+    ('wgrad', BF16, 16, 96, 192, 16, 20, 20, 2, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 16, 96, 192, 16, 10, 10, None, 0, None, None, ('fold', 'pub')),
+    ('wgrad', BF16, 16, 96, 432, 16, 20, 20, 1, None, 0, None, ('fold',)),
+    ('dgrad', BF16, 16, 96, 432, 16, 20, 20, None, 2, None, None, ('fold', 'pub')),
+    ('bwd', BF16, 16, 216, 96, 16, 20, 20, 0, 3, None, None, ('gate', 'slab', 'fold', 'pub')),
+    ('bwd', BF16, 16, 96, 216, 16, 20, 20, 0, 1, None, None, ('tail_c', 'slab', 'fold', 'pub')),
+    ('bwd', BF16, 16, 96, 216, 16, 20, 20, 0, 1, None, None, ('slab', 'fold', 'pub')),
+    ('bwd', BF16, 16, 48, 96, 16, 39, 39, 2, 0, None, None, ('rc',)),
+    ('bwd', BF16, 16, 48, 216, 16, 39, 39, 0, 2, None, None, ('rc',)),
+    ('bwd', BF16, 16, 108, 48, 16, 39, 39, 0, 3, None, None, ('gate',)),
+    ('bwd', BF16, 16, 48, 108, 16, 39, 39, 0, 1, None, None, ('rc',)),
+    ('bwd', BF16, 16, 24, 48, 16, 39, 39, 0, 0, None, None, ('rc',)),
+    ('bwd', BF16, 16, 24, 108, 16, 78, 78, 0, 2, None, None, ('tail_c', 'rc')),
+    ('bwd', BF16, 16, 54, 24, 16, 78, 78, 0, 3, None, None, ('gate',)),
+    ('bwd', BF16, 16, 24, 54, 16, 78, 78, 0, 1, None, None, ('tail_c', 'rc')),
+    ('bwd', BF16, 16, 24, 54, 16, 78, 78, 0, 1, None, None, ('tail_c', 'tail_r', 'rc')),
+    ('bwd', BF16, 16, 24, 24, 16, 156, 156, 2, 0, None, None, ('rc',)),
+    ('bwd', BF16, 16, 24, 54, 16, 156, 156, 0, 2, None, None, ('tail_c', 'rc')),
+    # config 5: X3D-XL inference, 30 views
+    ('fwd', F16, 30, 32, 72, 16, 156, 156, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 32, 32, 16, 156, 156, 2, None, 0, 0, ()),
+    ('fwd', F16, 30, 72, 32, 16, 78, 78, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd', 'oadd_ss')),
+    ('fwd', F16, 30, 32, 72, 16, 78, 78, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 72, 32, 16, 78, 78, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd')),
+    ('fwd', F16, 30, 32, 162, 16, 78, 78, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 32, 72, 16, 39, 39, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 162, 72, 16, 39, 39, 1, None, 2, 1, ('ss', 'oss', 'oadd', 'oadd_ss')),
+    ('fwd', F16, 30, 72, 162, 16, 39, 39, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 162, 72, 16, 39, 39, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd')),
+    ('fwd', F16, 30, 72, 306, 16, 39, 39, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 72, 136, 16, 39, 39, 2, None, 0, 0, ()),
+    ('fwd', F16, 30, 306, 136, 16, 20, 20, 1, None, 2, 1, ('ss', 'oss', 'oadd', 'oadd_ss')),
+    ('fwd', F16, 30, 136, 306, 16, 20, 20, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 306, 136, 16, 20, 20, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd')),
+    ('fwd', F16, 30, 136, 630, 16, 20, 20, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 136, 280, 16, 20, 20, 2, None, 0, 0, ()),
+    ('fwd', F16, 30, 630, 280, 16, 10, 10, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd', 'oadd_ss')),
+    ('fwd', F16, 30, 280, 630, 16, 10, 10, 1, None, 0, 0, ()),
+    ('fwd', F16, 30, 630, 280, 16, 10, 10, 1, None, 2, 1, ('ss', 'gate', 'oss', 'oadd')),
+]
+
+
+def pw_full_id(case):
+    e, dt, n, ci, co, t, h, w, s, epi, ia, oa, form = case
+    mode = ("" if s is None else f"-s{s}") + ("" if epi is None else f"-e{epi}") + ("" if ia is None else f"-a{ia}") + \
+        (f"-o{oa}" if oa else "")
+    return f"{e}-{str(dt)[6:]}-N{n}-{ci}to{co}-T{t}-{h}x{w}{mode}" + "".join(f"-{f}" for f in form)
+
+
+def pw_full_struct(case):
+    """The argument struct of a PW_FULL case over address-only operands, in the case's launch form (a fold is a real
+    hip.BnBwdFold the struct refers to by address; slabs are sized by the library's own dw_parts query)."""
+    import ctypes as C
+    from x3d_tf_amd import hip
+    e, dtype, n, ci, co, t, h, w, s, epi, ia, oa, form = case
+    A = _Addr.new
+    f = set(form)
+    opt = lambda k: A() if k in f else None
+    panel = A() if dtype != F32 else None
+    code = _code(dtype)
+    if e == "fwd":
+        return hip.PwFwdArgs(A(), A(), A(), opt("stats"), opt("ss"), opt("gate"), ia, n, ci, co, t, h, w, s, code, panel,
+                             in_add=opt("add"), in_add_scale_shift=opt("add_ss"), in_store=opt("store"),
+                             out_scale_shift=opt("oss"), out_add=opt("oadd"), out_add_scale_shift=opt("oadd_ss"), out_act=oa)
+    if e == "dgrad":
+        sw = epi == 3
+        a = hip.PwDgradArgs(A(), A(), A(), A(), A(), epi, A() if epi in (1, 2) else None, A() if sw else None,
+                            A() if sw else None, opt("gate"), A() if sw else None, n, ci, co, t, h, w, code, panel)
+        query = None
+    elif e == "wgrad":
+        a = hip.PwWgradArgs(A(), A(), A(), A(), opt("ss"), opt("gate"), ia, A(), n, ci, co, t, h, w, s, code)
+        query = hip.load().x3d_pw_wgrad_dw_parts
+    elif "rc" in f:
+        ho, wo = (-(-h // 2), -(-w // 2)) if s == 2 else (h, w)
+        a = hip.PwBwdArgs(A(), None, None, None, A(), epi, A() if epi in (1, 2) else None, None, None, None, None, A(), None, n,
+                          ci, co, t, ho, wo, code, opt("tail_c"), opt("tail_r"), opt("tail_c"), opt("tail_r"), A(), A(), A(),
+                          s, h, w)
+        query = None
+    else:
+        sw = epi == 3
+        a = hip.PwBwdArgs(A(), A(), A(), panel, A(), epi, None if sw else A(), A() if sw else None, A() if sw else None,
+                          opt("gate"), A() if sw else None, None if sw else A(), A(), n, ci, co, t, h, w, code, opt("tail_c"),
+                          opt("tail_r"), opt("tail_c"), opt("tail_r"))
+        query = hip.load().x3d_pw_bwd_dw_parts
+    if "fold" in f:
+        a._fold = hip.BnBwdFold(A(), 1.0, A(), A(), A() if "pub" in f else None, A() if "pub" in f else None,
+                                A() if "pub" in f else None)
+        a.coef_fold = hip.fold_address(a._fold)
+    if "slab" in f:
+        a.dw_slab_parts = int(query(C.byref(a)))
+        a.dw_slab = A()
+    return a
+
+
 # ---- whole-model cases (tests/test_model_gpu.py): variant, N, T, S --------------------------------------------------------
 MODEL_TRAIN_FP32 = [
     ("XS", 4, 4, 64), ("S", 2, 13, 64), ("M", 2, 4, 64), ("S", 3, 5, 96),

@@ -227,3 +227,116 @@ def test_every_dw_full_case_is_a_launch_of_a_full_size_plan():
     keys = {_dw_launch_key(e, st)[:9] for plan in DW_FULL_PLANS.values() for e, _, st in _dw_launches(plan)}
     stale = [S.dw_full_id(c) for c in S.DW_FULL if c[:9] not in keys]
     assert not stale, "DW_FULL cases that no full-size plan launches: " + ", ".join(stale)
+
+
+# ---- the pointwise launches of the same plans (shapes.PW_FULL; tests/test_full_size_gpu.py: test_pointwise_full_size) ----
+PW_FULL_PLANS = DW_FULL_PLANS
+_PW_ENTRIES = {"x3d_pw_fwd": "fwd", "x3d_pw_dgrad": "dgrad", "x3d_pw_wgrad": "wgrad", "x3d_pw_bwd": "bwd"}
+
+
+def _pw_launches(plan):
+    """(entry, kernel instantiation, argument struct) of every pointwise launch of a full-size dry plan."""
+    from x3d_tf_amd import hip
+    from x3d_tf_amd.config import get_config
+    from x3d_tf_amd.dispatch import BASELINE_CONFIGS
+    from x3d_tf_amd.model import X3D
+    variant, n, t, s, dtype, training, over = BASELINE_CONFIGS[plan] if isinstance(plan, int) else plan + ({},)
+    flat = [x for kv in over.items() for x in kv]
+    m = X3D(get_config(variant, flat or None), dtype=dtype, device="dry")
+    pl = m._plan(n, t, s, s, training)
+    out = []
+    for lst in (pl.fwd, pl.bwd):
+        for i, item in enumerate(lst):
+            if item is not None and item[0] in _PW_ENTRIES:
+                st = pl.structs[(id(lst), i)]
+                out.append((item[0], hip.kernel_name(st), st, _pw_launch_key(item[0], st)))   # (while the plan holds its folds)
+    m.release_plans()
+    return out
+
+
+def _pw_launch_key(entry, st):
+    """shapes.PW_FULL's key of a recorded pointwise launch (shapes.py documents the fields)."""
+    from x3d_tf_amd import hip
+    e = _PW_ENTRIES[entry]
+    dtype = [d for d in S.DTYPES if hip.dtype_code(d) == st.dtype][0]
+    v = lambda k: bool(getattr(st, k, None))
+    if e == "fwd":
+        flags = dict(stats=v("stats"), ss=v("in_scale_shift"), gate=v("in_gate"), add=v("in_add"), add_ss=v("in_add_scale_shift"),
+                     store=v("in_store"), oss=v("out_scale_shift"), oadd=v("out_add"), oadd_ss=v("out_add_scale_shift"))
+        mode = (st.stride, None, st.in_act, st.out_act)
+    elif e == "wgrad":
+        flags = dict(ss=v("in_scale_shift"), gate=v("in_gate"), slab=v("dw_slab"), fold=v("coef_fold"))
+        mode = (st.stride, None, st.in_act, None)
+    else:
+        fold = hip.FOLDS.get(st.coef_fold) if st.coef_fold else None
+        assert not st.coef_fold or fold is not None, "a coef_fold address that hip.FOLDS does not know"
+        flags = dict(gate=v("gate"), tail_c=v("tail_c"), tail_r=v("tail_r"), rc=v("rc_panel"), slab=v("dw_slab"),
+                     fold=fold is not None, pub=fold is not None and bool(fold.dgamma))
+        mode = (st.x_stride if e == "bwd" else None, st.epi, None, None)
+    h, w = (st.xH, st.xW) if e == "bwd" and st.x_stride == 2 else (st.H, st.W)
+    return (e, dtype, st.N, st.Cin, st.Cout, st.T, h, w) + mode + (tuple(f for f in S.PW_FLAGS if flags.get(f)),)
+
+
+def _pw_alts(key):
+    """The PW_FULL keys that may stand for a launch of this key: itself, and the same shape and form with the SE gate and / or
+    the fold's publishing added (the coverage test then requires that they dispatch the same kernel)."""
+    form = set(key[12])
+    extra = [set()] + [{"gate"}] + ([{"pub"}, {"gate", "pub"}] if "fold" in form else [])
+    out = []
+    for x in extra:
+        alt = key[:12] + (tuple(f for f in S.PW_FLAGS if f in form | x),)
+        if alt not in out:
+            out.append(alt)
+    return out
+
+
+@pytest.fixture(scope="module")
+def pw_plan_launches():
+    return {plan: _pw_launches(p) for plan, p in PW_FULL_PLANS.items()}
+
+
+def _pw_full_cover(launches):
+    """{launch key: message} of the launches without a full-size fp64 case that dispatches the plan's kernel."""
+    from x3d_tf_amd import hip
+    cases = set(S.PW_FULL)
+    missing = {}
+    for entry, kern, st, key in launches:
+        why = "no PW_FULL entry of this shape and form"
+        for a in [a for a in _pw_alts(key) if a in cases]:
+            case_kern = hip.kernel_name(S.pw_full_struct(a))
+            if case_kern == kern:
+                break
+            why = f"the PW_FULL case {S.pw_full_id(a)} runs {case_kern}"
+        else:
+            missing[key] = f"{S.pw_full_id(key)} ({kern}): {why}"
+    return missing
+
+
+@pytest.mark.parametrize("plan", list(PW_FULL_PLANS))
+def test_every_pointwise_launch_of_a_full_size_plan_has_a_full_size_case(pw_plan_launches, plan):
+    """Every x3d_pw_fwd / _dgrad / _wgrad / _bwd launch of the plan has a shapes.PW_FULL case (tests/test_full_size_gpu.py:
+    test_pointwise_full_size) at its real size and in its launch form, which dispatches the same kernel as the plan; and every
+    slab-form launch sizes its slabs as the case's struct does (x3d_pw_bwd_dw_parts / x3d_pw_wgrad_dw_parts)."""
+    import ctypes as C
+    from x3d_tf_amd import hip
+    launches = pw_plan_launches[plan]
+    assert launches, "the dry plan recorded no pointwise launches"
+    missing = _pw_full_cover(launches)
+    assert not missing, (f"plan {plan}: pointwise launches without a full-size fp64 case (tests/shapes.py PW_FULL):\n"
+                         + "\n".join(f"  {v}" for v in sorted(set(missing.values()))))
+    cases = set(S.PW_FULL)
+    for entry, _, st, key in launches:
+        if getattr(st, "dw_slab", None):
+            case = [a for a in _pw_alts(key) if a in cases][0]
+            query = hip.load().x3d_pw_wgrad_dw_parts if entry == "x3d_pw_wgrad" else hip.load().x3d_pw_bwd_dw_parts
+            cs = S.pw_full_struct(case)
+            assert st.dw_slab_parts == cs.dw_slab_parts == query(C.byref(cs)) > 0, S.pw_full_id(key)
+
+
+def test_every_pw_full_case_is_a_launch_of_a_full_size_plan(pw_plan_launches):
+    """... and no PW_FULL case is left over: each one is a launch key of a plan, or stands for one by the gate / publishing
+    rule."""
+    keys = {a for ls in pw_plan_launches.values() for _, _, _, key in ls for a in _pw_alts(key)}
+    stale = [S.pw_full_id(c) for c in S.PW_FULL if c not in keys]
+    assert not stale, "PW_FULL cases that no full-size plan launches: " + ", ".join(stale)
+    assert len(set(S.PW_FULL)) == len(S.PW_FULL), "duplicate PW_FULL entries"

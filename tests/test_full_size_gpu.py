@@ -12,6 +12,11 @@ same 12.8 M points, from inputs with the non-zero channel means of a normalised 
 part as in a real step; its BatchNorm sums go through replicated fp64 atomics.  Those cases run here as well, with the
 two-kernel plans (stem.hip) that the fp32 model and X3D-XL training use.
 
+Every depthwise launch (tests/shapes.py DW_FULL) and every pointwise launch (PW_FULL: the `a` / `c` / shortcut convs and conv5,
+x3d_pw_fwd / _dgrad / _wgrad / _bwd, each in its plan's form -- prologue, residual-tail fold, inference epilogue, weight-gradient
+slabs, the folded BatchNorm-backward finalize and its publishing) of BASELINE configs 2 - 5 and config 3 in fp16 run here too,
+at their real grids: tests/test_dispatch_coverage.py keeps both lists complete.
+
 The fp64 side is torch on the GPU (einsum / shifted slices), TEST SIDE ONLY, chunked over samples; it restates the same
 definitions the small cases check against the CPU oracle (test_pw_bwd_rc, test_pw_wgrad, test_dw3d_bwd), with the
 BatchNorm-backward coefficients DERIVED from the data (sum dY = 0 and sum dY * yhat = 0 per channel, as in a real step) instead
@@ -21,7 +26,7 @@ import pytest
 import torch
 
 from tests import shapes as S
-from tests.util import round_to, tie_slack_t, tol_gemm, tol_store
+from tests.util import bn_bwd_coef_sums as _bn_bwd_coef_sums, round_to, tie_slack_t, tol_gemm, tol_store
 
 pytestmark = pytest.mark.gpu
 HALF = [torch.bfloat16, torch.float16]
@@ -36,19 +41,6 @@ def _bn_bwd_coef(g, y, gamma):
     tensors themselves: fp64 statistics, as x3d_bn_finalize / x3d_bn_bwd_finalize produce them."""
     m = y.shape[0] * y.shape[2] * y.shape[3] * y.shape[4]
     return _bn_bwd_coef_sums(m, y.sum((0, 2, 3, 4)), (y * y).sum((0, 2, 3, 4)), g.sum((0, 2, 3, 4)), (g * y).sum((0, 2, 3, 4)), gamma)
-
-
-def _bn_bwd_coef_sums(m, sy, syy, sg, sgy, gamma):
-    """_bn_bwd_coef from the fp64 per-channel sums of y, y^2, g, g y over m points (tensors too large for one expression)."""
-    mean = sy / m
-    var = syy / m - mean * mean
-    invstd = 1.0 / torch.sqrt(var + 1e-5)
-    dbe = sg
-    dga = (sgy - mean * dbe) * invstd
-    k1 = gamma * invstd
-    b = -k1 * invstd * dga / m
-    c = -k1 * dbe / m - b * mean
-    return torch.stack([k1, b, c, torch.zeros_like(c)], 1).float()
 
 
 def _check(name, got, ref, rtol, atol):
@@ -827,3 +819,400 @@ def test_depthwise_full_size(gpu, case):
     name, msg = (_dw_forward_case if case[0] == "fwd" else _dw_backward_case)(gpu, case, seed)
     torch.cuda.synchronize()
     print(f"full-size depthwise {S.dw_full_id(case)} {name}: worst err / limit {msg}; {time.time() - t0:.1f} s")
+
+
+# ---- every pointwise launch of the full-size plans (tests/shapes.py PW_FULL: BASELINE configs 2 - 5, config 3 in fp16 too) ----
+def _pw_chunk(case):
+    """Samples per fp64 chunk: about 48 M elements of the wider side at a time."""
+    n, ci, co, t, h, w = case[2:8]
+    return max(1, min(n, 48_000_000 // (max(ci, co) * t * h * w)))
+
+
+def _pw_act(rn, shape, dtype, kind, gpu):
+    """An activation as a real step has it, sample by sample: "relu" a block output (post-ReLU, positive channel means), "raw"
+    a raw conv / depthwise output (channel means and scales of their own)."""
+    c = shape[1]
+    mu, sd = 0.5 * rn(c), 0.5 + 0.5 * rn(c).abs()
+    if kind == "relu":
+        mu = mu + 0.3
+    out = torch.empty(shape, dtype=dtype, device=gpu)
+    for i in range(shape[0]):
+        v = rn(*shape[1:]) * sd.view(-1, 1, 1, 1) + mu.view(-1, 1, 1, 1)
+        out[i] = (torch.relu(v) if kind == "relu" else v).to(dtype)
+    return out
+
+
+def _pw_ss(rn, c):
+    return torch.stack([1 + 0.3 * rn(c), 0.3 * rn(c)], 1)
+
+
+def _v(t, j=None):
+    return (t if j is None else t[:, j]).double().view(1, -1, 1, 1, 1)
+
+
+def _pw_bn_bwd(rn, g, yraw, ch):
+    """The BatchNorm-backward operands of a real step, from the data: mean / invstd of yraw (fp32, as x3d_bn_finalize keeps
+    them), the fp64 sums (sum g, sum g yraw) and gamma; coef = what x3d_bn_bwd_finalize / a coef_fold derives from them, so
+    sum dY = 0 and sum dY yraw = 0 per channel.  Returns (coef fp32 [C][4], sums, mi, gamma, count)."""
+    from tests.util import bn_bwd_fold64
+    co = g.shape[1]
+    m = g.numel() // co
+    acc = torch.zeros((4, co), dtype=torch.float64, device=g.device)
+    for i in range(0, g.shape[0], ch):
+        yd, gd = yraw[i:i + ch].double(), g[i:i + ch].double()
+        acc += torch.stack([yd.sum((0, 2, 3, 4)), (yd * yd).sum((0, 2, 3, 4)), gd.sum((0, 2, 3, 4)), (gd * yd).sum((0, 2, 3, 4))])
+    mean = acc[0] / m
+    mi = torch.stack([mean, 1.0 / torch.sqrt(acc[1] / m - mean * mean + 1e-5)], 1).float()
+    sums = torch.stack([acc[2], acc[3]], 1).contiguous()
+    gamma = 1 + 0.3 * rn(co)
+    return bn_bwd_fold64(sums, m, mi, gamma)[0].float(), sums, mi, gamma, m
+
+
+def _pw_dy32(coef, gd, yd):
+    """dYraw = A g + B yraw + C evaluated in fp32, as the kernels' coefficient prologue does (before any storage rounding)."""
+    c = coef.float()
+    return c[:, 0].view(1, -1, 1, 1, 1) * gd.float() + c[:, 1].view(1, -1, 1, 1, 1) * yd.float() + c[:, 2].view(1, -1, 1, 1, 1)
+
+
+def _pw_fold(ops, form, sums, m, mi, gamma, gpu):
+    """(coef_fold for the launch or None, its publishing outputs (dgamma, dbeta, coef_out) pre-filled, or None)."""
+    if "fold" not in form:
+        return None, None
+    if "pub" not in form:
+        return ops.bn_bwd_fold(sums, m, mi, gamma), None
+    co = gamma.numel()
+    pub = (torch.full((co,), 0.25, device=gpu), torch.full((co,), -0.5, device=gpu), torch.full((co, 4), 7.0, device=gpu))
+    return ops.bn_bwd_fold(sums, m, mi, gamma, *pub), pub
+
+
+def _pw_check_pub(pub, sums, m, mi, gamma):
+    """A publishing fold added dgamma / dbeta exactly once and wrote the coefficient table: against the fp64 formula from the
+    same operands, to 1e-6 of the magnitudes involved (the fp32 roundings of the value and of the += on the pre-filled
+    accumulator; a second publisher doubles the gradients)."""
+    from tests.util import bn_bwd_fold64
+    if pub is None:
+        return ""
+    cf, dga, dbe = bn_bwd_fold64(sums, m, mi, gamma)
+    e = max(_check_slack("dgamma", pub[0], dga + 0.25, 0.0, 0.0, 1e-6 * (dga.abs() + 0.25))[0],
+            _check_slack("dbeta", pub[1], dbe - 0.5, 0.0, 0.0, 1e-6 * (dbe.abs() + 0.5))[0],
+            _check_slack("coef_out", pub[2], cf, 0.0, 0.0, 1e-6 * cf.abs() + 1e-30)[0])
+    return f", fold publishing {e:.2e}"
+
+
+def _pw_fp32_chain(name, n, ci, co, p, cus):
+    """L of the fp32 weight-gradient kernels of config 2 (the probabilistic summation bound of test_stem_fp32_full_size): a
+    workgroup sums 32 points per step over its run of spb steps (MFMA accumulators, exact fp32 products), then one atomic or
+    slab per (sample, point chunk) of the channel pair; + the roundings of dY = A g + B y + C and of the prologue.
+    pw_wgrad_f32p_kernel / pw_wgrad_f32r_kernel: about two workgroups per CU (pw_wgrad_f32p.h wgrad_f32p_launch);
+    pw_wgrad_kernel: spb = total steps / 1024 in [4, 64] (pw_wgrad.hip pw_wgrad_launch)."""
+    args = [int(a) for a in name[name.index("<") + 1:-1].split(", ") if a.isdigit()]
+    steps = -(-p // 32)
+    if name.startswith(("pw_wgrad_f32p_kernel<", "pw_wgrad_f32r_kernel<")):
+        groups = -(-(-(-co // 32)) // args[0]) * -(-(-(-ci // 32)) // args[1])
+        per_n = max(max((2 * cus) // groups, n) // n, 1)
+        spb = min(max(-(-steps // per_n), 4), steps)
+    elif name.startswith("pw_wgrad_kernel<float"):
+        spb = min(max(min(steps * n // 1024, 64), 4), steps)
+    else:
+        raise AssertionError(f"no fp32 summation bound for {name}")
+    return 32 * spb + -(-steps // spb) * n + 8
+
+
+def _pw_dw_check(name, dtype, dw, fill, ref, absum, case, gpu):
+    """The weight gradient (accumulator pre-filled with `fill`): _wtol of its maximum for 16-bit storage; for fp32 the
+    probabilistic summation bound lambda sqrt(L) u sum |terms| (lambda = 6, L = _pw_fp32_chain), capped at 2e-5 of the
+    maximum.  (Measured on an MI355X: the bound is 2e-4 - 4e-4 of the maximum, the errors at most 6.3e-6 of it.)"""
+    import math
+    got = dw.double() - fill
+    if dtype != torch.float32:
+        tol = _wtol(dtype)
+        return f"dW {_frac('dw', got, ref, tol, tol * ref.abs().max().item()):.2e} (limit {tol:.0e} of max)"
+    e, dt, n, ci, co, t, h, w, s = case[:9]
+    p = t * -(-h // (s or 1)) * -(-w // (s or 1))
+    L = _pw_fp32_chain(name, n, ci, co, p, torch.cuda.get_device_properties(gpu).multi_processor_count)
+    lim = 6.0 * math.sqrt(L) * 2.0 ** -24 * absum + 2 * 2.0 ** -24 * abs(fill)
+    lim = lim.clamp_max(2e-5 * ref.abs().max().item())      # (2e-5 of the maximum, fp32 tol_gemm, where that is the tighter)
+    err, _ = _check_slack("dw", got, ref, 0.0, 0.0, lim)
+    return f"dW {err:.2e} (L {L}, limit {(lim / ref.abs().max()).max().item():.1e} of max)"
+
+
+def _pw_forward_case(gpu, case, seed):
+    """x3d_pw_fwd in the plan's form.  Inputs: the tail fold reads the raw `c` output of the block below (+ its shortcut: the
+    block input, or a raw shortcut conv output with bn_r) and stores relu(s x + t + [s_r] add + [t_r]); the `c` conv reads a
+    raw depthwise output through BN_b [* SE gate] -> swish; plain launches read a block output (post-ReLU).  y against the fp64
+    GEMM over the operands as the kernel rounds them (tol_gemm; the tail fold's operand is the stored in_store, the swish
+    prologue's output rounded to storage with the tie slack of tests.util.tie_slack_pw, at most 1e-4 of the outputs may need
+    it), through the inference epilogue where the case has it; in_store at tol_store; stats against fp64 sums of the stored y
+    at _stol."""
+    from x3d_tf_amd import hip, ops
+    from tests.util import pw_gemm64, pw_infer_epi64, pw_prologue64, tie_slack_pw
+    _, dtype, n, ci, co, t, h, w, stride, _, ia, oa, form = case
+    f = set(form)
+    g_ = torch.Generator(device=gpu)
+    g_.manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g_, device=gpu, dtype=torch.float32)
+    ho, wo = -(-h // stride), -(-w // stride)
+    wt = rn(co, ci) * (2.0 / ci) ** 0.5
+    kw = dict(in_act=ia)
+    if "store" in f:
+        x = _pw_act(rn, (n, ci, t, h, w), dtype, "raw", gpu)
+        kw.update(in_ss=_pw_ss(rn, ci), in_store=torch.full(x.shape, 7.0, dtype=dtype, device=gpu))
+        if "add" in f:
+            kw["in_add"] = _pw_act(rn, x.shape, dtype, "raw" if "add_ss" in f else "relu", gpu)
+            kw["in_add_ss"] = _pw_ss(rn, ci) if "add_ss" in f else None
+    elif "ss" in f:
+        x = _pw_act(rn, (n, ci, t, h, w), dtype, "raw", gpu)
+        kw.update(in_ss=_pw_ss(rn, ci), in_gate=0.2 + 0.8 * torch.rand((n, ci), generator=g_, device=gpu) if "gate" in f else None)
+    else:
+        x = _pw_act(rn, (n, ci, t, h, w), dtype, "relu", gpu)
+    if "oss" in f:
+        kw.update(out_ss=_pw_ss(rn, co), out_act=oa)
+        if "oadd" in f:
+            kw["out_add"] = _pw_act(rn, (n, co, t, ho, wo), dtype, "raw" if "oadd_ss" in f else "relu", gpu)
+            kw["out_add_ss"] = _pw_ss(rn, co) if "oadd_ss" in f else None
+    stats = torch.zeros((co, 2), dtype=torch.float64, device=gpu) if "stats" in f else None
+    wp = ops.pw_pack_weights([wt], dgrad=False, dtype=dtype)[0][0] if dtype != torch.float32 else None
+    y = ops.pw_fwd(x, wt, stats=stats, stride=stride, w_panel=wp, **kw)
+    torch.cuda.synchronize()
+    name = hip.kernel_name(S.pw_full_struct(case))
+    wr = round_to(wt, dtype)
+    rt, at = tol_gemm(dtype)
+    rs, as_ = tol_store(dtype)
+    worst = dict(y=0.0, in_store=0.0)
+    needed, CH = 0, _pw_chunk(case)
+    y1 = torch.zeros(co, dtype=torch.float64, device=gpu)
+    y2 = torch.zeros(co, dtype=torch.float64, device=gpu)
+    for i in range(0, n, CH):
+        sl = slice(i, i + CH)
+        slack = 0.0
+        if "store" in f:
+            v = _v(kw["in_ss"], 0) * x[sl].double() + _v(kw["in_ss"], 1)
+            if "add" in f:
+                a = kw["in_add"][sl].double()
+                v = v + (a * _v(kw["in_add_ss"], 0) + _v(kw["in_add_ss"], 1) if "add_ss" in f else a)
+            v = torch.relu(v)
+            worst["in_store"] = max(worst["in_store"], _frac(f"in_store[{i}]", kw["in_store"][sl], v, rs, as_ * v.abs().max().item()))
+            op = kw["in_store"][sl].double()            # (the GEMM operand is the stored block output)
+            del v
+        elif "ss" in f:
+            gate = None if kw["in_gate"] is None else kw["in_gate"][sl]
+            op = pw_prologue64(x[sl], kw["in_ss"], gate, ia, dtype)
+            if dtype != torch.float32:
+                slack = tie_slack_pw(pw_prologue64(x[sl], kw["in_ss"], gate, ia), dtype, wr.abs())
+        else:
+            op = x[sl].double()
+        ref = pw_gemm64(op, wr, stride)
+        del op
+        if "oss" in f:
+            ref = pw_infer_epi64(ref, kw["out_ss"], None if "oadd" not in f else kw["out_add"][sl], kw.get("out_add_ss"), oa)
+            slack = slack * kw["out_ss"][:, 0].double().abs().view(1, -1, 1, 1, 1)
+        e, nd = _check_slack(f"y[{i}:{i + CH}]", y[sl], ref, rt, at * max(ref.abs().max().item(), 1e-30), slack)
+        worst["y"], needed = max(worst["y"], e), needed + nd
+        del ref, slack
+        if stats is not None:
+            yd = y[sl].double()
+            y1 += yd.sum((0, 2, 3, 4))
+            y2 += (yd * yd).sum((0, 2, 3, 4))
+            del yd
+    frac = needed / y.numel()
+    assert frac < 1e-4, f"{frac:.2e} of the outputs needed the tie slack: a systematic error, not ties"
+    msg = f"y {worst['y']:.2e} ({frac:.1e} needed the tie slack)"
+    if "store" in f:
+        msg += f", in_store {worst['in_store']:.2e}"
+    if stats is not None:
+        sref = torch.stack([y1, y2], 1)
+        stol = _stol(dtype)
+        msg += f", stats {_frac('stats', stats, sref, stol, stol * max(1.0, sref.abs().max().item())):.2e}"
+    return name, msg
+
+
+def _pw_backward_case(gpu, case, seed):
+    """x3d_pw_dgrad / x3d_pw_wgrad / x3d_pw_bwd in the plan's form, with a real step's BatchNorm backward (_pw_bn_bwd: the
+    coefficient table, or the coef_fold that derives it from the same sums).  Conv inputs: a block output (post-ReLU) for the
+    `a` / shortcut convs, a raw depthwise output through BN_b [* SE gate] -> swish for the `c` convs (stride 2: the even
+    pixels).  dx against Wr^T dY with dY evaluated in fp32 and rounded to storage (tol_gemm + the dY tie slack, x 1.1 through
+    swish'), then its epilogue: add / strided add, swish' with the per-(n, c) sums (10 _stol), the tail fold's [x > 0] mask with
+    tail_sums_c / _r (10 _stol).  dW (accumulator pre-filled, slabs through x3d_dw_slab_reduce from a NaN-filled buffer) against
+    sum dY x^T over the operands as rounded (_pw_dw_check).  The recomputed-output form (rc) goes through ops.pw_bwd_rc
+    (prepare -> launch -> finish): y = Wr x, dx against the fold with its two panel operands rounded, dW against the
+    definition.  A publishing fold's dgamma / dbeta / table: _pw_check_pub."""
+    from x3d_tf_amd import hip, ops
+    from tests.util import pw_prologue64, tie_slack_pw
+    e, dtype, n, ci, co, t, h, w, s, epi, ia, _, form = case
+    f = set(form)
+    g_ = torch.Generator(device=gpu)
+    g_.manual_seed(seed)
+    rn = lambda *sh: torch.randn(*sh, generator=g_, device=gpu, dtype=torch.float32)
+    stride = 2 if s == 2 else 1
+    ho, wo = -(-h // stride), -(-w // stride)
+    half = dtype != torch.float32
+    wt = rn(co, ci) * (2.0 / ci) ** 0.5
+    wr = round_to(wt, dtype)
+    CH = _pw_chunk(case)
+    swish = epi == 3 or "ss" in f
+    # the conv input (as stored) and, for the `c` conv, its prologue
+    x = _pw_act(rn, (n, ci, t, h, w), dtype, "raw" if swish else "relu", gpu)
+    bss = _pw_ss(rn, ci) if swish else None
+    gate = 0.2 + 0.8 * torch.rand((n, ci), generator=g_, device=gpu) if "gate" in f else None
+    g = rn(n, co, t, ho, wo).to(dtype)
+    dx = torch.empty((n, ci, t, ho, wo), dtype=dtype, device=gpu) if e != "wgrad" else None
+    dw = torch.full((co, ci), 0.5, dtype=torch.float32, device=gpu)
+    add = None
+    if epi in (1, 2):
+        add = (rn(n, ci, t, ho, wo) if epi == 1 else rn(n, ci, t, -(-ho // 2), -(-wo // 2))).to(dtype)
+    nc = torch.zeros((n, ci, 2), dtype=torch.float64, device=gpu) if epi == 3 else None
+    tails = {k: (_pw_act(rn, (n, ci, t, ho, wo), dtype, "raw", gpu), torch.zeros((ci, 2), dtype=torch.float64, device=gpu))
+             for k in ("tail_c", "tail_r") if k in f}
+    pub = None
+    if "rc" in f:
+        yraw = None             # y = Wr x, recomputed: its statistics and the coefficients from an fp64 pass
+        xs = lambda sl: x[sl].double()[:, :, :, ::stride, ::stride]
+        acc = torch.zeros((4, co), dtype=torch.float64, device=gpu)
+        for i in range(0, n, CH):
+            yd, gd = torch.einsum("oc,ncthw->nothw", wr, xs(slice(i, i + CH))), g[i:i + CH].double()
+            acc[:2] += torch.stack([yd.sum((0, 2, 3, 4)), (yd * yd).sum((0, 2, 3, 4))])
+            del yd
+        m = n * t * ho * wo
+        mean = acc[0] / m
+        invstd = 1.0 / torch.sqrt(acc[1] / m - mean * mean + 1e-5)
+        for i in range(0, n, CH):
+            yd, gd = torch.einsum("oc,ncthw->nothw", wr, xs(slice(i, i + CH))), g[i:i + CH].double()
+            acc[2:] += torch.stack([gd.sum((0, 2, 3, 4)), (gd * yd).sum((0, 2, 3, 4))])
+            del yd, gd
+        coef = _bn_bwd_coef_sums(m, acc[0], acc[1], acc[2], acc[3], (1 + 0.3 * rn(co)).double())
+        tc, tr = tails.get("tail_c", (None, None)), tails.get("tail_r", (None, None))
+        assert ops.pw_bwd_rc(g, x, wt, coef, dx, dw, epi, add, tail_c=tc[0], tail_r=tr[0], tail_sums_c=tc[1], tail_sums_r=tr[1],
+                             x_stride=stride), "the recomputed-output form should cover this launch"
+    else:
+        yraw = _pw_act(rn, (n, co, t, ho, wo), dtype, "raw", gpu)
+        coef, sums, mi, gamma, m = _pw_bn_bwd(rn, g, yraw, CH)
+        fold, pub = _pw_fold(ops, f, sums, m, mi, gamma, gpu)
+        dp = ops.pw_pack_weights([wt], dtype=dtype)[0][1] if half and e != "wgrad" else None
+        swk = dict(braw=x, b_ss=bss, gate=gate, nc_sums=nc) if epi == 3 else {}
+        if e == "dgrad":
+            ops.pw_dgrad(g, yraw, coef, wt, dx, epi, add=add, w_panel=dp, coef_fold=fold, **swk)
+        elif e == "wgrad":
+            assert ops.pw_wgrad(g, yraw, coef, x, dw, in_ss=bss, in_gate=gate, in_act=ia, stride=stride, slab="slab" in f,
+                                coef_fold=fold), "the plan's slab form should be there"
+        else:
+            tc = tails.get("tail_c", (None, None))
+            assert ops.pw_bwd(g, yraw, coef, dp, dx, dw, epi, x=None if epi == 3 else x, add=add, tail_c=tc[0],
+                              tail_sums_c=tc[1], slab="slab" in f, coef_fold=fold, **swk), "the fused kernel should cover this launch"
+    torch.cuda.synchronize()
+    name = hip.kernel_name(S.pw_full_struct(case))
+    rt, at = tol_gemm(dtype)
+    cd = coef.double()
+    dw_ref = torch.zeros((co, ci), dtype=torch.float64, device=gpu)
+    dw_abs = torch.zeros_like(dw_ref)
+    worst, needed = 0.0, 0
+    tsum = {k: torch.zeros((ci, 2), dtype=torch.float64, device=gpu) for k in tails}
+    ncref = torch.zeros((n, ci, 2), dtype=torch.float64, device=gpu)
+    if "rc" in f:
+        w1 = round_to((wr * cd[:, 0:1]).float(), dtype)
+        mm = round_to(torch.einsum("oc,o,od->cd", wr, cd[:, 1], wr).float(), dtype)
+        c0 = (wr * cd[:, 2:3]).sum(0).view(1, -1, 1, 1, 1)
+    for i in range(0, n, CH):
+        sl = slice(i, i + CH)
+        gd = g[sl].double()
+        if "rc" in f:
+            xd = xs(sl)
+            dy = _v(cd, 0) * gd + _v(cd, 1) * torch.einsum("oc,ncthw->nothw", wr, xd) + _v(cd, 2)     # the definition
+            ref = torch.einsum("oc,nothw->ncthw", w1, gd) + torch.einsum("cd,ndthw->ncthw", mm, xd) + c0
+            slack = 0.0
+        else:
+            dy32 = _pw_dy32(coef, gd, yraw[sl].double())
+            dy = round_to(dy32, dtype)
+            xd = pw_prologue64(x[sl], bss, None if gate is None else gate[sl], 2, dtype) if swish else x[sl].double()
+            xd = xd[:, :, :, ::stride, ::stride]
+            if dtype == torch.float32:
+                mag = _v(cd[:, 0].abs()) * gd.abs() + _v(cd[:, 1].abs()) * yraw[sl].double().abs() + _v(cd[:, 2].abs())
+                dw_abs += torch.einsum("nothw,ncthw->oc", mag, xd.abs())
+                del mag
+            if e != "wgrad":
+                ref = torch.einsum("oc,nothw->ncthw", wr, dy)
+                slack = tie_slack_pw(dy32, dtype, wr.abs().t()) * (1.1 if epi == 3 else 1.0) if half else 0.0
+            del dy32
+        dw_ref += torch.einsum("nothw,ncthw->oc", dy, xd)
+        del dy, xd
+        if e != "wgrad":
+            if epi == 1:
+                ref += add[sl].double()
+            elif epi == 2:
+                ref[:, :, :, ::2, ::2] += add[sl].double()
+            elif epi == 3:
+                vb = (_v(bss, 0) * x[sl].double() + _v(bss, 1)) * (1.0 if gate is None else gate[sl].double()[:, :, None, None, None])
+                sg = torch.sigmoid(vb)
+                ref = ref * (sg * (1 + vb * (1 - sg)))
+                del vb, sg
+            if tails:
+                keep = x[sl] > 0
+                ref = ref * keep
+                slack = slack * keep if torch.is_tensor(slack) else slack
+                assert not bool((dx[sl][~keep] != 0).any()), "gradient leaked through a closed ReLU"
+            ew, nd = _check_slack(f"dx[{i}:{i + CH}]", dx[sl], ref, rt, at * max(ref.abs().max().item(), 1e-30), slack)
+            worst, needed = max(worst, ew), needed + nd
+            del ref, slack
+            ds = dx[sl].double()
+            if epi == 3:
+                ncref[sl] = torch.stack([ds.sum((2, 3, 4)), (ds * x[sl].double()).sum((2, 3, 4))], -1)
+            for k, (tt, _) in tails.items():
+                tsum[k] += torch.stack([ds.sum((0, 2, 3, 4)), (ds * tt[sl].double()).sum((0, 2, 3, 4))], 1)
+            del ds
+        del gd
+    msgs = []
+    st10 = 10 * _stol(dtype)
+    if e != "wgrad":
+        frac = needed / dx.numel()
+        assert frac < 1e-4, f"{frac:.2e} of the outputs needed the tie slack: a systematic error, not ties"
+        msgs.append(f"dx {worst:.2e} ({frac:.1e} needed the tie slack)")
+        if epi == 3:
+            msgs.append(f"nc_sums {_frac('nc_sums', nc, ncref, st10, st10 * max(1.0, ncref.abs().max().item())):.2e}")
+        for k, (_, got) in tails.items():
+            msgs.append(f"{k} sums {_frac(k, got, tsum[k], st10, st10 * max(1.0, tsum[k].abs().max().item())):.2e}")
+    if e != "dgrad":
+        msgs.append(_pw_dw_check(name, dtype, dw, 0.5, dw_ref, dw_abs, case, gpu))
+    else:
+        assert float((dw - 0.5).abs().max()) == 0.0
+    msg = ", ".join(msgs)
+    if pub is not None:
+        msg += _pw_check_pub(pub, sums, m, mi, gamma)
+    return name, msg
+
+
+@pytest.mark.parametrize("case", S.PW_FULL, ids=[S.pw_full_id(c) for c in S.PW_FULL])
+def test_pointwise_full_size(gpu, case):
+    """One pointwise launch of a full-size plan (tests/shapes.py PW_FULL; tests/test_dispatch_coverage.py keeps the list
+    complete), in its launch form, against fp64 on the GPU (tests.util.pw_gemm64 and its prologue / epilogue restatements),
+    sample chunk by sample chunk: _pw_forward_case / _pw_backward_case.  Prints the kernel, each check's worst error as a
+    fraction of its limit, and the seconds the case took."""
+    import time
+    t0 = time.time()
+    seed = 2000 + S.PW_FULL.index(case)
+    name, msg = (_pw_forward_case if case[0] == "fwd" else _pw_backward_case)(gpu, case, seed)
+    torch.cuda.synchronize()
+    print(f"full-size pointwise {S.pw_full_id(case)} {name}: worst err / limit {msg}; {time.time() - t0:.1f} s")
+
+
+@pytest.mark.parametrize("dtype", HALF)
+def test_pw_wgrad_generic_kernel_refuses_a_slab(gpu, dtype):
+    """x3d_pw_wgrad's 16-bit generic kernel (an odd point count on a row-misaligned x: pw_wgrad_bf16_kernel) has no slab form:
+    given a dw_slab it must refuse before any launch, not add into dw by atomics and leave the slabs unwritten."""
+    import ctypes as C
+    from x3d_tf_amd import hip
+    n, ci, co, t, h, w = 1, 48, 108, 13, 5, 5
+    g_ = torch.Generator(device=gpu)
+    g_.manual_seed(5)
+    xb = torch.randn(n * ci * t * h * w + 1, generator=g_, device=gpu).to(dtype)
+    g = torch.randn((n, co, t, h, w), generator=g_, device=gpu).to(dtype)
+    yraw = torch.randn((n, co, t, h, w), generator=g_, device=gpu).to(dtype)
+    coef = torch.randn((co, 4), generator=g_, device=gpu) * 0.5
+    dw = torch.full((co, ci), 0.5, device=gpu)
+    slab = torch.full((4 * co * ci,), float("nan"), device=gpu)
+    a = hip.PwWgradArgs(g.data_ptr(), yraw.data_ptr(), coef.data_ptr(), xb.data_ptr() + xb.element_size(), None, None, 0,
+                        dw.data_ptr(), n, ci, co, t, h, w, 1, hip.dtype_code(dtype))
+    assert hip.kernel_name(a).startswith("pw_wgrad_bf16_kernel<") and hip.load().x3d_pw_wgrad_dw_parts(C.byref(a)) == 0
+    a.dw_slab, a.dw_slab_parts = slab.data_ptr(), 4
+    with pytest.raises(hip.X3DHipError, match="slab"):
+        hip.call_struct("x3d_pw_wgrad", a)
+    torch.cuda.synchronize()
+    assert float((dw - 0.5).abs().max()) == 0.0 and bool(slab.isnan().all())

@@ -70,6 +70,65 @@ def test_dw_stencil64_matches_the_oracle(t, h, w, stride):
     assert torch.allclose(dw, dw_ref, rtol=0, atol=1e-11)
 
 
+@pytest.mark.parametrize("stride,act,gated", [(1, 0, False), (2, 0, False), (1, 1, False), (1, 2, True), (1, 2, False)])
+def test_pw_gemm64_matches_the_oracle(stride, act, gated):
+    """tests.util.pw_prologue64 / pw_gemm64 / pw_infer_epi64 / bn_bwd_coef_sums / bn_bwd_fold64 (the fp64 references of the
+    full-size pointwise tests, which run on the GPU) against the oracle: the prologue is act(gate * batch_norm(x)) with the BN
+    in inference form (its scale / shift table), the GEMM oracle.pointwise (odd extents at stride 2), the inference epilogue
+    act(batch_norm(conv) + [batch_norm(shortcut)]), and the BatchNorm-backward coefficients the autograd gradient of the
+    oracle's training-mode batch_norm."""
+    from tests.util import bn_bwd_coef_sums, bn_bwd_fold64, pw_gemm64, pw_infer_epi64, pw_prologue64
+    g = torch.Generator().manual_seed(11)
+    n, ci, co, t, h, w = 2, 5, 7, 3, 7, 9
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    bn = lambda c, pre: {f"{pre}/gamma": 1 + 0.3 * r(c), f"{pre}/beta": 0.3 * r(c), f"{pre}/moving_mean": r(c),
+                         f"{pre}/moving_variance": 0.5 + torch.rand(c, generator=g, dtype=torch.float64)}
+    ss_of = lambda p, pre: torch.stack([p[f"{pre}/gamma"] / torch.sqrt(p[f"{pre}/moving_variance"] + 1e-5),
+                                        p[f"{pre}/beta"] - p[f"{pre}/moving_mean"] * p[f"{pre}/gamma"] /
+                                        torch.sqrt(p[f"{pre}/moving_variance"] + 1e-5)], 1)
+    x = r(n, ci, t, h, w) + 0.5
+    wt = r(co, ci) * 0.3
+    p = {**bn(ci, "in"), **bn(co, "out"), **bn(co, "sc")}
+    gate = torch.rand((n, ci), generator=g, dtype=torch.float64) if gated else None
+    u = O.batch_norm(x, p, "in", False, 1e-5, 0.9) if act else x
+    if gate is not None:
+        u = u * gate[:, :, None, None, None]
+    u = torch.relu(u) if act == 1 else (u * torch.sigmoid(u) if act == 2 else u)
+    v = pw_prologue64(x, ss_of(p, "in") if act else None, gate, act)
+    assert torch.allclose(v, u, rtol=0, atol=1e-12)
+    acc = pw_gemm64(v, wt, stride)
+    ref = O.pointwise(u, wt, stride)
+    assert acc.shape == ref.shape and torch.allclose(acc, ref, rtol=0, atol=1e-12)
+    # the 16-bit operand: fp32 arithmetic, then the storage rounding
+    vb = pw_prologue64(x, ss_of(p, "in") if act else None, gate, act, torch.bfloat16)
+    assert torch.equal(vb, vb.float().to(torch.bfloat16).double()) and (vb - u).abs().max() <= 2 ** -8 * u.abs().max()
+    short = r(*ref.shape)
+    for add, add_ss, want in ((None, None, O.batch_norm(ref, p, "out", False, 1e-5, 0.9)),
+                              (short, None, O.batch_norm(ref, p, "out", False, 1e-5, 0.9) + short),
+                              (short, ss_of(p, "sc"), O.batch_norm(ref, p, "out", False, 1e-5, 0.9) + O.batch_norm(short, p, "sc", False, 1e-5, 0.9))):
+        got = pw_infer_epi64(acc, ss_of(p, "out"), add, add_ss, 1)
+        assert torch.allclose(got, torch.relu(want), rtol=0, atol=1e-12)
+    # BatchNorm backward: dY = A g + B y + C is the gradient of the training-mode batch_norm
+    y = (acc + r(co).view(1, -1, 1, 1, 1)).requires_grad_(True)
+    gr = r(*y.shape)
+    (dy_ref,) = torch.autograd.grad((O.batch_norm(y, p, "out", True, 1e-5, 0.9) * gr).sum(), [y])
+    yd = y.detach()
+    m = yd.numel() // co
+    red = lambda v: v.sum((0, 2, 3, 4))
+    coef = bn_bwd_coef_sums(m, red(yd), red(yd * yd), red(gr), red(gr * yd), p["out/gamma"]).double()
+    dy = coef[:, 0].view(1, -1, 1, 1, 1) * gr + coef[:, 1].view(1, -1, 1, 1, 1) * yd + coef[:, 2].view(1, -1, 1, 1, 1)
+    assert torch.allclose(dy, dy_ref, rtol=0, atol=1e-5 * dy_ref.abs().max().item())     # (the coefficients are fp32)
+    assert red(dy).abs().max() < 1e-5 * red(dy.abs()).max() and red(dy * yd).abs().max() < 1e-5 * red((dy * yd).abs()).max()
+    mean = red(yd) / m
+    mi = torch.stack([mean, 1 / torch.sqrt(red(yd * yd) / m - mean * mean + 1e-5)], 1)
+    cf, dga, dbe = bn_bwd_fold64(torch.stack([red(gr), red(gr * yd)], 1), m, mi, p["out/gamma"])
+    assert torch.equal(cf.float().double(), coef)
+    gam, bet = p["out/gamma"].clone().requires_grad_(True), p["out/beta"].clone().requires_grad_(True)
+    dg_ref, db_ref = torch.autograd.grad((O.batch_norm(yd, {**p, "out/gamma": gam, "out/beta": bet}, "out", True, 1e-5, 0.9) * gr).sum(),
+                                         [gam, bet])
+    assert torch.allclose(dbe, db_ref, rtol=0, atol=1e-10) and torch.allclose(dga, dg_ref, rtol=1e-6, atol=1e-10)
+
+
 def test_pointwise_bn_stem_against_numpy():
     g = torch.Generator().manual_seed(1)
     xt = torch.randn(2, 5, 3, 6, 7, generator=g, dtype=torch.float64)

@@ -56,6 +56,72 @@ def tie_slack_t(v, dtype, w_abs, eps_ulps=2e-4):
     return out
 
 
+def tie_slack_pw(v, dtype, w_abs, eps_ulps=2e-4):
+    """tie_slack on v's device, for any sample chunk of v ([n, K, T, H, W], the fp32 / fp64 prologue output before the
+    rounding): the full-size pointwise tests keep it on the GPU.  w_abs [M, K]; returns [n, M, T, H, W] fp64."""
+    return torch.einsum("mk,nkthw->nmthw", w_abs.detach().double().to(v.device), _tie_ulps(v.detach().double(), dtype, eps_ulps))
+
+
+def pw_prologue64(x, ss=None, gate=None, act=0, dtype=None):
+    """The input prologue of x3d_pw_fwd / x3d_pw_wgrad, v = act(gate[n, c] (s x + t)) (act 0 none, 1 ReLU, 2 swish), as the
+    16-bit GEMM operand: evaluated in fp32 like the kernels and rounded to `dtype` (tests.util.round_to); dtype None: the
+    fp64 value.  x [N, C, T, H, W]; ss [C, 2]; gate [N, C]."""
+    f = torch.float64 if dtype is None else torch.float32
+    v = x.to(f)
+    if ss is not None:
+        v = v * ss[:, 0].to(f).view(1, -1, 1, 1, 1) + ss[:, 1].to(f).view(1, -1, 1, 1, 1)
+    if gate is not None:
+        v = v * gate.to(f)[:, :, None, None, None]
+    if act == 1:
+        v = torch.relu(v)
+    elif act == 2:
+        v = v * torch.sigmoid(v)
+    return v.double() if dtype is None else round_to(v, dtype)
+
+
+def pw_gemm64(v, w, stride=1):
+    """The pointwise conv y[n, o] = sum_c w[o, c] v[n, c] (oracle.x3d_oracle.pointwise; stride 2 samples the even pixels) in
+    fp64 on v's device."""
+    if stride != 1:
+        v = v[:, :, :, ::stride, ::stride]
+    return torch.einsum("oc,ncthw->nothw", w.double().to(v.device), v.double())
+
+
+def pw_infer_epi64(acc, oss, add=None, add_ss=None, act=0):
+    """x3d_pw_fwd's inference epilogue y = act(s_o acc + t_o [+ s_r add + t_r | + add]) in fp64 (act 1: ReLU)."""
+    c = lambda t, j: t[:, j].double().view(1, -1, 1, 1, 1)
+    y = acc * c(oss, 0) + c(oss, 1)
+    if add is not None:
+        y = y + (add.double() * c(add_ss, 0) + c(add_ss, 1) if add_ss is not None else add.double())
+    return torch.relu(y) if act == 1 else y
+
+
+def bn_bwd_coef_sums(m, sy, syy, sg, sgy, gamma):
+    """[C][4] fp32 coefficients (A, B, C, 0) of the training-mode BatchNorm backward dY = A g + B y + C over m points per
+    channel, from the fp64 sums of y, y^2, g and g y (x3d_bn_finalize / x3d_bn_bwd_finalize arithmetic)."""
+    mean = sy / m
+    var = syy / m - mean * mean
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    dbe = sg
+    dga = (sgy - mean * dbe) * invstd
+    k1 = gamma * invstd
+    b = -k1 * invstd * dga / m
+    c = -k1 * dbe / m - b * mean
+    return torch.stack([k1, b, c, torch.zeros_like(c)], 1).float()
+
+
+def bn_bwd_fold64(sums, count, mi, gamma):
+    """What a publishing x3d_bn_bwd_fold derives from its operands, in fp64: (coef [C][4], dgamma, dbeta) from sums [C][2] =
+    (sum g, sum g y), mean_invstd [C][2] and gamma (common.h bn_bwd_coefs)."""
+    mean, invstd, g = mi[:, 0].double(), mi[:, 1].double(), gamma.double()
+    dbe = sums[:, 0].double()
+    dga = (sums[:, 1].double() - mean * dbe) * invstd
+    k1 = g * invstd
+    b = -k1 * invstd * dga / count
+    c = -k1 * dbe / count - b * mean
+    return torch.stack([k1, b, c, torch.zeros_like(c)], 1), dga, dbe
+
+
 def dw_same_pads(n, stride):
     """(output extent, pad before, pad after) of a 3-tap TF-SAME window along an extent of n at `stride` (156 -> 78: 0 / 1,
     39 -> 20: 1 / 1, 56 -> 56: 1 / 1)."""

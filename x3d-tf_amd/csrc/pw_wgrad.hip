@@ -279,11 +279,13 @@ extern "C" int x3d_pw_wgrad(const x3d_pw_wgrad_args* w, void* stream) {
     const int rc = pw_wgrad_v2_dispatch<f16>(a, vec, xpro, st);
     if (rc < 0 && x3d_parts_query) return X3D_OK;       // (query mode: the generic kernel has no slab form)
     X3D_REQUIRE(rc >= 0 || !w->coef_fold, "pw_wgrad: coef_fold is not taken by the generic kernel (x3d_pw_coef_fold_supported() == 0)");
+    X3D_REQUIRE(rc >= 0 || !w->dw_slab, "pw_wgrad: dw_slab given to the generic kernel, which has no slab form (x3d_pw_wgrad_dw_parts() == 0)");
     return rc >= 0 ? rc : pw_wgrad_bf16_dispatch<f16>(a, vec, xpro, st);
   }
   const int rc = pw_wgrad_v2_dispatch<bf16>(a, vec, xpro, st);
   if (rc < 0 && x3d_parts_query) return X3D_OK;
   X3D_REQUIRE(rc >= 0 || !w->coef_fold, "pw_wgrad: coef_fold is not taken by the generic kernel (x3d_pw_coef_fold_supported() == 0)");
+  X3D_REQUIRE(rc >= 0 || !w->dw_slab, "pw_wgrad: dw_slab given to the generic kernel, which has no slab form (x3d_pw_wgrad_dw_parts() == 0)");
   return rc >= 0 ? rc : pw_wgrad_bf16_dispatch<bf16>(a, vec, xpro, st);
 }
 
