@@ -48,8 +48,9 @@ extern "C" {
 /* Version of THIS header: bumped with every incompatible change of a signature or struct.  x3d_version() returns the value
  * the library was built with; a binding must refuse a library whose version differs from the header it was written against
  * (x3d_tf_amd/hip.py does): a stale libx3d_hip.so would otherwise take shifted arguments silently.
- * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit). */
-#define X3D_ABI_VERSION 134
+ * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit);
+ *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device). */
+#define X3D_ABI_VERSION 135
 int x3d_version(void);
 const char* x3d_last_error(void);
 
@@ -578,6 +579,58 @@ typedef struct {
 int x3d_train_clip(const x3d_train_clip_args* a, void* stream);
 /* extents of a H x W frame after random_short_side_resize with target `jitter` (transforms.py:126-141) */
 int x3d_train_resized_hw(int H, int W, float jitter, int* new_h, int* new_w);
+
+/* ------------------------------------------------------------------------------------------
+ * JPEG frames of the TFRecord input pipeline decoded on the device (reference dataloader.py:80-88:
+ * tf.image.decode_jpeg of every frame; create_tfrecords.py:64-65 writes them).
+ *     Baseline and extended-sequential Huffman JPEG, 8-bit, grey or YCbCr with luma sampling 1x1 / 2x1 / 2x2 and
+ *     chroma 1x1, optional restart intervals, any extents.  Bit-identical to the libjpeg defaults: ISLOW IDCT,
+ *     fancy (triangle) chroma upsampling, 16-bit fixed-point YCbCr -> RGB; grey replicated to RGB.
+ *     Anything else is reported per image (X3D_JPEG_UNSUPPORTED / X3D_JPEG_MALFORMED) for the caller to decode
+ *     on the host.
+ * x3d_jpeg_parse (host only, no GPU): reads the headers of n images (host pointers data[i], lengths[i]) into
+ *     imgs[i] and lays out one device scratch for all supported images (*scratch_bytes).  The caller then sets
+ *     `data_off` / `data_len` (where image i sits in the packed device copy of the bytes) and `out` (NULL: skip).
+ * x3d_jpeg_decode: three launches on `stream` (entropy decode, dequantise + IDCT, upsample + colour convert);
+ *     writes status[i] (device) per image: X3D_JPEG_OK, the parse status, X3D_JPEG_SKIPPED, or X3D_JPEG_CORRUPT
+ *     for an entropy segment that ends early or holds an invalid code or restart marker (that image's slot is
+ *     then not written).  Reads only bytes [data_off + ecs_off, data_off + ecs_end) and the tables of image i,
+ *     writes only its scratch range and out[0 .. height * width * 3).
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_JPEG_OK 0
+#define X3D_JPEG_UNSUPPORTED 1   /* valid JPEG outside the device decoder's scope (progressive, arithmetic, 12-bit, CMYK, ...) */
+#define X3D_JPEG_MALFORMED 2     /* header that cannot be parsed */
+#define X3D_JPEG_CORRUPT 3       /* (device) entropy-coded data ends early or is invalid */
+#define X3D_JPEG_SKIPPED 4       /* (device) supported, but `out` was NULL */
+typedef struct {
+  unsigned char* out;          /* device [height][width][3] uint8 (caller) */
+  long long data_off;          /* offset of the image in the packed device bytes (caller) */
+  long long coef_off;          /* int16 coefficients in the scratch, bytes (parse) */
+  long long plane_off;         /* uint8 component planes in the scratch, bytes (parse) */
+  int data_len;                /* bytes of the image (caller) */
+  int status;                  /* X3D_JPEG_* (parse) */
+  int height, width, ncomp;
+  int hs[3], vs[3];            /* sampling factors (1 x 1 for grey) */
+  int bw[3], bh[3];            /* component extents in 8x8 blocks */
+  int mcux, mcuy;              /* MCUs per row / column */
+  int dc_tbl[3], ac_tbl[3];    /* Huffman table of each component */
+  int huff_off[8];             /* offset of the 16 code-length counts of DC tables 0-3, AC tables 0-3 (-1: absent) */
+  int restart_interval;        /* MCUs per restart interval, 0: none */
+  int ecs_off, ecs_end;        /* entropy-coded segment, offsets from the image start */
+  unsigned short qt[3][64];    /* quantisation table of each component, natural order */
+} x3d_jpeg_image;
+typedef struct {
+  const unsigned char* data;             /* the packed bytes of all images */
+  const x3d_jpeg_image* images;          /* device copy of the descriptors */
+  const x3d_jpeg_image* host_images;     /* host: the same descriptors (launch extents, validation) */
+  int n;
+  void* scratch;
+  long long scratch_bytes;
+  int* status;                           /* [n] */
+} x3d_jpeg_decode_args;
+int x3d_jpeg_parse(const unsigned char* const* data, const int* lengths, int n, x3d_jpeg_image* imgs,
+                   long long* scratch_bytes);
+int x3d_jpeg_decode(const x3d_jpeg_decode_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * host helper: CRC32C (Castagnoli), the checksum of TF tensor-bundle checkpoints

@@ -169,6 +169,12 @@ class InputReader:
     to under mixed precision, dataloader.py:111-113), `seed`, `decoder` (path -> uint8 [F, H, W, 3] array for the
     non-TFRecord path), `num_workers` (decode threads), `prefetch` (batches kept ready).
 
+    `jpeg_decode` (TFRecords only): "host" (default) -- the workers decode every frame with `decode_jpeg`, as the
+    reference does; "device" -- the workers only parse the records, and each batch decodes just the frames its clips read,
+    all of them together on the GPU (`jpeg.decode_jpeg_batch`, bit-identical to `decode_jpeg`; frames outside the device
+    decoder's scope go to `decode_jpeg`).  The random draws, their order and the batches are those of the host mode.  In
+    device mode the batches are built on the reader's own stream and handed over with an event.
+
     Data parallelism (`rank`, `world`; default: the torchrun environment).  The reference feeds ONE dataset of global
     batches to MirroredStrategy, which splits each batch over the replicas (train.py:145-152, utils.py:160-167).  Here
     every process owns its reader, so the split is made at the source: `batch_size` stays the reference's GLOBAL batch
@@ -180,7 +186,8 @@ class InputReader:
 
     def __init__(self, cfg, is_training: bool, use_tfrecord: bool, mixed_precision: bool = False, device=None,
                  dtype: torch.dtype = torch.float32, seed: Optional[int] = None, decoder: Optional[Callable] = None,
-                 num_workers: int = 4, prefetch: int = 2, rank: Optional[int] = None, world: Optional[int] = None):
+                 num_workers: int = 4, prefetch: int = 2, rank: Optional[int] = None, world: Optional[int] = None,
+                 jpeg_decode: str = "host"):
         self._cfg = cfg
         self._is_training = bool(is_training)
         self._use_tfrecord = bool(use_tfrecord)
@@ -205,6 +212,11 @@ class InputReader:
         self._workers = max(1, int(num_workers))
         self._prefetch = max(1, int(prefetch))
         self.last_params: List[dict] = []      # the random draws of the clips of the last training batch (tests)
+        if jpeg_decode not in ("host", "device"):
+            raise ValueError(f"jpeg_decode must be 'host' or 'device', not {jpeg_decode!r}")
+        if jpeg_decode == "device" and not self._use_tfrecord:
+            raise ValueError("jpeg_decode='device' decodes the JPEG frames of TFRecords (use_tfrecord=True)")
+        self._jpeg_decode = jpeg_decode
 
     # -- decode ------------------------------------------------------------------------------------
     def decode_video(self, line: str) -> Tuple[np.ndarray, int]:
@@ -229,6 +241,26 @@ class InputReader:
         jpegs, num_frames, label = parse_sequence_example(serialized_example)
         n = num_frames if num_frames >= 0 else len(jpegs)
         return np.stack([decode_jpeg(j) for j in jpegs[:n]]), int(label)
+
+    def parse_frames(self, serialized_example: bytes) -> Tuple[Tuple[List[bytes], int, int], int]:
+        """jpeg_decode="device": SequenceExample -> ((the num_frames JPEG strings, H, W), label), no pixel decoded.  The
+        headers of all frames are read (one library call): a video whose frames differ in size fails as np.stack fails
+        in the host mode, and a frame whose header does not parse is handed to `decode_jpeg`, which raises as it does
+        there."""
+        from .jpeg import parse_headers
+        jpegs, num_frames, label = parse_sequence_example(serialized_example)
+        n = num_frames if num_frames >= 0 else len(jpegs)
+        jpegs = [bytes(j) for j in jpegs[:n]]
+        if not jpegs:
+            raise ValueError("need at least one array to stack")
+        imgs, _ = parse_headers(jpegs)
+        shapes = set()
+        for i, im in enumerate(imgs[:len(jpegs)]):
+            shapes.add(decode_jpeg(jpegs[i]).shape[:2] if im.status == 2 else (im.height, im.width))   # 2: X3D_JPEG_MALFORMED
+        if len(shapes) > 1:
+            raise ValueError("all input arrays must have the same shape")
+        h, w = shapes.pop()
+        return (jpegs, int(h), int(w)), int(label)
 
     # -- stages ------------------------------------------------------------------------------------
     def _shuffle(self, it: Iterator, size: int) -> Iterator:
@@ -307,7 +339,9 @@ class InputReader:
         return batch_size // self._world
 
     def _decoded(self, recs_factory: Callable[[], Iterator]) -> Iterator[Tuple[np.ndarray, int]]:
-        fn = self.parse_and_decode if self._use_tfrecord else self.decode_video
+        fn = self.decode_video
+        if self._use_tfrecord:
+            fn = self.parse_frames if self._jpeg_decode == "device" else self.parse_and_decode
         with ThreadPoolExecutor(self._workers) as ex:
             while True:
                 pending: "queue.Queue" = queue.Queue()
@@ -336,7 +370,57 @@ class InputReader:
         """dataloader.py:90-116: [B, T, S, S, 3] in training, [B * views * crops, T, S, S, 3] otherwise."""
         return torch.cat(clips, 0), torch.tensor(labels, dtype=torch.int64, device=self._device)
 
+    def _device_batch(self, items: List[Tuple[List[bytes], int, int]], labels: List[int]):
+        """jpeg_decode="device": one batch from parsed records.  Training: the draws of every clip in the host mode's order,
+        then only the T frames a clip reads -- (start + t * rate) mod F -- go into a compact [T, H, W, 3] video, which
+        make_train_clip reads with start = 0, rate = 1 (the same frames: views.hip's index formula).  Evaluation: the
+        frames x3d_eval_views reads, decoded into their slots of a full [F, H, W, 3] video (the others are never read).
+        Every frame of the batch is decoded in one decode_jpeg_batch call."""
+        from .jpeg import decode_jpeg_batch
+        from .views import draw_train_params, make_eval_views, make_train_clip
+        cfg = self._cfg
+        t_len = int(cfg.DATA.TEMP_DURATION)
+        frames: List[bytes] = []
+        slots: List[torch.Tensor] = []
+        videos: List[torch.Tensor] = []
+        params: List[dict] = []
+        for jpegs, h, w in items:
+            f = len(jpegs)
+            if self._is_training:
+                p = draw_train_params(f, h, w, cfg, self._gen)
+                params.append(p)
+                v = torch.empty((t_len, h, w, 3), dtype=torch.uint8, device=self._device)
+                rate = int(cfg.DATA.FRAME_RATE)
+                for t in range(t_len):
+                    frames.append(jpegs[(p["start"] + t * rate) % f])
+                    slots.append(v[t])
+            else:
+                v = torch.empty((f, h, w, 3), dtype=torch.uint8, device=self._device)
+                rate = f // t_len if f // t_len > 1 else 1                           # views.hip (transforms.py:51)
+                views = int(cfg.TEST.NUM_TEMPORAL_VIEWS)
+                for i in sorted({(k * rate) % f for k in range(views * t_len)}):
+                    frames.append(jpegs[i])
+                    slots.append(v[i])
+            videos.append(v)
+        decode_jpeg_batch(frames, self._device, out=slots, on_corrupt="host")
+        if self._is_training:
+            clips = [make_train_clip(v, cfg, params=dict(p, start=0), dtype=self._dtype, rate=1)[None]
+                     for v, p in zip(videos, params)]
+        else:
+            clips = [make_eval_views(v, cfg, dtype=self._dtype) for v in videos]
+        return self.process_batch(clips, labels) + (params,)
+
     def _batches(self, file_pattern: str, batch_size: Optional[int]) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        if self._jpeg_decode == "device":
+            items: List = []
+            dlabels: List[int] = []
+            for item, label in self._decoded(lambda: self._records(file_pattern, batch_size)):
+                items.append(item)
+                dlabels.append(label)
+                if len(items) == (batch_size or 1):
+                    yield self._device_batch(items, dlabels)
+                    items, dlabels = [], []
+            return
         clips: List[torch.Tensor] = []
         labels: List[int] = []
         self._batch_params: List[dict] = []
@@ -358,12 +442,21 @@ class InputReader:
         stop = threading.Event()
         END = object()
 
+        device_mode = self._jpeg_decode == "device" and self._device.type == "cuda"
+
         def work():
             try:
                 if self._device.type == "cuda":
                     torch.cuda.set_device(self._device)
+                if device_mode:       # the batches are made on the reader's own stream, handed over by an event
+                    stream = torch.cuda.Stream(self._device)
+                    torch.cuda.set_stream(stream)
                 for b in self._batches(file_pattern, batch_size):
-                    if self._device.type == "cuda":
+                    if device_mode:
+                        ev = torch.cuda.Event()
+                        ev.record(stream)
+                        b = b + (ev,)
+                    elif self._device.type == "cuda":
                         torch.cuda.current_stream().synchronize()     # the consumer thread uses another stream context
                     while not stop.is_set():
                         try:
@@ -387,6 +480,11 @@ class InputReader:
                 if isinstance(item, BaseException):
                     raise item
                 self.last_params = item[2]      # the draws of THIS batch (the producer thread runs `prefetch` batches ahead)
+                if device_mode:
+                    consumer = torch.cuda.current_stream(self._device)
+                    consumer.wait_event(item[3])
+                    item[0].record_stream(consumer)     # made on the reader's stream: not reused before the consumer is done
+                    item[1].record_stream(consumer)
                 yield item[0], item[1]
         finally:
             stop.set()

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X3D_HIP_LIB") or os.path.join(_HERE, "libx3d_hip.so")   # X3D_HIP_LIB: A/B builds (tools/build_variant.sh)
 
-ABI_VERSION = 134   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
+ABI_VERSION = 135   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = 0, 1, 2, 3
@@ -124,6 +124,22 @@ class SeBnbBwdArgs(C.Structure):
                 ("N", _i), ("C", _i), ("Wd", _i), ("reduce", DwReduceJob * 2)]
 
 
+class JpegImage(C.Structure):
+    """x3d_jpeg_image: one parsed JPEG (include/x3d_hip.h)."""
+    _fields_ = [("out", _vp), ("data_off", _ll), ("coef_off", _ll), ("plane_off", _ll), ("data_len", _i), ("status", _i),
+                ("height", _i), ("width", _i), ("ncomp", _i), ("hs", _i * 3), ("vs", _i * 3), ("bw", _i * 3), ("bh", _i * 3),
+                ("mcux", _i), ("mcuy", _i), ("dc_tbl", _i * 3), ("ac_tbl", _i * 3), ("huff_off", _i * 8),
+                ("restart_interval", _i), ("ecs_off", _i), ("ecs_end", _i), ("qt", (C.c_ushort * 64) * 3)]
+
+
+class JpegDecodeArgs(C.Structure):
+    _fields_ = [("data", _vp), ("images", _vp), ("host_images", _vp), ("n", _i), ("scratch", _vp), ("scratch_bytes", _ll),
+                ("status", _vp)]
+
+
+JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = 0, 1, 2, 3, 4
+
+
 _SIGS = {
     "x3d_version": ([], _i),
     "x3d_last_error": ([], C.c_char_p),
@@ -184,6 +200,8 @@ _SIGS = {
     "x3d_train_clip": ([C.POINTER(TrainClipArgs), _vp], _i),
     "x3d_train_resized_hw": ([_i, _i, _f, C.POINTER(_i), C.POINTER(_i)], _i),
     "x3d_crc32c": ([C.c_char_p, C.c_size_t, C.c_uint32], C.c_uint32),
+    "x3d_jpeg_parse": ([_vp, _vp, _i, C.POINTER(JpegImage), C.POINTER(_ll)], _i),
+    "x3d_jpeg_decode": ([C.POINTER(JpegDecodeArgs), _vp], _i),
 }
 
 _lib = None

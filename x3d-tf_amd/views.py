@@ -66,10 +66,11 @@ def draw_train_params(num_video_frames: int, height: int, width: int, cfg, gener
 
 
 def make_train_clip(video_u8: torch.Tensor, cfg, params: dict = None, generator: torch.Generator = None,
-                    dtype=torch.float32, out: torch.Tensor = None) -> torch.Tensor:
+                    dtype=torch.float32, out: torch.Tensor = None, rate: int = None) -> torch.Tensor:
     """video_u8: decoded video [F, H, W, 3] uint8 on the GPU (contiguous).  Returns one clip [T, S, S, 3]
     (channels-last) with T = cfg.DATA.TEMP_DURATION, S = cfg.DATA.TRAIN_CROP_SIZE, every cfg.DATA.FRAME_RATE-th frame
-    from a random start, the video looped.  `params` (see draw_train_params) fixes the random draws."""
+    from a random start, the video looped.  `params` (see draw_train_params) fixes the random draws.  `rate` overrides
+    cfg.DATA.FRAME_RATE (a video holding just the clip's frames is read with start = 0, rate = 1)."""
     if not video_u8.is_cuda or video_u8.dtype != torch.uint8 or not video_u8.is_contiguous():
         raise hip.X3DHipError("make_train_clip needs a contiguous uint8 GPU tensor [F, H, W, 3] (no CPU fallback)")
     if video_u8.dim() != 4 or video_u8.shape[-1] != 3:
@@ -82,7 +83,7 @@ def make_train_clip(video_u8: torch.Tensor, cfg, params: dict = None, generator:
         out = torch.empty((t, s, s, 3), dtype=dtype, device=video_u8.device)
     mean = (hip._f * 3)(*[float(m) for m in cfg.DATA.MEAN])
     std = (hip._f * 3)(*[float(m) for m in cfg.DATA.STD])
-    a = hip.TrainClipArgs(video_u8.data_ptr(), out.data_ptr(), f, h, w, t, int(cfg.DATA.FRAME_RATE), int(params["start"]),
+    a = hip.TrainClipArgs(video_u8.data_ptr(), out.data_ptr(), f, h, w, t, int(cfg.DATA.FRAME_RATE if rate is None else rate), int(params["start"]),
                           float(params["jitter"]), s, int(params["y0"]), int(params["x0"]), 1 if params.get("flip", True) else 0,
                           mean, std, hip.dtype_code(out.dtype))
     hip.call_struct("x3d_train_clip", a)
