@@ -49,8 +49,9 @@ extern "C" {
  * the library was built with; a binding must refuse a library whose version differs from the header it was written against
  * (x3d_tf_amd/hip.py does): a stale libx3d_hip.so would otherwise take shifted arguments silently.
  * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit);
- *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device). */
-#define X3D_ABI_VERSION 135
+ *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device);
+ *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP). */
+#define X3D_ABI_VERSION 136
 int x3d_version(void);
 const char* x3d_last_error(void);
 
@@ -512,6 +513,30 @@ int x3d_view_mean(const float* probs, float* out, int videos, int views, int M, 
  * floating-point atomics: the same inputs give bit-identical counters.  N * M < 2^31, k >= 1; N = 0 is a no-op. */
 int x3d_topk_metrics(const float* probs, const void* labels, int label_bytes, double* acc, int N, int M, int k,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Multi-label head (ABI 136; DATA.MULTI_LABEL): Dense(activation="sigmoid") + tf.keras.losses.BinaryCrossentropy().
+ * ------------------------------------------------------------------------------------------ */
+/* logits, targets [N][M] fp32, targets in [0, 1] (soft targets allowed).  probs = sigmoid(z).  Keras evaluates the loss on
+ * a sigmoid output in its logits form [TF-3p]:  loss_rows[n] = mean_j ( max(z,0) - z*y + log1p(exp(-|z|)) ), the terms
+ * and the row sum in fp64, stored as fp32;  dlogits = grad_scale * (sigmoid(z) - y) / M  (grad_scale = loss_scale /
+ * global_batch, as for x3d_softmax_xent).  Finite for any finite z.  targets == NULL: probs only (loss_rows and dlogits
+ * must then be NULL); loss_rows / dlogits may be NULL.  A NaN logit gives its row a NaN loss and its own dlogits element
+ * NaN.  One launch (one workgroup per row), no atomics.  N * M < 2^31. */
+int x3d_sigmoid_bce(const float* logits, const float* targets, float* probs, float* loss_rows, float* dlogits,
+                    float grad_scale, int N, int M, void* stream);
+/* out[v][m] = max over `views` consecutive rows (the "max" TEST.ENSEMBLE_METHOD); a NaN in any view gives NaN */
+int x3d_view_max(const float* probs, float* out, int videos, int views, int M, void* stream);
+/* Per-class average precision over an evaluation set (sklearn.metrics.average_precision_score).  scores, targets [N][M]
+ * fp32; ap double[M]; npos int[M].  Per class c, with positives = {i : targets[i][c] >= 0.5} and P = their number:
+ *   ap[c] = (1/P) * sum over positives i of TP(s >= s_i) / #{j : s_j >= s_i},   TP(s >= t) = #{positives with s >= t}
+ * Equal scores form one threshold (ties included exactly; -0 equals +0).  npos[c] = P.  P == 0: ap[c] = NaN (mAP drops
+ * the class); any NaN score in the column: ap[c] = NaN.  All counts are integers; the sum is fp64 in a fixed order with
+ * no floating-point atomics, so the same inputs give bit-identical ap.  One workgroup per class, O(N log P).
+ * Limits: N * M < 2^31 (refused otherwise); at most X3D_AP_MAX_POSITIVES positives per class -- a column with more is
+ * never truncated: its ap is NaN and npos[c] = -P (only possible when N > X3D_AP_MAX_POSITIVES). */
+#define X3D_AP_MAX_POSITIVES 32768
+int x3d_multilabel_ap(const float* scores, const float* targets, int N, int M, double* ap, int* npos, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K12  SGD with Nesterov momentum + L2 (train.py:89-92, model.py:47):

@@ -332,14 +332,16 @@ def resolve_prefix(path: str) -> str:
 
 
 def read_checkpoint(path: str, specs: Dict[str, object], expect_partial: bool = True, verify_crc: bool = True,
-                    with_momentum: bool = False, with_slots: Tuple[str, ...] = ()):
+                    with_momentum: bool = False, with_slots: Tuple[str, ...] = (), skipped: Optional[List[str]] = None):
     """Read every model variable named in `specs` from a bundle -> {native name: fp32 CPU tensor}.
 
     Keys of the bundle that the model does not own (optimizer iter/lr/momentum slots, the object graph) are
     ignored when expect_partial (eval.py:81 ``.expect_partial()``); model variables missing from the bundle
     always raise.  with_momentum: also return the SGD momentum slots ({name: tensor}).  with_slots=("momentum", "m",
     "v"): return (variables, {slot kind: {name: tensor}}, {optimizer hyper-parameter: value}) -- everything the
-    reference's `model.load_weights(latest)` (train.py:131-136) restores of the optimizer."""
+    reference's `model.load_weights(latest)` (train.py:131-136) restores of the optimizer.
+    skipped: a list -- variables whose bundle shape differs from the model's are left out (their slots too) and their
+    names appended to it, instead of raising (Keras' `load_weights(..., skip_mismatch=True)`)."""
     prefix = resolve_prefix(path)
     header, entries = read_index(prefix + ".index")
     n_shards = header.get("num_shards", 1)
@@ -373,6 +375,9 @@ def read_checkpoint(path: str, specs: Dict[str, object], expect_partial: bool = 
         if key not in entries:
             missing.append(name)
             continue
+        if skipped is not None and tuple(entries[key].shape) != tf_shape(spec):
+            skipped.append(name)
+            continue
         out[name] = fetch(key, spec)
     if missing:
         raise KeyError(f"{len(missing)} model variables missing from {prefix}: {missing[:4]}...")
@@ -387,7 +392,7 @@ def read_checkpoint(path: str, specs: Dict[str, object], expect_partial: bool = 
     for sk in slot_kinds:
         for name, spec in specs.items():
             k = f"{name}/.OPTIMIZER_SLOT/optimizer/{sk}{SUFFIX}"
-            if k in entries:
+            if k in entries and name in out:
                 slots[sk][name] = fetch(k, spec)
     if with_slots:
         hyper = {}
@@ -615,7 +620,7 @@ def _flat_slot(model, flat, k):
     return flat[o:o + model.params[k].numel()].view(model.params[k].shape)
 
 
-def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None):
+def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None, skip_mismatch=False):
     """Variables + optimizer state (reference train.py:131-136 `model.load_weights(latest)`): SGD `momentum` slots or
     Adam `m` / `v` slots into the model's flat slot buffers; the optimizer's hyper-parameter variables (`iter`, ...) are
     left in `model.optimizer_state` for the trainer (Trainer.resume restores its step counter from `iter`).
@@ -623,9 +628,19 @@ def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None):
     optimizer: the optimizer branch that will USE the slots ("sgd" | "adam" | None = whatever the bundle holds).  Slots of
     the other branch are not installed (Keras restores the variables and leaves a new optimizer's slots at zero): Adam's first
     moment is never SGD momentum or vice versa.  Whatever is installed is recorded in `model.slot_kind`, which
-    `apply_sgd` / `apply_adam` check before their first use of the buffers."""
-    sd, slots, hyper = read_checkpoint(path, model.specs, expect_partial=expect_partial, with_slots=("momentum", "m", "v"))
-    model.load_state_dict(sd)
+    `apply_sgd` / `apply_adam` check before their first use of the buffers.
+
+    skip_mismatch: variables whose bundle shape differs from the model's (fine-tuning a Kinetics-400 checkpoint into a
+    157-class model: fc2) are not loaded -- they keep their current values and their optimizer slots stay zero -- and
+    the list of their names is returned, with one warning.  By default such a variable raises ValueError and the model
+    is returned."""
+    skipped = [] if skip_mismatch else None
+    sd, slots, hyper = read_checkpoint(path, model.specs, expect_partial=expect_partial, with_slots=("momentum", "m", "v"),
+                                       skipped=skipped)
+    if skipped:
+        import warnings
+        warnings.warn(f"{len(skipped)} variables of {path} do not match the model's shapes and were not loaded: {skipped}")
+    model.load_state_dict(sd, strict=not skipped)
     kind = "adam" if slots["m"] or slots["v"] else "sgd" if slots["momentum"] else None
     model.flat_velocity.zero_()
     if getattr(model, "flat_second", None) is not None:
@@ -643,7 +658,7 @@ def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None):
                     _flat_slot(model, model.flat_second, k).copy_(v)
     model.slot_kind = kind if install else None
     model.optimizer_state = dict(hyper=hyper, kind=kind)
-    return model
+    return skipped if skip_mismatch else model
 
 
 def save_tf_checkpoint(model, prefix, optimizer_hyper=None, optimizer="sgd"):

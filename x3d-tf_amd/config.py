@@ -115,7 +115,8 @@ class CfgNode(dict):
 
 
 def get_default_config():
-    """Defaults with the keys and values of reference configs/default.py:3-140."""
+    """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
+    TEST.ENSEMBLE_METHOD (multi-label training)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -124,11 +125,14 @@ def get_default_config():
     c.DATA = CfgNode(dict(
         FRAME_RATE=1, TEMP_DURATION=1, NUM_INPUT_CHANNELS=3, TRAIN_JITTER_SCALES=[182, 228],
         TRAIN_CROP_SIZE=112, TEST_CROP_SIZE=160, MEAN=[0.45, 0.45, 0.45],
-        STD=[0.225, 0.225, 0.225]))
+        STD=[0.225, 0.225, 0.225],
+        # multi-label (Charades-style) datasets: sigmoid / binary cross-entropy head, multi-hot targets, mAP
+        MULTI_LABEL=False))
     c.TRAIN = CfgNode(dict(
         DATASET_SIZE=0, BATCH_SIZE=1, EPOCHS=1, OPTIMIZER="SGD", MOMENTUM=0.9, BASE_LR=0.1,
         WARMUP_EPOCHS=1, WARMUP_LR=0.01))
-    c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1))
+    # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
+    c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
         ENABLE=False, PROJECT_NAME="X3D-tf", GROUP_NAME=" ", MODE="online", TENSORBOARD=True))
     return c
@@ -146,6 +150,23 @@ def get_config(name, overrides=None, freeze=True):
     cfg.merge_from_file(config_path(name))
     if overrides:
         cfg.merge_from_list(list(overrides))
+    ensemble_method(cfg)
     if freeze:
         cfg.freeze()
     return cfg
+
+
+ENSEMBLE_METHODS = ("mean", "max")
+
+
+def multi_label(cfg) -> bool:
+    """cfg.DATA.MULTI_LABEL (False for a config tree without the key)."""
+    return bool(getattr(cfg.DATA, "MULTI_LABEL", False))
+
+
+def ensemble_method(cfg) -> str:
+    """cfg.TEST.ENSEMBLE_METHOD ("mean" for a config tree without the key); anything else raises ValueError."""
+    m = getattr(cfg.TEST, "ENSEMBLE_METHOD", "mean")
+    if m not in ENSEMBLE_METHODS:
+        raise ValueError(f"TEST.ENSEMBLE_METHOD must be one of {ENSEMBLE_METHODS}, not {m!r}")
+    return m

@@ -26,7 +26,7 @@ import struct
 import threading
 import warnings
 from concurrent.futures import ThreadPoolExecutor
-from typing import Callable, Dict, Iterable, Iterator, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -90,6 +90,12 @@ def _int64_feature(v: int) -> bytes:
     return _len(3, _len(1, _put_varint(v & 0xFFFFFFFFFFFFFFFF)))
 
 
+def _int64_list_feature(vs: Sequence[int]) -> bytes:
+    """Int64List of any length (packed; an empty list has no value field)"""
+    packed = b"".join(_put_varint(int(v) & 0xFFFFFFFFFFFFFFFF) for v in vs)
+    return _len(3, _len(1, packed) if vs else b"")
+
+
 def _bytes_feature(b: bytes) -> bytes:
     return _len(1, _len(1, b))
 
@@ -113,11 +119,17 @@ def decode_jpeg(data: bytes) -> np.ndarray:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def make_sequence_example(frames_u8: np.ndarray, class_id: int, quality: int = 90, encoded: Optional[List[bytes]] = None) -> bytes:
+def make_sequence_example(frames_u8: np.ndarray, class_id: Union[int, Sequence[int]], quality: int = 90,
+                          encoded: Optional[List[bytes]] = None) -> bytes:
     """create_tfrecords.py:48-82 `to_tf_example`: frames [F, H, W, 3] uint8 + label -> serialized SequenceExample
-    (`encoded`: already JPEG-encoded frames instead of `frames_u8`)."""
+    (`encoded`: already JPEG-encoded frames instead of `frames_u8`).  `class_id` may be a sequence of class ids (a
+    multi-label video, any number of them): they are written as one int64 list under video/class/label."""
     jpegs = encoded if encoded is not None else [encode_jpeg(f, quality) for f in frames_u8]
-    context = _map_entry("video/num_frames", _int64_feature(len(jpegs))) + _map_entry("video/class/label", _int64_feature(int(class_id)))
+    if isinstance(class_id, (int, np.integer)):
+        label = _int64_feature(int(class_id))
+    else:
+        label = _int64_list_feature([int(c) for c in class_id])
+    context = _map_entry("video/num_frames", _int64_feature(len(jpegs))) + _map_entry("video/class/label", label)
     flist = b"".join(_len(1, _bytes_feature(j)) for j in jpegs)
     return _len(1, context) + _len(2, _map_entry("video", flist))
 
@@ -139,7 +151,15 @@ def _int64_list(feature: bytes) -> List[int]:
 
 def parse_sequence_example(buf: bytes) -> Tuple[List[bytes], int, int]:
     """dataloader.py:63-88 `parse_and_decode` up to the JPEG decode: -> (JPEG strings of the frames, num_frames, label);
-    absent context features default to -1 as FixedLenFeature([], tf.int64, -1) does."""
+    absent context features default to -1 as FixedLenFeature([], tf.int64, -1) does.  Of a multi-label record this is
+    the first label (parse_sequence_example_labels returns them all)."""
+    frames, nf, lb = parse_sequence_example_labels(buf)
+    return frames, nf, (lb[0] if lb else -1)
+
+
+def parse_sequence_example_labels(buf: bytes) -> Tuple[List[bytes], int, List[int]]:
+    """parse_sequence_example with every label: -> (JPEG strings of the frames, num_frames, the video/class/label list,
+    empty when absent)."""
     top = _parse_proto(buf)
     ctx: Dict[str, bytes] = {}
     for feats in top.get(1, []):
@@ -157,7 +177,36 @@ def parse_sequence_example(buf: bytes) -> Tuple[List[bytes], int, int]:
             for feat in _parse_proto(e[2][0]).get(1, []):
                 for bl in _parse_proto(feat).get(1, []):
                     frames += _parse_proto(bl).get(1, [])
-    return frames, (nf[0] if nf else -1), (lb[0] if lb else -1)
+    return frames, (nf[0] if nf else -1), lb
+
+
+def parse_label_list(field: str) -> List[int]:
+    """The label field of a multi-label text line, "<l1>,<l2>,..." -> [l1, l2, ...] ("" -> [])."""
+    return [int(x) for x in field.split(",") if x.strip()]
+
+
+def multi_hot(label_lists: Sequence[Sequence[int]], num_classes: int, names: Optional[Sequence[str]] = None) -> torch.Tensor:
+    """[len(label_lists), num_classes] fp32 multi-hot targets on the host; a class id outside [0, num_classes) raises
+    ValueError naming its record (`names`)."""
+    t = torch.zeros((len(label_lists), num_classes), dtype=torch.float32)
+    for i, lbs in enumerate(label_lists):
+        for c in lbs:
+            if not 0 <= int(c) < num_classes:
+                who = names[i] if names is not None else f"#{i}"
+                raise ValueError(f"record {who}: class id {c} outside [0, {num_classes})")
+            t[i, int(c)] = 1.0
+    return t
+
+
+def _named_records(path: str, records: Iterator[bytes]) -> Iterator[Tuple[str, bytes]]:
+    """("<path>#<index in the file>", record) for every record of one file"""
+    for i, r in enumerate(records):
+        yield f"{path}#{i}", r
+
+
+def _label_of(labels: List[int], all_labels: bool):
+    """the label of a record: the first (-1 without one), or the whole list"""
+    return list(labels) if all_labels else int(labels[0] if labels else -1)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -182,7 +231,15 @@ class InputReader:
     cover the dataset) and yields batch_size // world clips per step -- `Trainer.fit`'s DATASET_SIZE // BATCH_SIZE steps
     are then one pass over the data, and the lr schedule sees the reference's epochs.  The file order is drawn from a
     generator seeded by `seed` alone (identical on every rank, or the shards would overlap: with world > 1 an unset seed
-    becomes 0); shuffle buffer and augmentation draws use (seed, rank)."""
+    becomes 0); shuffle buffer and augmentation draws use (seed, rank).
+
+    Multi-label mode (cfg.DATA.MULTI_LABEL): the second element of a batch is the targets [B, NUM_CLASSES] fp32
+    multi-hot on the device instead of the labels [B] -- built on the host from every label of the record
+    (`parse_sequence_example_labels`; text lines "<path> <l1>,<l2>,...") and copied with the batch.  A class id outside
+    [0, NUM_CLASSES) raises ValueError naming the record (TFRecords: "<file>#<index in the file>").  The random draws and
+    the batch order are those of the single-label mode."""
+
+    _multi = False        # multi-label mode (set from cfg in __init__)
 
     def __init__(self, cfg, is_training: bool, use_tfrecord: bool, mixed_precision: bool = False, device=None,
                  dtype: torch.dtype = torch.float32, seed: Optional[int] = None, decoder: Optional[Callable] = None,
@@ -217,13 +274,21 @@ class InputReader:
         if jpeg_decode == "device" and not self._use_tfrecord:
             raise ValueError("jpeg_decode='device' decodes the JPEG frames of TFRecords (use_tfrecord=True)")
         self._jpeg_decode = jpeg_decode
+        from .config import multi_label
+        self._multi = multi_label(cfg)
+        self._num_classes = int(cfg.NETWORK.NUM_CLASSES)
 
     # -- decode ------------------------------------------------------------------------------------
-    def decode_video(self, line: str) -> Tuple[np.ndarray, int]:
+    def decode_video(self, line: str) -> Tuple[np.ndarray, Union[int, List[int]]]:
         """dataloader.py:29-61: "<path> <label>" -> (all frames uint8 [F, H, W, 3], label); an undecodable video becomes
-        zeros [100, 240, 144, 3] with a warning, as in the reference."""
+        zeros [100, 240, 144, 3] with a warning, as in the reference.  Multi-label mode: "<path> <l1>,<l2>,..." -> the
+        list of class ids."""
         parts = line.strip().split(" ")
-        path, label = parts[0], int(parts[1])
+        path = parts[0]
+        if self._multi:
+            label = parse_label_list(parts[1] if len(parts) > 1 else "")
+        else:
+            label = int(parts[1])
         try:
             if self._decoder is None:
                 raise RuntimeError("no video decoder configured (the reference uses decord, which is not installed): "
@@ -236,19 +301,22 @@ class InputReader:
             video = np.zeros(FAILED_VIDEO_SHAPE, np.uint8)
         return video, label
 
-    def parse_and_decode(self, serialized_example: bytes) -> Tuple[np.ndarray, int]:
-        """dataloader.py:63-88: SequenceExample -> (video uint8 [num_frames, H, W, 3], label)."""
-        jpegs, num_frames, label = parse_sequence_example(serialized_example)
+    def parse_and_decode(self, serialized_example: bytes,
+                         all_labels: bool = False) -> Tuple[np.ndarray, Union[int, List[int]]]:
+        """dataloader.py:63-88: SequenceExample -> (video uint8 [num_frames, H, W, 3], label); all_labels: the record's
+        list of labels instead (multi-label mode)."""
+        jpegs, num_frames, labels = parse_sequence_example_labels(serialized_example)
         n = num_frames if num_frames >= 0 else len(jpegs)
-        return np.stack([decode_jpeg(j) for j in jpegs[:n]]), int(label)
+        return np.stack([decode_jpeg(j) for j in jpegs[:n]]), _label_of(labels, all_labels)
 
-    def parse_frames(self, serialized_example: bytes) -> Tuple[Tuple[List[bytes], int, int], int]:
+    def parse_frames(self, serialized_example: bytes,
+                     all_labels: bool = False) -> Tuple[Tuple[List[bytes], int, int], Union[int, List[int]]]:
         """jpeg_decode="device": SequenceExample -> ((the num_frames JPEG strings, H, W), label), no pixel decoded.  The
         headers of all frames are read (one library call): a video whose frames differ in size fails as np.stack fails
         in the host mode, and a frame whose header does not parse is handed to `decode_jpeg`, which raises as it does
         there."""
         from .jpeg import parse_headers
-        jpegs, num_frames, label = parse_sequence_example(serialized_example)
+        jpegs, num_frames, labels = parse_sequence_example_labels(serialized_example)
         n = num_frames if num_frames >= 0 else len(jpegs)
         jpegs = [bytes(j) for j in jpegs[:n]]
         if not jpegs:
@@ -260,7 +328,7 @@ class InputReader:
         if len(shapes) > 1:
             raise ValueError("all input arrays must have the same shape")
         h, w = shapes.pop()
-        return (jpegs, int(h), int(w)), int(label)
+        return (jpegs, int(h), int(w)), _label_of(labels, all_labels)
 
     # -- stages ------------------------------------------------------------------------------------
     def _shuffle(self, it: Iterator, size: int) -> Iterator:
@@ -285,6 +353,8 @@ class InputReader:
             if self._is_training:
                 files = [files[i] for i in self._rng_files.permutation(len(files))]     # list_files(shuffle=True)
             its = [read_tfrecords(f) for f in files]
+            if self._multi:      # records carry their name (for the class-id check of process_batch)
+                its = [_named_records(f, it) for f, it in zip(files, its)]
 
             def interleave():                    # cycle over the open files, one record each (dataloader.py:149-155)
                 live = list(its)
@@ -304,6 +374,8 @@ class InputReader:
             # the rank-independent generator BEFORE the split -- every rank sees every video over the epochs, as the
             # replicas of the reference's one shuffled dataset do (a per-rank shuffle of a fixed shard would not)
             lines = [lines[i] for i in self._rng_files.permutation(len(lines))]
+        if self._multi:
+            lines = [(ln.strip().split(" ")[0], ln) for ln in lines]
         return self._shard(iter(lines), batch_size)
 
     def _shard(self, it: Iterator, local_batch: Optional[int] = None) -> Iterator:
@@ -342,6 +414,13 @@ class InputReader:
         fn = self.decode_video
         if self._use_tfrecord:
             fn = self.parse_frames if self._jpeg_decode == "device" else self.parse_and_decode
+        if self._multi:          # (name, record) -> (video, (name, labels))
+            base = fn
+            kw = dict(all_labels=True) if self._use_tfrecord else {}
+
+            def fn(item):
+                video, labels = base(item[1], **kw)
+                return video, (item[0], labels)
         with ThreadPoolExecutor(self._workers) as ex:
             while True:
                 pending: "queue.Queue" = queue.Queue()
@@ -367,7 +446,12 @@ class InputReader:
         return make_eval_views(v, self._cfg, dtype=self._dtype)
 
     def process_batch(self, clips: List[torch.Tensor], labels: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """dataloader.py:90-116: [B, T, S, S, 3] in training, [B * views * crops, T, S, S, 3] otherwise."""
+        """dataloader.py:90-116: [B, T, S, S, 3] in training, [B * views * crops, T, S, S, 3] otherwise.  Multi-label
+        mode: `labels` holds (record name, class ids) pairs and become the multi-hot targets [B, NUM_CLASSES]."""
+        if self._multi:
+            names = [nm for nm, _ in labels]
+            targets = multi_hot([lbs for _, lbs in labels], self._num_classes, names)
+            return torch.cat(clips, 0), targets.to(self._device, non_blocking=True)
         return torch.cat(clips, 0), torch.tensor(labels, dtype=torch.int64, device=self._device)
 
     def _device_batch(self, items: List[Tuple[List[bytes], int, int]], labels: List[int]):

@@ -1,7 +1,10 @@
 """Evaluation driver: the part of the reference's eval.py (:75-89) that runs after the model is built --
 `model.load_weights(latest_checkpoint).expect_partial()`, then `model.evaluate(...)` with
 SparseCategoricalCrossentropy, SparseCategoricalAccuracy ('acc') and SparseTopKCategoricalAccuracy(k=5)
-('top_5_acc') (eval.py:48-66).  Videos come as decoded uint8 tensors; the views are built on the GPU (views.py)."""
+('top_5_acc') (eval.py:48-66).  Videos come as decoded uint8 tensors; the views are built on the GPU (views.py).
+
+With DATA.MULTI_LABEL the model's outputs are per-class sigmoids and the metrics are the binary cross-entropy and the mean
+average precision over the classes (`DeviceMAP`, x3d_multilabel_ap)."""
 from typing import Dict, Iterable, Tuple
 
 import torch
@@ -96,19 +99,105 @@ class DeviceMetrics:
         return {"loss": loss / d + reg, "acc": top1 / d, "top_5_acc": topk / d, "videos": int(round(n))}
 
 
+class DeviceMAP:
+    """Mean average precision of a multi-label evaluation: `update` appends the batch's probabilities and targets to device
+    buffers (a device copy, no host read), `result()` runs x3d_multilabel_ap once over everything seen.
+
+    result(): {"loss", "mAP", "videos", "classes"} -- loss = Keras BinaryCrossentropy of the probabilities, q = clip(p,
+    1e-7, 1 - 1e-7), -(y log q + (1 - y) log(1 - q)) averaged over classes and videos in fp64, plus the L2 term; mAP = the
+    mean of the per-class AP over the `classes` classes with a positive (classes without one are dropped, as SlowFast's
+    get_map does; a NaN score makes its class's AP and so the mAP NaN)."""
+
+    def __init__(self, reg_loss=0.0):
+        self.reg_loss = reg_loss      # float, or a device tensor (model.regularization_loss()): read in result()
+        self._scores = []
+        self._targets = []
+
+    def update(self, probs: torch.Tensor, targets: torch.Tensor):
+        """probs [videos, classes] fp32 on the GPU; targets [videos, classes] (float / uint8 / bool, moved to probs' device)."""
+        if probs.dim() != 2 or tuple(targets.shape) != tuple(probs.shape):
+            raise ValueError(f"DeviceMAP: probs {tuple(probs.shape)} and targets {tuple(targets.shape)} must be one [N, M] shape")
+        self._scores.append(probs.detach().to(torch.float32, copy=True))      # the model's output buffer is reused
+        self._targets.append(targets.detach().to(probs.device, torch.float32, non_blocking=True, copy=True))
+
+    def _cat(self):
+        if len(self._scores) > 1:
+            self._scores = [torch.cat(self._scores, 0)]
+            self._targets = [torch.cat(self._targets, 0)]
+        return (self._scores[0], self._targets[0]) if self._scores else (None, None)
+
+    def all_reduce_(self, group=None, device=None):
+        """All-gathers the scores and targets of every rank in rank order (no-op without a multi-rank process group).
+        The shards are of equal size: the reader drops the trailing partial global batch (InputReader._shard)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        s, t = self._cat()
+        if s is None:
+            raise ValueError("DeviceMAP.all_reduce_: no batch on this rank")
+        if device is None:
+            device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+        world = dist.get_world_size(group)
+        out = []
+        for x in (s, t):
+            xs = x.to(device)
+            parts = [torch.empty_like(xs) for _ in range(world)]
+            dist.all_gather(parts, xs, group=group)
+            out.append(torch.cat(parts, 0).to(s.device))
+        self._scores, self._targets = [out[0]], [out[1]]
+        return self
+
+    def result(self) -> Dict[str, float]:
+        from . import ops
+        s, t = self._cat()
+        reg = float(self.reg_loss.item()) if torch.is_tensor(self.reg_loss) else float(self.reg_loss)
+        if s is None:
+            return {"loss": float("nan"), "mAP": float("nan"), "videos": 0, "classes": 0}
+        ap, npos = ops.multilabel_ap(s, t)
+        q = s.double().clamp(1e-7, 1.0 - 1e-7)
+        y = t.double()
+        loss = float((-(y * q.log() + (1.0 - y) * (1.0 - q).log())).mean())
+        ap, npos = ap.cpu(), npos.cpu()
+        have = npos > 0
+        m_ap = float(ap[have].mean()) if bool(have.any()) else float("nan")
+        return {"loss": loss + reg, "mAP": m_ap, "videos": int(s.shape[0]), "classes": int(have.sum())}
+
+
+def _targets_of(label, num_classes: int) -> torch.Tensor:
+    """a multi-label video's label: a [classes] target tensor / array, or class ids (an int or a sequence of them)"""
+    import numpy as np
+    if torch.is_tensor(label) or isinstance(label, np.ndarray):
+        t = torch.as_tensor(label).float().cpu()
+        if t.dim() == 1 and t.shape[0] == num_classes:
+            return t
+        if t.dim() != 1:
+            raise ValueError(f"multi-label target of shape {tuple(t.shape)}, expected [{num_classes}]")
+        label = t.long().tolist()
+    from .dataloader import multi_hot
+    ids = [int(label)] if isinstance(label, (int, np.integer)) else [int(c) for c in label]
+    return multi_hot([ids], num_classes)[0]
+
+
 def evaluate(model, cfg, videos: Iterable[Tuple[torch.Tensor, int]], batch_videos: int = None) -> Dict[str, float]:
     """videos: iterable of (uint8 [F, H, W, 3] GPU tensor, label).  Batches `batch_videos` videos
-    (default cfg.TEST.BATCH_SIZE) of views x crops clips each through `model(clips, training=False)`."""
+    (default cfg.TEST.BATCH_SIZE) of views x crops clips each through `model(clips, training=False)`.  Multi-label models
+    (DATA.MULTI_LABEL): label = the video's class ids (an int or a sequence) or its [classes] targets; returns the
+    DeviceMAP result."""
     bv = int(batch_videos or cfg.TEST.BATCH_SIZE)
     nv = num_views(cfg)
     # `model.evaluate` reports cross-entropy + the model's regularisation losses (weight_decay * sum w^2, model.py:47)
-    m = Metrics(float(model.regularization_loss().item()) if hasattr(model, "regularization_loss") else 0.0)
+    reg = float(model.regularization_loss().item()) if hasattr(model, "regularization_loss") else 0.0
+    multi = bool(getattr(model, "multi_label", False))
+    m = DeviceMAP(reg) if multi else Metrics(reg)
     clips, labels = [], []
 
     def flush():
         if clips:
             probs = model(torch.cat(clips, 0), training=False)
-            m.update(probs.float(), torch.tensor(labels))
+            if multi:
+                m.update(probs.float(), torch.stack(labels).to(probs.device))
+            else:
+                m.update(probs.float(), torch.tensor(labels))
             clips.clear()
             labels.clear()
 
@@ -116,7 +205,7 @@ def evaluate(model, cfg, videos: Iterable[Tuple[torch.Tensor, int]], batch_video
         c = make_eval_views(video, cfg, dtype=model.dtype)
         assert c.shape[0] == nv
         clips.append(c)
-        labels.append(int(label))
+        labels.append(_targets_of(label, model.num_classes) if multi else int(label))
         if len(clips) == bv:
             flush()
     flush()
@@ -130,8 +219,11 @@ def evaluate_dataset(model, cfg, batches: Iterable[Tuple[torch.Tensor, torch.Ten
     `batches` yields (clips [B * views * crops, T, S, S, 3], labels [B]) as `dataloader.InputReader` does in evaluation
     mode (the views were built on the GPU while the batch was assembled).  Under torchrun the reader hands every rank its
     share of each global batch; the counters are summed over the ranks ONCE at the end, so every rank returns the metric of
-    the whole dataset (the same videos the single-process run evaluates: the reader drops the same trailing partial batch)."""
-    m = Metrics(float(model.regularization_loss().item()) if hasattr(model, "regularization_loss") else 0.0)
+    the whole dataset (the same videos the single-process run evaluates: the reader drops the same trailing partial batch).
+    Multi-label models: `batches` yield (clips, targets [B, classes]) and the result is DeviceMAP's (the scores and targets
+    of all ranks are gathered once)."""
+    reg = float(model.regularization_loss().item()) if hasattr(model, "regularization_loss") else 0.0
+    m = DeviceMAP(reg) if getattr(model, "multi_label", False) else Metrics(reg)
     dev = None
     for clips, labels in batches:
         m.update(model(clips, training=False).float(), labels)

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X3D_HIP_LIB") or os.path.join(_HERE, "libx3d_hip.so")   # X3D_HIP_LIB: A/B builds (tools/build_variant.sh)
 
-ABI_VERSION = 135   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
+ABI_VERSION = 136   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = 0, 1, 2, 3
@@ -137,6 +137,8 @@ class JpegDecodeArgs(C.Structure):
                 ("status", _vp)]
 
 
+AP_MAX_POSITIVES = 32768   # X3D_AP_MAX_POSITIVES
+
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = 0, 1, 2, 3, 4
 
 
@@ -191,6 +193,9 @@ _SIGS = {
     "x3d_softmax_xent": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
     "x3d_view_mean": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "x3d_topk_metrics": ([_vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
+    "x3d_sigmoid_bce": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
+    "x3d_view_max": ([_vp, _vp, _i, _i, _i, _vp], _i),
+    "x3d_multilabel_ap": ([_vp, _vp, _i, _i, _vp, _vp, _vp], _i),
     "x3d_sgd_nesterov": ([_vp, _vp, _vp, _vp, _f, _f, _f, _f, _ll, _vp], _i),
     "x3d_adam": ([_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _ll, _ll, _vp], _i),
     "x3d_all_finite": ([_vp, _ll, _vp, _vp], _i),

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import hip
+from .config import ensemble_method, multi_label
 from .arch import Arch, BlockSpec, ParamSpec, block_prefix, build_arch, param_specs, same_pad, summary_rows
 from .hip import (ACT_NONE, ACT_RELU, ACT_SWISH, EPI_ADD, EPI_ADD_STRIDED, EPI_STORE, EPI_SWISH_BWD)
 from .params import init_params
@@ -335,6 +336,10 @@ class X3D:
         self.arch: Arch = build_arch(cfg)
         self.num_classes = self.arch.num_classes
         self._num_preds = self.arch.num_preds
+        # DATA.MULTI_LABEL: sigmoid / binary cross-entropy head on [N, classes] targets instead of softmax on labels;
+        # TEST.ENSEMBLE_METHOD: mean (x3d_view_mean) or max (x3d_view_max) over the views x crops of a video
+        self.multi_label = multi_label(cfg)
+        self.ensemble_method = ensemble_method(cfg)
         self._bn_cfg = cfg.NETWORK.BN
         self.dtype = dtype
         self.in_channels = in_channels
@@ -528,12 +533,16 @@ class X3D:
             elif strict:
                 raise KeyError(f"unexpected parameter {k}")
 
-    def load_weights(self, path, expect_partial=True, optimizer=None):
+    def load_weights(self, path, expect_partial=True, optimizer=None, skip_mismatch=False):
         """Keras-style ``load_weights`` on a TF tensor-bundle checkpoint prefix or directory
         (reference train.py:131-143, eval.py:78-81).  optimizer: "sgd" | "adam" -- the branch that will use the
-        optimizer slots (slots written by the other branch are left at zero); None installs what the bundle holds."""
+        optimizer slots (slots written by the other branch are left at zero); None installs what the bundle holds.
+        skip_mismatch: variables whose bundle shape differs from the model's (a 400-class fc2 loaded into a 157-class
+        model) keep their current values and zero optimizer slots instead of raising; their names are returned (with one
+        warning).  Returns the model, or with skip_mismatch=True the list of skipped variable names."""
         from .checkpoint import load_tf_checkpoint
-        return load_tf_checkpoint(self, path, expect_partial=expect_partial, optimizer=optimizer)
+        return load_tf_checkpoint(self, path, expect_partial=expect_partial, optimizer=optimizer,
+                                  skip_mismatch=skip_mismatch)
 
     def _claim_slots(self, kind):
         """The slot buffers hold state of ONE optimizer branch (`slot_kind`: set by load_weights, then by the first update).
@@ -730,9 +739,7 @@ class X3D:
         pl.rec(F, "x3d_dense_fwd", pl.pooled, None, 1.0, p["fc1/kernel"], None, pl.h1, ACT_RELU, n, c5, a.fc1_out)
         pl.rec(F, "x3d_dense_fwd", pl.h1, None, 1.0, p["fc2/kernel"], p["fc2/bias"], pl.logits, ACT_NONE, n, a.fc1_out,
                a.num_classes)
-        pl.rec(F, "x3d_softmax_xent", pl.logits, None, pl.probs, None, None, 1.0, n, a.num_classes)
-        pl.out = pl.f32(n // a.num_preds, a.num_classes)
-        pl.rec(F, "x3d_view_mean", pl.probs, pl.out, n // a.num_preds, a.num_preds, a.num_classes)
+        self._rec_infer_head(pl, F, n)
         items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
         pl.bn_eval_table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
         F[0] = ("x3d_bn_eval_coef_batched", pl.lib.x3d_bn_eval_coef_batched,
@@ -965,20 +972,24 @@ class X3D:
         pl.rec(F, "x3d_dense_fwd", pl.h1, pl.drop_mask, float(pl.drop_scale), p["fc2/kernel"], p["fc2/bias"],
                pl.logits, ACT_NONE, n, a.fc1_out, a.num_classes)
         if training:
-            pl.labels = torch.zeros(n, dtype=torch.int32, device=self.device)
             pl.loss_rows = pl.f32(n)
             pl.dlogits = pl.f32(n, a.num_classes)
             pl.grad_scale_slot = len(F)
-            pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
-                   a.num_classes)
+            if self.multi_label:
+                pl.labels = None
+                pl.targets = torch.zeros(n, a.num_classes, dtype=torch.float32, device=self.device)
+                pl.rec(F, "x3d_sigmoid_bce", pl.logits, pl.targets, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
+                       a.num_classes)
+            else:
+                pl.labels = torch.zeros(n, dtype=torch.int32, device=self.device)
+                pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
+                       a.num_classes)
             self._record_backward(pl)
         else:
-            pl.rec(F, "x3d_softmax_xent", pl.logits, None, pl.probs, None, None, 1.0, n, a.num_classes)
             if n % a.num_preds:
                 raise ValueError(f"inference batch {n} is not a multiple of views*crops={a.num_preds} "
                                  "(reference model.py:125)")
-            pl.out = pl.f32(n // a.num_preds, a.num_classes)
-            pl.rec(F, "x3d_view_mean", pl.probs, pl.out, n // a.num_preds, a.num_preds, a.num_classes)
+            self._rec_infer_head(pl, F, n)
 
         if not training:
             items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
@@ -995,6 +1006,23 @@ class X3D:
         self._resolve(pl, pl.bwd)
         pl.wrap_side(pl.bwd)
         return pl
+
+    def _rec_infer_head(self, pl: _Plan, F, n):
+        """probabilities of the logits (softmax, or sigmoid with DATA.MULTI_LABEL), then the views x crops of every video
+        combined by TEST.ENSEMBLE_METHOD (mean, or element-wise max) into pl.out [n / num_preds, classes]"""
+        a = self.arch
+        if self.multi_label:
+            pl.rec(F, "x3d_sigmoid_bce", pl.logits, None, pl.probs, None, None, 1.0, n, a.num_classes)
+        else:
+            pl.rec(F, "x3d_softmax_xent", pl.logits, None, pl.probs, None, None, 1.0, n, a.num_classes)
+        pl.out = pl.f32(n // a.num_preds, a.num_classes)
+        views = "x3d_view_max" if self.ensemble_method == "max" else "x3d_view_mean"
+        pl.rec(F, views, pl.probs, pl.out, n // a.num_preds, a.num_preds, a.num_classes)
+
+    def _head_probs_only(self, pl: _Plan, n):
+        """probabilities of a training plan's logits without a loss (call(training=True))"""
+        name = "x3d_sigmoid_bce" if self.multi_label else "x3d_softmax_xent"
+        hip.call(name, pl.logits.data_ptr(), None, pl.probs.data_ptr(), None, None, 1.0, n, self.num_classes)
 
     @staticmethod
     def _resolve(pl: _Plan, lst):
@@ -1454,7 +1482,8 @@ class X3D:
 
     def call(self, input, training=False):
         """Forward pass (reference model.py:113-127).  Returns fp32 probabilities: ``[N, classes]`` when
-        training, ``[N / (views*crops), classes]`` (view-averaged) otherwise."""
+        training, ``[N / (views*crops), classes]`` (views combined by TEST.ENSEMBLE_METHOD) otherwise.  With
+        DATA.MULTI_LABEL the probabilities are per-class sigmoids instead of a softmax."""
         n, t, h, w, _ = input.shape
         pl = self._plan(n, t, h, w, training)
         self._bind_input(pl, input)
@@ -1462,10 +1491,9 @@ class X3D:
         if training:
             pl.zero_buf.zero_()
             self._draw_dropout(pl)
-            # forward only: stop before the loss kernel (labels unknown); softmax without labels
+            # forward only: stop before the loss kernel (labels unknown); softmax (sigmoid) without labels
             pl.run(pl.fwd, 0, pl.grad_scale_slot)
-            hip.call("x3d_softmax_xent", pl.logits.data_ptr(), None, pl.probs.data_ptr(), None, None, 1.0, n,
-                     self.num_classes)
+            self._head_probs_only(pl, n)
             return pl.probs
         pl.zero_buf.zero_()
         pl.run(pl.fwd)
@@ -1474,6 +1502,9 @@ class X3D:
     def forward_backward(self, input, labels, global_batch=None, on_stage_done=None, loss_scale=1.0):
         """One training forward + backward.  Fills ``self.grads`` (data gradients only; the L2 term is
         applied by the optimizer), updates BN moving statistics, returns the plan (loss_rows, probs).
+
+        labels: [N] class indices; with DATA.MULTI_LABEL the targets [N, classes] in [0, 1] (float, uint8 or bool;
+            multi-hot or soft), and the loss is Keras BinaryCrossentropy on sigmoid outputs (x3d_sigmoid_bce).
 
         global_batch: divisor of the loss mean (defaults to the local batch; data-parallel callers pass
             world_size * local batch so that summing gradients over ranks gives the global mean).
@@ -1487,10 +1518,13 @@ class X3D:
         n, t, h, w, _ = input.shape
         pl = self._plan(n, t, h, w, True)
         self._bind_input(pl, input)
-        if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
-            if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
-                raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
-        pl.labels.copy_(labels.to(self.device, non_blocking=True).to(torch.int32))
+        if self.multi_label:
+            self._bind_targets(pl, labels, n)
+        else:
+            if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
+                if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
+                    raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
+            pl.labels.copy_(labels.to(self.device, non_blocking=True).to(torch.int32))
         # (round 4: the panel packing, the gradient-buffer zeroing and the dropout draw -- ~70 us the stem does not depend on -- on a
         # second stream beside the stem's two convolutions, joined in front of the first pointwise conv: 22.30 -> 22.63 ms per step,
         # three alternating runs on one box; the fork / join costs more than it hides.  Not kept.)
@@ -1500,8 +1534,12 @@ class X3D:
         self._draw_dropout(pl)
         gb = float(global_batch or n)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
-        hip.call("x3d_softmax_xent", pl.logits.data_ptr(), pl.labels.data_ptr(), pl.probs.data_ptr(),
-                 pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+        if self.multi_label:
+            hip.call("x3d_sigmoid_bce", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+        else:
+            hip.call("x3d_softmax_xent", pl.logits.data_ptr(), pl.labels.data_ptr(), pl.probs.data_ptr(),
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
         if on_stage_done is None:
             pl.run(pl.bwd)
         else:
@@ -1513,6 +1551,21 @@ class X3D:
                 on_stage_done(stage)
                 start = stop
         return pl
+
+    def _bind_targets(self, pl: _Plan, targets, n):
+        """multi-label targets [n, classes] (float / uint8 / bool) -> pl.targets fp32.  Host targets are checked for shape
+        and range (they are on the host anyway); device targets for shape only."""
+        if not torch.is_tensor(targets):
+            targets = torch.as_tensor(targets)
+        if tuple(targets.shape) != (n, self.num_classes):
+            raise ValueError(f"multi-label targets must be [{n}, {self.num_classes}], got {tuple(targets.shape)}")
+        if not (targets.dtype.is_floating_point or targets.dtype in (torch.uint8, torch.bool)):
+            raise ValueError(f"multi-label targets must be float, uint8 or bool, got {targets.dtype}")
+        if not targets.is_cuda:
+            t = targets.float()
+            if not bool(torch.isfinite(t).all()) or float(t.min()) < 0.0 or float(t.max()) > 1.0:
+                raise ValueError("multi-label targets must lie in [0, 1]")
+        pl.targets.copy_(targets.to(self.device, non_blocking=True))
 
     def regularization_loss(self):
         """weight_decay * sum(w^2) over the L2-regularised kernels (reference model.py:47)."""

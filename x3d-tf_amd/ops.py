@@ -493,6 +493,74 @@ def topk_metrics(probs, labels, acc, k=5):
     return acc
 
 
+
+def _f32_2d(name, what, t, shape=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = f"[{shape[0]}, {shape[1]}]" if shape is not None else "[N, M]"
+        raise ValueError(f"{name}: {what} must be {want} float32, got {tuple(t.shape)} {t.dtype}")
+
+
+def sigmoid_bce(logits, targets, probs, loss_rows=None, dlogits=None, grad_scale=1.0):
+    """probs = sigmoid(logits); with targets [N, M] fp32 in [0, 1]: loss_rows [N] = Keras BinaryCrossentropy per row,
+    dlogits = grad_scale * (probs - targets) / M (x3d_sigmoid_bce: the rules are in include/x3d_hip.h).  targets=None
+    computes probs only.  One launch, does not synchronise."""
+    _chk(logits, targets, probs, loss_rows, dlogits)
+    _f32_2d("sigmoid_bce", "logits", logits)
+    n, m = logits.shape
+    _f32_2d("sigmoid_bce", "probs", probs, (n, m))
+    if targets is not None:
+        _f32_2d("sigmoid_bce", "targets", targets, (n, m))
+    elif loss_rows is not None or dlogits is not None:
+        raise ValueError("sigmoid_bce: loss_rows / dlogits need targets")
+    if dlogits is not None:
+        _f32_2d("sigmoid_bce", "dlogits", dlogits, (n, m))
+    if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() != n):
+        raise ValueError(f"sigmoid_bce: loss_rows must be {n} float32, got {loss_rows.numel()} {loss_rows.dtype}")
+    hip.call("x3d_sigmoid_bce", ptr(logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(dlogits),
+             float(grad_scale), n, m)
+    return probs
+
+
+def view_max(probs, out, views):
+    """out[v] = element-wise max of probs[v * views : (v + 1) * views] (NaN propagates)."""
+    _chk(probs, out)
+    _f32_2d("view_max", "probs", probs)
+    if probs.shape[0] % int(views) or int(views) < 1:
+        raise ValueError(f"view_max: {probs.shape[0]} rows are not a multiple of views = {views}")
+    _f32_2d("view_max", "out", out, (probs.shape[0] // int(views), probs.shape[1]))
+    hip.call("x3d_view_max", ptr(probs), ptr(out), out.shape[0], int(views), probs.shape[1])
+    return out
+
+
+def multilabel_ap(scores, targets, ap=None, npos=None, check=True):
+    """Per-class average precision of scores [N, M] fp32 against targets [N, M] fp32 (>= 0.5 = positive):
+    (ap [M] float64, npos [M] int32), x3d_multilabel_ap (the rules are in include/x3d_hip.h).  A class without positives
+    or with a NaN score has ap NaN.  One launch; it synchronises only when N > AP_MAX_POSITIVES and `check` is set, to
+    raise if a class has more positives than the kernel holds (npos < 0: never truncated)."""
+    _chk(scores, targets, ap, npos)
+    _f32_2d("multilabel_ap", "scores", scores)
+    n, m = scores.shape
+    _f32_2d("multilabel_ap", "targets", targets, (n, m))
+    if n < 1 or m < 1:
+        raise ValueError(f"multilabel_ap: empty [{n}, {m}]")
+    if n * m >= 2 ** 31:
+        raise ValueError(f"multilabel_ap: N * M = {n * m} >= 2^31")
+    if scores.device != targets.device:
+        raise ValueError("multilabel_ap: scores and targets must be on one device")
+    if ap is None:
+        ap = torch.empty(m, dtype=torch.float64, device=scores.device)
+    if npos is None:
+        npos = torch.empty(m, dtype=torch.int32, device=scores.device)
+    if ap.dtype != torch.float64 or ap.numel() != m or npos.dtype != torch.int32 or npos.numel() != m:
+        raise ValueError(f"multilabel_ap: ap must be {m} float64 and npos {m} int32")
+    hip.call("x3d_multilabel_ap", ptr(scores), ptr(targets), n, m, ptr(ap), ptr(npos))
+    if check and n > hip.AP_MAX_POSITIVES:
+        over = npos < 0
+        if bool(over.any()):
+            cls = over.nonzero().flatten().tolist()
+            raise ValueError(f"multilabel_ap: classes {cls[:5]} have more than {hip.AP_MAX_POSITIVES} positives")
+    return ap, npos
+
 def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
     _chk(w, v, g, l2_mask)
     hip.call("x3d_sgd_nesterov", ptr(w), ptr(v), ptr(g), ptr(l2_mask), float(lr), float(momentum),

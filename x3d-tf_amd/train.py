@@ -50,6 +50,8 @@ class SaveSchedule:
 
 
 TRAIN_METRICS = ("acc", "top_5_acc")
+MULTI_LABEL_METRICS = ("mAP",)
+_DEFAULT_METRICS = object()      # fit(metrics=...) default: TRAIN_METRICS, or MULTI_LABEL_METRICS for a multi-label model
 
 
 def _validation_source(validation_data, epochs_to_run: int):
@@ -105,9 +107,11 @@ class Trainer:
         self._stats_work = None
         xdist.broadcast_([model.flat_params, model.flat_velocity], 0, group)
         self.epoch = 0
+        self.skipped_keys = []                # variables of the pretrained checkpoint resume(skip_mismatch=True) did not load
 
     def step(self, clips, labels, lr: Optional[float] = None):
-        """clips: this replica's shard [B, T, H, W, 3]; labels [B].  Returns the plan (loss_rows, probs)."""
+        """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
+        plan (loss_rows, probs)."""
         m = self.model
         n = clips.shape[0]
         if lr is None:
@@ -140,7 +144,7 @@ class Trainer:
 
     def fit(self, dataset, epochs: Optional[int] = None, steps_per_epoch: Optional[int] = None, model_dir: Optional[str] = None,
             initial_epoch: Optional[int] = None, on_step=None, validation_data=None, validation_steps: Optional[int] = None,
-            metrics=TRAIN_METRICS, save_freq="epoch"):
+            metrics=_DEFAULT_METRICS, save_freq="epoch"):
         """The loop `model.fit(dataset, epochs, steps_per_epoch, initial_epoch, validation_data, callbacks)` runs in reference
         train.py:145-152, with the metrics it was compiled with (train.py:102-108), its LearningRateScheduler (per-epoch
         `lr_schedule`, train.py:114-125) and ModelCheckpoint (utils.py:128-132) callbacks -- nothing else of the Keras harness
@@ -159,18 +163,28 @@ class Trainer:
             after every step (skipped fp16 steps too, as Keras updates compiled metrics), read once per epoch.
         save_freq: "epoch" or a positive int (`SaveSchedule`); rank 0 writes the checkpoints into `model_dir`.
 
+        Multi-label models (DATA.MULTI_LABEL): batches are (clips, targets [B, classes]); `metrics` defaults to ("mAP",) --
+            the mean average precision of the epoch's training probabilities (evaluate.DeviceMAP), "acc" / "top_5_acc" are
+            refused -- and validation fills `val_loss` / `val_mAP`.
+
         self.history: per-epoch lists like keras.callbacks.History.history -- `loss` (= the returned list), `lr`, the
         requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating."""
-        from .evaluate import DeviceMetrics
+        from .evaluate import DeviceMAP, DeviceMetrics
         tr = self.cfg.TRAIN
         epochs = int(tr.EPOCHS if epochs is None else epochs)
         steps = int(steps_per_epoch if steps_per_epoch is not None else tr.DATASET_SIZE // tr.BATCH_SIZE)
         if steps <= 0:
             raise ValueError("steps_per_epoch must be positive (cfg.TRAIN.DATASET_SIZE // cfg.TRAIN.BATCH_SIZE)")
+        multi = bool(getattr(self.model, "multi_label", False))
+        known = MULTI_LABEL_METRICS if multi else TRAIN_METRICS
+        if metrics is _DEFAULT_METRICS:
+            metrics = known
         metrics = tuple(metrics or ())
-        unknown = [k for k in metrics if k not in TRAIN_METRICS]
+        unknown = [k for k in metrics if k not in known]
         if unknown:
-            raise ValueError(f"unknown metrics {unknown}: fit computes {TRAIN_METRICS}")
+            kind = "a multi-label model" if multi else "fit"
+            raise ValueError(f"unknown metrics {unknown}: {kind} computes {known}")
+        val_keys = ("loss",) + known
         schedule = SaveSchedule(save_freq)
         if initial_epoch is not None:
             self.epoch = int(initial_epoch)
@@ -180,18 +194,18 @@ class Trainer:
         self.history = {"loss": [], "lr": []}
         self.history.update({k: [] for k in metrics})
         if val_source is not None:
-            self.history.update({"val_loss": [], "val_acc": [], "val_top_5_acc": []})
+            self.history.update({"val_" + k: [] for k in val_keys})
         writer = model_dir is not None and xdist.env_world()[0] == 0
         while self.epoch < epochs:
             lr = lr_schedule(self.epoch, self.cfg)
             tot = torch.zeros((), dtype=torch.float64, device=self.model.device)
-            train_m = DeviceMetrics() if metrics else None
+            train_m = (DeviceMAP() if multi else DeviceMetrics()) if metrics else None
             for _ in range(steps):
                 clips, labels = next(it)
                 pl = self.step(clips, labels, lr)
                 tot += self.loss(pl).double()
                 if train_m is not None:
-                    train_m.update(pl.probs, pl.labels)
+                    train_m.update(pl.probs, pl.targets if multi else pl.labels)
                 if on_step is not None:
                     on_step(self, pl)
                 ckpt = schedule.after_batch(self.epoch)
@@ -208,7 +222,7 @@ class Trainer:
                     self.history[k].append(r[k])
             if val_source is not None:
                 r = self.validate(val_source(), validation_steps)
-                for k in ("loss", "acc", "top_5_acc"):
+                for k in val_keys:
                     self.history["val_" + k].append(r[k])
             if ckpt is not None and writer:
                 self.save_checkpoint(model_dir, ckpt)
@@ -218,11 +232,12 @@ class Trainer:
         """`model.evaluate` inside `fit` (reference train.py:148-151): `model(clips, training=False)` over `batches` (the
         first `steps` of them when given) into a DeviceMetrics, counters summed over the ranks once.  Unlike
         `evaluate_dataset` this releases no plan, so the training plan is still cached in the next epoch.  Returns
-        {"loss", "acc", "top_5_acc", "videos"}."""
+        {"loss", "acc", "top_5_acc", "videos"}; for a multi-label model the DeviceMAP result {"loss", "mAP", "videos",
+        "classes"} (batches of (clips, targets))."""
         import itertools
-        from .evaluate import DeviceMetrics
+        from .evaluate import DeviceMAP, DeviceMetrics
         m = self.model
-        dm = DeviceMetrics(m.regularization_loss())
+        dm = (DeviceMAP if getattr(m, "multi_label", False) else DeviceMetrics)(m.regularization_loss())
         it = iter(batches)
         try:
             for clips, labels in itertools.islice(it, None if steps is None else int(steps)):
@@ -277,12 +292,14 @@ class Trainer:
         self.model.save_weights(prefix, optimizer_hyper=hyper, optimizer=self.optimizer)
         return prefix
 
-    def resume(self, model_dir: str, pretrained_ckpt: Optional[str] = None) -> int:
+    def resume(self, model_dir: str, pretrained_ckpt: Optional[str] = None, skip_mismatch: bool = False) -> int:
         """train.py:131-143: load the latest `ckpt-<epoch>` of `model_dir` if there is one; returns the epoch to
         continue from (0 without a checkpoint) and sets `self.epoch`.  Without one, `pretrained_ckpt` (the reference's
         --pretrained_ckpt) is loaded when given -- a directory through its latest checkpoint (FileNotFoundError when it
         holds none), anything else as a checkpoint prefix -- with the same optimizer-slot and `iter` rules, and training
-        starts at epoch 0."""
+        starts at epoch 0.  skip_mismatch applies to `pretrained_ckpt` only: its variables whose shapes differ from the
+        model's (a Kinetics-400 fc2 in a 157-class model) are not loaded (model.load_weights(skip_mismatch=True)); the
+        names skipped are in `self.skipped_keys`."""
         import os
         from .checkpoint import latest_checkpoint
         path = latest_checkpoint(model_dir)
@@ -293,7 +310,7 @@ class Trainer:
                 if not found:
                     raise FileNotFoundError(f"pretrained_ckpt {pre}: the directory holds no checkpoint")
                 pre = found
-            self._load(pre)
+            self._load(pre, skip_mismatch=skip_mismatch)
             self.epoch = 0
             return 0
         if not path:
@@ -302,10 +319,13 @@ class Trainer:
         self.epoch = int(os.path.basename(path).split("-")[1])
         return self.epoch
 
-    def _load(self, path: str):
+    def _load(self, path: str, skip_mismatch: bool = False):
         """Weights + this optimizer branch's slots from the checkpoint prefix `path`; sets `opt_step` from its `iter`."""
         m = self.model
-        m.load_weights(path, optimizer=self.optimizer)   # weights + this branch's optimizer slots; unknown keys tolerated as Keras does
+        if skip_mismatch:
+            self.skipped_keys = m.load_weights(path, optimizer=self.optimizer, skip_mismatch=True)
+        else:
+            m.load_weights(path, optimizer=self.optimizer)   # weights + this branch's optimizer slots; unknown keys tolerated as Keras does
         st = getattr(m, "optimizer_state", None) or {}
         kind = st.get("kind")
         if kind is not None and kind != self.optimizer:
