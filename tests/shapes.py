@@ -543,6 +543,144 @@ def pw_full_struct(case):
     return a
 
 
+# ---- every other launch of the same plans (tests/test_full_size_gpu.py: test_aux_full_size; tests/test_dispatch_coverage.py
+# keeps the list complete): BatchNorm bookkeeping, the residual tail's backward, squeeze-excite with the slab reductions it
+# carries, the head, the loss.  One key per launch form, read from the recorded arguments (C ABI order; the struct for
+# x3d_se_bnb_bwd), with every argument that picks an instantiation (the dtype, P -- VEC and the small-plane tail_bwd -- and
+# the null / non-null optional pointers):
+#   ("tail_bwd", dtype, N, C, P, has_r)                   ("relu_bn_bwd_reduce", dtype, N, C, P, "dy" | "dpool", g_written)
+#   ("pool_fwd", dtype, N, C, P)                          ("subsample2", dtype, planes, H, W)
+#   ("se_fwd", N, C, Wd, P)                               ("se_bnb_bwd", N, C, Wd, P, has_se, ((slab parts, elems), ...))
+#   ("dense_fwd", N, K, M, act, mask_scale | None, bias)  ("dense_bwd", N, K, M, act, mask_scale | None, dx, db)
+#   ("softmax_xent", N, M, grad_scale, training)          ("view_mean", videos, views, M)
+#   ("bn_finalize", C, count, update_moving)              ("bn_bwd_finalize", C, count)
+#   ("bn_bwd_finalize_rc", dtype, C, count, prepare Cin | 0, (finish Cout, Cin) | None)
+#   ("bn_eval_coef_batched", channels of every table item)
+_XL_BN = (32, 72, 72, 32, 32, 72, 72, 32, 72, 72, 32, 72, 72, 32, 72, 72, 32, 162, 162, 72, 72, 162, 162, 72, 162, 162, 72, 162,
+           162, 72, 162, 162, 72, 162, 162, 72, 162, 162, 72, 162, 162, 72, 162, 162, 72, 162, 162, 72, 306, 306, 136, 136, 306,
+           306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136,
+           306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306,
+           136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306, 306, 136, 306,
+           306, 136, 630, 630, 280, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630,
+           280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630, 630, 280, 630,
+           630, 280, 630)
+AUX_FULL = [
+    # bn_finalize
+    ("bn_finalize", 24, 2662400, 1), ("bn_finalize", 54, 2662400, 1), ("bn_finalize", 54, 665600, 1),
+    ("bn_finalize", 24, 665600, 1), ("bn_finalize", 108, 665600, 1), ("bn_finalize", 108, 166400, 1),
+    ("bn_finalize", 48, 166400, 1), ("bn_finalize", 216, 166400, 1), ("bn_finalize", 216, 41600, 1),
+    ("bn_finalize", 96, 41600, 1), ("bn_finalize", 432, 41600, 1), ("bn_finalize", 432, 10400, 1),
+    ("bn_finalize", 192, 10400, 1), ("bn_finalize", 24, 12845056, 1), ("bn_finalize", 54, 12845056, 1),
+    ("bn_finalize", 54, 3211264, 1), ("bn_finalize", 24, 3211264, 1), ("bn_finalize", 108, 3211264, 1),
+    ("bn_finalize", 108, 802816, 1), ("bn_finalize", 48, 802816, 1), ("bn_finalize", 216, 802816, 1),
+    ("bn_finalize", 216, 200704, 1), ("bn_finalize", 96, 200704, 1), ("bn_finalize", 432, 200704, 1),
+    ("bn_finalize", 432, 50176, 1), ("bn_finalize", 192, 50176, 1), ("bn_finalize", 24, 6230016, 1),
+    ("bn_finalize", 54, 6230016, 1), ("bn_finalize", 54, 1557504, 1), ("bn_finalize", 24, 1557504, 1),
+    ("bn_finalize", 108, 1557504, 1), ("bn_finalize", 108, 389376, 1), ("bn_finalize", 48, 389376, 1),
+    ("bn_finalize", 216, 389376, 1), ("bn_finalize", 216, 102400, 1), ("bn_finalize", 96, 102400, 1),
+    ("bn_finalize", 432, 102400, 1), ("bn_finalize", 432, 25600, 1), ("bn_finalize", 192, 25600, 1),
+    # se_fwd
+    ("se_fwd", 32, 54, 8, 20800), ("se_fwd", 32, 108, 8, 5200), ("se_fwd", 32, 216, 16, 1300), ("se_fwd", 32, 432, 32, 325),
+    ("se_fwd", 64, 54, 8, 50176), ("se_fwd", 64, 108, 8, 12544), ("se_fwd", 64, 216, 16, 3136), ("se_fwd", 64, 432, 32, 784),
+    ("se_fwd", 16, 54, 8, 97344), ("se_fwd", 16, 108, 8, 24336), ("se_fwd", 16, 216, 16, 6400), ("se_fwd", 16, 432, 32, 1600),
+    ("se_fwd", 30, 72, 8, 97344), ("se_fwd", 30, 162, 16, 24336), ("se_fwd", 30, 306, 24, 6400), ("se_fwd", 30, 630, 40, 1600),
+    # subsample2
+    ("subsample2", F32, 39936, 10, 10), ("subsample2", BF16, 98304, 14, 14), ("subsample2", F16, 98304, 14, 14),
+    ("subsample2", BF16, 6144, 78, 78), ("subsample2", F16, 15360, 78, 78),
+    # pool_fwd
+    ("pool_fwd", F32, 32, 432, 325), ("pool_fwd", BF16, 64, 432, 784), ("pool_fwd", F16, 64, 432, 784),
+    ("pool_fwd", BF16, 16, 432, 1600), ("pool_fwd", F16, 30, 630, 1600),
+    # dense_fwd
+    ("dense_fwd", 32, 432, 2048, 1, None, False), ("dense_fwd", 32, 2048, 400, 0, 2.0, True),
+    ("dense_fwd", 64, 432, 2048, 1, None, False), ("dense_fwd", 64, 2048, 400, 0, 2.0, True),
+    ("dense_fwd", 16, 432, 2048, 1, None, False), ("dense_fwd", 16, 2048, 400, 0, 2.0, True),
+    ("dense_fwd", 30, 630, 2048, 1, None, False), ("dense_fwd", 30, 2048, 400, 0, None, True),
+    # softmax_xent
+    ("softmax_xent", 32, 400, 0.03125, True), ("softmax_xent", 64, 400, 0.015625, True),
+    ("softmax_xent", 16, 400, 0.0625, True), ("softmax_xent", 30, 400, 1.0, False),
+    # dense_bwd
+    ("dense_bwd", 32, 2048, 400, 0, 2.0, True, True), ("dense_bwd", 32, 432, 2048, 1, None, True, False),
+    ("dense_bwd", 64, 2048, 400, 0, 2.0, True, True), ("dense_bwd", 64, 432, 2048, 1, None, True, False),
+    ("dense_bwd", 16, 2048, 400, 0, 2.0, True, True), ("dense_bwd", 16, 432, 2048, 1, None, True, False),
+    # relu_bn_bwd_reduce
+    ("relu_bn_bwd_reduce", F32, 32, 432, 325, "dpool", True), ("relu_bn_bwd_reduce", F32, 32, 24, 83200, "dy", False),
+    ("relu_bn_bwd_reduce", BF16, 64, 432, 784, "dpool", True), ("relu_bn_bwd_reduce", F16, 64, 432, 784, "dpool", True),
+    ("relu_bn_bwd_reduce", BF16, 16, 432, 1600, "dpool", True),
+    # tail_bwd
+    ("tail_bwd", F32, 32, 192, 325, False), ("tail_bwd", F32, 32, 192, 325, True), ("tail_bwd", F32, 32, 96, 1300, False),
+    ("tail_bwd", F32, 32, 96, 1300, True), ("tail_bwd", F32, 32, 48, 5200, False), ("tail_bwd", F32, 32, 48, 5200, True),
+    ("tail_bwd", F32, 32, 24, 20800, False), ("tail_bwd", F32, 32, 24, 20800, True), ("tail_bwd", BF16, 64, 192, 784, False),
+    ("tail_bwd", BF16, 64, 192, 784, True), ("tail_bwd", BF16, 64, 96, 3136, False), ("tail_bwd", BF16, 64, 96, 3136, True),
+    ("tail_bwd", BF16, 64, 48, 12544, False), ("tail_bwd", BF16, 64, 48, 12544, True), ("tail_bwd", F16, 64, 192, 784, False),
+    ("tail_bwd", F16, 64, 192, 784, True), ("tail_bwd", F16, 64, 96, 3136, False), ("tail_bwd", F16, 64, 96, 3136, True),
+    ("tail_bwd", F16, 64, 48, 12544, False), ("tail_bwd", F16, 64, 48, 12544, True), ("tail_bwd", BF16, 16, 192, 1600, False),
+    ("tail_bwd", BF16, 16, 192, 1600, True), ("tail_bwd", BF16, 16, 96, 6400, False), ("tail_bwd", BF16, 16, 96, 6400, True),
+    ("tail_bwd", BF16, 16, 48, 24336, False), ("tail_bwd", BF16, 16, 48, 24336, True),
+    # se_bnb_bwd
+    ("se_bnb_bwd", 32, 432, 0, 325, False, ((32, 82944),)), ("se_bnb_bwd", 32, 432, 32, 325, True, ((32, 82944), (32, 82944))),
+    ("se_bnb_bwd", 32, 432, 0, 325, False, ((32, 82944), (32, 82944))),
+    ("se_bnb_bwd", 32, 216, 16, 1300, True, ((128, 20736),)),
+    ("se_bnb_bwd", 32, 216, 0, 1300, False, ((128, 20736), (128, 20736))),
+    ("se_bnb_bwd", 32, 216, 16, 1300, True, ((128, 20736), (128, 20736))), ("se_bnb_bwd", 32, 108, 0, 5200, False, ()),
+    ("se_bnb_bwd", 32, 108, 8, 5200, True, ()), ("se_bnb_bwd", 32, 54, 8, 20800, True, ()),
+    ("se_bnb_bwd", 32, 54, 0, 20800, False, ()), ("se_bnb_bwd", 64, 432, 0, 784, False, ((124, 82944),)),
+    ("se_bnb_bwd", 64, 432, 32, 784, True, ((124, 82944), (64, 82944))),
+    ("se_bnb_bwd", 64, 432, 0, 784, False, ((124, 82944), (64, 82944))),
+    ("se_bnb_bwd", 64, 216, 16, 3136, True, ((251, 20736),)),
+    ("se_bnb_bwd", 64, 216, 0, 3136, False, ((251, 20736), (251, 20736))),
+    ("se_bnb_bwd", 64, 216, 16, 3136, True, ((251, 20736), (251, 20736))), ("se_bnb_bwd", 64, 108, 0, 12544, False, ()),
+    ("se_bnb_bwd", 64, 108, 8, 12544, True, ()), ("se_bnb_bwd", 64, 54, 8, 50176, True, ()),
+    ("se_bnb_bwd", 64, 54, 0, 50176, False, ()), ("se_bnb_bwd", 16, 432, 32, 1600, True, ((115, 82944),)),
+    ("se_bnb_bwd", 16, 432, 0, 1600, False, ((115, 82944), (56, 82944))),
+    ("se_bnb_bwd", 16, 432, 32, 1600, True, ((115, 82944), (56, 82944))),
+    ("se_bnb_bwd", 16, 216, 0, 6400, False, ((247, 20736),)),
+    ("se_bnb_bwd", 16, 216, 16, 6400, True, ((247, 20736), (247, 20736))),
+    ("se_bnb_bwd", 16, 216, 0, 6400, False, ((247, 20736), (247, 20736))), ("se_bnb_bwd", 16, 108, 8, 24336, True, ()),
+    ("se_bnb_bwd", 16, 108, 0, 24336, False, ()), ("se_bnb_bwd", 16, 54, 8, 97344, True, ()),
+    ("se_bnb_bwd", 16, 54, 0, 97344, False, ()),
+    # bn_bwd_finalize
+    ("bn_bwd_finalize", 432, 41600), ("bn_bwd_finalize", 96, 41600), ("bn_bwd_finalize", 216, 166400),
+    ("bn_bwd_finalize", 48, 166400), ("bn_bwd_finalize", 108, 665600), ("bn_bwd_finalize", 24, 665600),
+    ("bn_bwd_finalize", 54, 2662400), ("bn_bwd_finalize", 24, 2662400),
+    # bn_bwd_finalize_rc
+    ("bn_bwd_finalize_rc", BF16, 96, 200704, 48, None), ("bn_bwd_finalize_rc", BF16, 216, 802816, 48, (96, 48)),
+    ("bn_bwd_finalize_rc", BF16, 48, 802816, 0, (216, 48)), ("bn_bwd_finalize_rc", BF16, 108, 802816, 48, None),
+    ("bn_bwd_finalize_rc", BF16, 48, 802816, 0, (108, 48)), ("bn_bwd_finalize_rc", BF16, 48, 802816, 24, None),
+    ("bn_bwd_finalize_rc", BF16, 108, 3211264, 24, (48, 24)), ("bn_bwd_finalize_rc", BF16, 24, 3211264, 0, (108, 24)),
+    ("bn_bwd_finalize_rc", BF16, 54, 3211264, 24, None), ("bn_bwd_finalize_rc", BF16, 24, 3211264, 0, (54, 24)),
+    ("bn_bwd_finalize_rc", BF16, 24, 3211264, 24, None), ("bn_bwd_finalize_rc", BF16, 54, 12845056, 24, (24, 24)),
+    ("bn_bwd_finalize_rc", BF16, 24, 12845056, 0, (54, 24)), ("bn_bwd_finalize_rc", F16, 96, 200704, 48, None),
+    ("bn_bwd_finalize_rc", F16, 216, 802816, 48, (96, 48)), ("bn_bwd_finalize_rc", F16, 48, 802816, 0, (216, 48)),
+    ("bn_bwd_finalize_rc", F16, 108, 802816, 48, None), ("bn_bwd_finalize_rc", F16, 48, 802816, 0, (108, 48)),
+    ("bn_bwd_finalize_rc", F16, 48, 802816, 24, None), ("bn_bwd_finalize_rc", F16, 108, 3211264, 24, (48, 24)),
+    ("bn_bwd_finalize_rc", F16, 24, 3211264, 0, (108, 24)), ("bn_bwd_finalize_rc", F16, 54, 3211264, 24, None),
+    ("bn_bwd_finalize_rc", F16, 24, 3211264, 0, (54, 24)), ("bn_bwd_finalize_rc", F16, 24, 3211264, 24, None),
+    ("bn_bwd_finalize_rc", F16, 54, 12845056, 24, (24, 24)), ("bn_bwd_finalize_rc", F16, 24, 12845056, 0, (54, 24)),
+    ("bn_bwd_finalize_rc", BF16, 96, 102400, 48, None), ("bn_bwd_finalize_rc", BF16, 216, 389376, 48, (96, 48)),
+    ("bn_bwd_finalize_rc", BF16, 48, 389376, 0, (216, 48)), ("bn_bwd_finalize_rc", BF16, 108, 389376, 48, None),
+    ("bn_bwd_finalize_rc", BF16, 48, 389376, 0, (108, 48)), ("bn_bwd_finalize_rc", BF16, 48, 389376, 24, None),
+    ("bn_bwd_finalize_rc", BF16, 108, 1557504, 24, (48, 24)), ("bn_bwd_finalize_rc", BF16, 24, 1557504, 0, (108, 24)),
+    ("bn_bwd_finalize_rc", BF16, 54, 1557504, 24, None), ("bn_bwd_finalize_rc", BF16, 24, 1557504, 0, (54, 24)),
+    ("bn_bwd_finalize_rc", BF16, 24, 1557504, 24, None), ("bn_bwd_finalize_rc", BF16, 54, 6230016, 24, (24, 24)),
+    ("bn_bwd_finalize_rc", BF16, 24, 6230016, 0, (54, 24)),
+    # bn_eval_coef_batched: the whole X3D-XL inference BatchNorm table (config 5), channels of its 171 items in table order
+    ("bn_eval_coef_batched", _XL_BN),
+    # view_mean
+    ("view_mean", 1, 30, 400),
+]
+
+
+def aux_full_id(case):
+    e = case[0]
+    if e == "bn_eval_coef_batched":
+        return f"{e}-{len(case[1])}items"
+    f = lambda v: str(v)[6:] if isinstance(v, torch.dtype) else ("x".join(map(str, v)) if isinstance(v, tuple) and v and
+                                                                  isinstance(v[0], int) else str(v))
+    parts = [f(v) if not (isinstance(v, tuple) and v and isinstance(v[0], tuple)) else "+".join(f(j) for j in v) or "nojobs"
+             for v in case[1:]]
+    return "-".join([e] + [p if p else "none" for p in parts])
+
+
 # ---- whole-model cases (tests/test_model_gpu.py): variant, N, T, S --------------------------------------------------------
 MODEL_TRAIN_FP32 = [
     ("XS", 4, 4, 64), ("S", 2, 13, 64), ("M", 2, 4, 64), ("S", 3, 5, 96),

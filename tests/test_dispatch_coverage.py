@@ -340,3 +340,105 @@ def test_every_pw_full_case_is_a_launch_of_a_full_size_plan(pw_plan_launches):
     stale = [S.pw_full_id(c) for c in S.PW_FULL if c not in keys]
     assert not stale, "PW_FULL cases that no full-size plan launches: " + ", ".join(stale)
     assert len(set(S.PW_FULL)) == len(S.PW_FULL), "duplicate PW_FULL entries"
+
+
+# ---- every other launch of the same plans (shapes.AUX_FULL; tests/test_full_size_gpu.py: test_aux_full_size) ---------------
+AUX_FULL_PLANS = DW_FULL_PLANS
+# covered elsewhere: the pointwise and depthwise lists above, the stem's full-size tests, and the side-stream join (no kernel)
+_AUX_ELSEWHERE = ("x3d_pw_fwd", "x3d_pw_dgrad", "x3d_pw_wgrad", "x3d_pw_bwd", "x3d_dw3d_fwd", "x3d_dw3d_bwd", "x3d_stem_fwd",
+                  "x3d_stem_bwd", "x3d_stem_s_fwd", "x3d_stem_s_wgrad", "x3d_dwt_fwd", "x3d_dwt_bwd", "side_join")
+
+
+def _dtype_of(code):
+    from x3d_tf_amd import hip
+    return [d for d in S.DTYPES if hip.dtype_code(d) == code][0]
+
+
+def _nz(p):
+    return bool(p)
+
+
+# one key extractor per entry name, over the recorded argument tuple `a` (C ABI order, the stream excluded), the plan and
+# the launch's argument struct; shapes.py documents the fields
+_AUX_KEYS = {
+    "x3d_tail_bwd": lambda a, pl, st: ("tail_bwd", _dtype_of(a[9]), a[6], a[7], a[8], _nz(a[3])),
+    "x3d_relu_bn_bwd_reduce": lambda a, pl, st: ("relu_bn_bwd_reduce", _dtype_of(a[9]), a[6], a[7], a[8],
+                                                 "dy" if _nz(a[0]) else "dpool", _nz(a[4])),
+    "x3d_pool_fwd": lambda a, pl, st: ("pool_fwd", _dtype_of(a[6]), a[3], a[4], a[5]),
+    "x3d_subsample2": lambda a, pl, st: ("subsample2", _dtype_of(a[5]), a[2], a[3], a[4]),
+    "x3d_se_fwd": lambda a, pl, st: ("se_fwd", a[9], a[10], a[11], int(a[1])),
+    "x3d_se_bnb_bwd": lambda a, pl, st: ("se_bnb_bwd", st.N, st.C, st.Wd, int(st.P), bool(st.w1),
+                                         tuple((j.parts, j.elems) for j in st.reduce if j.slab)),
+    "x3d_dense_fwd": lambda a, pl, st: ("dense_fwd", a[7], a[8], a[9], a[6], a[2] if _nz(a[1]) else None, _nz(a[4])),
+    "x3d_dense_bwd": lambda a, pl, st: ("dense_bwd", a[10], a[11], a[12], a[2], a[5] if _nz(a[4]) else None, _nz(a[7]),
+                                        _nz(a[9])),
+    "x3d_softmax_xent": lambda a, pl, st: ("softmax_xent", a[6], a[7], a[5], _nz(a[1])),
+    "x3d_view_mean": lambda a, pl, st: ("view_mean", a[2], a[3], a[4]),
+    "x3d_bn_finalize": lambda a, pl, st: ("bn_finalize", a[11], int(a[1]), a[8]),
+    "x3d_bn_bwd_finalize": lambda a, pl, st: ("bn_bwd_finalize", a[7], int(a[1])),
+    "x3d_bn_bwd_finalize_rc": lambda a, pl, st: ("bn_bwd_finalize_rc", _dtype_of(a[18]), a[7], int(a[1]), a[11],
+                                                 (a[16], a[17]) if _nz(a[12]) else None),
+    "x3d_bn_eval_coef_batched": lambda a, pl, st: ("bn_eval_coef_batched", tuple(it.C for it in pl.bn_eval_items)),
+}
+# standalone halves of the recomputed-output backward: covered by a PW_FULL `rc` case of the same (Cout, Cin, dtype), which
+# runs both at full size through ops.pw_bwd_rc
+_AUX_RC = {"x3d_pw_bwd_rc_prepare": lambda a: (a[4], a[5], _dtype_of(a[6])),
+           "x3d_pw_bwd_rc_finish": lambda a: (a[4], a[5], _dtype_of(a[6]))}
+
+
+def _aux_launches(plan):
+    """(entry, key) of every launch of a full-size dry plan that the pointwise / depthwise / stem lists do not cover; an
+    entry name this file does not know fails here (a new launch needs a key and a full-size case)."""
+    from x3d_tf_amd.config import get_config
+    from x3d_tf_amd.dispatch import BASELINE_CONFIGS
+    from x3d_tf_amd.model import X3D
+    variant, n, t, s, dtype, training, over = BASELINE_CONFIGS[plan] if isinstance(plan, int) else plan + ({},)
+    flat = [x for kv in over.items() for x in kv]
+    m = X3D(get_config(variant, flat or None), dtype=dtype, device="dry")
+    pl = m._plan(n, t, s, s, training)
+    out, unknown = [], set()
+    for lst in (pl.fwd, pl.bwd):
+        for i, item in enumerate(lst):
+            if item is None or item[0] in _AUX_ELSEWHERE:
+                continue
+            name, args = item[0], item[2]
+            if name in _AUX_RC:
+                out.append((name, ("rc",) + _AUX_RC[name](args)))
+            elif name in _AUX_KEYS:
+                out.append((name, _AUX_KEYS[name](args, pl, pl.structs.get((id(lst), i)))))
+            else:
+                unknown.add(name)
+    m.release_plans()
+    assert not unknown, f"launches tests/test_dispatch_coverage.py has no AUX_FULL key for: {sorted(unknown)}"
+    return out
+
+
+@pytest.fixture(scope="module")
+def aux_plan_launches():
+    return {plan: _aux_launches(p) for plan, p in AUX_FULL_PLANS.items()}
+
+
+def _pw_rc_cases():
+    return {(co, ci, dt) for (e, dt, n, ci, co, *_r, form) in S.PW_FULL if e == "bwd" and "rc" in form}
+
+
+@pytest.mark.parametrize("plan", list(AUX_FULL_PLANS))
+def test_every_aux_launch_of_a_full_size_plan_has_a_full_size_case(aux_plan_launches, plan):
+    """Every launch of the plan outside the pointwise, depthwise and stem families (BatchNorm bookkeeping, residual-tail
+    backward, squeeze-excite, slab reductions, head, loss) has a shapes.AUX_FULL case at its real size and in its launch form;
+    a standalone x3d_pw_bwd_rc_prepare / _finish has a PW_FULL `rc` case of its (Cout, Cin, dtype)."""
+    launches = aux_plan_launches[plan]
+    assert launches, "the dry plan recorded no other launches"
+    cases, rc = set(S.AUX_FULL), _pw_rc_cases()
+    missing = sorted({f"{e}: {key[1:] if key[0] == 'rc' else S.aux_full_id(key)}" for e, key in launches
+                      if (key[1:] not in rc if key[0] == "rc" else key not in cases)})
+    assert not missing, (f"plan {plan}: launches without a full-size fp64 case (tests/shapes.py AUX_FULL):\n"
+                         + "\n".join(f"  {v}" for v in missing))
+
+
+def test_every_aux_full_case_is_a_launch_of_a_full_size_plan(aux_plan_launches):
+    """... and no AUX_FULL case is left over from a plan that no longer launches it, nor listed twice."""
+    keys = {key for ls in aux_plan_launches.values() for _, key in ls}
+    stale = [S.aux_full_id(c) for c in S.AUX_FULL if c not in keys]
+    assert not stale, "AUX_FULL cases that no full-size plan launches: " + ", ".join(stale)
+    assert len(set(S.AUX_FULL)) == len(S.AUX_FULL), "duplicate AUX_FULL entries"
