@@ -274,7 +274,7 @@ def test_train_step_half_block_by_block(gpu, name, n, t, s, dtype):
         worst["y"] = max(worst["y"], _scaled(pre + "/out", B.y, y_ref, atol_))
         grads = torch.autograd.grad(y_ref, [xin] + [leaf[k] for k in names], grad_outputs=dy)
         dx_ref = grads[0]
-        if (bi > 0 and pl.blocks[bi - 1].tail_folded) or (bi == 0 and getattr(pl, "stem_bwd_folded", False)):
+        if (bi > 0 and pl.blocks[bi - 1].tail_folded) or (bi == 0 and pl.stem_bwd_folded):
             # this block's `a` backward already applied the Add + ReLU backward of the block below (whose y is B.x): what it
             # stored is the masked gradient.  (dy above is then masked as well: the oracle's ReLU backward re-applies the same
             # mask, which changes nothing.)  Block 0: the same fold with the stem's ReLU (B.x = y0 = relu(bn(t_raw))).
@@ -362,7 +362,7 @@ def test_recomputed_output_backward_against_the_stored_output_backward(gpu, name
     xg = x.to(gpu)
     pl = m.forward_backward(xg, labels.to(gpu), loss_scale=ls)          # builds the plan
     torch.cuda.synchronize()
-    assert any(getattr(B, "a_bwd_rc", False) for B in pl.blocks), "no recomputed-output launch in this plan: nothing to compare"
+    assert any(B.a_bwd_rc for B in pl.blocks), "no recomputed-output launch in this plan: nothing to compare"
     alt = record_alternate_backward(m, pl, xg, pw_bwd_rc=False)
     assert not any(alt.info["a_bwd_rc"])
     names_rc = {i for i, (nm, fn, a_) in enumerate(pl.bwd) if nm == "x3d_bn_bwd_finalize_rc"}
@@ -376,10 +376,10 @@ def test_recomputed_output_backward_against_the_stored_output_backward(gpu, name
         for k in m.grads:
             if k.startswith(pre + "/"):
                 reach[k] = seen
-        if getattr(B, "r_bwd_rc", False):
+        if B.r_bwd_rc:
             reach[pre + "/residual/kernel"] = True
             seen = True
-        if getattr(B, "a_bwd_rc", False):
+        if B.a_bwd_rc:
             reach[pre + "/bottleneck/a/kernel"] = True
             seen = True
     for k in m.grads:
@@ -415,7 +415,7 @@ def test_recomputed_output_backward_against_the_stored_output_backward(gpu, name
 
         def run_alt():
             alt.extra.zero_()
-            return run_split(alt.lst, alt.owned[5])         # (owned: the alternate list's scratch buffers, se_scratch sixth)
+            return run_split(alt.lst, alt.rec.se_scratch)      # (rec: the alternate backward record, which owns its scratch)
 
         for runner in (lambda: run_split(pl.bwd, pl.se_scratch), run_alt, lambda: run_split(pl.bwd, pl.se_scratch)):
             pl.zero_buf.copy_(snap)

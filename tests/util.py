@@ -230,11 +230,13 @@ def rnd(shape, dtype, gen, scale=1.0):
 
 
 class AltBackward:
-    """A second backward launch list recorded over the SAME forward buffers of a training plan with other plan options
-    (record_alternate_backward).  run() replays it from the forward state `snapshot` captured."""
+    """A second backward pass (`rec`: x3d_tf_amd.plan.Backward) recorded over the SAME forward buffers of a training plan with
+    other plan options (record_alternate_backward).  run() replays it from the forward state `snapshot` captured."""
 
-    def __init__(self, model, pl, lst, extra):
-        self.model, self.pl, self.lst, self.extra = model, pl, lst, extra
+    def __init__(self, model, pl, rec, extra):
+        self.model, self.pl, self.rec, self.lst, self.extra = model, pl, rec, rec.launches, extra
+        self.info = dict(tail_folded=[r.tail_folded for r in rec.blocks], a_bwd_rc=[r.a_bwd_rc for r in rec.blocks],
+                         stem_bwd_folded=rec.stem_bwd_folded)
 
     def run(self):
         self.extra.zero_()
@@ -246,48 +248,15 @@ def record_alternate_backward(model, pl, x, **options):
     the forward tensors the plan already owns -- so that two backward variants (e.g. pw_bwd_rc on / off) can be compared on
     bit-identical forward state, where the backward pass is a LINEAR map of the upstream gradient and differences do not
     amplify.  New fp64 accumulators of the second list live in their own zeroed buffer; x = the bound input batch (the
-    stem's weight-gradient launch of the new list is bound to it).  Test-side only: pokes at plan internals."""
-    import torch
-    from x3d_tf_amd.model import PLAN_DEFAULTS, X3D
+    stem's weight-gradient launch of the new list is bound to it).  The plan's own backward pass is left as it is: the
+    record (`.rec`) owns the second list's scratch buffers."""
+    from x3d_tf_amd.model import PLAN_DEFAULTS
+    from x3d_tf_amd.plan import record_backward
     assert all(k in PLAN_DEFAULTS for k in options)
-    saved_opt, saved_fuse, saved_rc = model.opt, model._fuse_pw_bwd, model._rc_pw_bwd
-    saved_bwd, saved_marks = pl.bwd, dict(pl.bwd_stage_marks)
-    saved_pl = {k: getattr(pl, k, None) for k in ("gbuf", "dv", "ga", "rtmp", "coef_nc", "se_scratch", "g5", "dh1", "dpooled",
-                                                  "ds", "stem_bwd_folded")}
-    saved_b = [{k: getattr(B, k, None) for k in ("bwd_start", "bwd_stop", "dy_view", "dx_view", "tail_folded", "a_bwd_rc",
-                                                 "r_bwd_rc", "db", "nc_sums")} for B in pl.blocks]
-    try:
-        model.opt = dict(model.opt, **{k: bool(v) for k, v in options.items()})
-        model._fuse_pw_bwd, model._rc_pw_bwd = model.opt["fused_pw_bwd"], model.opt["pw_bwd_rc"]
-        for B in pl.blocks:
-            B.tail_folded = False
-        pl.bwd, pl.bwd_stage_marks = [], {}
-        n0 = len(pl._zero_chunks)
-        model._record_backward(pl)
-        alt = pl.bwd
-        new = pl._zero_chunks[n0:]
-        extra = torch.zeros(max(sum(c[0] for c in new), 1), dtype=torch.float64, device=model.device)
-        off = 0
-        for numel, shape in new:
-            pl._zero_views.append(extra[off:off + numel].view(shape))
-            off += numel
-        X3D._resolve(pl, alt)
-        for f, handle in getattr(pl, "bwd_folds", []):          # (folds recorded by either list: the same accumulators)
-            f.sums = pl._zero_views[handle].data_ptr()
-        info = dict(tail_folded=[bool(B.tail_folded) for B in pl.blocks], a_bwd_rc=[bool(getattr(B, "a_bwd_rc", False)) for B in pl.blocks],
-                    stem_bwd_folded=bool(getattr(pl, "stem_bwd_folded", False)))
-        # the scratch buffers of the new list are referenced from argument structs by ADDRESS only (the plan keeps them alive as
-        # attributes, which are restored to the first list's below): hold them here, or the allocator hands their memory out again
-        owned = [getattr(pl, k, None) for k in saved_pl] + [extra]
-    finally:
-        model.opt, model._fuse_pw_bwd, model._rc_pw_bwd = saved_opt, saved_fuse, saved_rc
-        pl.bwd, pl.bwd_stage_marks = saved_bwd, saved_marks
-        for k, v in saved_pl.items():
-            setattr(pl, k, v)
-        for B, d in zip(pl.blocks, saved_b):
-            for k, v in d.items():
-                setattr(B, k, v)
-    model._bind_input(pl, x)          # (the input slots include the new list's stem launch)
-    ab = AltBackward(model, pl, alt, extra)
-    ab.info, ab.owned = info, owned
-    return ab
+    first = len(pl._zero_chunks)
+    rec = record_backward(model, pl, dict(model.opt, **{k: bool(v) for k, v in options.items()}))
+    extra = pl.carve(first)           # the accumulators the new list added
+    pl.resolve()
+    pl.input_slots += rec.input_slots
+    model._bind_input(pl, x)          # (the input slots now include the new list's stem launch)
+    return AltBackward(model, pl, rec, extra)

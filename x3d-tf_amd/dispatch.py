@@ -1,7 +1,7 @@
 """Which kernel instantiation runs behind every conv launch of a configuration -- without a GPU.
 
-A DRY model (``X3D(cfg, device="dry")``) records the same launch list as a real one (same code: model.py
-``_make_plan`` / ``_record_backward``) over address-only buffers; the library's own dispatch, in dry-run mode
+A DRY model (``X3D(cfg, device="dry")``) records the same launch list as a real one (same code: plan.py
+``record_training`` / ``record_inference`` / ``record_backward``) over address-only buffers; the library's own dispatch, in dry-run mode
 (``x3d_pw_kernel_name`` / ``x3d_dw3d_kernel_name``), then names the instantiation of each launch.  Used by
 tests/test_dispatch_coverage.py (every instantiation the BASELINE configurations launch at full size has an
 oracle-parity case under ``-m gpu``), bench.py (roofline rows name the kernels rocprofv3 lists) and the profiling tools.
