@@ -50,8 +50,9 @@ extern "C" {
  * (x3d_tf_amd/hip.py does): a stale libx3d_hip.so would otherwise take shifted arguments silently.
  * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit);
  *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device);
- *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP). */
-#define X3D_ABI_VERSION 136
+ *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP);
+ *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing). */
+#define X3D_ABI_VERSION 137
 int x3d_version(void);
 const char* x3d_last_error(void);
 
@@ -501,6 +502,14 @@ int x3d_dense_bwd(const float* dy, const float* y, int act, const float* x, cons
  * [0, M) is never used as an index: its loss row is NaN and its dlogits row zero. */
 int x3d_softmax_xent(const float* logits, const int* labels, float* probs, float* loss_rows,
                      float* dlogits, float grad_scale, int N, int M, void* stream);
+/* The same loss on dense target rows (ABI 137; label smoothing, mixup / CutMix): targets [N][M] fp32, y_j >= 0,
+ * S = sum_j y_j.  loss_rows[n] = sum_j y_j * (-log q_j) + S * log sum_k q_k;
+ * dL/dp_j = [1e-7 <= p_j <= 1-1e-7] * (-y_j / q_j + S / sum_k q_k), dlogits = grad_scale * p * (dL/dp - sum_k p_k dL/dp_k):
+ * a one-hot row gives x3d_softmax_xent's result.  targets == NULL: probs only (loss_rows and dlogits must then be NULL);
+ * loss_rows / dlogits may be NULL.  A NaN anywhere in a target row gives that row a NaN loss and a zero dlogits row.  One
+ * workgroup per row, no atomics.  N * M < 2^31. */
+int x3d_softmax_xent_soft(const float* logits, const float* targets, float* probs, float* loss_rows,
+                          float* dlogits, float grad_scale, int N, int M, void* stream);
 /* out[v][m] = mean over `views` consecutive rows (model.py:123-126) */
 int x3d_view_mean(const float* probs, float* out, int videos, int views, int M, void* stream);
 /* Keras metrics of a batch of probabilities (ABI 134; reference train.py:102-108 compile(metrics=[acc, top_5_acc]),
@@ -537,6 +546,35 @@ int x3d_view_max(const float* probs, float* out, int videos, int views, int M, v
  * never truncated: its ap is NaN and npos[c] = -P (only possible when N > X3D_AP_MAX_POSITIVES). */
 #define X3D_AP_MAX_POSITIVES 32768
 int x3d_multilabel_ap(const float* scores, const float* targets, int N, int M, double* ap, int* npos, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mixup / CutMix (ABI 137; MIXUP.* of the config): a batch mixed with its own reverse, clip i with clip N-1-i.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_MIX_MIXUP 1
+#define X3D_MIX_CUTMIX 2
+/* x, out: channels-last clip batches [N][T][H][W][C] of storage type dtype (X3D_F32 / X3D_BF16 / X3D_F16), contiguous.
+ *   X3D_MIX_MIXUP:  out_i = lam * x_i + (1 - lam) * x_{N-1-i} for every element: fp32 arithmetic on the stored values, one
+ *                   round-to-nearest-even to the storage type.  lam = 1 returns x and lam = 0 the reversed batch, bit for bit.
+ *   X3D_MIX_CUTMIX: the box [y0, y1) x [x0, x1) of every frame of clip i is replaced by the same box of clip N-1-i, everything
+ *                   else is copied: bit-exact (lam is checked but not used; an empty box returns x).
+ * out may equal x (in place: one thread owns both ends of a pair, so no second copy of the batch exists; CutMix then touches
+ * the box only) or be a buffer that does not overlap it.  With odd N the middle clip is its own partner and comes out
+ * bit-identical.  Any alignment of the element type is accepted; every offset is 64-bit.
+ * Refused: null pointers, non-positive extents, N > 131070, an unknown mode or dtype, lam outside [0, 1] or not finite, for
+ * CutMix a box that is not inside the frame (0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W), out overlapping x without being
+ * equal to it.  Nothing is written then. */
+int x3d_mix_clips(const void* x, void* out, int mode, float lam, int y0, int y1, int x0, int x1, int N, int T, int H, int W,
+                  int C, int dtype, void* stream);
+/* The soft targets of a mixed batch, out [N][M] fp32 (fp64 arithmetic, rounded once).  Exactly one of labels / targets:
+ *   labels [N] int32:     s(c)_j = (1 - eps) * [j == c] + eps / M;  out_i = lam * s(label_i) + (1 - lam) * s(label_{N-1-i}),
+ *                         0 <= eps < 1.  A label outside [0, M) is never used as an index: its row and its partner's row are
+ *                         all NaN.  hard [N] int32 (may be NULL) = the class the training metrics count against: label_i if
+ *                         lam >= 0.5, else label_{N-1-i}; a buffer of its own, not `labels`.
+ *   targets [N][M] fp32:  out_i = lam * t_i + (1 - lam) * t_{N-1-i};  out may equal targets (in place) or must not overlap
+ *                         it; eps must be 0 and hard NULL.
+ * The middle row of an odd batch is s(label) / t itself.  One workgroup per pair.  N * M < 2^31. */
+int x3d_mix_targets(const int* labels, const float* targets, float* out, int* hard, float lam, float eps, int N, int M,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K12  SGD with Nesterov momentum + L2 (train.py:89-92, model.py:47):

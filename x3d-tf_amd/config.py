@@ -7,6 +7,7 @@ is a small attribute-access node with the same surface the hot path uses:
 item access, ``dict(cfg)``.
 """
 import ast
+import collections
 import copy
 import os
 
@@ -116,7 +117,7 @@ class CfgNode(dict):
 
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
-    TEST.ENSEMBLE_METHOD (multi-label training)."""
+    TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -130,7 +131,13 @@ def get_default_config():
         MULTI_LABEL=False))
     c.TRAIN = CfgNode(dict(
         DATASET_SIZE=0, BATCH_SIZE=1, EPOCHS=1, OPTIMIZER="SGD", MOMENTUM=0.9, BASE_LR=0.1,
-        WARMUP_EPOCHS=1, WARMUP_LR=0.01))
+        WARMUP_EPOCHS=1, WARMUP_LR=0.01,
+        # label smoothing of the softmax head: targets (1 - eps) * one_hot + eps / classes (0 = off)
+        LABEL_SMOOTHING=0.0))
+    # mixup / CutMix of a training batch with its own reverse (names as PySlowFast's MIXUP section): ALPHA / CUTMIX_ALPHA are the
+    # Beta parameters of the two modes (0 = that mode off), PROB the chance a batch is mixed at all, SWITCH_PROB the chance of
+    # CutMix when both modes are on
+    c.MIXUP = CfgNode(dict(ENABLE=False, ALPHA=0.8, CUTMIX_ALPHA=1.0, PROB=1.0, SWITCH_PROB=0.5))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -151,6 +158,7 @@ def get_config(name, overrides=None, freeze=True):
     if overrides:
         cfg.merge_from_list(list(overrides))
     ensemble_method(cfg)
+    mix_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -170,3 +178,29 @@ def ensemble_method(cfg) -> str:
     if m not in ENSEMBLE_METHODS:
         raise ValueError(f"TEST.ENSEMBLE_METHOD must be one of {ENSEMBLE_METHODS}, not {m!r}")
     return m
+
+
+MixSettings = collections.namedtuple("MixSettings", "enable alpha cutmix_alpha prob switch_prob label_smoothing")
+
+
+def mix_settings(cfg) -> MixSettings:
+    """cfg.MIXUP.* and cfg.TRAIN.LABEL_SMOOTHING as one tuple (a config tree without the keys: everything off).  ValueError
+    for a negative alpha, ENABLE with both alphas 0, PROB / SWITCH_PROB outside [0, 1], LABEL_SMOOTHING outside [0, 1), and
+    LABEL_SMOOTHING > 0 with DATA.MULTI_LABEL (smoothing is defined for the softmax head; mixup / CutMix work with both)."""
+    mx = getattr(cfg, "MIXUP", None)
+    s = MixSettings(bool(getattr(mx, "ENABLE", False)), float(getattr(mx, "ALPHA", 0.0)),
+                    float(getattr(mx, "CUTMIX_ALPHA", 0.0)), float(getattr(mx, "PROB", 1.0)),
+                    float(getattr(mx, "SWITCH_PROB", 0.5)), float(getattr(cfg.TRAIN, "LABEL_SMOOTHING", 0.0)))
+    if not (s.alpha >= 0.0 and s.cutmix_alpha >= 0.0):      # (NaN fails too)
+        raise ValueError(f"MIXUP.ALPHA / MIXUP.CUTMIX_ALPHA must be >= 0, not {s.alpha} / {s.cutmix_alpha}")
+    if s.enable and s.alpha == 0.0 and s.cutmix_alpha == 0.0:
+        raise ValueError("MIXUP.ENABLE needs MIXUP.ALPHA > 0 or MIXUP.CUTMIX_ALPHA > 0")
+    if not 0.0 <= s.prob <= 1.0:
+        raise ValueError(f"MIXUP.PROB must lie in [0, 1], not {s.prob}")
+    if not 0.0 <= s.switch_prob <= 1.0:
+        raise ValueError(f"MIXUP.SWITCH_PROB must lie in [0, 1], not {s.switch_prob}")
+    if not 0.0 <= s.label_smoothing < 1.0:
+        raise ValueError(f"TRAIN.LABEL_SMOOTHING must lie in [0, 1), not {s.label_smoothing}")
+    if s.label_smoothing > 0.0 and multi_label(cfg):
+        raise ValueError("TRAIN.LABEL_SMOOTHING is defined for the softmax head only, not with DATA.MULTI_LABEL")
+    return s

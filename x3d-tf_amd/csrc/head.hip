@@ -296,6 +296,90 @@ extern "C" int x3d_softmax_xent(const float* logits, const int* labels, float* p
   return X3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same loss on a dense target row y (label smoothing, mixup / CutMix): Keras CategoricalCrossentropy on probabilities.
+//   S = sum_j y_j;  L = sum_j y_j * (-log q_j) + S * log sum_k q_k                                     [TF-3p]
+//   dL/dp_j = [1e-7 <= p_j <= 1-1e-7] * (-y_j / q_j + S / sum q);   dz = p * (dL/dp - sum_k p_k dL/dp_k)
+// A one-hot row gives the expressions of softmax_xent_kernel.  One block per sample, no atomics.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void softmax_xent_soft_kernel(const float* __restrict__ logits,
+                                                                const float* __restrict__ targets, float* probs,
+                                                                float* loss_rows, float* dlogits, float grad_scale, int M) {
+  __shared__ float scratch[24];
+  __shared__ float bc[6];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const float* z = logits + (long long)n * M;
+  float mx = -INFINITY;
+  for (int j = tid; j < M; j += 256) mx = fmaxf(mx, z[j]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if ((tid & 63) == 0) scratch[tid >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
+  __syncthreads();
+  float red[1] = {0.f};
+  for (int j = tid; j < M; j += 256) red[0] += expf(z[j] - mx);
+  block_sum<1>(red, scratch);
+  if (tid == 0) bc[0] = red[0];
+  __syncthreads();
+  const float inv = 1.f / bc[0];
+  __syncthreads();
+  const float* y = targets ? targets + (long long)n * M : nullptr;
+  // sum q, sum_k p_k*[in range], S, sum y*(-log q), sum [in range]*y*p/q, #NaN targets
+  float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int j = tid; j < M; j += 256) {
+    const float p = expf(z[j] - mx) * inv;
+    probs[(long long)n * M + j] = p;
+    if (!y) continue;
+    const float q = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
+    const bool in = (p >= 1e-7f && p <= 1.f - 1e-7f);
+    const float yj = y[j];
+    r6[0] += q;
+    r6[1] += in ? p : 0.f;
+    if (yj != yj) { r6[5] += 1.f; continue; }
+    r6[2] += yj;
+    r6[3] += yj * -logf(q);
+    r6[4] += in ? yj * p / q : 0.f;
+  }
+  if (!y) return;
+  block_sum<6>(r6, scratch);
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) bc[i] = r6[i];
+  }
+  __syncthreads();
+  const float sumq = bc[0], sum_p_in = bc[1], S = bc[2];
+  if (bc[5] > 0.f) {
+    // a NaN target (x3d_mix_targets writes one for a label outside [0, M)): NaN loss row, no gradient from this sample
+    if (tid == 0 && loss_rows) loss_rows[n] = __builtin_nanf("");
+    if (dlogits)
+      for (int j = tid; j < M; j += 256) dlogits[(long long)n * M + j] = 0.f;
+    return;
+  }
+  if (tid == 0 && loss_rows) loss_rows[n] = bc[3] + S * logf(sumq);
+  if (dlogits) {
+    // inner = sum_k p_k * dL/dp_k = S * sum_p_in / sumq - sum_k [in range] * y_k * p_k / q_k
+    const float inner = S * sum_p_in / sumq - bc[4];
+    for (int j = tid; j < M; j += 256) {
+      const float p = expf(z[j] - mx) * inv;
+      const bool in = (p >= 1e-7f && p <= 1.f - 1e-7f);
+      const float q = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
+      const float dldp = in ? S / sumq - y[j] / q : 0.f;
+      dlogits[(long long)n * M + j] = grad_scale * p * (dldp - inner);
+    }
+  }
+}
+
+extern "C" int x3d_softmax_xent_soft(const float* logits, const float* targets, float* probs, float* loss_rows,
+                                     float* dlogits, float grad_scale, int N, int M, void* stream) {
+  X3D_REQUIRE(logits && probs && N > 0 && M > 0, "softmax_xent_soft: bad args (N=%d M=%d)", N, M);
+  X3D_REQUIRE(targets || (!loss_rows && !dlogits), "softmax_xent_soft: loss/grad need targets");
+  X3D_REQUIRE((long long)N * M < (1LL << 31), "softmax_xent_soft: N*M = %lld >= 2^31", (long long)N * M);
+  hipLaunchKernelGGL(softmax_xent_soft_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, targets, probs,
+                     loss_rows, dlogits, grad_scale, M);
+  X3D_LAUNCH_CHECK("softmax_xent_soft");
+  return X3D_OK;
+}
+
 __global__ void view_mean_kernel(const float* __restrict__ probs, float* out, int views, int M) {
   const int v = blockIdx.y;
   const int m = blockIdx.x * blockDim.x + threadIdx.x;

@@ -11,9 +11,10 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X3D_HIP_LIB") or os.path.join(_HERE, "libx3d_hip.so")   # X3D_HIP_LIB: A/B builds (tools/build_variant.sh)
 
-ABI_VERSION = 136   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
+ABI_VERSION = 137   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
+MIX_MIXUP, MIX_CUTMIX = 1, 2
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = 0, 1, 2, 3
 
 _vp, _i, _f, _d, _ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
@@ -191,11 +192,14 @@ _SIGS = {
     "x3d_dense_fwd": ([_vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "x3d_dense_bwd": ([_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "x3d_softmax_xent": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
+    "x3d_softmax_xent_soft": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
     "x3d_view_mean": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "x3d_topk_metrics": ([_vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
     "x3d_sigmoid_bce": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
     "x3d_view_max": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "x3d_multilabel_ap": ([_vp, _vp, _i, _i, _vp, _vp, _vp], _i),
+    "x3d_mix_clips": ([_vp, _vp, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "x3d_mix_targets": ([_vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp], _i),
     "x3d_sgd_nesterov": ([_vp, _vp, _vp, _vp, _f, _f, _f, _f, _ll, _vp], _i),
     "x3d_adam": ([_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _ll, _ll, _vp], _i),
     "x3d_all_finite": ([_vp, _ll, _vp, _vp], _i),

@@ -446,6 +446,8 @@ class X3D:
 
         labels: [N] class indices; with DATA.MULTI_LABEL the targets [N, classes] in [0, 1] (float, uint8 or bool;
             multi-hot or soft), and the loss is Keras BinaryCrossentropy on sigmoid outputs (x3d_sigmoid_bce).
+            A single-label model also takes soft targets [N, classes] (floating point, finite, >= 0: label smoothing,
+            mixup / CutMix) and then runs x3d_softmax_xent_soft instead of x3d_softmax_xent; `plan.labels` is not touched.
 
         global_batch: divisor of the loss mean (defaults to the local batch; data-parallel callers pass
             world_size * local batch so that summing gradients over ranks gives the global mean).
@@ -459,9 +461,15 @@ class X3D:
         n, t, h, w, _ = input.shape
         pl = self._plan(n, t, h, w, True)
         self._bind_input(pl, input)
+        soft = (not self.multi_label and torch.is_tensor(labels) and labels.dim() == 2
+                and labels.dtype.is_floating_point)
         if self.multi_label:
             self._bind_targets(pl, labels, n)
+        elif soft:
+            pl.use_soft_targets(True)
+            self._bind_targets(pl, labels, n, what="soft")
         else:
+            pl.use_soft_targets(False)
             if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
                 if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
                     raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
@@ -478,6 +486,9 @@ class X3D:
         if self.multi_label:
             hip.call("x3d_sigmoid_bce", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
                      pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+        elif soft:
+            hip.call("x3d_softmax_xent_soft", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
         else:
             hip.call("x3d_softmax_xent", pl.logits.data_ptr(), pl.labels.data_ptr(), pl.probs.data_ptr(),
                      pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
@@ -493,20 +504,25 @@ class X3D:
                 start = stop
         return pl
 
-    def _bind_targets(self, pl: _Plan, targets, n):
+    def _bind_targets(self, pl: _Plan, targets, n, what="multi-label"):
         """multi-label targets [n, classes] (float / uint8 / bool) -> pl.targets fp32.  Host targets are checked for shape
-        and range (they are on the host anyway); device targets for shape only."""
+        and range (they are on the host anyway); device targets for shape only.  what="soft": the dense target rows of a
+        single-label model (label smoothing, mixup / CutMix): finite and >= 0."""
         if not torch.is_tensor(targets):
             targets = torch.as_tensor(targets)
         if tuple(targets.shape) != (n, self.num_classes):
-            raise ValueError(f"multi-label targets must be [{n}, {self.num_classes}], got {tuple(targets.shape)}")
+            raise ValueError(f"{what} targets must be [{n}, {self.num_classes}], got {tuple(targets.shape)}")
         if not (targets.dtype.is_floating_point or targets.dtype in (torch.uint8, torch.bool)):
-            raise ValueError(f"multi-label targets must be float, uint8 or bool, got {targets.dtype}")
+            raise ValueError(f"{what} targets must be float, uint8 or bool, got {targets.dtype}")
         if not targets.is_cuda:
             t = targets.float()
-            if not bool(torch.isfinite(t).all()) or float(t.min()) < 0.0 or float(t.max()) > 1.0:
+            if what == "soft":
+                if not bool(torch.isfinite(t).all()) or float(t.min()) < 0.0:
+                    raise ValueError("soft targets must be finite and >= 0")
+            elif not bool(torch.isfinite(t).all()) or float(t.min()) < 0.0 or float(t.max()) > 1.0:
                 raise ValueError("multi-label targets must lie in [0, 1]")
-        pl.targets.copy_(targets.to(self.device, non_blocking=True))
+        if targets.data_ptr() != pl.targets.data_ptr():     # (the trainer builds mixed targets in pl.targets itself)
+            pl.targets.copy_(targets.to(self.device, non_blocking=True))
 
     def regularization_loss(self):
         """weight_decay * sum(w^2) over the L2-regularised kernels (reference model.py:47)."""

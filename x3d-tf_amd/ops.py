@@ -561,6 +561,74 @@ def multilabel_ap(scores, targets, ap=None, npos=None, check=True):
             raise ValueError(f"multilabel_ap: classes {cls[:5]} have more than {hip.AP_MAX_POSITIVES} positives")
     return ap, npos
 
+
+def softmax_xent_soft(logits, targets, probs, loss_rows=None, dlogits=None, grad_scale=1.0):
+    """probs = softmax(logits); with dense target rows [N, M] fp32 (label smoothing, mixup / CutMix): loss_rows [N] = Keras
+    CategoricalCrossentropy on the probabilities and its gradient (x3d_softmax_xent_soft: the rules are in
+    include/x3d_hip.h; a one-hot row gives softmax_xent's result).  targets=None computes probs only.  One launch, does not
+    synchronise."""
+    _chk(logits, targets, probs, loss_rows, dlogits)
+    _f32_2d("softmax_xent_soft", "logits", logits)
+    n, m = logits.shape
+    _f32_2d("softmax_xent_soft", "probs", probs, (n, m))
+    if targets is not None:
+        _f32_2d("softmax_xent_soft", "targets", targets, (n, m))
+    elif loss_rows is not None or dlogits is not None:
+        raise ValueError("softmax_xent_soft: loss_rows / dlogits need targets")
+    if dlogits is not None:
+        _f32_2d("softmax_xent_soft", "dlogits", dlogits, (n, m))
+    if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() != n):
+        raise ValueError(f"softmax_xent_soft: loss_rows must be {n} float32, got {loss_rows.numel()} {loss_rows.dtype}")
+    hip.call("x3d_softmax_xent_soft", ptr(logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(dlogits),
+             float(grad_scale), n, m)
+    return probs
+
+
+MIX_MODES = {"mixup": hip.MIX_MIXUP, "cutmix": hip.MIX_CUTMIX}
+
+
+def mix_clips(x, mode, lam, box=(0, 0, 0, 0), out=None):
+    """Mixes the channels-last clip batch x [N, T, H, W, C] (fp32 / bf16 / fp16) with its own reverse, clip i with clip
+    N-1-i (x3d_mix_clips: the rules are in include/x3d_hip.h).  mode "mixup": out_i = lam * x_i + (1 - lam) * x_{N-1-i};
+    "cutmix": box = (y0, y1, x0, x1) of every frame is swapped between the two clips.  out=None allocates, out=x mixes in
+    place.  One or two launches, does not synchronise."""
+    if mode not in MIX_MODES:
+        raise ValueError(f"mix_clips: mode must be one of {sorted(MIX_MODES)}, not {mode!r}")
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(x, out)
+    if x.dim() != 5:
+        raise ValueError(f"mix_clips: expected a clip batch [N, T, H, W, C], got {tuple(x.shape)}")
+    if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError(f"mix_clips: out must be {tuple(x.shape)} {x.dtype} on {x.device}")
+    n, t, h, w, c = x.shape
+    y0, y1, x0, x1 = (int(v) for v in box)
+    hip.call("x3d_mix_clips", ptr(x), ptr(out), MIX_MODES[mode], float(lam), y0, y1, x0, x1, n, t, h, w, c,
+             hip.dtype_code(x.dtype))
+    return out
+
+
+def mix_targets(labels, num_classes, lam, eps=0.0, out=None, hard=None):
+    """Soft targets [N, M] fp32 of a batch mixed with its own reverse (x3d_mix_targets: the rules are in include/x3d_hip.h).
+    labels [N] int32: smoothed one-hot rows mixed with weight lam; `hard` [N] int32, when given, receives the class the
+    training metrics count against.  labels [N, M] float32 (multi-hot / soft targets): the rows mixed, eps must be 0; out
+    may be the targets themselves.  One launch, does not synchronise."""
+    _chk(labels, out, hard)
+    n, m = labels.shape[0], int(num_classes)
+    if out is None:
+        out = torch.empty((n, m), dtype=torch.float32, device=labels.device)
+    _f32_2d("mix_targets", "out", out, (n, m))
+    if hard is not None and (hard.dtype != torch.int32 or hard.numel() != n):
+        raise ValueError(f"mix_targets: hard must be {n} int32, got {hard.numel()} {hard.dtype}")
+    if labels.dim() == 1:
+        if labels.dtype != torch.int32:
+            raise ValueError(f"mix_targets: class labels must be int32, got {labels.dtype}")
+        hip.call("x3d_mix_targets", ptr(labels), None, ptr(out), ptr(hard), float(lam), float(eps), n, m)
+    else:
+        _f32_2d("mix_targets", "targets", labels, (n, m))
+        hip.call("x3d_mix_targets", None, ptr(labels), ptr(out), ptr(hard), float(lam), float(eps), n, m)
+    return out
+
 def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
     _chk(w, v, g, l2_mask)
     hip.call("x3d_sgd_nesterov", ptr(w), ptr(v), ptr(g), ptr(l2_mask), float(lr), float(momentum),

@@ -208,6 +208,7 @@ class _Plan:
         self.blocks: List[Block] = []
         self.bn_eval_items: List = []
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
+        self._head_hard = self._head_soft = None   # the two loss launches of a single-label training plan (use_soft_targets)
 
     # -- allocation ------------------------------------------------------------------------------
     def act(self, *shape):
@@ -302,6 +303,25 @@ class _Plan:
         self.stem_bwd_folded, self.se_scratch = bw.stem_bwd_folded, bw.se_scratch
         for B, r in zip(self.blocks, bw.blocks):
             vars(B).update(vars(r))
+
+    def use_soft_targets(self, soft: bool):
+        """Single-label training plans: which loss the head slot (fwd[grad_scale_slot]) holds -- x3d_softmax_xent on
+        `labels`, as recorded, or x3d_softmax_xent_soft on the dense rows in `targets`.  The targets buffer and the second
+        entry come into being with the first soft call, so a plan that never sees soft targets allocates nothing for them."""
+        slot = self.grad_scale_slot
+        if not soft:
+            if self._head_hard is not None:
+                self.fwd[slot] = self._head_hard
+            return
+        if self._head_soft is None:
+            m = self.model
+            self._head_hard = self.fwd[slot]
+            self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
+            tmp = []
+            self.rec(tmp, "x3d_softmax_xent_soft", self.logits, self.targets, self.probs, self.loss_rows, self.dlogits,
+                     1.0 / self.n, self.n, m.num_classes)
+            self._head_soft = tmp[0]
+        self.fwd[slot] = self._head_soft
 
     def run(self, lst, start=0, stop=None):
         if self.model.dry:
@@ -576,6 +596,7 @@ def record_training(model, n, t, h, w) -> _Plan:
                a.num_classes)
     else:
         pl.labels = torch.zeros(n, dtype=torch.int32, device=model.device)
+        pl.targets = None                  # soft targets: allocated by the first call that brings some (use_soft_targets)
         pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
                a.num_classes)
     pl.install_backward(record_backward(model, pl, model.opt))

@@ -10,6 +10,8 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
+from .config import mix_settings
+from .mix import NO_MIX, draw_mix_params
 
 
 def lr_schedule(epoch, cfg):
@@ -75,7 +77,7 @@ class Trainer:
     """
 
     def __init__(self, model, cfg, momentum: Optional[float] = None, sync_moving_stats: bool = True, group=None,
-                 loss_scale="auto"):
+                 loss_scale="auto", mix_seed: int = 0):
         self.optimizer = cfg.TRAIN.OPTIMIZER.lower()
         if self.optimizer not in ("sgd", "adam"):   # reference train.py:88-97: SGD(nesterov) / Adam / NotImplementedError
             raise NotImplementedError(f"{cfg.TRAIN.OPTIMIZER} not supported")
@@ -106,16 +108,31 @@ class Trainer:
         self._slot = dict(self._launch_at)
         self._stats_work = None
         xdist.broadcast_([model.flat_params, model.flat_velocity], 0, group)
+        # soft-target training (MIXUP.*, TRAIN.LABEL_SMOOTHING; both off by default: `step` is then what it was).  The draws
+        # come from a host generator seeded with mix_seed + rank: ranks mix differently, a rerun repeats.
+        self.mix = mix_settings(cfg)
+        if self.mix.label_smoothing > 0.0 and getattr(model, "multi_label", False):
+            raise ValueError("TRAIN.LABEL_SMOOTHING is defined for the softmax head only, not for a multi-label model")
+        self._mix_active = self.mix.enable or self.mix.label_smoothing > 0.0
+        if self._mix_active:
+            import numpy as np
+            rank = torch.distributed.get_rank(group) if torch.distributed.is_initialized() else xdist.env_world()[0]
+            self._mix_rng = np.random.default_rng(int(mix_seed) + rank)
+        self._mix_buf = self._mix_labels = None
+        self.last_mix = NO_MIX                # MixParams of the last step
         self.epoch = 0
         self.skipped_keys = []                # variables of the pretrained checkpoint resume(skip_mismatch=True) did not load
 
     def step(self, clips, labels, lr: Optional[float] = None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
-        plan (loss_rows, probs)."""
+        plan (loss_rows, probs).  With MIXUP.ENABLE or TRAIN.LABEL_SMOOTHING the batch is mixed and the targets are built
+        first (`_mix_batch`; `last_mix` holds the parameters drawn)."""
         m = self.model
         n = clips.shape[0]
         if lr is None:
             lr = lr_schedule(self.epoch, self.cfg)
+        if self._mix_active:
+            clips, labels = self._mix_batch(clips, labels)
         pl = m.forward_backward(clips, labels, global_batch=n * self.world,
                                 on_stage_done=self._on_stage_done if self.collectives else None,
                                 loss_scale=self.loss_scale)
@@ -141,6 +158,54 @@ class Trainer:
             self.loss_scale *= 2.0
             self._good_steps = 0
         return pl
+
+    def _mix_batch(self, clips, labels):
+        """Soft-target training: draws this batch's MixParams, mixes the clips with the reversed batch (x3d_mix_clips) and
+        builds the soft targets in the plan's `targets` (x3d_mix_targets).  Returns what `forward_backward` gets.  The
+        caller's tensors are never written: the clips are mixed in place only where bringing them to the device and the
+        storage type -- which binding them would do anyway -- made a copy, else into a buffer the trainer keeps.  With
+        smoothing only (mode "none") the clips are passed through and lam = 1.  Single-label models: `plan.labels` receives
+        the hard labels the training metrics count against.  Launches only, no host synchronisation."""
+        from . import ops
+        m = self.model
+        n, t, h, w, _ = clips.shape
+        p = draw_mix_params(self.cfg, h, w, self._mix_rng)
+        self.last_mix = p
+        pl = m._plan(n, t, h, w, True)
+        if p.mode != "none":
+            x = clips
+            if not x.is_cuda:
+                x = x.to(m.device, non_blocking=True)
+            if not x.is_contiguous():
+                x = x.contiguous()
+            if x.dtype != m.dtype:
+                x = x.to(m.dtype)
+            if x is clips or x.data_ptr() == clips.data_ptr():
+                if self._mix_buf is None or self._mix_buf.shape != x.shape or self._mix_buf.dtype != x.dtype:
+                    self._mix_buf = torch.empty_like(x)
+                out = self._mix_buf
+            else:
+                out = x
+            clips = ops.mix_clips(x, p.mode, p.lam, (p.y0, p.y1, p.x0, p.x1), out=out)
+        if m.multi_label:
+            m._bind_targets(pl, labels, n)
+            if p.mode != "none":
+                ops.mix_targets(pl.targets, m.num_classes, p.lam, out=pl.targets)
+        else:
+            if not torch.is_tensor(labels):
+                labels = torch.as_tensor(labels)
+            if labels.dim() != 1:
+                raise ValueError(f"labels must be {n} class indices when MIXUP / LABEL_SMOOTHING build the targets, got "
+                                 f"{tuple(labels.shape)}")
+            if not labels.is_cuda:   # as forward_backward: host labels are validated for free, device labels by the kernel
+                if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= m.num_classes:
+                    raise ValueError(f"labels must be {n} class indices in [0, {m.num_classes})")
+            if self._mix_labels is None or self._mix_labels.numel() != n:
+                self._mix_labels = torch.zeros(n, dtype=torch.int32, device=m.device)
+            self._mix_labels.copy_(labels.to(m.device, non_blocking=True).to(torch.int32))
+            pl.use_soft_targets(True)
+            ops.mix_targets(self._mix_labels, m.num_classes, p.lam, self.mix.label_smoothing, out=pl.targets, hard=pl.labels)
+        return clips, pl.targets
 
     def fit(self, dataset, epochs: Optional[int] = None, steps_per_epoch: Optional[int] = None, model_dir: Optional[str] = None,
             initial_epoch: Optional[int] = None, on_step=None, validation_data=None, validation_steps: Optional[int] = None,
