@@ -51,28 +51,114 @@ def test_stale_library_is_refused(tmp_path, monkeypatch):
         hip.load(hip.LIB_PATH)
 
 
-def test_struct_layouts_match_header():
-    """field order of the ctypes mirrors == field order of the C structs"""
-    text = open(os.path.join(ROOT, "include", "x3d_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    pairs = {"x3d_pw_fwd_args": hip.PwFwdArgs, "x3d_pw_dgrad_args": hip.PwDgradArgs,
-             "x3d_pw_wgrad_args": hip.PwWgradArgs, "x3d_pw_bwd_args": hip.PwBwdArgs,
-             "x3d_pw_pack_item": hip.PwPackItem, "x3d_bn_eval_item": hip.BnEvalItem, "x3d_eval_views_args": hip.EvalViewsArgs, "x3d_dw3d_fwd_args": hip.Dw3dFwdArgs,
-             "x3d_dw3d_bwd_args": hip.Dw3dBwdArgs, "x3d_se_bnb_bwd_args": hip.SeBnbBwdArgs,
-             "x3d_bn_fold": hip.BnFold, "x3d_train_clip_args": hip.TrainClipArgs}
-    for cname, cls in pairs.items():
-        body = re.search(r"typedef struct \{([^{}]*)\} " + cname + ";", text).group(1)
-        fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            names = decl.split(",")
-            first = names[0].split()[-1].lstrip("*")
-            fields.append(first)
-            fields += [n.strip().lstrip("*") for n in names[1:]]
-        fields = [re.sub(r"\[\d+\]$", "", f) for f in fields]   # float mean[3] -> mean
-        assert fields == [f[0] for f in cls._fields_], cname
+def _header_structs():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "x3d_hip.h")).read(), flags=re.S)
+    return re.findall(r"typedef struct \{[^{}]*\}\s*(x3d_\w+)\s*;", text)
+
+
+def _hip_structs():
+    """C name -> class, from the public names of hip (x3d_pw_fwd_args <- PwFwdArgs)"""
+    import ctypes
+    return {"x3d_" + re.sub(r"(?<!^)([A-Z])", r"_\1", n).lower(): c for n, c in vars(hip).items()
+            if not n.startswith("_") and isinstance(c, type) and issubclass(c, ctypes.Structure)}
+
+
+def test_every_header_struct_has_a_class():
+    assert len(_header_structs()) == 16
+    assert sorted(_header_structs()) == sorted(_hip_structs())
+
+
+def test_struct_layouts_match_the_compiler(tmp_path):
+    """sizeof, and offset and size of every field, of all argument structs: what the C++ compiler makes of include/x3d_hip.h
+    (tests/abi_layout_probe.cpp, field lists written out by hand) == what ctypes makes of the classes hip.py derives from it"""
+    import ctypes
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        import pytest
+        pytest.skip("hipcc not available")
+    exe = tmp_path / "abi_layout_probe"
+    r = subprocess.run([hipcc, "-x", "c++", "-O0", os.path.join(ROOT, "tests", "abi_layout_probe.cpp"),
+                        "-I" + os.path.join(ROOT, "include"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    compiled = {}
+    for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        name, *nums = line.split()
+        compiled[name] = tuple(int(n) for n in nums)
+    ours = {}
+    for cname, cls in _hip_structs().items():
+        ours[cname] = (ctypes.sizeof(cls),)
+        for f, _ in cls._fields_:
+            ours[f"{cname}.{f}"] = (getattr(cls, f).offset, getattr(cls, f).size)
+    assert sorted(n for n in compiled if "." not in n) == sorted(_header_structs())    # the probe covers every struct
+    assert compiled == ours, {k: (compiled.get(k), ours.get(k)) for k in set(compiled) | set(ours) if compiled.get(k) != ours.get(k)}
+
+
+def test_pinned_signatures():
+    """argument and return types of one entry point per mapping rule, and of the long long / double / float positions a
+    32-bit or wrong-width slot would corrupt silently, written out literally"""
+    from ctypes import POINTER as P, c_char_p, c_double as d, c_float as f, c_int as i, c_longlong as ll, c_size_t, c_uint32, c_void_p as vp
+    sigs = {
+        "x3d_version": ([], i),
+        "x3d_last_error": ([], c_char_p),
+        "x3d_stats_stride": ([i], ll),
+        "x3d_tail_fwd": ([vp, vp, vp, vp, vp, i, i, ll, i, vp], i),
+        "x3d_tail_fwd_bn": ([vp, P(hip.BnFold), vp, P(hip.BnFold), vp, i, i, ll, i, vp], i),
+        "x3d_pool_fwd": ([vp, vp, vp, i, i, ll, i, vp], i),
+        "x3d_subsample2": ([vp, vp, ll, i, i, i, vp], i),
+        "x3d_sgd_nesterov": ([vp, vp, vp, vp, f, f, f, f, ll, vp], i),
+        "x3d_adam": ([vp, vp, vp, vp, vp, f, f, f, f, f, f, ll, ll, vp], i),
+        "x3d_nthwc_to_ncthw": ([vp, i, vp, i, i, i, ll, vp], i),
+        "x3d_bn_finalize": ([vp, d, vp, vp, vp, vp, f, f, i, vp, vp, i, vp], i),
+        "x3d_se_fwd": ([vp, d, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp], i),
+        "x3d_dense_fwd": ([vp, vp, f, vp, vp, vp, i, i, i, i, vp], i),
+        "x3d_mix_clips": ([vp, vp, i, f, i, i, i, i, i, i, i, i, i, i, vp], i),
+        "x3d_mix_targets": ([vp, vp, vp, vp, f, f, i, i, vp], i),
+        "x3d_pw_fwd": ([P(hip.PwFwdArgs), vp], i),
+        "x3d_pw_kernel_name": ([P(hip.PwFwdArgs), P(hip.PwDgradArgs), P(hip.PwWgradArgs), P(hip.PwBwdArgs), c_char_p, i], i),
+        "x3d_dw_slab_reduce": ([P(hip.DwReduceJob), i, vp], i),
+        "x3d_bn_eval_coef_batched": ([vp, i, f, vp], i),      # items: device memory
+        "x3d_pw_pack_weights": ([vp, i, i, vp], i),            # items: device memory
+        "x3d_train_resized_hw": ([i, i, f, P(i), P(i)], i),
+        "x3d_jpeg_parse": ([vp, vp, i, P(hip.JpegImage), P(ll)], i),
+        "x3d_crc32c": ([c_char_p, c_size_t, c_uint32], c_uint32),
+    }
+    lib = hip.load()
+    for name, (argtypes, restype) in sigs.items():
+        fn = getattr(lib, name)
+        assert (list(fn.argtypes), fn.restype) == (argtypes, restype), name
+    # pointer fields of the structs: addresses held as integers, except the BatchNorm fold x3d_dw3d_fwd takes by reference
+    fields = {cls: dict(cls._fields_) for cls in (hip.PwDgradArgs, hip.PwWgradArgs, hip.PwBwdArgs, hip.Dw3dFwdArgs,
+                                                  hip.JpegDecodeArgs, hip.BnFold, hip.JpegImage)}
+    for cls in (hip.PwDgradArgs, hip.PwWgradArgs, hip.PwBwdArgs):
+        assert fields[cls]["coef_fold"] is vp
+    assert fields[hip.JpegDecodeArgs]["images"] is vp and fields[hip.JpegDecodeArgs]["host_images"] is vp
+    assert fields[hip.JpegDecodeArgs]["scratch_bytes"] is ll and fields[hip.JpegImage]["data_off"] is ll
+    assert fields[hip.Dw3dFwdArgs]["in_bn"] is P(hip.BnFold)
+    assert fields[hip.BnFold]["count"] is d and fields[hip.BnFold]["eps"] is f
+
+
+def test_header_parser_is_strict():
+    """a declaration the parser does not understand is an error that names it, never a silent skip"""
+    import pytest
+    good = "#define X3D_ABI_VERSION 7\ntypedef struct {\n  const float* w;\n  int N, C;\n} x3d_t;\nint x3d_f(const x3d_t* a, void* stream);\n"
+    consts, structs, sigs = hip._parse_header(good)
+    assert consts == {"ABI_VERSION": 7} and list(sigs) == ["x3d_f"] and [n for n, _ in structs["x3d_t"]._fields_] == ["w", "N", "C"]
+    bad = {
+        "int x3d_g(const half* x, int n);": r"line 7.*half.*x3d_g",                     # unknown pointee
+        "int x3d_g(unsigned n);": r"line 7.*unsigned.*x3d_g",                           # unknown scalar
+        "int x3d_g(int (*cb)(int), int n);": r"line 7.*x3d_g",                          # function pointer
+        "int x3d_g(int n)\nint x3d_h(int n);": r"line 7.*x3d_g",                        # missing semicolon
+        "typedef struct { float* a, b; } x3d_u;": r"line 7.*float\* a, b",               # pointer declarator list
+        "typedef struct {\n  int n;\n  short s;\n} x3d_u;": r"line 9.*short s",              # unknown field type: its own line
+        "typedef struct { int n; int m } x3d_u;": r"line 7.*int m",                     # field without a semicolon
+        "enum x3d_e { A, B };": r"line 7.*enum",                                        # not a prototype or struct
+        "#define X3D_SCALE 1.5f": r"line 7.*X3D_SCALE",                                 # constant that is not an integer
+    }
+    for decl, message in bad.items():
+        with pytest.raises(hip.X3DHipError, match=message):
+            hip._parse_header(good + decl + "\nint x3d_tail(int n);\n")
 
 
 def test_missing_library_fails_loudly(tmp_path):

@@ -5,17 +5,13 @@ device memory (``tensor.data_ptr()``) and the current HIP stream.
 """
 import ctypes as C
 import os
+import re
+import weakref
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("X3D_HIP_LIB") or os.path.join(_HERE, "libx3d_hip.so")   # X3D_HIP_LIB: A/B builds (tools/build_variant.sh)
-
-ABI_VERSION = 137   # X3D_ABI_VERSION of the include/x3d_hip.h the signatures below were written against
-F32, BF16, F16 = 0, 1, 2
-ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = 0, 1, 2, 3
-MIX_MIXUP, MIX_CUTMIX = 1, 2
-EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = 0, 1, 2, 3
 
 _vp, _i, _f, _d, _ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
 
@@ -24,72 +20,141 @@ class X3DHipError(RuntimeError):
     pass
 
 
-class PwFwdArgs(C.Structure):
-    _fields_ = [("x", _vp), ("w", _vp), ("y", _vp), ("stats", _vp), ("in_scale_shift", _vp),
-                ("in_gate", _vp), ("in_act", _i), ("N", _i), ("Cin", _i), ("Cout", _i), ("T", _i),
-                ("H", _i), ("W", _i), ("stride", _i), ("dtype", _i), ("w_panel", _vp),
-                ("in_add", _vp), ("in_add_scale_shift", _vp), ("in_store", _vp),
-                ("out_scale_shift", _vp), ("out_add", _vp), ("out_add_scale_shift", _vp), ("out_act", _i)]
+# ---- include/x3d_hip.h is the single statement of the ABI: constants, argument structs and signatures are read from it ----
+_SCALARS = {"int": _i, "float": _f, "double": _d, "long long": _ll, "unsigned short": C.c_ushort,
+            "size_t": C.c_size_t, "uint32_t": C.c_uint32}
+_POINTEES = set(_SCALARS) | {"void", "unsigned char"}   # data pointers: callers hand over integers from data_ptr() -> c_void_p
+# Where Python passes a host object instead of an address the header cannot say so.  (struct or function, field or parameter)
+# -> ctypes type, or the name of a header struct for a pointer to it.  A pointer to a header struct in a PARAMETER is
+# POINTER(struct) by default (callers pass byref(args)); inside a struct it is an address held as an integer (coef_fold via
+# fold_address(), which dispatch._struct_pointers follows; JpegDecodeArgs.images / host_images).
+_OVERRIDES = {
+    ("x3d_dw3d_fwd_args", "in_bn"): "x3d_bn_fold",                  # plan.py assigns ctypes.pointer(BnFold) to the field
+    ("x3d_bn_eval_coef_batched", "items"): _vp,                     # the item table lives in device memory: data_ptr()
+    ("x3d_pw_pack_weights", "items"): _vp,                          # likewise
+    ("x3d_crc32c", "data"): C.c_char_p,                             # callers pass bytes
+    ("x3d_train_resized_hw", "new_h"): C.POINTER(_i),               # host out-parameters: byref(c_int())
+    ("x3d_train_resized_hw", "new_w"): C.POINTER(_i),
+    ("x3d_jpeg_parse", "scratch_bytes"): C.POINTER(_ll),            # host out-parameter: byref(c_longlong())
+}
+_ITEM = re.compile(r"(?:((?:\w+[\s*]+)+))?(\w+)((?:\[\d+\])*)$")    # [type] name [dims]: `const float* w`, `Cin`, `qt[3][64]`
+_DECL = re.compile(r"(?:typedef\s+struct\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>x3d_\w+)"
+                   r"|(?P<ret>[\w\s*]+?)(?P<fn>x3d_\w+)\s*\((?P<params>[^(){};]*)\))\s*;\s*")
 
 
-class PwDgradArgs(C.Structure):
-    _fields_ = [("g", _vp), ("yraw", _vp), ("coef", _vp), ("w", _vp), ("dx", _vp), ("epi", _i),
-                ("add", _vp), ("braw", _vp), ("b_scale_shift", _vp), ("gate", _vp), ("nc_sums", _vp),
-                ("N", _i), ("Cin", _i), ("Cout", _i), ("T", _i), ("H", _i), ("W", _i), ("dtype", _i),
-                ("w_panel", _vp), ("coef_fold", _vp)]
+def _parse_header(text, overrides=_OVERRIDES):
+    """(constants, structs, signatures) of a header in the style of include/x3d_hip.h; a declaration this does not understand
+    raises X3DHipError naming its line."""
+    text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group().count("\n"), text, flags=re.S)   # line numbers survive
+    consts, structs, sigs = {}, {}, {}
+
+    def fail(pos, why):
+        decl = " ".join(text[pos:].split(";")[0].split())
+        raise X3DHipError(f"x3d_hip.h line {text.count(chr(10), 0, pos) + 1}: {why}: `{decl[:120]}`")
+
+    def ctype(pos, owner, ty, name, param):
+        words = ty.replace("*", " ").split()
+        base, stars = " ".join(w for w in words if w != "const"), ty.count("*")
+        over = overrides.get((owner, name))
+        if over is not None:
+            return C.POINTER(structs[over]) if isinstance(over, str) else over
+        if not stars and (base in _SCALARS or base in structs):
+            return _SCALARS.get(base) or structs[base]
+        if stars == 1 and base == "char":
+            return C.c_char_p
+        if stars == 1 and base in structs and param:
+            return C.POINTER(structs[base])
+        if stars and (base in _POINTEES or base in structs):
+            return _vp
+        fail(pos, f"unknown type `{ty.strip()}` of `{name}`")
+
+    def items(pos, owner, decl, param):
+        """`int N, Cin` / `float mean[3]` / `const void* x` -> [(name, ctype)]"""
+        out, ty = [], None
+        for part in decl.split(","):
+            m = _ITEM.match(part.strip())
+            if not m or not (m.group(1) or ty) or (m.group(1) and out) or (out and "*" in ty):
+                fail(pos, "cannot read declaration")
+            ty = m.group(1) or ty
+            ct = ctype(pos, owner, ty, m.group(2), param)
+            for n in reversed(re.findall(r"\d+", m.group(3))):
+                ct = ct * int(n)
+            out.append((m.group(2), ct))
+        return out
+
+    def directive(m):
+        d = re.fullmatch(r"#\s*define\s+X3D_(\w+)\s+(-?\d+)\s*", m.group())
+        if d:
+            consts[d.group(1)] = int(d.group(2))
+        elif not re.match(r"#\s*(ifn?def|endif|include|define\s+\w+\s*$)", m.group()):
+            fail(m.start(), "cannot read directive")
+        return ""
+    text = re.sub(r"^[ \t]*#.*$", directive, text, flags=re.M)
+    text = re.sub(r'^(extern "C" \{|\})[ \t]*$', "", text, flags=re.M)
+    pos = re.match(r"\s*", text).end()
+    while pos < len(text):
+        m = _DECL.match(text, pos) or fail(pos, "cannot read declaration")
+        if m.group("struct"):
+            fields, end = [], 0
+            for d in re.finditer(r"\s*([^;]+);", m.group("body")):
+                fields += items(m.start("body") + d.start(1), m.group("struct"), d.group(1), False)
+                end = d.end()
+            if m.group("body")[end:].strip():
+                fail(m.start("body") + end, "cannot read declaration")
+            name = "".join(w.capitalize() for w in m.group("struct")[4:].split("_"))      # x3d_pw_fwd_args -> PwFwdArgs
+            structs[m.group("struct")] = type(name, (C.Structure,), {"_fields_": fields})
+        else:
+            fn, params = m.group("fn"), m.group("params").strip()
+            args = [] if params == "void" else [a for p in params.split(",") for a in items(pos, fn, p, True)]
+            sigs[fn] = ([t for _, t in args], ctype(pos, fn, m.group("ret"), "(return value)", False))
+        pos = m.end()
+    return consts, structs, sigs
 
 
-class PwBwdArgs(C.Structure):
-    _fields_ = [("g", _vp), ("yraw", _vp), ("coef", _vp), ("w_panel", _vp), ("dx", _vp), ("epi", _i),
-                ("add", _vp), ("braw", _vp), ("b_scale_shift", _vp), ("gate", _vp), ("nc_sums", _vp),
-                ("x", _vp), ("dw", _vp),
-                ("N", _i), ("Cin", _i), ("Cout", _i), ("T", _i), ("H", _i), ("W", _i), ("dtype", _i),
-                ("tail_c", _vp), ("tail_r", _vp), ("tail_sums_c", _vp), ("tail_sums_r", _vp),
-                ("rc_panel", _vp), ("rc_c0", _vp), ("rc_sums", _vp), ("x_stride", _i), ("xH", _i), ("xW", _i),
-                ("dw_slab", _vp), ("dw_slab_parts", _i), ("coef_fold", _vp)]
+with open(os.path.join(os.path.dirname(_HERE), "include", "x3d_hip.h")) as _fh:
+    _CONSTS, _STRUCTS, _SIGS = _parse_header(_fh.read())
 
 
-class DwReduceJob(C.Structure):
-    _fields_ = [("slab", _vp), ("dw", _vp), ("parts", _i), ("elems", _i)]
+def _consts(*names):
+    return [_CONSTS[n] for n in names]
 
 
-class EvalViewsArgs(C.Structure):
-    _fields_ = [("video", _vp), ("out", _vp), ("F", _i), ("H", _i), ("W", _i), ("T", _i), ("views", _i),
-                ("crops", _i), ("size", _i), ("mean", _f * 3), ("std", _f * 3), ("dtype", _i)]
+def _struct(cname, doc=None):
+    _STRUCTS[cname].__doc__ = doc
+    return _STRUCTS[cname]
 
 
-class TrainClipArgs(C.Structure):
-    _fields_ = [("video", _vp), ("out", _vp), ("F", _i), ("H", _i), ("W", _i), ("T", _i), ("rate", _i), ("start", _i),
-                ("jitter", _f), ("size", _i), ("y0", _i), ("x0", _i), ("flip", _i), ("mean", _f * 3), ("std", _f * 3),
-                ("dtype", _i)]
+# one line per exported name: a constant or struct the header renames fails here, at import
+ABI_VERSION = _consts("ABI_VERSION")[0]   # load() refuses a library built from another version of the header
+F32, BF16, F16 = _consts("F32", "BF16", "F16")
+ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = _consts("ACT_NONE", "ACT_RELU", "ACT_SWISH", "ACT_SIGMOID")
+MIX_MIXUP, MIX_CUTMIX = _consts("MIX_MIXUP", "MIX_CUTMIX")
+EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = _consts("EPI_STORE", "EPI_ADD", "EPI_ADD_STRIDED", "EPI_SWISH_BWD")
+AP_MAX_POSITIVES = _consts("AP_MAX_POSITIVES")[0]
+JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = _consts(
+    "JPEG_OK", "JPEG_UNSUPPORTED", "JPEG_MALFORMED", "JPEG_CORRUPT", "JPEG_SKIPPED")
 
-
-class BnEvalItem(C.Structure):
-    _fields_ = [("gamma", _vp), ("beta", _vp), ("moving_mean", _vp), ("moving_var", _vp), ("scale_shift", _vp),
-                ("mean_invstd", _vp), ("C", _i)]
-
-
-class PwPackItem(C.Structure):
-    _fields_ = [("w", _vp), ("fwd_panel", _vp), ("dgrad_panel", _vp), ("Cout", _i), ("Cin", _i)]
-
-
-class PwWgradArgs(C.Structure):
-    _fields_ = [("g", _vp), ("yraw", _vp), ("coef", _vp), ("x", _vp), ("in_scale_shift", _vp),
-                ("in_gate", _vp), ("in_act", _i), ("dw", _vp), ("N", _i), ("Cin", _i), ("Cout", _i),
-                ("T", _i), ("H", _i), ("W", _i), ("stride", _i), ("dtype", _i), ("dw_slab", _vp), ("dw_slab_parts", _i),
-                ("coef_fold", _vp)]
-
-
-class BnBwdFold(C.Structure):
-    """x3d_bn_bwd_fold: the BatchNorm-backward finalize folded into its consumers (coef_fold of the backward argument structs)."""
-    _fields_ = [("sums", _vp), ("count", _d), ("mean_invstd", _vp), ("gamma", _vp), ("dgamma", _vp), ("dbeta", _vp),
-                ("coef_out", _vp)]
-
+PwFwdArgs = _struct("x3d_pw_fwd_args")
+PwDgradArgs = _struct("x3d_pw_dgrad_args")
+PwBwdArgs = _struct("x3d_pw_bwd_args")
+DwReduceJob = _struct("x3d_dw_reduce_job")
+EvalViewsArgs = _struct("x3d_eval_views_args")
+TrainClipArgs = _struct("x3d_train_clip_args")
+BnEvalItem = _struct("x3d_bn_eval_item")
+PwPackItem = _struct("x3d_pw_pack_item")
+PwWgradArgs = _struct("x3d_pw_wgrad_args")
+BnBwdFold = _struct("x3d_bn_bwd_fold", "x3d_bn_bwd_fold: the BatchNorm-backward finalize folded into its consumers (coef_fold "
+                    "of the backward argument structs).")
+BnFold = _struct("x3d_bn_fold")
+Dw3dFwdArgs = _struct("x3d_dw3d_fwd_args")
+Dw3dBwdArgs = _struct("x3d_dw3d_bwd_args")
+SeBnbBwdArgs = _struct("x3d_se_bnb_bwd_args")
+JpegImage = _struct("x3d_jpeg_image", "x3d_jpeg_image: one parsed JPEG (include/x3d_hip.h).")
+JpegDecodeArgs = _struct("x3d_jpeg_decode_args")
 
 # address -> BnBwdFold: argument structs refer to a fold by address (tools that walk a plan's pointers follow it).  Weak values:
 # the plan (or the ops wrapper) that built a fold keeps it alive for as long as its launches exist; an entry whose owner is gone
 # disappears with it instead of accumulating -- and instead of handing dispatch._struct_pointers stale device addresses.
-import weakref  # noqa: E402
 FOLDS = weakref.WeakValueDictionary()
 
 
@@ -99,119 +164,6 @@ def fold_address(f: BnBwdFold) -> int:
     FOLDS[a] = f
     return a
 
-
-class BnFold(C.Structure):
-    _fields_ = [("stats", _vp), ("count", _d), ("gamma", _vp), ("beta", _vp), ("moving_mean", _vp), ("moving_var", _vp),
-                ("eps", _f), ("momentum", _f), ("update_moving", _i), ("scale_shift", _vp), ("mean_invstd", _vp)]
-
-
-class Dw3dFwdArgs(C.Structure):
-    _fields_ = [("x", _vp), ("w", _vp), ("y", _vp), ("in_scale_shift", _vp), ("in_act", _i),
-                ("stats", _vp), ("pool", _vp), ("N", _i), ("C", _i), ("T", _i), ("H", _i), ("W", _i),
-                ("stride", _i), ("dtype", _i), ("in_bn", C.POINTER(BnFold))]
-
-
-class Dw3dBwdArgs(C.Structure):
-    _fields_ = [("dv", _vp), ("braw", _vp), ("coef_nc", _vp), ("araw", _vp), ("a_scale_shift", _vp),
-                ("w", _vp), ("ga", _vp), ("a_sums", _vp), ("dw", _vp), ("N", _i), ("C", _i), ("T", _i),
-                ("H", _i), ("W", _i), ("stride", _i), ("dtype", _i)]
-
-
-class SeBnbBwdArgs(C.Structure):
-    _fields_ = [("nc_sums", _vp), ("pool_sums", _vp), ("P", _d), ("b_scale_shift", _vp),
-                ("b_mean_invstd", _vp), ("gamma_b", _vp), ("w1", _vp), ("b1", _vp), ("w2", _vp),
-                ("b2", _vp), ("gate", _vp), ("hidden", _vp), ("dw1", _vp), ("db1", _vp), ("dw2", _vp),
-                ("db2", _vp), ("dgamma_b", _vp), ("dbeta_b", _vp), ("coef_nc", _vp), ("scratch", _vp),
-                ("N", _i), ("C", _i), ("Wd", _i), ("reduce", DwReduceJob * 2)]
-
-
-class JpegImage(C.Structure):
-    """x3d_jpeg_image: one parsed JPEG (include/x3d_hip.h)."""
-    _fields_ = [("out", _vp), ("data_off", _ll), ("coef_off", _ll), ("plane_off", _ll), ("data_len", _i), ("status", _i),
-                ("height", _i), ("width", _i), ("ncomp", _i), ("hs", _i * 3), ("vs", _i * 3), ("bw", _i * 3), ("bh", _i * 3),
-                ("mcux", _i), ("mcuy", _i), ("dc_tbl", _i * 3), ("ac_tbl", _i * 3), ("huff_off", _i * 8),
-                ("restart_interval", _i), ("ecs_off", _i), ("ecs_end", _i), ("qt", (C.c_ushort * 64) * 3)]
-
-
-class JpegDecodeArgs(C.Structure):
-    _fields_ = [("data", _vp), ("images", _vp), ("host_images", _vp), ("n", _i), ("scratch", _vp), ("scratch_bytes", _ll),
-                ("status", _vp)]
-
-
-AP_MAX_POSITIVES = 32768   # X3D_AP_MAX_POSITIVES
-
-JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = 0, 1, 2, 3, 4
-
-
-_SIGS = {
-    "x3d_version": ([], _i),
-    "x3d_last_error": ([], C.c_char_p),
-    "x3d_stem_s_nthwc_supported": ([_i, _i, _i, _i], _i),
-    "x3d_stem_s_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_stem_s_wgrad": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_dwt_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_dwt_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_stem_fused_supported": ([_i] * 9, _i),
-    "x3d_stem_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_stem_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_stats_replicas": ([], _i),
-    "x3d_stats_stride": ([_i], _ll),
-    "x3d_bn_finalize": ([_vp, _d, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp], _i),
-    "x3d_bn_eval_coef_batched": ([_vp, _i, _f, _vp], _i),
-    "x3d_bn_bwd_finalize": ([_vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "x3d_pw_fwd": ([C.POINTER(PwFwdArgs), _vp], _i),
-    "x3d_pw_fwd_tail_supported": ([C.POINTER(PwFwdArgs)], _i),
-    "x3d_pw_dgrad": ([C.POINTER(PwDgradArgs), _vp], _i),
-    "x3d_pw_wgrad": ([C.POINTER(PwWgradArgs), _vp], _i),
-    "x3d_pw_wgrad_dw_parts": ([C.POINTER(PwWgradArgs)], _i),
-    "x3d_pw_bwd_supported": ([C.POINTER(PwBwdArgs)], _i),
-    "x3d_pw_bwd": ([C.POINTER(PwBwdArgs), _vp], _i),
-    "x3d_pw_bwd_dw_parts": ([C.POINTER(PwBwdArgs)], _i),
-    "x3d_pw_coef_fold_supported": ([C.POINTER(PwDgradArgs), C.POINTER(PwWgradArgs), C.POINTER(PwBwdArgs)], _i),
-    "x3d_dw_slab_reduce": ([C.POINTER(DwReduceJob), _i, _vp], _i),
-    "x3d_pw_bwd_rc_panel_elems": ([_i, _i], _ll),
-    "x3d_pw_bwd_rc_sums_elems": ([_i, _i], _ll),
-    "x3d_pw_bwd_rc_prepare": ([_vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_pw_bwd_rc_finish": ([_vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_bn_bwd_finalize_rc": ([_vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_pw_kernel_name": ([C.POINTER(PwFwdArgs), C.POINTER(PwDgradArgs), C.POINTER(PwWgradArgs), C.POINTER(PwBwdArgs),
-                            C.c_char_p, _i], _i),
-    "x3d_pw_panel_elems": ([_i, _i], _ll),
-    "x3d_pw_pack_weights": ([_vp, _i, _i, _vp], _i),
-    "x3d_dw3d_fwd": ([C.POINTER(Dw3dFwdArgs), _vp], _i),
-    "x3d_dw3d_bwd": ([C.POINTER(Dw3dBwdArgs), _vp], _i),
-    "x3d_dw3d_kernel_name": ([C.POINTER(Dw3dFwdArgs), C.POINTER(Dw3dBwdArgs), C.c_char_p, _i], _i),
-    "x3d_se_fwd": ([_vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_se_bnb_bwd": ([C.POINTER(SeBnbBwdArgs), _vp], _i),
-    "x3d_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _i, _vp], _i),
-    "x3d_tail_fwd_bn": ([_vp, C.POINTER(BnFold), _vp, C.POINTER(BnFold), _vp, _i, _i, _ll, _i, _vp], _i),
-    "x3d_tail_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _i, _vp], _i),
-    "x3d_relu_bn_bwd_reduce": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _i, _vp], _i),
-    "x3d_pool_fwd": ([_vp, _vp, _vp, _i, _i, _ll, _i, _vp], _i),
-    "x3d_subsample2": ([_vp, _vp, _ll, _i, _i, _i, _vp], _i),
-    "x3d_dense_fwd": ([_vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
-    "x3d_dense_bwd": ([_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_softmax_xent": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
-    "x3d_softmax_xent_soft": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
-    "x3d_view_mean": ([_vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_topk_metrics": ([_vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
-    "x3d_sigmoid_bce": ([_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp], _i),
-    "x3d_view_max": ([_vp, _vp, _i, _i, _i, _vp], _i),
-    "x3d_multilabel_ap": ([_vp, _vp, _i, _i, _vp, _vp, _vp], _i),
-    "x3d_mix_clips": ([_vp, _vp, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "x3d_mix_targets": ([_vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp], _i),
-    "x3d_sgd_nesterov": ([_vp, _vp, _vp, _vp, _f, _f, _f, _f, _ll, _vp], _i),
-    "x3d_adam": ([_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _ll, _ll, _vp], _i),
-    "x3d_all_finite": ([_vp, _ll, _vp, _vp], _i),
-    "x3d_l2_sumsq": ([_vp, _vp, _vp, _ll, _vp], _i),
-    "x3d_nthwc_to_ncthw": ([_vp, _i, _vp, _i, _i, _i, _ll, _vp], _i),
-    "x3d_eval_views": ([C.POINTER(EvalViewsArgs), _vp], _i),
-    "x3d_train_clip": ([C.POINTER(TrainClipArgs), _vp], _i),
-    "x3d_train_resized_hw": ([_i, _i, _f, C.POINTER(_i), C.POINTER(_i)], _i),
-    "x3d_crc32c": ([C.c_char_p, C.c_size_t, C.c_uint32], C.c_uint32),
-    "x3d_jpeg_parse": ([_vp, _vp, _i, C.POINTER(JpegImage), C.POINTER(_ll)], _i),
-    "x3d_jpeg_decode": ([C.POINTER(JpegDecodeArgs), _vp], _i),
-}
 
 _lib = None
 

@@ -182,7 +182,6 @@ def bn_bwd_finalize(sums, count, mi, gamma, coef, dgamma, dbeta):
 def pw_pack_weights(weights, dgrad=True, dtype=torch.bfloat16):
     """fp32 [Cout, Cin] weights -> list of (fwd_panel, dgrad_panel) LDS-image panels of the 16-bit storage type `dtype`,
     one launch (x3d_pw_pack_weights)."""
-    import ctypes as C
     lib = hip.load()
     items = (hip.PwPackItem * len(weights))()
     out = []
@@ -259,11 +258,10 @@ def pw_bwd(g, yraw, coef, w_panel, dx, dw, epi, x=None, add=None, braw=None, b_s
                       ptr(tail_c), ptr(tail_r), ptr(tail_sums_c), ptr(tail_sums_r))
     if coef_fold is not None:
         a.coef_fold = hip.fold_address(coef_fold)
-    import ctypes as C
-    if not hip.load().x3d_pw_bwd_supported(C.byref(a)):
+    if not hip.load().x3d_pw_bwd_supported(ctypes.byref(a)):
         return False
     if slab:
-        parts = int(hip.load().x3d_pw_bwd_dw_parts(C.byref(a)))
+        parts = int(hip.load().x3d_pw_bwd_dw_parts(ctypes.byref(a)))
         if parts <= 0:
             return None
         buf = torch.full((parts * cout * cin,), float("nan"), dtype=torch.float32, device=g.device)   # (every slab element must be written)
@@ -311,8 +309,7 @@ def pw_bwd_rc(g, x, w, coef, dx, dw, epi, add, tail_c=None, tail_r=None, tail_su
     a = hip.PwBwdArgs(ptr(g), None, None, None, ptr(dx), epi, ptr(add), None, None, None, None, ptr(x), None, n, cin, cout,
                       t, h, ww, hip.dtype_code(g.dtype), ptr(tail_c), ptr(tail_r), ptr(tail_sums_c), ptr(tail_sums_r),
                       ptr(panel), ptr(c0), ptr(sums), x_stride, x.shape[3], x.shape[4])
-    import ctypes as C
-    if not lib.x3d_pw_bwd_supported(C.byref(a)):
+    if not lib.x3d_pw_bwd_supported(ctypes.byref(a)):
         return False
     dt = hip.dtype_code(g.dtype)
     hip.call("x3d_pw_bwd_rc_prepare", ptr(w), ptr(coef), ptr(panel), ptr(c0), cout, cin, dt)
@@ -343,8 +340,7 @@ def pw_wgrad(g, yraw, coef, x, dw, in_ss=None, in_gate=None, in_act=ACT_NONE, st
     if coef_fold is not None:
         a.coef_fold = hip.fold_address(coef_fold)
     if slab:
-        import ctypes as C
-        parts = int(hip.load().x3d_pw_wgrad_dw_parts(C.byref(a)))
+        parts = int(hip.load().x3d_pw_wgrad_dw_parts(ctypes.byref(a)))
         if parts <= 0:
             return None
         buf = torch.full((parts * cout * cin,), float("nan"), dtype=torch.float32, device=g.device)   # (every slab element must be written)
