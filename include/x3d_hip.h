@@ -51,8 +51,9 @@ extern "C" {
  * History (latest): 133 x3d_subsample2; 134 x3d_topk_metrics (device-side accuracy / top-k counters for Trainer.fit);
  *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device);
  *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP);
- *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing). */
-#define X3D_ABI_VERSION 137
+ *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing);
+ *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing). */
+#define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
 
@@ -642,6 +643,74 @@ typedef struct {
 int x3d_train_clip(const x3d_train_clip_args* a, void* stream);
 /* extents of a H x W frame after random_short_side_resize with target `jitter` (transforms.py:126-141) */
 int x3d_train_resized_hw(int H, int W, float jitter, int* new_h, int* new_w);
+
+/* ------------------------------------------------------------------------------------------
+ * batched training augmentation (ABI 138; AUG.* of the config, x3d_tf_amd/aug.py): N decoded videos of DIFFERENT extents ->
+ * the whole clip batch out [N][T][size][size][3] (X3D_F32 / X3D_BF16 / X3D_F16, channels-last) in ONE launch, or two when
+ * a clip's contrast needs the mean of its geometric output.  The stages and where their definitions come from:
+ *     geometry  "jitter" rows: x3d_train_clip's (reference transforms.py:31-47, 112-147, 199-206), bit for bit;
+ *               "rrc" rows: torchvision RandomResizedCrop [TV-3p] -- the box [ry0, ry0+rh) x [rx0, rx0+rw) of the source
+ *               frame resampled to size x size with half-pixel-centre bilinear weights, no antialias, taps clamped to the
+ *               box (torch.nn.functional.interpolate(mode="bilinear", align_corners=False) on the crop), fp32, NOT
+ *               truncated to uint8;  frame j = (start + j * rate) mod F;  the mirror is applied last.
+ *     colour    PySlowFast color_jitter + grayscale [PSF-3p] on the 0-255 scale, never clamped, hence affine per pixel:
+ *               v_c = sum_k M[c][k] * x_k + K * m, m = mean over the T*size*size pixels of the clip's geometric output of
+ *               0.299 R + 0.587 G + 0.114 B (aug.fold_color folds the drawn chain into M and K).
+ *     normalise (v / 255 - mean) / std   (utils.py:42-72)
+ *     erase     timm RandomErasing [TIMM-3p]: the box [ey0, ey1) x [ex0, ex1) of the OUTPUT crop, the same in all T frames,
+ *               becomes 0 (X3D_AUG_ERASE_CONST) or N(0, 1) noise (X3D_AUG_ERASE_PIXEL): Philox4x32-10 (Salmon et al., SC'11)
+ *               with key = the CLIP'S OWN 64-bit seed (columns SEED_LO, SEED_HI of its row), counter = (pixel index in the
+ *               clip lo, hi, clip index, 0), Box-Muller on 24-bit uniforms of the four output words -> one normal per
+ *               channel.  Stateless: the same (seed, clip index, element) gives the same value on every run, whatever the
+ *               other clips of the batch are.
+ *     One round-to-nearest-even to the storage type.  All arithmetic fp32 without contraction.
+ * Per-clip parameters are rows of plain tables (no struct): videos [N] device addresses of the uint8 videos [F][H][W][3];
+ * geom int32 [N][X3D_AUG_GEOM_COLS]; color fp32 [N][X3D_AUG_COLOR_COLS] = M row-major, then K.  geom and color are DEVICE
+ * copies (read by the kernels) of host_geom and host_color (HOST, read by this call: validation, and whether any clip has
+ * K != 0).  THE CALLER MUST UPLOAD EXACTLY host_geom AND host_color: the call copies nothing (it neither allocates nor
+ * synchronises), so it validates the host rows and cannot see the device rows.  The kernels clamp every tap to the H x W
+ * the device row states, take the frame index modulo max(F, 1) and treat a crop extent below 1 as 1, so a device row that
+ * differs gives a wrong picture but no division by zero; only F, H, W larger than the allocation read outside it, exactly
+ * as a wrong x3d_train_clip_args does.  mean, std: HOST float[3].  scratch: x3d_train_clips_aug_scratch(N, T, size) bytes of device memory, 8-byte
+ * aligned, the caller's; it need not be zeroed.
+ * The mean pass (only when some K != 0; clips with K == 0 skip it): X3D_AUG_MEAN_PARTS workgroups per clip each write ONE
+ * fp64 partial sum of their share of the pixels into scratch; the apply pass adds a clip's partials in ascending order.
+ * No floating-point atomics: the same inputs give the same bits on every run.
+ * Refused before any launch (X3D_ERR_INVALID): a null table / pointer, N <= 0 or N > 65535, non-positive extents, start
+ * outside [0, F), an unknown mode / dtype / erase_mode, a "jitter" crop outside its resized frame (or nh, nw < size), an
+ * "rrc" box outside its frame or empty, an erase box outside the crop (0 <= ey0 <= ey1 <= size, likewise x; an empty box:
+ * no erase), a non-finite colour coefficient.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_AUG_CROP_JITTER 0
+#define X3D_AUG_CROP_RRC 1
+#define X3D_AUG_ERASE_CONST 0
+#define X3D_AUG_ERASE_PIXEL 1
+#define X3D_AUG_MEAN_PARTS 32
+#define X3D_AUG_GEOM_COLS 18
+#define X3D_AUG_G_F 0         /* frames, height, width of the clip's video */
+#define X3D_AUG_G_H 1
+#define X3D_AUG_G_W 2
+#define X3D_AUG_G_START 3
+#define X3D_AUG_G_MODE 4      /* X3D_AUG_CROP_* */
+#define X3D_AUG_G_NH 5        /* jitter: extents after the short-side resize (x3d_train_resized_hw) */
+#define X3D_AUG_G_NW 6
+#define X3D_AUG_G_Y0 7        /* jitter: crop offset in the resized frame;  rrc: top-left corner of the box */
+#define X3D_AUG_G_X0 8
+#define X3D_AUG_G_BH 9        /* rrc: box extents */
+#define X3D_AUG_G_BW 10
+#define X3D_AUG_G_FLIP 11
+#define X3D_AUG_G_EY0 12      /* erase box in the output crop, [EY0, EY1) x [EX0, EX1) */
+#define X3D_AUG_G_EY1 13
+#define X3D_AUG_G_EX0 14
+#define X3D_AUG_G_EX1 15
+#define X3D_AUG_G_SEED_LO 16  /* the clip's 64-bit noise seed (X3D_AUG_ERASE_PIXEL), low and high word */
+#define X3D_AUG_G_SEED_HI 17
+#define X3D_AUG_COLOR_COLS 10
+#define X3D_AUG_C_K 9         /* coefficient of the mean gray m (columns 0-8: M) */
+long long x3d_train_clips_aug_scratch(int N, int T, int size);
+int x3d_train_clips_aug(const long long* videos, const int* geom, const float* color, const int* host_geom,
+                        const float* host_color, void* out, void* scratch, int N, int T, int rate, int size,
+                        const float* mean, const float* std, int erase_mode, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * JPEG frames of the TFRecord input pipeline decoded on the device (reference dataloader.py:80-88:

@@ -117,7 +117,8 @@ class CfgNode(dict):
 
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
-    TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training)."""
+    TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
+    AUG.* (batched training augmentation)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -138,6 +139,14 @@ def get_default_config():
     # Beta parameters of the two modes (0 = that mode off), PROB the chance a batch is mixed at all, SWITCH_PROB the chance of
     # CutMix when both modes are on
     c.MIXUP = CfgNode(dict(ENABLE=False, ALPHA=0.8, CUTMIX_ALPHA=1.0, PROB=1.0, SWITCH_PROB=0.5))
+    # training augmentation built on the device in one batched call (aug.py, x3d_train_clips_aug; names after PySlowFast's AUG /
+    # DATA sections); inert unless ENABLE.  CROP "jitter": the reference's short-side resize + random crop; "rrc": a
+    # random-resized crop of RRC_SCALE area fraction and RRC_RATIO aspect.  FLIP_PROB 1.0 is the reference's mirror of every
+    # clip.  BRIGHTNESS / CONTRAST / SATURATION: strengths v, factor 1 + U(-v, v), 0 = that op off; COLOR_PROB the chance a
+    # clip gets the colour chain, GRAYSCALE_PROB that it is turned grey after it.  RE_*: random erasing.
+    c.AUG = CfgNode(dict(ENABLE=False, CROP="jitter", RRC_SCALE=[0.08, 1.0], RRC_RATIO=[0.75, 1.3333], FLIP_PROB=0.5,
+                         BRIGHTNESS=0.4, CONTRAST=0.4, SATURATION=0.4, COLOR_PROB=1.0, GRAYSCALE_PROB=0.0, RE_PROB=0.25,
+                         RE_MODE="pixel", RE_AREA=[0.02, 0.3333], RE_RATIO=[0.3, 3.3333]))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -159,6 +168,7 @@ def get_config(name, overrides=None, freeze=True):
         cfg.merge_from_list(list(overrides))
     ensemble_method(cfg)
     mix_settings(cfg)
+    aug_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -203,4 +213,57 @@ def mix_settings(cfg) -> MixSettings:
         raise ValueError(f"TRAIN.LABEL_SMOOTHING must lie in [0, 1), not {s.label_smoothing}")
     if s.label_smoothing > 0.0 and multi_label(cfg):
         raise ValueError("TRAIN.LABEL_SMOOTHING is defined for the softmax head only, not with DATA.MULTI_LABEL")
+    return s
+
+
+AUG_CROPS = ("jitter", "rrc")
+AUG_RE_MODES = ("pixel", "const")
+AugSettings = collections.namedtuple("AugSettings", "enable crop rrc_scale rrc_ratio flip_prob brightness contrast saturation "
+                                     "color_prob grayscale_prob re_prob re_mode re_area re_ratio")
+_AUG_OFF = AugSettings(False, "jitter", (0.08, 1.0), (0.75, 1.3333), 0.5, 0.4, 0.4, 0.4, 1.0, 0.0, 0.25, "pixel",
+                       (0.02, 0.3333), (0.3, 3.3333))
+
+
+def aug_settings(cfg) -> AugSettings:
+    """cfg.AUG.* as one tuple (a config tree without the section: off, the defaults otherwise).  ValueError for a range that is
+    not 0 < lo <= hi (RRC_SCALE, RRC_RATIO, RE_AREA, RE_RATIO), a probability outside [0, 1] (FLIP_PROB, COLOR_PROB,
+    GRAYSCALE_PROB, RE_PROB), a strength outside [0, 1) (BRIGHTNESS, CONTRAST, SATURATION: the factor 1 + U(-v, v) stays
+    positive), an unknown CROP or RE_MODE."""
+    a = getattr(cfg, "AUG", None)
+    if a is None:
+        return _AUG_OFF
+
+    def rng(key, dflt):
+        v = getattr(a, key, dflt)
+        try:
+            lo, hi = (float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"AUG.{key} must be a pair [lo, hi], not {v!r}")
+        if not 0.0 < lo <= hi or hi == float("inf"):          # (NaN fails too)
+            raise ValueError(f"AUG.{key} must satisfy 0 < lo <= hi, not {v!r}")
+        return lo, hi
+
+    def prob(key, dflt):
+        v = float(getattr(a, key, dflt))
+        if not 0.0 <= v <= 1.0:
+            raise ValueError(f"AUG.{key} must lie in [0, 1], not {v}")
+        return v
+
+    def strength(key, dflt):
+        v = float(getattr(a, key, dflt))
+        if not 0.0 <= v < 1.0:
+            raise ValueError(f"AUG.{key} must lie in [0, 1), not {v}")
+        return v
+    d = _AUG_OFF
+    s = AugSettings(bool(getattr(a, "ENABLE", False)), getattr(a, "CROP", d.crop), rng("RRC_SCALE", d.rrc_scale),
+                    rng("RRC_RATIO", d.rrc_ratio), prob("FLIP_PROB", d.flip_prob), strength("BRIGHTNESS", d.brightness),
+                    strength("CONTRAST", d.contrast), strength("SATURATION", d.saturation), prob("COLOR_PROB", d.color_prob),
+                    prob("GRAYSCALE_PROB", d.grayscale_prob), prob("RE_PROB", d.re_prob), getattr(a, "RE_MODE", d.re_mode),
+                    rng("RE_AREA", d.re_area), rng("RE_RATIO", d.re_ratio))
+    if s.crop not in AUG_CROPS:
+        raise ValueError(f"AUG.CROP must be one of {AUG_CROPS}, not {s.crop!r}")
+    if s.re_mode not in AUG_RE_MODES:
+        raise ValueError(f"AUG.RE_MODE must be one of {AUG_RE_MODES}, not {s.re_mode!r}")
+    if s.rrc_scale[1] > 1.0 or s.re_area[1] > 1.0:
+        raise ValueError(f"AUG.RRC_SCALE / AUG.RE_AREA are area fractions (<= 1), not {s.rrc_scale} / {s.re_area}")
     return s

@@ -237,7 +237,13 @@ class InputReader:
     multi-hot on the device instead of the labels [B] -- built on the host from every label of the record
     (`parse_sequence_example_labels`; text lines "<path> <l1>,<l2>,...") and copied with the batch.  A class id outside
     [0, NUM_CLASSES) raises ValueError naming the record (TFRecords: "<file>#<index in the file>").  The random draws and
-    the batch order are those of the single-label mode."""
+    the batch order are those of the single-label mode.
+
+    Augmentation (cfg.AUG.ENABLE, training): every clip's `aug.AugParams` are drawn with `aug.draw_aug_params` from a NumPy
+    generator derived from (seed, rank), in record order, and the batch is built by one `views.make_train_batch_aug` call
+    in both `jpeg_decode` modes (device decode still decodes only the T frames a clip reads); `last_params` holds the
+    AugParams.  With AUG.ENABLE off nothing differs from the above: the same draws from the torch generator in the same
+    order, one x3d_train_clip launch per clip."""
 
     _multi = False        # multi-label mode (set from cfg in __init__)
 
@@ -274,8 +280,13 @@ class InputReader:
         if jpeg_decode == "device" and not self._use_tfrecord:
             raise ValueError("jpeg_decode='device' decodes the JPEG frames of TFRecords (use_tfrecord=True)")
         self._jpeg_decode = jpeg_decode
-        from .config import multi_label
+        from .config import aug_settings, multi_label
         self._multi = multi_label(cfg)
+        # AUG.ENABLE (training): aug.AugParams per clip instead of draw_train_params, from a NumPy generator of their own -- a
+        # child of the (seed, rank) generator's seed sequence, so neither the shuffle buffer's stream nor the torch
+        # generator's changes -- and the batch built by one make_train_batch_aug call
+        self._aug = self._is_training and aug_settings(cfg).enable
+        self._rng_aug = np.random.default_rng(self._rng.bit_generator.seed_seq.spawn(1)[0]) if self._aug else None
         self._num_classes = int(cfg.NETWORK.NUM_CLASSES)
 
     # -- decode ------------------------------------------------------------------------------------
@@ -438,6 +449,11 @@ class InputReader:
     def _clips(self, video: np.ndarray) -> torch.Tensor:
         from .views import draw_train_params, make_eval_views, make_train_clip
         v = torch.from_numpy(video).to(self._device, non_blocking=True)
+        if self._aug:               # the batch is built in one call when it is complete (_aug_batch)
+            from .aug import draw_aug_params
+            f, h, w, _ = video.shape
+            self._batch_params.append(draw_aug_params(self._cfg, f, h, w, self._rng_aug))
+            return v
         if self._is_training:
             f, h, w, _ = video.shape
             p = draw_train_params(f, h, w, self._cfg, self._gen)
@@ -445,14 +461,23 @@ class InputReader:
             return make_train_clip(v, self._cfg, params=p, dtype=self._dtype)[None]
         return make_eval_views(v, self._cfg, dtype=self._dtype)
 
-    def process_batch(self, clips: List[torch.Tensor], labels: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    def process_batch(self, clips: List[torch.Tensor], labels: List[int],
+                      batch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """dataloader.py:90-116: [B, T, S, S, 3] in training, [B * views * crops, T, S, S, 3] otherwise.  Multi-label
-        mode: `labels` holds (record name, class ids) pairs and become the multi-hot targets [B, NUM_CLASSES]."""
+        mode: `labels` holds (record name, class ids) pairs and become the multi-hot targets [B, NUM_CLASSES].
+        `batch`: the finished clip tensor (AUG.ENABLE builds it in one call, `_aug_batch`); `clips` is then not read."""
+        if batch is None:
+            batch = torch.cat(clips, 0)
         if self._multi:
             names = [nm for nm, _ in labels]
             targets = multi_hot([lbs for _, lbs in labels], self._num_classes, names)
-            return torch.cat(clips, 0), targets.to(self._device, non_blocking=True)
-        return torch.cat(clips, 0), torch.tensor(labels, dtype=torch.int64, device=self._device)
+            return batch, targets.to(self._device, non_blocking=True)
+        return batch, torch.tensor(labels, dtype=torch.int64, device=self._device)
+
+    def _aug_batch(self, videos: List[torch.Tensor], params: List, rate: Optional[int] = None) -> torch.Tensor:
+        """AUG.ENABLE: the batch [B, T, S, S, 3] from its uploaded videos, one make_train_batch_aug call"""
+        from .views import make_train_batch_aug
+        return make_train_batch_aug(videos, self._cfg, params_list=params, dtype=self._dtype, rate=rate)
 
     def _device_batch(self, items: List[Tuple[List[bytes], int, int]], labels: List[int]):
         """jpeg_decode="device": one batch from parsed records.  Training: the draws of every clip in the host mode's order,
@@ -471,12 +496,18 @@ class InputReader:
         for jpegs, h, w in items:
             f = len(jpegs)
             if self._is_training:
-                p = draw_train_params(f, h, w, cfg, self._gen)
+                if self._aug:
+                    from .aug import draw_aug_params
+                    p = draw_aug_params(cfg, f, h, w, self._rng_aug)
+                    start = p.start
+                else:
+                    p = draw_train_params(f, h, w, cfg, self._gen)
+                    start = p["start"]
                 params.append(p)
                 v = torch.empty((t_len, h, w, 3), dtype=torch.uint8, device=self._device)
                 rate = int(cfg.DATA.FRAME_RATE)
                 for t in range(t_len):
-                    frames.append(jpegs[(p["start"] + t * rate) % f])
+                    frames.append(jpegs[(start + t * rate) % f])
                     slots.append(v[t])
             else:
                 v = torch.empty((f, h, w, 3), dtype=torch.uint8, device=self._device)
@@ -487,6 +518,9 @@ class InputReader:
                     slots.append(v[i])
             videos.append(v)
         decode_jpeg_batch(frames, self._device, out=slots, on_corrupt="host")
+        if self._aug:
+            batch = self._aug_batch(videos, [p._replace(start=0) for p in params], rate=1)
+            return self.process_batch([], labels, batch=batch) + (params,)
         if self._is_training:
             clips = [make_train_clip(v, cfg, params=dict(p, start=0), dtype=self._dtype, rate=1)[None]
                      for v, p in zip(videos, params)]
@@ -514,7 +548,8 @@ class InputReader:
             labels.append(label)
             if len(clips) == bs:
                 params, self._batch_params = self._batch_params, []
-                yield self.process_batch(clips, labels) + (params,)
+                batch = self._aug_batch(clips, params) if self._aug else None
+                yield self.process_batch(clips, labels, batch=batch) + (params,)
                 clips, labels = [], []
         # drop_remainder=True (dataloader.py:186): a trailing partial batch is not emitted
 

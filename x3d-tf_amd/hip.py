@@ -36,6 +36,8 @@ _OVERRIDES = {
     ("x3d_train_resized_hw", "new_h"): C.POINTER(_i),               # host out-parameters: byref(c_int())
     ("x3d_train_resized_hw", "new_w"): C.POINTER(_i),
     ("x3d_jpeg_parse", "scratch_bytes"): C.POINTER(_ll),            # host out-parameter: byref(c_longlong())
+    ("x3d_train_clips_aug", "mean"): C.POINTER(_f),                 # host float[3]: callers pass a ctypes array
+    ("x3d_train_clips_aug", "std"): C.POINTER(_f),
 }
 _ITEM = re.compile(r"(?:((?:\w+[\s*]+)+))?(\w+)((?:\[\d+\])*)$")    # [type] name [dims]: `const float* w`, `Cin`, `qt[3][64]`
 _DECL = re.compile(r"(?:typedef\s+struct\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>x3d_\w+)"
@@ -131,6 +133,11 @@ ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID = _consts("ACT_NONE", "ACT_RELU", "AC
 MIX_MIXUP, MIX_CUTMIX = _consts("MIX_MIXUP", "MIX_CUTMIX")
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = _consts("EPI_STORE", "EPI_ADD", "EPI_ADD_STRIDED", "EPI_SWISH_BWD")
 AP_MAX_POSITIVES = _consts("AP_MAX_POSITIVES")[0]
+AUG_CROP_JITTER, AUG_CROP_RRC, AUG_ERASE_CONST, AUG_ERASE_PIXEL = _consts("AUG_CROP_JITTER", "AUG_CROP_RRC", "AUG_ERASE_CONST",
+                                                                          "AUG_ERASE_PIXEL")
+AUG_MEAN_PARTS, AUG_GEOM_COLS, AUG_COLOR_COLS, AUG_C_K = _consts("AUG_MEAN_PARTS", "AUG_GEOM_COLS", "AUG_COLOR_COLS", "AUG_C_K")
+# column -> index of the int32 geometry table of x3d_train_clips_aug: AUG_G["START"] ...
+AUG_G = {n[6:]: v for n, v in _CONSTS.items() if n.startswith("AUG_G_")}
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = _consts(
     "JPEG_OK", "JPEG_UNSUPPORTED", "JPEG_MALFORMED", "JPEG_CORRUPT", "JPEG_SKIPPED")
 
