@@ -589,6 +589,42 @@ int x3d_sgd_nesterov(float* w, float* v, const float* g, const unsigned char* l2
  * w -= lr * sqrt(1 - b2^step) / (1 - b1^step) * m / (sqrt(v) + eps).  `step` counts from 1. */
 int x3d_adam(float* w, float* m, float* v, const float* g, const unsigned char* l2_mask, float lr, float beta1,
              float beta2, float eps, float weight_decay, float grad_scale, long long step, long long n, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * The solver step around K12 (SOLVER.* of the config): global-norm gradient clipping, gradient accumulation
+ * and an exponential moving average (EMA) of the weights, decided and applied on the device.  Added under ABI 138 without a
+ * version bump: new symbols only, no existing prototype, struct or constant changed.  No floating-point atomics.
+ *
+ * x3d_grad_sumsq: out[0] = sum over i of (double)g[i]^2, squared and accumulated in fp64; the per-workgroup partials are
+ *     added in a fixed ascending order, so the same input gives the same bits on every run.  out[1] = the number of
+ *     non-finite g[i] (as a double; 0.0 = all finite); those entries add nothing to out[0].  Two launches (partials, final
+ *     sum); nothing allocates or synchronises.  scratch: x3d_grad_sumsq_scratch(n) doubles of device memory, the caller's
+ *     (a fixed function of n: twice the partial count); it need not be zeroed.
+ * x3d_sgd_nesterov_ex / x3d_adam_ex: x3d_sgd_nesterov / x3d_adam with
+ *     norm: NULL, or the out[2] of x3d_grad_sumsq over the same g.  The gradient is multiplied by
+ *           c = grad_scale * min(1, max_norm / (sqrt(norm[0]) * grad_scale + 1e-6))
+ *           instead of grad_scale: torch.nn.utils.clip_grad_norm_'s rule on the UNSCALED gradient g * grad_scale; computed
+ *           on the device in fp64 and rounded once (no clipping: exactly grad_scale).  If norm[1] != 0 the launch writes
+ *           NOTHING: w, the slots and ema stay bit for bit, the step is skipped.
+ *     ema:  NULL, or [n]: ema[i] = ema_decay * ema[i] + (1 - ema_decay) * w_new[i] in the same pass, evaluated as
+ *           ema[i] + (1 - ema_decay) * (w_new[i] - ema[i]) (w == ema is a fixed point).
+ *     norm == NULL and ema == NULL: bit-identical to x3d_sgd_nesterov / x3d_adam -- the update arithmetic is one device
+ *     function both call.  16-byte aligned arrays (l2_mask 4-byte) move as 16-byte vectors, anything else by element.
+ * x3d_ema_update: the same EMA rule over n floats the optimizer does not own (the BatchNorm moving statistics behind the
+ *     trainable block).  norm: NULL, or skip when norm[1] != 0.
+ * x3d_grad_accum: acc = g (first != 0) or acc += g, exact fp32.  acc may be g itself (acc = 2 g).
+ * Refused before any launch (X3D_ERR_INVALID): a null required pointer, n <= 0, max_norm <= 0 or not finite with norm, a
+ * decay outside [0, 1) with ema (x3d_ema_update: always), a float pointer that is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+long long x3d_grad_sumsq_scratch(long long n);
+int x3d_grad_sumsq(const float* g, long long n, double* scratch, double* out, void* stream);
+int x3d_sgd_nesterov_ex(float* w, float* v, const float* g, const unsigned char* l2_mask, float lr, float momentum,
+                        float weight_decay, float grad_scale, const double* norm, float max_norm,
+                        float* ema, float ema_decay, long long n, void* stream);
+int x3d_adam_ex(float* w, float* m, float* v, const float* g, const unsigned char* l2_mask, float lr, float beta1, float beta2,
+                float eps, float weight_decay, float grad_scale, long long step, const double* norm, float max_norm,
+                float* ema, float ema_decay, long long n, void* stream);
+int x3d_ema_update(float* ema, const float* w, float decay, const double* norm, long long n, void* stream);
+int x3d_grad_accum(float* acc, const float* g, long long n, int first, void* stream);
 /* LossScaleOptimizer support (Keras mixed_float16, train.py:99-100): *flag (device int the caller set to 1) is cleared
  * when any of the n values is inf / nan -- the step is then skipped and the loss scale halved. */
 int x3d_all_finite(const float* g, long long n, int* flag, void* stream);

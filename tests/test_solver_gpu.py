@@ -1,0 +1,580 @@
+"""The solver step on the device: x3d_grad_sumsq, the _ex optimizer launches (clip coefficient and skip decided on the
+device, EMA in the same pass), x3d_ema_update, x3d_grad_accum against fp64 host references, and the Trainer paths built on
+them (SOLVER.CLIP_GRAD_L2NORM / ACCUM_STEPS / EMA_DECAY).
+
+u = 2^-24 is the unit roundoff of fp32: one correctly rounded operation is off by at most u times its result."""
+import json
+import os
+import socket
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+U = 2.0 ** -24
+F32 = np.float32
+
+# (n, offset of every pointer in elements, with l2 mask): the edges of the vector / one-element paths (n % 4, n < 4), the
+# workgroup boundary (256), more than one workgroup, the grid-stride wrap (1024 workgroups x 256 threads x 4 elements =
+# 1 048 576 elements per sweep), every pointer misaligned by one float (mask: one byte), and no mask at all
+CASES = [(1, 0, True), (3, 0, True), (255, 0, True), (256, 0, True), (257, 0, True), (4100, 0, True), (2_500_003, 0, True),
+         (4099, 1, True), (4100, 0, False)]
+IDS = [f"n{n}" + ("_misaligned" if off else "") + ("" if mask else "_nomask") for n, off, mask in CASES]
+WRAP = 2_000_001                     # an index of the largest case that only a second sweep of the grid reaches
+
+
+def _host(n, seed, gscale_inv=1024.0):
+    """w, v (second slot: >= 0), g (a loss-scaled gradient), l2 mask"""
+    rng = np.random.default_rng(seed)
+    w = rng.standard_normal(n).astype(F32)
+    v = (0.1 * rng.standard_normal(n)).astype(F32)
+    g = (gscale_inv * rng.standard_normal(n)).astype(F32)
+    mask = (rng.random(n) < 0.7).astype(np.uint8)
+    return w, v, g, mask
+
+
+def _dev(a, gpu, off=0):
+    """a copy of `a` on the device whose first element sits `off` elements behind an aligned allocation"""
+    if a is None:
+        return None
+    buf = torch.zeros(a.size + off + 8, dtype=torch.from_numpy(a[:1]).dtype, device=gpu)
+    t = buf[off:off + a.size]
+    t.copy_(torch.from_numpy(a))
+    return t
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int32 if a.dtype == F32 else np.int64)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _sumsq(g_dev):
+    from x3d_tf_amd import ops
+    return ops.grad_sumsq(g_dev)
+
+
+def _coef(norm0, gs, max_norm):
+    """the documented clip rule in fp64 (gs, max_norm: the fp32 values the ABI passes)"""
+    gs, max_norm = float(F32(gs)), float(F32(max_norm))
+    return gs * min(1.0, max_norm / (np.sqrt(norm0) * gs + 1e-6))
+
+
+# ---- x3d_grad_sumsq ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,_mask", CASES, ids=IDS)
+def test_grad_sumsq(gpu, n, off, _mask):
+    """out[0] against np.sum(g64 ** 2): the squares are exact in fp64 (24-bit inputs), so only the n - 1 additions round,
+    each by at most 2^-53 of a partial sum that is <= the total (non-negative terms): relative n * 2^-53 in ANY order."""
+    from x3d_tf_amd import hip
+    g = _host(n, 11)[2]
+    gd = _dev(g, gpu, off)
+    out = _np(_sumsq(gd))
+    want = np.sum(g.astype(np.float64) ** 2)
+    assert out[1] == 0.0
+    assert abs(out[0] - want) <= n * 2.0 ** -53 * want, (out[0], want)
+    assert np.array_equal(_bits(_np(_sumsq(gd))), _bits(out))          # the same bits on every run
+    assert int(hip.load().x3d_grad_sumsq_scratch(n)) >= 2
+    # two inf and one nan: first and last element and (largest case) the wrap region; they count and add nothing
+    if n >= 3:
+        bad = sorted({0, n - 1, WRAP if n > WRAP else n // 2})
+        g2 = g.copy()
+        g2[bad] = [np.inf, np.nan, -np.inf]
+        out2 = _np(_sumsq(_dev(g2, gpu, off)))
+        keep = np.ones(n, bool)
+        keep[bad] = False
+        want2 = np.sum(g[keep].astype(np.float64) ** 2)
+        assert out2[1] == 3.0
+        assert abs(out2[0] - want2) <= n * 2.0 ** -53 * max(want2, np.finfo(np.float64).tiny), (out2[0], want2)
+    # magnitudes whose squares leave the fp32 range in either direction
+    for mag in (1e-30, 1e18):
+        g3 = (g / 1024.0 * mag).astype(F32)
+        out3 = _np(_sumsq(_dev(g3, gpu, off)))
+        want3 = np.sum(g3.astype(np.float64) ** 2)
+        assert want3 > 0 and np.isfinite(want3)
+        assert out3[1] == 0.0 and abs(out3[0] - want3) <= n * 2.0 ** -53 * want3, (mag, out3[0], want3)
+
+
+# ---- the optimizers ---------------------------------------------------------------------------------------------------
+SGD = dict(lr=F32(0.1), mom=F32(0.9), wd=F32(5e-5))
+ADAM = dict(lr=F32(1e-3), b1=F32(0.9), b2=F32(0.999), eps=F32(1e-7), wd=F32(5e-5), step=3)
+
+
+def _sgd_plain(w, v, g, mask, gs):
+    from x3d_tf_amd import hip
+    hip.call("x3d_sgd_nesterov", _p(w), _p(v), _p(g), _p(mask), float(SGD["lr"]), float(SGD["mom"]), float(SGD["wd"]),
+             float(gs), w.numel())
+
+
+def _sgd_ex(w, v, g, mask, gs, norm=None, max_norm=0.0, ema=None, decay=0.0):
+    from x3d_tf_amd import hip
+    hip.call("x3d_sgd_nesterov_ex", _p(w), _p(v), _p(g), _p(mask), float(SGD["lr"]), float(SGD["mom"]), float(SGD["wd"]),
+             float(gs), _p(norm), float(max_norm), _p(ema), float(decay), w.numel())
+
+
+def _adam_plain(w, m, v, g, mask, gs):
+    from x3d_tf_amd import hip
+    a = ADAM
+    hip.call("x3d_adam", _p(w), _p(m), _p(v), _p(g), _p(mask), float(a["lr"]), float(a["b1"]), float(a["b2"]),
+             float(a["eps"]), float(a["wd"]), float(gs), a["step"], w.numel())
+
+
+def _adam_ex(w, m, v, g, mask, gs, norm=None, max_norm=0.0, ema=None, decay=0.0):
+    from x3d_tf_amd import hip
+    a = ADAM
+    hip.call("x3d_adam_ex", _p(w), _p(m), _p(v), _p(g), _p(mask), float(a["lr"]), float(a["b1"]), float(a["b2"]),
+             float(a["eps"]), float(a["wd"]), float(gs), a["step"], _p(norm), float(max_norm), _p(ema), float(decay),
+             w.numel())
+
+
+def _sgd_ref(w, v, g, mask, c, hp=None):
+    """fp64 of the documented rule with the fp32 hyper-parameters the ABI passes; returns w', v' and the limit.
+
+    Limit 8 u (|w| + |mom v| + lr |c g + 2 wd w|), the derivation: the kernel rounds (1) c itself, (2) g c, (3) the FMA
+    that adds 2 wd w, (4) lr g', (5) the FMA mom v - lr g', (6) the FMA w + mom v', (7) the FMA ... - lr g'.  Each is off by
+    at most u of its result, every result is bounded by the bracket (|g'| by its third term or, where c g and 2 wd w cancel,
+    by 2 wd |w| << |w|), and an error made in g' reaches w' with the factor lr (1 + mom) < 2 lr: roundings (1)-(3) count
+    twice in the worst case, which is what the 8 leaves room for beyond the 7 steps on average."""
+    lr, mom, wd = (float(F32((hp or SGD)[k])) for k in ("lr", "mom", "wd"))
+    w, v, g = (a.astype(np.float64) for a in (w, v, g))
+    gi = c * g + (2.0 * wd * w * mask if mask is not None else 0.0)
+    vn = mom * v - lr * gi
+    wn = w + mom * vn - lr * gi
+    return wn, vn, 8 * U * (np.abs(w) + np.abs(mom * v) + lr * np.abs(gi))
+
+
+def _adam_ref(w, m, v, g, mask, c):
+    """fp64 Adam with the ABI's fp32 hyper-parameters; returns (w', m', v') and their limits.
+
+    With G = |c g| + 2 wd |w| (>= |g'| and every intermediate of it):
+      m' = b1 m + (1 - b1) g':  roundings of c, g c, the L2 FMA, b1 m, and the FMA: |dm| <= 8 u (|b1 m| + (1 - b1) G)
+      v' = b2 v + (1 - b2) g'^2: the square doubles the relative error of g' (3 u -> 6 u), then (1 - b2) g', the FMA and
+           b2 v round: |dv| <= 16 u (|b2 v| + (1 - b2) G^2)
+      w' = w - lr_t m' / (sqrt(v') + eps): the quotient moves with dm and dv -- bounded by evaluating it at the ends of
+           [m' - dm, m' + dm] x [v' - dv, v' + dv] -- and lr_t m', sqrt, + eps, the division and the subtraction round:
+           |dw| <= 8 u (|w| + |step|) + (step at the worst corner - step)."""
+    a = ADAM
+    lr, b1, b2, eps, wd = (float(a[k]) for k in ("lr", "b1", "b2", "eps", "wd"))
+    lr_t = float(F32(lr * np.sqrt(1.0 - b2 ** a["step"]) / (1.0 - b1 ** a["step"])))
+    w, m, v, g = (x.astype(np.float64) for x in (w, m, v, g))
+    l2 = 2.0 * wd * w * mask if mask is not None else np.zeros_like(w)
+    gi = c * g + l2
+    G = np.abs(c * g) + np.abs(l2)
+    mn = b1 * m + (1.0 - b1) * gi
+    vn = b2 * v + (1.0 - b2) * gi * gi
+    dm = 8 * U * (np.abs(b1 * m) + (1.0 - b1) * G)
+    dv = 16 * U * (np.abs(b2 * v) + (1.0 - b2) * G * G)
+    step = lr_t * mn / (np.sqrt(vn) + eps)
+    worst = lr_t * (np.abs(mn) + dm) / (np.sqrt(np.maximum(vn - dv, 0.0)) + eps)
+    dw = 8 * U * (np.abs(w) + np.abs(step)) + (worst - np.abs(step))
+    return (w - step, mn, vn), (dw, dm, dv)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,with_mask", CASES, ids=IDS)
+def test_ex_without_extras_is_the_plain_kernel_bit_for_bit(gpu, n, off, with_mask):
+    w, v, g, mask = _host(n, 21)
+    mask = mask if with_mask else None
+    m2 = np.abs(v) * 0.01
+    for gs in (1.0, 1.0 / 1024.0, 0.37):
+        a = [_dev(x, gpu, off) for x in (w, v, g, mask)]
+        b = [_dev(x, gpu, off) for x in (w, v, g, mask)]
+        _sgd_plain(*a, gs)
+        _sgd_ex(*b, gs)
+        assert np.array_equal(_bits(_np(a[0])), _bits(_np(b[0]))) and np.array_equal(_bits(_np(a[1])), _bits(_np(b[1])))
+        a = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+        b = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+        _adam_plain(*a, gs)
+        _adam_ex(*b, gs)
+        for x, y in zip(a[:3], b[:3]):
+            assert np.array_equal(_bits(_np(x)), _bits(_np(y)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,with_mask", CASES, ids=IDS)
+def test_clip_above_and_below_the_norm(gpu, n, off, with_mask):
+    """grad_scale = 1/1024 on a gradient of scale 1024: a kernel that compared max_norm with the SCALED norm would clip
+    the 'below' case a thousandfold and the 'above' case by the wrong factor."""
+    w, v, g, mask = _host(n, 31)
+    mask = mask if with_mask else None
+    m2 = np.abs(v) * 0.01
+    gs = F32(1.0 / 1024.0)
+    total = np.sqrt(np.sum(g.astype(np.float64) ** 2)) * float(gs)           # the unscaled norm
+    # below the limit: nothing is clipped, the coefficient is grad_scale itself -> the plain kernel's bits
+    big = 2.0 * total + 1.0
+    a = [_dev(x, gpu, off) for x in (w, v, g, mask)]
+    b = [_dev(x, gpu, off) for x in (w, v, g, mask)]
+    norm = _sumsq(b[2])
+    _sgd_plain(*a, gs)
+    _sgd_ex(*b, gs, norm, big)
+    assert np.array_equal(_bits(_np(a[0])), _bits(_np(b[0]))) and np.array_equal(_bits(_np(a[1])), _bits(_np(b[1])))
+    a = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+    b = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+    _adam_plain(*a, gs)
+    _adam_ex(*b, gs, _sumsq(b[3]), big)
+    for x, y in zip(a[:3], b[:3]):
+        assert np.array_equal(_bits(_np(x)), _bits(_np(y)))
+    # above: the documented formula in fp64, the coefficient from the kernel's own out[0]
+    small = 0.5 * total
+    b = [_dev(x, gpu, off) for x in (w, v, g, mask)]
+    norm = _sumsq(b[2])
+    c = _coef(_np(norm)[0], gs, small)
+    assert c < float(gs) and abs(c * np.sqrt(_np(norm)[0]) - float(F32(small))) < 1e-5 * small + 2e-6
+    _sgd_ex(*b, gs, norm, small)
+    wn, vn, lim = _sgd_ref(w, v, g, mask, c)
+    assert np.all(np.abs(_np(b[0]) - wn) <= lim), np.max(np.abs(_np(b[0]) - wn) / lim)
+    assert np.all(np.abs(_np(b[1]) - vn) <= lim), np.max(np.abs(_np(b[1]) - vn) / lim)
+    b = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+    norm = _sumsq(b[3])
+    c = _coef(_np(norm)[0], gs, small)
+    _adam_ex(*b, gs, norm, small)
+    want, lims = _adam_ref(w, v, m2, g, mask, c)
+    for got, ref, lim, name in zip(b[:3], want, lims, "wmv"):
+        err = np.abs(_np(got) - ref)
+        assert np.all(err <= lim), (name, np.max(err / np.maximum(lim, 1e-300)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,with_mask", CASES, ids=IDS)
+def test_non_finite_gradient_skips_the_launch(gpu, n, off, with_mask):
+    """norm[1] != 0: w, the slots and ema are what they were, bit for bit -- both optimizers and x3d_ema_update"""
+    from x3d_tf_amd import ops
+    w, v, g, mask = _host(n, 41)
+    mask = mask if with_mask else None
+    m2 = np.abs(v) * 0.01
+    e = (w * 0.5).astype(F32)
+    g[n // 2] = np.inf
+    gd = _dev(g, gpu, off)
+    norm = _sumsq(gd)
+    assert _np(norm)[1] == 1.0
+    wd_, vd, md, ed, kd = (_dev(x, gpu, off) for x in (w, v, m2, e, mask))
+    _sgd_ex(wd_, vd, gd, kd, 1.0, norm, 1.0, ed, 0.9)
+    _adam_ex(wd_, vd, md, gd, kd, 1.0, norm, 1.0, ed, 0.9)
+    ops.ema_update(ed, wd_, 0.9, norm)
+    for got, was in ((wd_, w), (vd, v), (md, m2), (ed, e)):
+        assert np.array_equal(_bits(_np(got)), _bits(was))
+    ops.ema_update(ed, wd_, 0.9)                                             # (and without the norm it does run)
+    assert not np.array_equal(_bits(_np(ed)), _bits(e))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,with_mask", CASES, ids=IDS)
+def test_ema(gpu, n, off, with_mask):
+    """ema' = d ema + (1 - d) w', evaluated as ema + (1 - d)(w' - ema): the subtraction, (1 - d) (for d < 1/2) and the FMA
+    round -- 3 u max(|ema|, |w'|) at most, inside the 4 u per step."""
+    from x3d_tf_amd import ops
+    w, v, g, mask = _host(n, 51, gscale_inv=1.0)
+    mask = mask if with_mask else None
+    d32 = F32(0.9)
+    d = float(d32)
+    e0 = (0.5 * w + 0.1).astype(F32)
+    wd_, vd, gd, kd, ed = (_dev(x, gpu, off) for x in (w, v, g, mask, e0))
+    w2, v2 = _dev(w, gpu, off), _dev(v, gpu, off)                            # the same run without the EMA
+    ref, prev, budget = e0.astype(np.float64), e0, np.zeros(n)
+    for k in range(3):
+        _sgd_ex(wd_, vd, gd, kd, 1.0, None, 0.0, ed, d32)
+        _sgd_ex(w2, v2, gd, kd, 1.0)
+        wk, ek = _np(wd_).copy(), _np(ed).copy()
+        assert np.array_equal(_bits(wk), _bits(_np(w2))) and np.array_equal(_bits(_np(vd)), _bits(_np(v2)))
+        lim = 4 * U * np.maximum(np.abs(prev), np.abs(wk)).astype(np.float64)
+        one = d * prev.astype(np.float64) + (1.0 - d) * wk.astype(np.float64)
+        assert np.all(np.abs(ek - one) <= lim), (k, np.max(np.abs(ek - one) / np.maximum(lim, 1e-300)))
+        ref = d * ref + (1.0 - d) * wk.astype(np.float64)
+        budget = d * budget + lim                                            # earlier errors decay with d
+        assert np.all(np.abs(ek - ref) <= budget)
+        prev = ek
+    # the Adam launch writes the same EMA of its own w'
+    m2 = np.abs(v) * 0.01
+    a = [_dev(x, gpu, off) for x in (w, v, m2, g, mask)]
+    ea = _dev(e0, gpu, off)
+    _adam_ex(*a, 1.0, None, 0.0, ea, d32)
+    wa = _np(a[0]).astype(np.float64)
+    one = d * e0.astype(np.float64) + (1.0 - d) * wa
+    assert np.all(np.abs(_np(ea) - one) <= 4 * U * np.maximum(np.abs(e0), np.abs(wa)))
+    # d close to 1 and w == ema: a fixed point within 1 ulp
+    same = _dev(w, gpu, off)
+    ops.ema_update(same, _dev(w, gpu, off), 0.9999)
+    assert np.all(np.abs(_np(same).astype(np.float64) - w) <= np.spacing(np.abs(w)))
+    # x3d_ema_update on its own follows the same rule
+    e1 = _dev(e0, gpu, off)
+    ops.ema_update(e1, _dev(w, gpu, off), d32)
+    one = d * e0.astype(np.float64) + (1.0 - d) * w.astype(np.float64)
+    assert np.all(np.abs(_np(e1) - one) <= 4 * U * np.maximum(np.abs(e0), np.abs(w)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,off,_mask", CASES, ids=IDS)
+def test_grad_accum(gpu, n, off, _mask):
+    from x3d_tf_amd import ops
+    a, _, g, _ = _host(n, 61, gscale_inv=3.0)
+    g[0] = np.nan
+    acc, gd = _dev(a, gpu, off), _dev(g, gpu, off)
+    ops.grad_accum(acc, gd, first=True)
+    assert np.array_equal(_bits(_np(acc)), _bits(g))                         # a copy, bit for bit (the NaN too)
+    g[0] = 0.25
+    acc, gd = _dev(a, gpu, off), _dev(g, gpu, off)
+    ops.grad_accum(acc, gd)
+    assert np.array_equal(_bits(_np(acc)), _bits(a + g))                     # exactly the fp32 sum
+    ops.grad_accum(gd, gd)                                                   # acc aliasing g
+    assert np.array_equal(_bits(_np(gd)), _bits(g + g))
+
+
+# ---- the Trainer, XS config -------------------------------------------------------------------------------------------
+CLASSES = 10
+OPTS = ["DATA.TEMP_DURATION", 4, "DATA.TRAIN_CROP_SIZE", 32, "DATA.TEST_CROP_SIZE", 32, "TEST.NUM_TEMPORAL_VIEWS", 1,
+        "TEST.NUM_SPATIAL_CROPS", 3, "TEST.BATCH_SIZE", 2, "NETWORK.NUM_CLASSES", CLASSES, "NETWORK.DROPOUT_RATE", 0.0,
+        "TRAIN.BATCH_SIZE", 2, "TRAIN.DATASET_SIZE", 4, "TRAIN.EPOCHS", 2]
+
+
+def _cfg(*extra):
+    import x3d_tf_amd as x
+    return x.get_config("XS", OPTS + list(extra))
+
+
+def _batches(k, seed=5, views=1):
+    """k seeded (clips [2 * views, 4, 32, 32, 3], labels [2]) batches on the host"""
+    gen = torch.Generator().manual_seed(seed)
+    return [(torch.randn(2 * views, 4, 32, 32, 3, generator=gen), torch.randint(0, CLASSES, (2,), generator=gen))
+            for _ in range(k)]
+
+
+def _trainer(cfg, gpu, seed=1):
+    from x3d_tf_amd.model import X3D
+    from x3d_tf_amd.train import Trainer
+    m = X3D(cfg, dtype=torch.float32, device=gpu, seed=seed)
+    return m, Trainer(m, cfg)
+
+
+@pytest.mark.gpu
+def test_trainer_clipping(gpu):
+    from x3d_tf_amd import hip
+    (x1, y1), = _batches(1)
+    lr, max_norm = 0.5, 0.05
+    m, tr = _trainer(_cfg("SOLVER.CLIP_GRAD_L2NORM", max_norm), gpu)
+    nt = m.n_trainable_flat
+    w0 = _np(m.flat_params[:nt]).astype(np.float64)
+    tr.step(x1.to(gpu), y1.to(gpu), lr)
+    g = _np(m.flat_grads).astype(np.float64)                                 # the update leaves the gradient in place
+    norm = np.sqrt(np.sum(g * g))
+    assert abs(float(tr.last_grad_norm.item()) - norm) <= 1e-6 * norm
+    assert norm > max_norm and tr.opt_step == 1                          # the clip is active
+    # first step, zero velocity: w' - w = -lr (1 + mom) (c g + 2 wd w)  ->  the norm of the data part is max_norm
+    mom, wd = float(F32(tr.momentum)), float(F32(m.arch.weight_decay))
+    mask = _np(m.l2_mask).astype(np.float64)
+    dw = _np(m.flat_params[:nt]).astype(np.float64) - w0
+    data = dw / (-float(F32(lr)) * (1.0 + mom)) - 2.0 * wd * w0 * mask
+    assert abs(np.sqrt(np.sum(data * data)) - max_norm) <= 1e-3 * max_norm
+    c = max_norm / (norm + 1e-6)
+    assert np.sqrt(np.sum((data - c * g) ** 2)) <= 1e-3 * max_norm
+    # a huge max_norm clips nothing: the step's parameters = the unclipped _ex launch on the same gradient, bit for bit
+    m, tr = _trainer(_cfg("SOLVER.CLIP_GRAD_L2NORM", 1e30), gpu)
+    w0, v0 = m.flat_params.clone(), m.flat_velocity.clone()
+    tr.step(x1.to(gpu), y1.to(gpu), lr)
+    w1, v1 = m.flat_params.clone(), m.flat_velocity.clone()
+    w, v = w0.clone(), v0.clone()
+    hip.call("x3d_sgd_nesterov_ex", w.data_ptr(), v.data_ptr(), m.flat_grads.data_ptr(), m.l2_mask.data_ptr(), lr,
+             float(tr.momentum), float(m.arch.weight_decay), 1.0, None, 0.0, None, 0.0, nt)
+    assert torch.equal(w[:nt], w1[:nt]) and torch.equal(v, v1) and not torch.equal(w1[:nt], w0[:nt])
+
+
+# "The total is g1 + g2" compares one backward pass with another run of the same pass (a twin model), and some
+# weight-gradient kernels add with fp32 atomics, so the yardstick is the run-to-run spread of the UNCHANGED backward: twin
+# models with the same seed on the same batch through `forward_backward`, max |g_a - g_b| / max |g| over their pairs.  It is
+# measured by _accum_run in the same process, on the box the test runs on (tools/solver_bench.py --spread prints it too); the
+# limit is 4 x that spread, floored at 2^-23 (one fp32 rounding of the sum, relative to the largest gradient).
+def _accum_limit(spread):
+    return max(4 * spread, 2.0 ** -23)
+
+
+_ACCUM = {}
+
+
+def _accum_run(gpu):
+    """the two micro-batches of one accumulation, once for the tests that look at them"""
+    if _ACCUM:
+        return _ACCUM
+    (x1, y1), (x2, y2) = [(a.to(gpu), b.to(gpu)) for a, b in _batches(2)]
+    lr = 0.1
+    m, tr = _trainer(_cfg("SOLVER.ACCUM_STEPS", 2), gpu)
+    w0, v0 = m.flat_params.clone(), m.flat_velocity.clone()
+    tr.step(x1, y1, lr)
+    _ACCUM.update(after1=(m.flat_params.clone(), m.flat_velocity.clone(), tr.opt_step), w0=w0, v0=v0,
+                  g1=m.flat_grads.clone())
+    tr.step(x2, y2, lr)
+    _ACCUM.update(total=m.flat_grads.clone(), w2=m.flat_params.clone(), v2=m.flat_velocity.clone(), opt_step=tr.opt_step,
+                  lr=lr, mom=tr.momentum, wd=m.arch.weight_decay, mask=m.l2_mask.clone(), nt=m.n_trainable_flat)
+    # twins with the same seed (hence the same weights): the second micro-batch alone, twice -> g2 and the spread
+    from x3d_tf_amd.model import X3D
+    twins = []
+    for _ in range(3):
+        t = X3D(_cfg(), dtype=torch.float32, device=gpu, seed=1)
+        t.forward_backward(x2, y2, global_batch=4)
+        twins.append(t.flat_grads.clone())
+    scale = twins[0].abs().max()
+    _ACCUM.update(g2=twins[0], spread=max(float((twins[i] - twins[j]).abs().max() / scale) for i, j in ((0, 1), (0, 2), (1, 2))))
+    return _ACCUM
+
+
+@pytest.mark.gpu
+def test_trainer_accumulation(gpu):
+    """The spread of the backward (XS, 2 x 4 x 32 x 32, fp32 storage) is measured in this process (_accum_run) and printed
+    with the error of the total (-s).  No figure from an MI355X run is recorded here yet: UNMEASURED."""
+    r = _accum_run(gpu)
+    limit = _accum_limit(r["spread"])
+    print(f"backward run-to-run spread (relative to max |g|): {r['spread']:.3e}; limit {limit:.3e}")
+    w1, v1, step1 = r["after1"]
+    assert torch.equal(w1[:r["nt"]], r["w0"][:r["nt"]]) and torch.equal(v1, r["v0"]) and step1 == 0
+    assert r["opt_step"] == 1
+    want = r["g1"].double() + r["g2"].double()
+    scale = float(want.abs().max())
+    err = float((r["total"].double() - want).abs().max()) / scale
+    print(f"|total - (g1 + g2)| / max |g| = {err:.3e}")
+    assert err <= limit, (err, r["spread"])
+    # the weights: SGD on that total, within the kernel's limit (test_clip_above_and_below_the_norm: _sgd_ref)
+    nt = r["nt"]
+    wn, vn, lim = _sgd_ref(_np(r["w0"][:nt]), _np(r["v0"]), _np(r["total"]), _np(r["mask"]).astype(np.float64), 1.0,
+                           hp=dict(lr=r["lr"], mom=r["mom"], wd=r["wd"]))
+    assert np.all(np.abs(_np(r["w2"][:nt]) - wn) <= lim) and np.all(np.abs(_np(r["v2"]) - vn) <= lim)
+    assert not torch.equal(r["w2"][:nt], r["w0"][:nt])
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _rehearsal_worker(rank, port, tmp):
+    """one rank with every collective live (X3D_DIST_REHEARSE=1): the same two micro-batches"""
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
+                      X3D_DIST_BACKEND="gloo", X3D_DIST_REHEARSE="1")
+    import torch.distributed as dist
+    from x3d_tf_amd import dist as xd
+    xd.init_process_group()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    (x1, y1), (x2, y2) = [(a.to(dev), b.to(dev)) for a, b in _batches(2)]
+    m, tr = _trainer(_cfg("SOLVER.ACCUM_STEPS", 2), dev)
+    assert tr.collectives
+    tr.step(x1, y1, 0.1)
+    launched1, step1 = tr.reducer.launched, tr.opt_step
+    tr.step(x2, y2, 0.1)
+    torch.save(dict(total=m.flat_grads.cpu(), w2=m.flat_params.cpu()), os.path.join(tmp, "rehearsal.pt"))
+    with open(os.path.join(tmp, "rehearsal.json"), "w") as f:
+        json.dump(dict(launched1=launched1, step1=step1, launched=tr.reducer.launched, buckets=len(tr.reducer.buckets),
+                       opt_step=tr.opt_step), f)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+def test_trainer_accumulation_under_collectives(gpu, tmp_path):
+    """the accumulator joins each bucket in the backward hook, in front of that bucket's all-reduce: the same total, and
+    one round of buckets per update, not one per micro-batch"""
+    r = _accum_run(gpu)
+    mp.spawn(_rehearsal_worker, args=(_free_port(), str(tmp_path)), nprocs=1, join=True)
+    info = json.load(open(tmp_path / "rehearsal.json"))
+    assert info["launched1"] == 0 and info["step1"] == 0
+    assert info["launched"] == info["buckets"] > 1 and info["opt_step"] == 1
+    got = torch.load(tmp_path / "rehearsal.pt")
+    want = r["total"].cpu().double()
+    err = float((got["total"].double() - want).abs().max()) / float(want.abs().max())
+    print(f"|total(collectives) - total| / max |g| = {err:.3e}")
+    assert err <= _accum_limit(r["spread"]), (err, r["spread"])
+
+
+@pytest.mark.gpu
+def test_trainer_ema_in_fit(gpu, tmp_path):
+    from x3d_tf_amd.checkpoint import latest_checkpoint
+    from x3d_tf_amd.model import X3D
+    from x3d_tf_amd.train import Trainer
+    cfg = _cfg("SOLVER.EMA_DECAY", 0.5)
+    run = str(tmp_path / "run")
+    train = [(a.to(gpu), b.to(gpu)) for a, b in _batches(4, seed=7)]
+    val = [(a.to(gpu), b.to(gpu)) for a, b in _batches(2, seed=9, views=3)]
+    m, tr = _trainer(cfg, gpu)
+    assert torch.equal(tr.ema, m.flat_params) and tr.ema.data_ptr() != m.flat_params.data_ptr()
+    tr.fit(iter(train), model_dir=run, validation_data=lambda: val, metrics=())
+    assert tr.epoch == 2 and tr.opt_step == 4 and "grad_norm" not in tr.history
+    assert not torch.equal(tr.ema, m.flat_params)
+    nt = m.n_trainable_flat
+    assert not torch.equal(tr.ema[nt:], m.flat_params[nt:])                  # the moving statistics are averaged too
+    before, ema_before = m.flat_params.clone(), tr.ema.clone()
+    with tr.ema_scope():
+        assert torch.equal(m.flat_params, ema_before) and torch.equal(tr.ema, before)
+        inside = tr.validate(val)
+    assert torch.equal(m.flat_params, before) and torch.equal(tr.ema, ema_before)
+    outside = tr.validate(val)
+    assert abs(tr.history["val_loss"][-1] - inside["loss"]) < 1e-6 and inside["loss"] != outside["loss"]
+    # the EMA model as a bundle of its own; the training checkpoint is still what latest_checkpoint names
+    assert os.path.exists(os.path.join(run, "ema", "ckpt-2.index"))
+    assert latest_checkpoint(run) == os.path.join(run, "ckpt-2")
+    fresh = X3D(cfg, dtype=torch.float32, device=gpu, seed=3)
+    fresh.load_weights(os.path.join(run, "ema"))
+    assert torch.equal(fresh.flat_params, tr.ema)
+    t2 = Trainer(X3D(cfg, dtype=torch.float32, device=gpu, seed=4), cfg)
+    assert t2.resume(run) == 2
+    assert torch.equal(t2.ema, tr.ema) and torch.equal(t2.model.flat_params, m.flat_params)
+    # without EMA_EVAL validation sees the raw weights
+    m3, tr3 = _trainer(_cfg("SOLVER.EMA_DECAY", 0.5, "SOLVER.EMA_EVAL", False), gpu)
+    tr3.fit(iter(train), epochs=1, validation_data=lambda: val, metrics=())
+    assert abs(tr3.history["val_loss"][-1] - tr3.validate(val)["loss"]) < 1e-6
+    with pytest.raises(ValueError):
+        with _trainer(_cfg(), gpu)[1].ema_scope():
+            pass
+
+
+@pytest.mark.gpu
+def test_default_config_makes_the_calls_it_always_made(gpu, monkeypatch):
+    """SOLVER at its defaults = a config tree without the section: the same library calls per step, none of the new ones"""
+    from x3d_tf_amd import hip
+    (x1, y1), = _batches(1)
+    x1, y1 = x1.to(gpu), y1.to(gpu)
+    cfg = _cfg()
+    old = cfg.clone()
+    old.defrost()
+    del old["SOLVER"]
+    calls = []
+    real = hip.call
+
+    def recorder(name, *args):
+        calls.append(name)
+        return real(name, *args)
+
+    seqs = []
+    for c in (cfg, old):
+        m, tr = _trainer(c, gpu)
+        assert tr.ema is None and tr._grad_acc is None
+        tr.step(x1, y1, 0.1)                                                 # (plan recorded, buffers allocated)
+        monkeypatch.setattr(hip, "call", recorder)
+        calls.clear()
+        tr.step(x1, y1, 0.1)
+        monkeypatch.setattr(hip, "call", real)
+        seqs.append(list(calls))
+        assert tr.ema is None and tr._grad_acc is None and getattr(m, "_norm_out", None) is None
+    assert seqs[0] == seqs[1] and seqs[0][-1] == "x3d_sgd_nesterov"
+    new = {"x3d_grad_sumsq", "x3d_sgd_nesterov_ex", "x3d_adam_ex", "x3d_ema_update", "x3d_grad_accum"}
+    assert not new & set(seqs[0])
+    # and the switches do reach them
+    m, tr = _trainer(_cfg("SOLVER.CLIP_GRAD_L2NORM", 1.0, "SOLVER.EMA_DECAY", 0.9, "SOLVER.ACCUM_STEPS", 2), gpu)
+    monkeypatch.setattr(hip, "call", recorder)
+    calls.clear()
+    tr.step(x1, y1, 0.1)
+    tr.step(x1, y1, 0.1)
+    monkeypatch.setattr(hip, "call", real)
+    assert [c for c in calls if c in new] == ["x3d_grad_accum", "x3d_grad_accum", "x3d_grad_sumsq", "x3d_sgd_nesterov_ex",
+                                              "x3d_ema_update"]

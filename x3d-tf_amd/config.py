@@ -118,7 +118,7 @@ class CfgNode(dict):
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
-    AUG.* (batched training augmentation)."""
+    AUG.* (batched training augmentation), SOLVER.* (gradient clipping, accumulation, weight EMA)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -147,6 +147,10 @@ def get_default_config():
     c.AUG = CfgNode(dict(ENABLE=False, CROP="jitter", RRC_SCALE=[0.08, 1.0], RRC_RATIO=[0.75, 1.3333], FLIP_PROB=0.5,
                          BRIGHTNESS=0.4, CONTRAST=0.4, SATURATION=0.4, COLOR_PROB=1.0, GRAYSCALE_PROB=0.0, RE_PROB=0.25,
                          RE_MODE="pixel", RE_AREA=[0.02, 0.3333], RE_RATIO=[0.3, 3.3333]))
+    # the solver step around the optimizer (all off by default; CLIP_GRAD_L2NORM as PySlowFast's SOLVER section): the max global
+    # L2 norm of the unscaled, all-reduced gradient (0 = off), micro-batches per optimizer update, the decay of the weight EMA
+    # (0 = off) and whether fit's validation runs on the EMA weights
+    c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -169,6 +173,7 @@ def get_config(name, overrides=None, freeze=True):
     ensemble_method(cfg)
     mix_settings(cfg)
     aug_settings(cfg)
+    solver_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -267,3 +272,27 @@ def aug_settings(cfg) -> AugSettings:
     if s.rrc_scale[1] > 1.0 or s.re_area[1] > 1.0:
         raise ValueError(f"AUG.RRC_SCALE / AUG.RE_AREA are area fractions (<= 1), not {s.rrc_scale} / {s.re_area}")
     return s
+
+
+SolverSettings = collections.namedtuple("SolverSettings", "clip_grad_l2norm accum_steps ema_decay ema_eval")
+_SOLVER_OFF = SolverSettings(0.0, 1, 0.0, True)
+
+
+def solver_settings(cfg) -> SolverSettings:
+    """cfg.SOLVER.* as one tuple (a config tree without the section: everything off).  ValueError for a negative or
+    non-finite CLIP_GRAD_L2NORM, an ACCUM_STEPS that is not an integer >= 1, an EMA_DECAY outside [0, 1)."""
+    import math
+    sv = getattr(cfg, "SOLVER", None)
+    if sv is None:
+        return _SOLVER_OFF
+    d = _SOLVER_OFF
+    clip = float(getattr(sv, "CLIP_GRAD_L2NORM", d.clip_grad_l2norm))
+    if not (clip >= 0.0 and math.isfinite(clip)):           # (NaN fails too)
+        raise ValueError(f"SOLVER.CLIP_GRAD_L2NORM must be finite and >= 0 (0 = off), not {clip}")
+    accum = getattr(sv, "ACCUM_STEPS", d.accum_steps)
+    if isinstance(accum, bool) or not isinstance(accum, int) or accum < 1:
+        raise ValueError(f"SOLVER.ACCUM_STEPS must be an integer >= 1, not {accum!r}")
+    decay = float(getattr(sv, "EMA_DECAY", d.ema_decay))
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"SOLVER.EMA_DECAY must lie in [0, 1), not {decay}")
+    return SolverSettings(clip, accum, decay, bool(getattr(sv, "EMA_EVAL", d.ema_eval)))

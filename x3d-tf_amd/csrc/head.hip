@@ -1,5 +1,5 @@
-// Classification head on pooled vectors (reference model.py:95-111,119-127; loss train.py:104) and
-// the optimizer (train.py:89-92).  All fp32; sizes are [N <= a few hundred] x [432..2048] x [400].
+// Classification head on pooled vectors (reference model.py:95-111,119-127; loss train.py:104) and the
+// loss-scaling / L2-loss helpers of the train step (the optimizer itself: solver.hip).  All fp32; sizes are [N <= a few hundred] x [432..2048] x [400].
 #include "common.h"
 
 // y[n][m] = act(sum_k xm[n][k]*w[m][k] + b[m]), xm = x * (mask ? mask*mask_scale : 1).
@@ -397,64 +397,7 @@ extern "C" int x3d_view_mean(const float* probs, float* out, int videos, int vie
   return X3D_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// SGD + Nesterov momentum + L2 (flat arrays)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sgd_nesterov_kernel(float* __restrict__ w, float* __restrict__ v,
-                                                           const float* __restrict__ g,
-                                                           const unsigned char* __restrict__ l2, float lr, float mom,
-                                                           float wd, float gscale, long long n) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float gi = g[i] * gscale;
-  const float wi = w[i];
-  if (l2 && l2[i]) gi += 2.f * wd * wi;
-  const float vi = mom * v[i] - lr * gi;
-  v[i] = vi;
-  w[i] = wi + mom * vi - lr * gi;
-}
-
-extern "C" int x3d_sgd_nesterov(float* w, float* v, const float* g, const unsigned char* l2_mask, float lr,
-                                float momentum, float weight_decay, float grad_scale, long long n, void* stream) {
-  X3D_REQUIRE(w && v && g && n > 0, "sgd_nesterov: bad args");
-  hipLaunchKernelGGL(sgd_nesterov_kernel, dim3((unsigned)ceil_div_ll(n, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                     v, g, l2_mask, lr, momentum, weight_decay, grad_scale, n);
-  X3D_LAUNCH_CHECK("sgd_nesterov");
-  return X3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Adam (tf.optimizers.Adam(learning_rate), the reference's other optimizer branch, train.py:93-95; Keras defaults
-// beta_1 = 0.9, beta_2 = 0.999, epsilon = 1e-7, no amsgrad):  g' = g*grad_scale + 2*wd*w (where l2_mask)
-//   m = b1*m + (1-b1)*g' ; v = b2*v + (1-b2)*g'^2 ; w -= lr*sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)        [TF-3p]
-// One launch over the flat parameter buffer, like x3d_sgd_nesterov.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                                   const float* __restrict__ g, const unsigned char* __restrict__ l2,
-                                                   float lr_t, float b1, float b2, float eps, float wd, float gscale,
-                                                   long long n) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float gi = g[i] * gscale;
-  const float wi = w[i];
-  if (l2 && l2[i]) gi += 2.f * wd * wi;
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  w[i] = wi - lr_t * mi / (sqrtf(vi) + eps);
-}
-
-extern "C" int x3d_adam(float* w, float* m, float* v, const float* g, const unsigned char* l2_mask, float lr, float beta1,
-                        float beta2, float eps, float weight_decay, float grad_scale, long long step, long long n,
-                        void* stream) {
-  X3D_REQUIRE(w && m && v && g && n > 0 && step >= 1, "adam: bad args (step counts from 1)");
-  const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ceil_div_ll(n, 256)), dim3(256), 0, (hipStream_t)stream, w, m, v, g,
-                     l2_mask, (float)lr_t, beta1, beta2, eps, weight_decay, grad_scale, n);
-  X3D_LAUNCH_CHECK("adam");
-  return X3D_OK;
-}
+// (SGD-Nesterov and Adam, with their clipping / EMA forms: solver.hip)
 
 // ------------------------------------------------------------------------------------------------
 // LossScaleOptimizer support (train.py:99-100, Keras mixed_float16): are all gradients finite?  *flag (device int,

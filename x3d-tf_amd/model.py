@@ -531,22 +531,64 @@ class X3D:
                  self.n_trainable_flat)
         return acc * self.arch.weight_decay
 
-    def apply_sgd(self, lr, momentum=0.9, grad_scale=1.0):
-        """SGD(momentum, nesterov=True) + L2 (reference train.py:89-92, model.py:47), one launch."""
-        self._claim_slots("sgd")
-        hip.call("x3d_sgd_nesterov", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
-                 self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
-                 float(self.arch.weight_decay), float(grad_scale), self.n_trainable_flat)
+    def grad_norm_sq(self):
+        """x3d_grad_sumsq over `flat_grads` into buffers the model keeps: the device [2] fp64 tensor (sum of squares of the
+        raw gradient, number of non-finite entries) the `norm=` of apply_sgd / apply_adam reads.  Two launches, no
+        synchronisation; the tensor is overwritten by the next call."""
+        if getattr(self, "_norm_out", None) is None:
+            n_scratch = int(hip.load().x3d_grad_sumsq_scratch(self.n_trainable_flat))
+            self._norm_scratch = torch.empty(n_scratch, dtype=torch.float64, device=self.device)
+            self._norm_out = torch.zeros(2, dtype=torch.float64, device=self.device)
+        hip.call("x3d_grad_sumsq", self.flat_grads.data_ptr(), self.n_trainable_flat, self._norm_scratch.data_ptr(),
+                 self._norm_out.data_ptr())
+        return self._norm_out
 
-    def apply_adam(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+    def _solver_extras(self, norm, max_norm, ema):
+        """(norm pointer, ema pointer) of an _ex launch, checked: `ema` covers at least the trainable block."""
+        if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2 or not norm.is_cuda):
+            raise ValueError("norm must be the device [2] float64 tensor of grad_norm_sq()")
+        if norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f"max_norm must be positive with norm, not {max_norm}")
+        if ema is not None and (ema.dtype != torch.float32 or ema.numel() < self.n_trainable_flat or not ema.is_cuda
+                                or not ema.is_contiguous()):
+            raise ValueError(f"ema must be a contiguous device float32 buffer of at least {self.n_trainable_flat} elements")
+        return (None if norm is None else norm.data_ptr()), (None if ema is None else ema.data_ptr())
+
+    def apply_sgd(self, lr, momentum=0.9, grad_scale=1.0, norm=None, max_norm=0.0, ema=None, ema_decay=0.0):
+        """SGD(momentum, nesterov=True) + L2 (reference train.py:89-92, model.py:47), one launch.
+        norm (grad_norm_sq()) + max_norm: the gradient is clipped to that global L2 norm and a non-finite gradient skips
+        the update, both decided on the device; ema: a flat fp32 buffer that receives ema_decay * ema + (1 - ema_decay) * w
+        in the same pass (x3d_sgd_nesterov_ex).  With neither this is the x3d_sgd_nesterov launch it always was."""
+        self._claim_slots("sgd")
+        if norm is None and ema is None:
+            hip.call("x3d_sgd_nesterov", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
+                     self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
+                     float(self.arch.weight_decay), float(grad_scale), self.n_trainable_flat)
+            return
+        pn, pe = self._solver_extras(norm, max_norm, ema)
+        hip.call("x3d_sgd_nesterov_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
+                 self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
+                 float(self.arch.weight_decay), float(grad_scale), pn, float(max_norm), pe, float(ema_decay),
+                 self.n_trainable_flat)
+
+    def apply_adam(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, norm=None, max_norm=0.0, ema=None,
+                   ema_decay=0.0):
         """Adam + L2 (reference train.py:93-95: tf.optimizers.Adam(learning_rate), Keras defaults), one launch.  The first
-        moment lives in `flat_velocity` (the slot the SGD branch uses for momentum), the second in `flat_second`."""
+        moment lives in `flat_velocity` (the slot the SGD branch uses for momentum), the second in `flat_second`.
+        norm / max_norm / ema / ema_decay: as apply_sgd (x3d_adam_ex)."""
         self._claim_slots("adam")
         if getattr(self, "flat_second", None) is None:
             self.flat_second = torch.zeros_like(self.flat_velocity)
-        hip.call("x3d_adam", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
+        if norm is None and ema is None:
+            hip.call("x3d_adam", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
+                     self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
+                     float(self.arch.weight_decay), float(grad_scale), int(step), self.n_trainable_flat)
+            return
+        pn, pe = self._solver_extras(norm, max_norm, ema)
+        hip.call("x3d_adam_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
                  self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
-                 float(self.arch.weight_decay), float(grad_scale), int(step), self.n_trainable_flat)
+                 float(self.arch.weight_decay), float(grad_scale), int(step), pn, float(max_norm), pe, float(ema_decay),
+                 self.n_trainable_flat)
 
     def grads_finite(self) -> bool:
         """True when every entry of the flat gradient buffer is finite (x3d_all_finite; synchronises)."""

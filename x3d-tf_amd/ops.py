@@ -631,6 +631,52 @@ def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
              float(weight_decay), float(grad_scale), w.numel())
 
 
+def _f32_flat(op, name, t, n=None):
+    if t.dtype != torch.float32 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{op}: {name} must be contiguous float32" + (f" of {n} elements" if n is not None else "")
+                         + f", got {t.numel()} {t.dtype}")
+
+
+def grad_sumsq(g, out=None, scratch=None):
+    """out [2] fp64 = (sum of squares of g in fp64, number of non-finite entries) (x3d_grad_sumsq: the rules are in
+    include/x3d_hip.h).  The same bits on every run.  out / scratch=None allocate.  Two launches, does not synchronise."""
+    _chk(g, out, scratch)
+    _f32_flat("grad_sumsq", "g", g)
+    n = g.numel()
+    need = int(hip.load().x3d_grad_sumsq_scratch(n))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float64, device=g.device)
+    elif scratch.dtype != torch.float64 or scratch.numel() < need:
+        raise ValueError(f"grad_sumsq: scratch must hold {need} float64, got {scratch.numel()} {scratch.dtype}")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=g.device)
+    elif out.dtype != torch.float64 or out.numel() != 2:
+        raise ValueError(f"grad_sumsq: out must be 2 float64, got {out.numel()} {out.dtype}")
+    hip.call("x3d_grad_sumsq", ptr(g), n, ptr(scratch), ptr(out))
+    return out
+
+
+def ema_update(ema, w, decay, norm=None):
+    """ema = decay * ema + (1 - decay) * w in place (x3d_ema_update); norm: the [2] fp64 result of grad_sumsq, the update
+    is skipped on the device when its second entry is not 0.  One launch, does not synchronise."""
+    _chk(ema, w, norm)
+    _f32_flat("ema_update", "ema", ema)
+    _f32_flat("ema_update", "w", w, ema.numel())
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f"ema_update: decay must lie in [0, 1), not {decay}")
+    hip.call("x3d_ema_update", ptr(ema), ptr(w), float(decay), ptr(norm), ema.numel())
+    return ema
+
+
+def grad_accum(acc, g, first=False):
+    """acc = g (first) or acc += g, exact fp32 (x3d_grad_accum); acc may be g.  One launch, does not synchronise."""
+    _chk(acc, g)
+    _f32_flat("grad_accum", "acc", acc)
+    _f32_flat("grad_accum", "g", g, acc.numel())
+    hip.call("x3d_grad_accum", ptr(acc), ptr(g), acc.numel(), 1 if first else 0)
+    return acc
+
+
 def l2_sumsq(w, l2_mask, out):
     _chk(w, l2_mask, out)
     hip.call("x3d_l2_sumsq", ptr(w), ptr(l2_mask), ptr(out), w.numel())

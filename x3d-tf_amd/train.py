@@ -3,6 +3,7 @@ momentum, SparseCategoricalCrossentropy on the model's probabilities + L2 regula
 warm-up/cosine learning-rate schedule -- as an explicit step loop over the HIP model, data-parallel
 over RCCL when launched with torchrun.
 """
+import contextlib
 import math
 import os
 from typing import Optional
@@ -10,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
-from .config import mix_settings
+from .config import mix_settings, solver_settings
 from .mix import NO_MIX, draw_mix_params
 
 
@@ -49,6 +50,18 @@ class SaveSchedule:
     def after_epoch(self, epoch: int) -> Optional[int]:
         """Called when epoch index `epoch` has finished; the checkpoint number to write now, or None."""
         return epoch + 1 if self.save_freq == "epoch" else None
+
+
+def check_accum_schedule(steps_per_epoch: int, save_freq, accum_steps: int):
+    """`fit` counts batches as steps; with SOLVER.ACCUM_STEPS = A > 1 an epoch and a step-based checkpoint must both end on an
+    optimizer update (a checkpoint inside an accumulation would drop the micro-batches gathered so far).  ValueError else."""
+    if accum_steps <= 1:
+        return
+    if steps_per_epoch % accum_steps:
+        raise ValueError(f"steps_per_epoch ({steps_per_epoch}) must be a multiple of SOLVER.ACCUM_STEPS ({accum_steps})")
+    if isinstance(save_freq, int) and not isinstance(save_freq, bool) and save_freq % accum_steps:
+        raise ValueError(f"save_freq ({save_freq}) must be a multiple of SOLVER.ACCUM_STEPS ({accum_steps}): a checkpoint "
+                         "must not fall inside an accumulation")
 
 
 TRAIN_METRICS = ("acc", "top_5_acc")
@@ -122,6 +135,15 @@ class Trainer:
         self.last_mix = NO_MIX                # MixParams of the last step
         self.epoch = 0
         self.skipped_keys = []                # variables of the pretrained checkpoint resume(skip_mismatch=True) did not load
+        # the solver step around the optimizer (SOLVER.*; all off by default: `step` is then what it was, launch for launch)
+        self.solver = solver_settings(cfg)
+        self._clip = self.solver.clip_grad_l2norm > 0.0
+        self._accum = self.solver.accum_steps
+        self._micro = 0                       # micro-batches gathered of the running accumulation
+        self._grad_acc = None                 # their summed local gradients (allocated by the first accumulation)
+        self.last_grad_norm = None            # device scalar: global L2 norm of the unscaled gradient of the last update
+        # weight EMA: trainable block + moving statistics, laid out as flat_params; starts from the (broadcast) weights
+        self.ema = model.flat_params.clone() if self.solver.ema_decay > 0.0 else None
 
     def step(self, clips, labels, lr: Optional[float] = None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
@@ -133,15 +155,25 @@ class Trainer:
             lr = lr_schedule(self.epoch, self.cfg)
         if self._mix_active:
             clips, labels = self._mix_batch(clips, labels)
+        if self._accum > 1:
+            return self._accum_step(clips, labels, lr, n)
         pl = m.forward_backward(clips, labels, global_batch=n * self.world,
                                 on_stage_done=self._on_stage_done if self.collectives else None,
                                 loss_scale=self.loss_scale)
         self.reducer.mark_backward_done()     # (an event on the compute stream: finish() measures the exposed exchange from it)
         self.reducer.finish()
+        self._finish_stats()
+        return self._update(pl, lr)
+
+    def _finish_stats(self):
         if self._stats_work is not None:      # mirrored-variable MEAN aggregation of the BN moving statistics [TF-3p]
             self._stats_work.wait()
             self._stats_work = None
-            m.moving_stats_flat().div_(self.world)
+            self.model.moving_stats_flat().div_(self.world)
+
+    def _update(self, pl, lr):
+        """Finite check (fp16 loss scaling), clip, optimizer, EMA on the all-reduced gradient in `flat_grads`."""
+        m = self.model
         if self.dynamic_scale:                # after the all-reduce: every replica sees the same sums, takes the same branch
             if not m.grads_finite():
                 self.loss_scale = max(self.loss_scale / 2.0, 1.0)
@@ -150,14 +182,55 @@ class Trainer:
                 return pl                     # LossScaleOptimizer skips the update
             self._good_steps += 1
         self.opt_step += 1
+        grad_scale = 1.0 / self.loss_scale
+        extras = {}
+        if self._clip:
+            # the norm stays on the device: the _ex launch derives the clip coefficient from it, and skips itself (weights,
+            # slots and EMA untouched) when the gradient holds an inf / nan.  `opt_step` has counted such a step all the
+            # same -- the host never learns of it -- so after one Adam's bias correction runs one step ahead.
+            norm = m.grad_norm_sq()
+            self.last_grad_norm = norm[0].sqrt() * grad_scale
+            extras.update(norm=norm, max_norm=self.solver.clip_grad_l2norm)
+        if self.ema is not None:
+            extras.update(ema=self.ema, ema_decay=self.solver.ema_decay)
         if self.optimizer == "adam":
-            m.apply_adam(lr, self.opt_step, grad_scale=1.0 / self.loss_scale)
+            m.apply_adam(lr, self.opt_step, grad_scale=grad_scale, **extras)
         else:
-            m.apply_sgd(lr, self.momentum, grad_scale=1.0 / self.loss_scale)
+            m.apply_sgd(lr, self.momentum, grad_scale=grad_scale, **extras)
+        if self.ema is not None:              # the moving statistics behind the trainable block: skipped together with the step
+            from . import ops
+            ops.ema_update(self.ema[m.n_trainable_flat:], m.moving_stats_flat(), self.solver.ema_decay, extras.get("norm"))
         if self.dynamic_scale and self._good_steps >= self.growth_steps:
             self.loss_scale *= 2.0
             self._good_steps = 0
         return pl
+
+    def _accum_step(self, clips, labels, lr, n):
+        """One micro-batch of SOLVER.ACCUM_STEPS = A > 1.  Micro-batches 1..A-1 add their local gradient to the accumulator
+        (no gradient all-reduce; weights, slots, EMA and `opt_step` untouched; the moving statistics are averaged as always).
+        Micro-batch A adds the accumulator back -- under data parallelism bucket by bucket in the backward hook, in front of
+        that bucket's all-reduce, so the exchange still hides behind the backward pass -- and updates on the total, which
+        `flat_grads` then holds.  The loss scale changes with an update only, so it is one value within an accumulation."""
+        from . import ops
+        m = self.model
+        self._micro += 1
+        last = self._micro == self._accum
+        if self._grad_acc is None:
+            self._grad_acc = torch.zeros_like(m.flat_grads)
+        hook = (self._on_stage_done if last else self._on_stage_done_no_grads) if self.collectives else None
+        pl = m.forward_backward(clips, labels, global_batch=n * self.world * self._accum, on_stage_done=hook,
+                                loss_scale=self.loss_scale)
+        if not last:
+            ops.grad_accum(self._grad_acc, m.flat_grads, first=self._micro == 1)
+            self._finish_stats()
+            return pl
+        self._micro = 0
+        if not self.collectives:
+            ops.grad_accum(m.flat_grads, self._grad_acc)
+        self.reducer.mark_backward_done()
+        self.reducer.finish()
+        self._finish_stats()
+        return self._update(pl, lr)
 
     def _mix_batch(self, clips, labels):
         """Soft-target training: draws this batch's MixParams, mixes the clips with the reversed batch (x3d_mix_clips) and
@@ -233,13 +306,18 @@ class Trainer:
             refused -- and validation fills `val_loss` / `val_mAP`.
 
         self.history: per-epoch lists like keras.callbacks.History.history -- `loss` (= the returned list), `lr`, the
-        requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating."""
+        requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating.
+
+        SOLVER.* (INTEGRATION.md): with CLIP_GRAD_L2NORM `history["grad_norm"]` is the epoch's mean gradient norm before
+        clipping; with ACCUM_STEPS = A every batch is a micro-batch, steps_per_epoch and an integer save_freq must be multiples
+        of A (ValueError); with EMA_DECAY and EMA_EVAL validation runs on the EMA weights (`ema_scope`)."""
         from .evaluate import DeviceMAP, DeviceMetrics
         tr = self.cfg.TRAIN
         epochs = int(tr.EPOCHS if epochs is None else epochs)
         steps = int(steps_per_epoch if steps_per_epoch is not None else tr.DATASET_SIZE // tr.BATCH_SIZE)
         if steps <= 0:
             raise ValueError("steps_per_epoch must be positive (cfg.TRAIN.DATASET_SIZE // cfg.TRAIN.BATCH_SIZE)")
+        check_accum_schedule(steps, save_freq, self.solver.accum_steps)
         multi = bool(getattr(self.model, "multi_label", False))
         known = MULTI_LABEL_METRICS if multi else TRAIN_METRICS
         if metrics is _DEFAULT_METRICS:
@@ -258,6 +336,8 @@ class Trainer:
         history = []
         self.history = {"loss": [], "lr": []}
         self.history.update({k: [] for k in metrics})
+        if self._clip:
+            self.history["grad_norm"] = []
         if val_source is not None:
             self.history.update({"val_" + k: [] for k in val_keys})
         writer = model_dir is not None and xdist.env_world()[0] == 0
@@ -265,10 +345,15 @@ class Trainer:
             lr = lr_schedule(self.epoch, self.cfg)
             tot = torch.zeros((), dtype=torch.float64, device=self.model.device)
             train_m = (DeviceMAP() if multi else DeviceMetrics()) if metrics else None
+            gn_tot, updates = (torch.zeros((), dtype=torch.float64, device=self.model.device) if self._clip else None), 0
             for _ in range(steps):
                 clips, labels = next(it)
+                before = self.opt_step
                 pl = self.step(clips, labels, lr)
                 tot += self.loss(pl).double()
+                if gn_tot is not None and self.opt_step != before:     # an update ran (not inside an accumulation / fp16 skip)
+                    gn_tot += self.last_grad_norm
+                    updates += 1
                 if train_m is not None:
                     train_m.update(pl.probs, pl.targets if multi else pl.labels)
                 if on_step is not None:
@@ -281,12 +366,15 @@ class Trainer:
             history.append(float(tot.item()) / steps)
             self.history["loss"].append(history[-1])
             self.history["lr"].append(lr)
+            if gn_tot is not None:            # mean over the epoch's updates; read once per epoch, like the loss
+                self.history["grad_norm"].append(float(gn_tot.item()) / max(updates, 1))
             if train_m is not None:
                 r = train_m.all_reduce_(self.group).result()
                 for k in metrics:
                     self.history[k].append(r[k])
             if val_source is not None:
-                r = self.validate(val_source(), validation_steps)
+                with (self.ema_scope() if self.ema is not None and self.solver.ema_eval else contextlib.nullcontext()):
+                    r = self.validate(val_source(), validation_steps)
                 for k in val_keys:
                     self.history["val_" + k].append(r[k])
             if ckpt is not None and writer:
@@ -337,7 +425,40 @@ class Trainer:
             return
         i = self._launch_at.get(stage)
         if i is not None:
+            if self._accum > 1:               # the last micro-batch of an accumulation: the earlier ones join their bucket first
+                from . import ops
+                b = self.reducer.buckets[i]
+                lo = b.storage_offset() - self.model.flat_grads.storage_offset()
+                ops.grad_accum(b, self._grad_acc[lo:lo + b.numel()])
             self.reducer.launch(i)
+
+    def _on_stage_done_no_grads(self, stage):
+        """backward hook of the micro-batches inside an accumulation: the moving statistics only, no gradient all-reduce"""
+        if stage == "fwd":
+            self._on_stage_done(stage)
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Within the scope the model IS the EMA model: the contents of `flat_params` and `self.ema` are swapped (every
+        plan holds addresses into `flat_params`, so the values move, not the buffers) and swapped back on exit, bit for bit.
+        Nothing the inference path derives from the weights outlives a call -- the bf16 / fp16 weight panels are repacked
+        and the BatchNorm coefficients recomputed at the head of every forward -- so the swap has nothing to invalidate."""
+        if self.ema is None:
+            raise ValueError("ema_scope needs SOLVER.EMA_DECAY > 0")
+        p = self.model.flat_params
+
+        if getattr(self, "_ema_swap", None) is None:
+            self._ema_swap = torch.empty_like(p)      # kept: a scope is entered for every validation and every checkpoint
+
+        def swap():
+            self._ema_swap.copy_(p)
+            p.copy_(self.ema)
+            self.ema.copy_(self._ema_swap)
+        swap()
+        try:
+            yield self
+        finally:
+            swap()
 
     # -- checkpoints in the reference's layout (utils.py:128-132 ModelCheckpoint 'ckpt-{epoch:d}', train.py:131-136) --
     def save_checkpoint(self, model_dir: str, epoch: int) -> str:
@@ -355,6 +476,13 @@ class Trainer:
         else:
             hyper.update(momentum=self.momentum)
         self.model.save_weights(prefix, optimizer_hyper=hyper, optimizer=self.optimizer)
+        if self.ema is not None:
+            # the EMA model as a bundle of its own, in its own directory: `<model_dir>/checkpoint` still names ckpt-<epoch>,
+            # and model.load_weights("<model_dir>/ema") loads the EMA weights for evaluation
+            os.makedirs(os.path.join(model_dir, "ema"), exist_ok=True)
+            with self.ema_scope():
+                self.model.save_weights(os.path.join(model_dir, "ema", f"ckpt-{int(epoch)}"), optimizer_hyper=hyper,
+                                        optimizer=self.optimizer)
         return prefix
 
     def resume(self, model_dir: str, pretrained_ckpt: Optional[str] = None, skip_mismatch: bool = False) -> int:
@@ -382,6 +510,13 @@ class Trainer:
             return 0
         self._load(path)
         self.epoch = int(os.path.basename(path).split("-")[1])
+        if self.ema is not None:              # the EMA of that epoch (save_checkpoint: <model_dir>/ema/ckpt-<epoch>), if there
+            ema_prefix = os.path.join(model_dir, "ema", os.path.basename(path))
+            if os.path.exists(ema_prefix + ".index"):
+                from .checkpoint import read_checkpoint
+                sd = read_checkpoint(ema_prefix, self.model.specs)
+                with self.ema_scope():
+                    self.model.load_state_dict(sd)
         return self.epoch
 
     def _load(self, path: str, skip_mismatch: bool = False):
@@ -406,6 +541,8 @@ class Trainer:
             if self.optimizer == "adam" and kind is None:
                 m.flat_velocity.zero_()
                 self.opt_step = 0
+        if self.ema is not None:              # restart the EMA from the loaded weights (resume replaces it by a saved one)
+            self.ema.copy_(m.flat_params)
 
     def loss(self, pl):
         """global-batch mean cross-entropy + L2 term (what Keras reports as `loss`)."""
