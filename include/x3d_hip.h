@@ -749,6 +749,85 @@ int x3d_train_clips_aug(const long long* videos, const int* geom, const float* c
                         const float* mean, const float* std, int erase_mode, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * RandAugment on the uint8 frames (AUG.AA_TYPE of the config, x3d_tf_amd/aug.py draw_randaug; added under ABI 138 without a
+ * bump: new symbols only).  N decoded videos of DIFFERENT extents; clip n takes its T sampled frames
+ * (start + j * rate) mod F and sends them through `layers` ops, one op per (clip, layer), every frame of a clip with the
+ * same op and argument.  Runs BEFORE x3d_train_clips_aug, which then reads the result as a video of F = T frames with
+ * start = 0, rate = 1.  The ops (timm rand_augment_transform as PySlowFast applies it to clips; PIL's arithmetic):
+ *     INVERT 255 - v;  SOLARIZE v < IARG ? v : 255 - v;  SOLARIZE_ADD v < 128 ? min(255, v + IARG) : v;
+ *     POSTERIZE v & ~(2^(8 - IARG) - 1), IARG >= 8: identity;
+ *     AUTOCONTRAST per frame and channel, lo / hi = min / max: hi <= lo identity, else
+ *         lut[i] = clamp(trunc(i * (255.0 / (hi - lo)) - lo * (255.0 / (hi - lo))), 0, 255) in fp64 (two products, one difference);
+ *     EQUALIZE per frame and channel, histogram h: fewer than 2 non-empty bins identity; step = (sum h - last non-empty bin)
+ *         / 255 (integer), step == 0 identity; else n = step / 2, for i = 0..255: lut[i] = min(255, n / step), n += h[i];
+ *     COLOR / CONTRAST / BRIGHTNESS / SHARPNESS out = d + f * (v - d) with f = FARG: t = fl32(f * fl32(v - d)), r = fl32(d + t)
+ *         (no contraction), result 0 if r <= 0, 255 if r >= 255, else trunc(r).  d: COLOR the pixel's
+ *         L = (19595 R + 38470 G + 7471 B + 32768) >> 16; BRIGHTNESS 0; CONTRAST the frame's constant
+ *         trunc(sum L / (H * W) + 0.5) (exact integer sum, fp64 division); SHARPNESS (sum k v + 6) / 13 (integer) over the
+ *         3 x 3 neighbourhood with k = 1 except 5 at the centre, the frame's one-pixel border copied unchanged;
+ *     ROTATE / SHEAR_X / SHEAR_Y / TRANSLATE_X / TRANSLATE_Y one inverse affine map, bilinear: the six X3D_RA_X_A..F columns
+ *         are SIGNED FIXED POINT WITH 32 FRACTIONAL BITS in int64 (the host builds the matrix in fp64, folds the +0.5 pixel
+ *         centres into C and F, rounds to nearest).  Output pixel (x, y): sx = A x + B y + C, sy = D x + E y + F in int64;
+ *         outside [0, W) x [0, H): the fill colour; else subtract half a pixel, tap = floor, weight fx, fy = the top 8
+ *         fractional bits, taps clamped to the frame,
+ *         ((p00 (256 - fx) + p01 fx)(256 - fy) + (p10 (256 - fx) + p11 fx) fy + 32768) >> 16.
+ *     COPY the sampled frames unchanged (a clip without an applied op whose video is not already its T frames);
+ *     NONE the clip takes no part in the layer (its workgroups return at once; SRC / DST are not read).
+ * Tables (plain arrays, no struct; the DEVICE copies are read by the kernels, the HOST copies validated by this call before
+ * any launch -- THE CALLER UPLOADS EXACTLY THE HOST TABLES, as for x3d_train_clips_aug):
+ *     videos int64 [N]: device addresses of the uint8 videos [F][H][W][3] (device table only);
+ *     clips  int32 [N][X3D_RA_CLIP_COLS]: F, H, W, start;
+ *     ops    int32 [N][layers][X3D_RA_OP_COLS]: op code, IARG, FARG (the bits of an fp32), 0;
+ *     xform  int64 [N][layers][X3D_RA_X_COLS]: A..F, then SRC and DST: byte offsets into `work` of the T x H x W x 3 bytes
+ *            the layer reads and writes; SRC = -1 reads the sampled frames straight from the video.  The caller ping-pongs
+ *            each clip between two ranges of its own and keeps the ranges of different clips disjoint.
+ * work: device, work_bytes bytes, the caller's.  scratch: x3d_randaug_scratch(N, T) bytes of device memory, 8-byte aligned; the
+ * call zeroes it itself (hipMemsetAsync on `stream`) before each statistics launch.  fill_r/g/b: the fill colour, 0..255.
+ * Launches: per layer one apply launch over the whole batch (grid z = clip, y = frame; a workgroup reads its clip's op from the
+ * device table), preceded -- only when some clip's op in that layer is AUTOCONTRAST, EQUALIZE or CONTRAST -- by one
+ * statistics launch whose workgroups return at once for every other clip: LDS histograms (or the L sum) per workgroup,
+ * flushed with INTEGER atomics (sums commute: the same bits on every run; no floating-point atomics).  A layer in which every
+ * clip has NONE launches nothing.  Neither allocates nor synchronises.
+ * Refused before any launch (X3D_ERR_INVALID): a null table / pointer, N <= 0 or N > 65535, T, rate, layers <= 0, T > 65535,
+ * F, H or W <= 0 (or H, W > 32768), start outside [0, F), an unknown op, a non-finite FARG of the four blend ops, POSTERIZE
+ * bits outside [0, 8], a matrix coefficient out of range (|A|, |B|, |D|, |E| >= 2^45, |C|, |F| >= 2^60), SRC < -1, a SRC or DST
+ * range outside [0, work_bytes), SRC and DST ranges of one (clip, layer) overlapping, a fill colour outside 0..255.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_RA_NONE 0
+#define X3D_RA_AUTOCONTRAST 1
+#define X3D_RA_EQUALIZE 2
+#define X3D_RA_INVERT 3
+#define X3D_RA_ROTATE 4
+#define X3D_RA_POSTERIZE 5
+#define X3D_RA_SOLARIZE 6
+#define X3D_RA_SOLARIZE_ADD 7
+#define X3D_RA_COLOR 8
+#define X3D_RA_CONTRAST 9
+#define X3D_RA_BRIGHTNESS 10
+#define X3D_RA_SHARPNESS 11
+#define X3D_RA_SHEAR_X 12
+#define X3D_RA_SHEAR_Y 13
+#define X3D_RA_TRANSLATE_X 14
+#define X3D_RA_TRANSLATE_Y 15
+#define X3D_RA_COPY 16
+#define X3D_RA_CLIP_COLS 4    /* F, H, W, start */
+#define X3D_RA_OP_COLS 4
+#define X3D_RA_O_OP 0
+#define X3D_RA_O_IARG 1       /* POSTERIZE bits, SOLARIZE threshold, SOLARIZE_ADD addend */
+#define X3D_RA_O_FARG 2       /* the factor of COLOR / CONTRAST / BRIGHTNESS / SHARPNESS: the bits of an fp32 */
+#define X3D_RA_X_COLS 8
+#define X3D_RA_X_A 0          /* inverse affine map, 32 fractional bits: sx = A x + B y + C, sy = D x + E y + F */
+#define X3D_RA_X_SRC 6
+#define X3D_RA_X_DST 7
+#define X3D_RA_FRAC_BITS 32
+#define X3D_RA_STAT_WORDS 772 /* uint32 words of scratch per (clip, frame): 3 x 256 histogram, the L sum (uint64), padding */
+long long x3d_randaug_scratch(int N, int T);
+int x3d_randaug_clips(const long long* videos, const int* clips, const int* ops, const long long* xform,
+                      const int* host_clips, const int* host_ops, const long long* host_xform, void* work,
+                      long long work_bytes, void* scratch, int N, int T, int rate, int layers, int fill_r, int fill_g,
+                      int fill_b, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * JPEG frames of the TFRecord input pipeline decoded on the device (reference dataloader.py:80-88:
  * tf.image.decode_jpeg of every frame; create_tfrecords.py:64-65 writes them).
  *     Baseline and extended-sequential Huffman JPEG, 8-bit, grey or YCbCr with luma sampling 1x1 / 2x1 / 2x2 and

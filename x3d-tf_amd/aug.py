@@ -18,7 +18,10 @@ erase      timm's `RandomErasing` [TIMM-3p], one box per clip: with probability 
            area = U(RE_AREA) * S * S, aspect = exp(U(log RE_RATIO)), h = round(sqrt(area * aspect)),
            w = round(sqrt(area / aspect)), accepted when 0 < h < S and 0 < w < S, top ~ U{0..S-h}, left ~ U{0..S-w}; no box if
            all fail.  The box is in OUTPUT-crop coordinates (after the mirror).
-seed       63 bits for the noise of RE_MODE "pixel"."""
+seed       63 bits for the noise of RE_MODE "pixel".
+
+RandAugment (AUG.AA_TYPE) is drawn separately, by `draw_randaug` below (its own record type and its own generator: AugParams
+and the draws above do not move), and runs on the uint8 frames before all of the above (x3d_randaug_clips)."""
 import collections
 import math
 
@@ -147,3 +150,112 @@ def fold_color(params: AugParams):
     if params.gray:
         m = np.outer(np.ones(3), w) @ m
     return m, float(k)
+
+
+# ---- RandAugment (AUG.AA_TYPE; config.RandAugSpec) -----------------------------------------------------------------------
+# timm's `rand_augment_transform` [TIMM-3p] as PySlowFast's rand_augment.py applies it to clips: ONE op and argument per layer
+# and clip, applied to every sampled frame, on the uint8 frames at their decoded size (x3d_randaug_clips, before
+# x3d_train_clips_aug).  The two op sets hold the same 15 ops in timm's order; "increasing" changes the level mappings of
+# Posterize, Solarize and the four ImageEnhance ops so that every op grows stronger with the magnitude.
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast",
+               "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+RANDAUG_SIGNED = ("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+RANDAUG_ENHANCE = ("Color", "Contrast", "Brightness", "Sharpness")
+RANDAUG_GEOMETRIC = RANDAUG_SIGNED
+# name: one of RANDAUG_OPS or "none" (the layer's draw missed its probability).  arg: Rotate degrees (counter-clockwise, as
+# PIL.Image.rotate), ShearX / ShearY the shear factor, TranslateXRel / TranslateYRel the offset in PIXELS (fraction * W / H
+# of the video it was drawn for), Color / Contrast / Brightness / Sharpness the ImageEnhance factor, Posterize bits kept,
+# Solarize threshold, SolarizeAdd addend (threshold 128); None for AutoContrast, Equalize, Invert and "none".
+RandAugOp = collections.namedtuple("RandAugOp", "name arg")
+RANDAUG_NONE = RandAugOp("none", None)
+
+
+def randaug_arg(name: str, magnitude: float, inc: bool, negate: bool, height: int, width: int):
+    """The argument of op `name` at `magnitude` (0..10), L = magnitude / 10; `negate` is the coin of the "±" ops:
+    Rotate ±30 L degrees; ShearX / ShearY ±0.3 L; TranslateXRel / TranslateYRel ±0.45 L of W / H (returned in pixels);
+    Color / Contrast / Brightness / Sharpness 0.1 + 1.8 L, increasing: max(0.1, 1 ± 0.9 L); Posterize int(4 L) bits,
+    increasing: 4 - int(4 L); Solarize int(256 L), increasing: 256 - int(256 L); SolarizeAdd int(110 L); else None."""
+    lv = float(magnitude) / 10.0
+    sign = -1.0 if negate else 1.0
+    if name == "Rotate":
+        return sign * 30.0 * lv
+    if name in ("ShearX", "ShearY"):
+        return sign * 0.3 * lv
+    if name == "TranslateXRel":
+        return sign * 0.45 * lv * int(width)
+    if name == "TranslateYRel":
+        return sign * 0.45 * lv * int(height)
+    if name in RANDAUG_ENHANCE:
+        return max(0.1, 1.0 + sign * 0.9 * lv) if inc else 0.1 + 1.8 * lv
+    if name == "Posterize":
+        return 4 - int(4 * lv) if inc else int(4 * lv)
+    if name == "Solarize":
+        return 256 - int(256 * lv) if inc else int(256 * lv)
+    if name == "SolarizeAdd":
+        return int(110 * lv)
+    if name in ("AutoContrast", "Equalize", "Invert"):
+        return None
+    raise ValueError(f"unknown RandAugment op {name!r}")
+
+
+def draw_randaug(spec, height: int, width: int, rng: np.random.Generator):
+    """The RandAugment draws of one clip from a video of height x width: a tuple of spec.layers RandAugOp.
+
+    ORDER OF THE DRAWS, per layer, layers in ascending order (pinned by tests/test_randaug.py):
+      1. the op:         rng.integers(0, 15), an index into RANDAUG_OPS (uniform, with replacement)
+      2. the apply coin: rng.random() < spec.prob; a miss ends the layer with RANDAUG_NONE -- draws 3 and 4 are not made
+      3. the magnitude:  only when spec.mstd > 0: clip(rng.normal(spec.magnitude, spec.mstd), 0, 10)
+      4. the sign coin:  only for the "±" ops (Rotate, ShearX/Y, TranslateX/YRel) and, with spec.inc, the four ImageEnhance
+                         ops: negated when rng.random() < 0.5
+    The magnitude is drawn for every applied op, also for those that take no argument."""
+    h, w = int(height), int(width)
+    if h <= 0 or w <= 0:
+        raise ValueError(f"draw_randaug: frame {h} x {w}")
+    out = []
+    for _ in range(int(spec.layers)):
+        name = RANDAUG_OPS[int(rng.integers(0, len(RANDAUG_OPS)))]
+        if not rng.random() < spec.prob:
+            out.append(RANDAUG_NONE)
+            continue
+        mag = float(spec.magnitude)
+        if spec.mstd > 0.0:
+            mag = min(max(float(rng.normal(spec.magnitude, spec.mstd)), 0.0), 10.0)
+        negate = False
+        if name in RANDAUG_SIGNED or (spec.inc and name in RANDAUG_ENHANCE):
+            negate = bool(rng.random() < 0.5)
+        out.append(RandAugOp(name, randaug_arg(name, mag, spec.inc, negate, h, w)))
+    return tuple(out)
+
+
+def randaug_matrix(op: RandAugOp, height: int, width: int):
+    """The inverse affine map (a, b, c, d, e, f) of a geometric op in fp64, in PIL's convention: output pixel (x, y) reads the
+    source position (a (x + 0.5) + b (y + 0.5) + c, d (x + 0.5) + e (y + 0.5) + f).  Rotate as PIL.Image.rotate builds it
+    (expand=False, centre (W / 2, H / 2), sine and cosine rounded to 15 decimals); ShearX (1, s, 0; 0, 1, 0); ShearY
+    (1, 0, 0; s, 1, 0); TranslateXRel / TranslateYRel an offset of `arg` pixels."""
+    h, w = int(height), int(width)
+    v = float(op.arg)
+    if op.name == "Rotate":
+        ang = -math.radians(v % 360.0)
+        m = [round(math.cos(ang), 15), round(math.sin(ang), 15), 0.0, round(-math.sin(ang), 15), round(math.cos(ang), 15), 0.0]
+        cx, cy = w / 2.0, h / 2.0
+        m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
+        m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+        return tuple(m)
+    if op.name == "ShearX":
+        return (1.0, v, 0.0, 0.0, 1.0, 0.0)
+    if op.name == "ShearY":
+        return (1.0, 0.0, 0.0, v, 1.0, 0.0)
+    if op.name == "TranslateXRel":
+        return (1.0, 0.0, v, 0.0, 1.0, 0.0)
+    if op.name == "TranslateYRel":
+        return (1.0, 0.0, 0.0, 0.0, 1.0, v)
+    raise ValueError(f"{op.name!r} is not a geometric op")
+
+
+def randaug_fixed_matrix(op: RandAugOp, height: int, width: int, frac_bits: int = 32):
+    """randaug_matrix with the half-pixel centres folded into c and f (sx = a x + b y + (c + a / 2 + b / 2), likewise sy) and
+    every coefficient rounded to nearest as signed fixed point with `frac_bits` fractional bits: six Python ints."""
+    a, b, c, d, e, f = randaug_matrix(op, height, width)
+    c, f = c + 0.5 * a + 0.5 * b, f + 0.5 * d + 0.5 * e
+    one = float(1 << frac_bits)
+    return tuple(int(round(k * one)) for k in (a, b, c, d, e, f))

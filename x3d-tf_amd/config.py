@@ -10,6 +10,7 @@ import ast
 import collections
 import copy
 import os
+import re
 
 import yaml
 
@@ -118,7 +119,7 @@ class CfgNode(dict):
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
-    AUG.* (batched training augmentation), SOLVER.* (gradient clipping, accumulation, weight EMA)."""
+    AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -146,7 +147,10 @@ def get_default_config():
     # clip gets the colour chain, GRAYSCALE_PROB that it is turned grey after it.  RE_*: random erasing.
     c.AUG = CfgNode(dict(ENABLE=False, CROP="jitter", RRC_SCALE=[0.08, 1.0], RRC_RATIO=[0.75, 1.3333], FLIP_PROB=0.5,
                          BRIGHTNESS=0.4, CONTRAST=0.4, SATURATION=0.4, COLOR_PROB=1.0, GRAYSCALE_PROB=0.0, RE_PROB=0.25,
-                         RE_MODE="pixel", RE_AREA=[0.02, 0.3333], RE_RATIO=[0.3, 3.3333]))
+                         RE_MODE="pixel", RE_AREA=[0.02, 0.3333], RE_RATIO=[0.3, 3.3333],
+                         # RandAugment on the uint8 frames before everything above (x3d_randaug_clips), written as PySlowFast /
+                         # timm write it: "rand-m7-n4-mstd0.5-inc1" (randaug_settings); "" = off
+                         AA_TYPE=""))
     # the solver step around the optimizer (all off by default; CLIP_GRAD_L2NORM as PySlowFast's SOLVER section): the max global
     # L2 norm of the unscaled, all-reduced gradient (0 = off), micro-batches per optimizer update, the decay of the weight EMA
     # (0 = off) and whether fit's validation runs on the EMA weights
@@ -173,6 +177,7 @@ def get_config(name, overrides=None, freeze=True):
     ensemble_method(cfg)
     mix_settings(cfg)
     aug_settings(cfg)
+    randaug_settings(cfg)
     solver_settings(cfg)
     if freeze:
         cfg.freeze()
@@ -272,6 +277,63 @@ def aug_settings(cfg) -> AugSettings:
     if s.rrc_scale[1] > 1.0 or s.re_area[1] > 1.0:
         raise ValueError(f"AUG.RRC_SCALE / AUG.RE_AREA are area fractions (<= 1), not {s.rrc_scale} / {s.re_area}")
     return s
+
+
+# RandAugment (AUG.AA_TYPE): magnitude 0..10, layers (ops drawn per clip), mstd (sigma of the magnitude noise), inc (the
+# "increasing" op set: every op grows stronger with the magnitude), prob (chance a drawn op is applied)
+RandAugSpec = collections.namedtuple("RandAugSpec", "magnitude layers mstd inc prob")
+_AA_FIELD = re.compile(r"(mstd|inc|m|n|p)(.+)")
+
+
+def parse_aa_type(text: str) -> RandAugSpec:
+    """"rand" followed by "-"-separated fields in any order: m<int 0..10> magnitude (default 10), n<int >= 1> layers (2),
+    mstd<float >= 0> magnitude noise (0), inc<0|1> the increasing op set (0), p<float in [0, 1]> per-op probability (0.5).
+    ValueError for anything else: another policy name, an unknown or repeated field, a value outside its range."""
+    def bad(why):
+        return ValueError(f"AUG.AA_TYPE {text!r}: {why} (grammar: rand[-m<0..10>][-n<int>=1>][-mstd<float>=0>][-inc<0|1>][-p<0..1>])")
+    if not isinstance(text, str):
+        raise bad("not a string")
+    parts = text.split("-")
+    if parts[0] != "rand":
+        raise bad("only the 'rand' policy is implemented")
+    vals = dict(m=10, n=2, mstd=0.0, inc=0, p=0.5)
+    seen = set()
+    for part in parts[1:]:
+        f = _AA_FIELD.fullmatch(part)
+        if not f:
+            raise bad(f"cannot read field {part!r}")
+        key, val = f.groups()
+        if key in seen:
+            raise bad(f"field {key!r} given twice")
+        seen.add(key)
+        if key in ("m", "n", "inc"):
+            if not re.fullmatch(r"\d+", val):
+                raise bad(f"{key} takes a non-negative integer, not {val!r}")
+            v = int(val)
+            if (key == "m" and v > 10) or (key == "n" and v < 1) or (key == "inc" and v > 1):
+                raise bad(f"{key} = {v} out of range")
+        else:
+            if not re.fullmatch(r"\d+(\.\d*)?|\.\d+", val):
+                raise bad(f"{key} takes a non-negative decimal number, not {val!r}")
+            v = float(val)
+            if key == "p" and v > 1.0:
+                raise bad(f"p = {v} outside [0, 1]")
+        vals[key] = v
+    return RandAugSpec(vals["m"], vals["n"], vals["mstd"], bool(vals["inc"]), vals["p"])
+
+
+def randaug_settings(cfg):
+    """cfg.AUG.AA_TYPE as a RandAugSpec; None for "" and for a config tree without the key (or without AUG).  ValueError for a
+    string outside the grammar (parse_aa_type) and for AA_TYPE set while AUG.ENABLE is off (the batched call is the only path
+    that runs it: a silently ignored policy would be a wrong recipe)."""
+    a = getattr(cfg, "AUG", None)
+    text = getattr(a, "AA_TYPE", "") if a is not None else ""
+    if text == "":
+        return None
+    spec = parse_aa_type(text)
+    if not bool(getattr(a, "ENABLE", False)):
+        raise ValueError(f"AUG.AA_TYPE = {text!r} needs AUG.ENABLE")
+    return spec
 
 
 SolverSettings = collections.namedtuple("SolverSettings", "clip_grad_l2norm accum_steps ema_decay ema_eval")

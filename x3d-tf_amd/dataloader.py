@@ -242,7 +242,9 @@ class InputReader:
     Augmentation (cfg.AUG.ENABLE, training): every clip's `aug.AugParams` are drawn with `aug.draw_aug_params` from a NumPy
     generator derived from (seed, rank), in record order, and the batch is built by one `views.make_train_batch_aug` call
     in both `jpeg_decode` modes (device decode still decodes only the T frames a clip reads); `last_params` holds the
-    AugParams.  With AUG.ENABLE off nothing differs from the above: the same draws from the torch generator in the same
+    AugParams.  With AUG.AA_TYPE set on top, every clip's RandAugment ops are drawn with `aug.draw_randaug` from a further
+    generator of their own (the existing draws and their order do not move) and handed to the same call; `last_randaug`
+    holds them.  With AUG.ENABLE off nothing differs from the above: the same draws from the torch generator in the same
     order, one x3d_train_clip launch per clip."""
 
     _multi = False        # multi-label mode (set from cfg in __init__)
@@ -287,6 +289,13 @@ class InputReader:
         # generator's changes -- and the batch built by one make_train_batch_aug call
         self._aug = self._is_training and aug_settings(cfg).enable
         self._rng_aug = np.random.default_rng(self._rng.bit_generator.seed_seq.spawn(1)[0]) if self._aug else None
+        # AUG.AA_TYPE: every clip's RandAugment ops (aug.draw_randaug) from a further generator of their own -- the NEXT child of
+        # the same seed sequence, spawned only when the policy is on, so the AugParams stream above does not move
+        from .config import randaug_settings
+        self._randaug = randaug_settings(cfg) if self._aug else None
+        self._rng_ra = (np.random.default_rng(self._rng.bit_generator.seed_seq.spawn(1)[0])
+                        if self._randaug is not None else None)
+        self.last_randaug: List[tuple] = []    # the RandAugment draws of the last training batch ([] with AA_TYPE off)
         self._num_classes = int(cfg.NETWORK.NUM_CLASSES)
 
     # -- decode ------------------------------------------------------------------------------------
@@ -453,6 +462,9 @@ class InputReader:
             from .aug import draw_aug_params
             f, h, w, _ = video.shape
             self._batch_params.append(draw_aug_params(self._cfg, f, h, w, self._rng_aug))
+            if self._randaug is not None:
+                from .aug import draw_randaug
+                self._batch_randaug.append(draw_randaug(self._randaug, h, w, self._rng_ra))
             return v
         if self._is_training:
             f, h, w, _ = video.shape
@@ -474,10 +486,14 @@ class InputReader:
             return batch, targets.to(self._device, non_blocking=True)
         return batch, torch.tensor(labels, dtype=torch.int64, device=self._device)
 
-    def _aug_batch(self, videos: List[torch.Tensor], params: List, rate: Optional[int] = None) -> torch.Tensor:
-        """AUG.ENABLE: the batch [B, T, S, S, 3] from its uploaded videos, one make_train_batch_aug call"""
+    def _aug_batch(self, videos: List[torch.Tensor], params: List, rate: Optional[int] = None,
+                   randaug: Optional[List] = None) -> torch.Tensor:
+        """AUG.ENABLE: the batch [B, T, S, S, 3] from its uploaded videos, one make_train_batch_aug call (`randaug`: the
+        clips' RandAugment ops when AUG.AA_TYPE is set)"""
         from .views import make_train_batch_aug
-        return make_train_batch_aug(videos, self._cfg, params_list=params, dtype=self._dtype, rate=rate)
+        if self._randaug is None:
+            return make_train_batch_aug(videos, self._cfg, params_list=params, dtype=self._dtype, rate=rate)
+        return make_train_batch_aug(videos, self._cfg, params_list=params, dtype=self._dtype, rate=rate, randaug_list=randaug)
 
     def _device_batch(self, items: List[Tuple[List[bytes], int, int]], labels: List[int]):
         """jpeg_decode="device": one batch from parsed records.  Training: the draws of every clip in the host mode's order,
@@ -493,6 +509,7 @@ class InputReader:
         slots: List[torch.Tensor] = []
         videos: List[torch.Tensor] = []
         params: List[dict] = []
+        randaug: List[tuple] = []
         for jpegs, h, w in items:
             f = len(jpegs)
             if self._is_training:
@@ -500,6 +517,9 @@ class InputReader:
                     from .aug import draw_aug_params
                     p = draw_aug_params(cfg, f, h, w, self._rng_aug)
                     start = p.start
+                    if self._randaug is not None:
+                        from .aug import draw_randaug
+                        randaug.append(draw_randaug(self._randaug, h, w, self._rng_ra))
                 else:
                     p = draw_train_params(f, h, w, cfg, self._gen)
                     start = p["start"]
@@ -519,14 +539,14 @@ class InputReader:
             videos.append(v)
         decode_jpeg_batch(frames, self._device, out=slots, on_corrupt="host")
         if self._aug:
-            batch = self._aug_batch(videos, [p._replace(start=0) for p in params], rate=1)
-            return self.process_batch([], labels, batch=batch) + (params,)
+            batch = self._aug_batch(videos, [p._replace(start=0) for p in params], rate=1, randaug=randaug)
+            return self.process_batch([], labels, batch=batch) + (params, randaug)
         if self._is_training:
             clips = [make_train_clip(v, cfg, params=dict(p, start=0), dtype=self._dtype, rate=1)[None]
                      for v, p in zip(videos, params)]
         else:
             clips = [make_eval_views(v, cfg, dtype=self._dtype) for v in videos]
-        return self.process_batch(clips, labels) + (params,)
+        return self.process_batch(clips, labels) + (params, randaug)
 
     def _batches(self, file_pattern: str, batch_size: Optional[int]) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         if self._jpeg_decode == "device":
@@ -542,14 +562,16 @@ class InputReader:
         clips: List[torch.Tensor] = []
         labels: List[int] = []
         self._batch_params: List[dict] = []
+        self._batch_randaug: List[tuple] = []
         bs = batch_size or 1
         for video, label in self._decoded(lambda: self._records(file_pattern, batch_size)):
             clips.append(self._clips(video))
             labels.append(label)
             if len(clips) == bs:
                 params, self._batch_params = self._batch_params, []
-                batch = self._aug_batch(clips, params) if self._aug else None
-                yield self.process_batch(clips, labels, batch=batch) + (params,)
+                randaug, self._batch_randaug = self._batch_randaug, []
+                batch = self._aug_batch(clips, params, randaug=randaug) if self._aug else None
+                yield self.process_batch(clips, labels, batch=batch) + (params, randaug)
                 clips, labels = [], []
         # drop_remainder=True (dataloader.py:186): a trailing partial batch is not emitted
 
@@ -599,9 +621,10 @@ class InputReader:
                 if isinstance(item, BaseException):
                     raise item
                 self.last_params = item[2]      # the draws of THIS batch (the producer thread runs `prefetch` batches ahead)
+                self.last_randaug = item[3]
                 if device_mode:
                     consumer = torch.cuda.current_stream(self._device)
-                    consumer.wait_event(item[3])
+                    consumer.wait_event(item[4])
                     item[0].record_stream(consumer)     # made on the reader's stream: not reused before the consumer is done
                     item[1].record_stream(consumer)
                 yield item[0], item[1]

@@ -138,6 +138,15 @@ AUG_CROP_JITTER, AUG_CROP_RRC, AUG_ERASE_CONST, AUG_ERASE_PIXEL = _consts("AUG_C
 AUG_MEAN_PARTS, AUG_GEOM_COLS, AUG_COLOR_COLS, AUG_C_K = _consts("AUG_MEAN_PARTS", "AUG_GEOM_COLS", "AUG_COLOR_COLS", "AUG_C_K")
 # column -> index of the int32 geometry table of x3d_train_clips_aug: AUG_G["START"] ...
 AUG_G = {n[6:]: v for n, v in _CONSTS.items() if n.startswith("AUG_G_")}
+# RandAugment (x3d_randaug_clips): op name as aug.RandAugOp spells it -> X3D_RA_* code, and the table geometry views.py fills
+RA_OPS = {name: _CONSTS["RA_" + const] for name, const in dict(
+    none="NONE", AutoContrast="AUTOCONTRAST", Equalize="EQUALIZE", Invert="INVERT", Rotate="ROTATE", Posterize="POSTERIZE",
+    Solarize="SOLARIZE", SolarizeAdd="SOLARIZE_ADD", Color="COLOR", Contrast="CONTRAST", Brightness="BRIGHTNESS",
+    Sharpness="SHARPNESS", ShearX="SHEAR_X", ShearY="SHEAR_Y", TranslateXRel="TRANSLATE_X", TranslateYRel="TRANSLATE_Y",
+    copy="COPY").items()}
+RA_CLIP_COLS, RA_OP_COLS, RA_X_COLS, RA_FRAC_BITS = _consts("RA_CLIP_COLS", "RA_OP_COLS", "RA_X_COLS", "RA_FRAC_BITS")
+RA_O_OP, RA_O_IARG, RA_O_FARG, RA_X_A, RA_X_SRC, RA_X_DST = _consts("RA_O_OP", "RA_O_IARG", "RA_O_FARG", "RA_X_A", "RA_X_SRC",
+                                                                    "RA_X_DST")
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = _consts(
     "JPEG_OK", "JPEG_UNSUPPORTED", "JPEG_MALFORMED", "JPEG_CORRUPT", "JPEG_SKIPPED")
 

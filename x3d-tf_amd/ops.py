@@ -625,6 +625,22 @@ def mix_targets(labels, num_classes, lam, eps=0.0, out=None, hard=None):
         hip.call("x3d_mix_targets", None, ptr(labels), ptr(out), ptr(hard), float(lam), float(eps), n, m)
     return out
 
+def randaug_clips(videos, randaug_list, t, rate=1, starts=None, fill=(0, 0, 0)):
+    """RandAugment on uint8 GPU videos [F_i, H_i, W_i, 3] (x3d_randaug_clips; the rules are in include/x3d_hip.h): clip i =
+    frames (starts[i] + j * rate) mod F_i, j < t, through the ops randaug_list[i] (a tuple of aug.RandAugOp, one per layer).
+    Returns one uint8 tensor [t, H_i, W_i, 3] per clip; a clip no layer touches whose video already is its t frames comes
+    back as videos[i] itself."""
+    from . import views
+    videos = list(videos)
+    if not videos:
+        raise ValueError("randaug_clips: empty batch")
+    views._check_videos("randaug_clips", videos)
+    if len(randaug_list) != len(videos):
+        raise ValueError(f"{len(videos)} videos but {len(randaug_list)} op tuples")
+    starts = [0] * len(videos) if starts is None else [int(v) for v in starts]
+    return views.randaug_clips(videos, randaug_list, int(t), int(rate), starts, fill)[0]
+
+
 def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
     _chk(w, v, g, l2_mask)
     hip.call("x3d_sgd_nesterov", ptr(w), ptr(v), ptr(g), ptr(l2_mask), float(lr), float(momentum),
