@@ -52,7 +52,8 @@ extern "C" {
  *   135 x3d_jpeg_parse / x3d_jpeg_decode (JPEG frames decoded on the device);
  *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP);
  *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing);
- *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing). */
+ *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing);
+ *   138 (additions only, no bump) x3d_drop_path_draw / x3d_tail_fwd_dp / x3d_tail_bwd_dp (stochastic depth). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -467,6 +468,22 @@ int x3d_tail_fwd(const void* c_raw, const float* c_scale_shift, const void* shor
  * if r_raw: sums_r [C][2] += (sum g, sum g*r_raw) */
 int x3d_tail_bwd(void* dy_g, const void* y, const void* c_raw, const void* r_raw, double* sums_c,
                  double* sums_r, int N, int C, long long P, int dtype, void* stream);
+/* K9d stochastic depth (drop-path) of the bottleneck branch, per sample: keep[n] is 0 (dropped) or 1 / (1 - rate) (kept).
+ *     y = relu(keep[n] * (s_c*c + t_c) + shortcut); a dropped sample's c_raw is not loaded (y = relu(shortcut)).
+ *     shortcut must not be NULL (the stem's BN + ReLU has no branch to drop). */
+int x3d_tail_fwd_dp(const void* c_raw, const float* c_scale_shift, const void* shortcut,
+                    const float* r_scale_shift /* NULL: identity */, const float* keep /* [N] */, void* y, int N, int C,
+                    long long P, int dtype, void* stream);
+/* g = dy * [y > 0] in place over dy (the shortcut path's gradient); g_branch = keep[n] * g rounded to the storage type (what
+ * the `c` conv backward reads); sums_c [C][2] += (sum g_branch, sum g_branch*c_raw) over g_branch AS STORED; if r_raw:
+ * sums_r [C][2] += (sum g, sum g*r_raw).  A dropped sample: g_branch = 0, c_raw not loaded, nothing added to sums_c. */
+int x3d_tail_bwd_dp(void* dy_g, void* g_branch, const void* y, const void* c_raw, const void* r_raw, const float* keep,
+                    double* sums_c, double* sums_r, int N, int C, long long P, int dtype, void* stream);
+/* The keep table of one step, keep [L][N]: u = (Philox4x32-10(key = (seed_lo, seed_hi), counter = (step_lo, step_hi, l, n))[0]
+ * >> 8) * 2^-24; keep[l][n] = u >= rates[l] ? 1.0f / (1.0f - rates[l]) : 0.  state (device, 4 x uint32: seed_lo, seed_hi,
+ * step_lo, step_hi): the launch reads the 64-bit step, uses that one value for the whole table and stores step + 1 -- so the
+ * same recorded launch draws a new table every step with no host involvement.  One workgroup; L * N <= 65536. */
+int x3d_drop_path_draw(float* keep, const float* rates /* [L], device */, void* state, int L, int N, void* stream);
 /* generic ReLU+BN backward reduce for stem / conv5: z = s*yraw + t.
  *   dy != NULL : g = dy * [z > 0]                (g may alias dy)
  *   dy == NULL : g = dpool[n][c] / P * [z > 0]   (global-average-pool backward, model.py:94,118)

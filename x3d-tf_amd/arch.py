@@ -8,6 +8,8 @@ import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
+from .config import drop_path_settings
+
 
 def round_width(width, multiplier, min_depth=8, divisor=8):
     """Scale a channel count and snap it to a multiple of ``divisor`` (reference utils.py:7-30).
@@ -77,6 +79,7 @@ class Arch:
     weight_decay: float
     num_preds: int               # TEST.NUM_TEMPORAL_VIEWS * TEST.NUM_SPATIAL_CROPS (model.py:25)
     se_ratio: float = 0.0625
+    drop_path_rate: float = 0.0  # NETWORK.DROP_PATH_RATE: stochastic depth of the bottleneck branches (drop_path_rates)
 
     @property
     def blocks(self) -> List[BlockSpec]:
@@ -137,7 +140,18 @@ def build_arch(cfg) -> Arch:
         conv5_out=stages[-1].inner, fc1_out=2048, bn_eps=float(net.BN.EPS),
         bn_momentum=float(net.BN.MOMENTUM), dropout_rate=float(net.DROPOUT_RATE),
         weight_decay=float(net.WEIGHT_DECAY),
-        num_preds=cfg.TEST.NUM_TEMPORAL_VIEWS * cfg.TEST.NUM_SPATIAL_CROPS)
+        num_preds=cfg.TEST.NUM_TEMPORAL_VIEWS * cfg.TEST.NUM_SPATIAL_CROPS,
+        drop_path_rate=drop_path_settings(cfg))
+
+
+def drop_path_rates(arch: Arch) -> List[float]:
+    """Per residual block, in network order: the chance that its bottleneck branch is dropped for a sample of a training
+    step -- linear in depth, rate_l = drop_path_rate * l / (L - 1): the first block is never dropped, the last at the
+    configured rate (a network of one block: that rate)."""
+    n = len(arch.blocks)
+    if n == 1:
+        return [arch.drop_path_rate]
+    return [arch.drop_path_rate * l / (n - 1) for l in range(n)]
 
 
 # --------------------------------------------------------------------------------------

@@ -119,11 +119,15 @@ class CfgNode(dict):
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
-    AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA)."""
+    AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA),
+    NETWORK.DROP_PATH_RATE (stochastic depth)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
         BOTTLENECK_WIDTH_FACTOR=1.0, NUM_CLASSES=400, DROPOUT_RATE=0.0, WEIGHT_DECAY=0.00005,
+        # stochastic depth (PySlowFast's DROPCONNECT_RATE): the chance that the bottleneck branch of the LAST residual block is
+        # dropped for a sample of a training step; linear in depth from 0 at the first block (0 = off)
+        DROP_PATH_RATE=0.0,
         BN=dict(MOMENTUM=0.9, EPS=1e-5)))
     c.DATA = CfgNode(dict(
         FRAME_RATE=1, TEMP_DURATION=1, NUM_INPUT_CHANNELS=3, TRAIN_JITTER_SCALES=[182, 228],
@@ -179,6 +183,7 @@ def get_config(name, overrides=None, freeze=True):
     aug_settings(cfg)
     randaug_settings(cfg)
     solver_settings(cfg)
+    drop_path_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -358,3 +363,11 @@ def solver_settings(cfg) -> SolverSettings:
     if not 0.0 <= decay < 1.0:
         raise ValueError(f"SOLVER.EMA_DECAY must lie in [0, 1), not {decay}")
     return SolverSettings(clip, accum, decay, bool(getattr(sv, "EMA_EVAL", d.ema_eval)))
+
+
+def drop_path_settings(cfg) -> float:
+    """cfg.NETWORK.DROP_PATH_RATE (0.0 for a config tree without the key).  ValueError outside [0, 1) and for NaN."""
+    rate = float(getattr(cfg.NETWORK, "DROP_PATH_RATE", 0.0))
+    if not 0.0 <= rate < 1.0:           # (NaN fails too)
+        raise ValueError(f"NETWORK.DROP_PATH_RATE must lie in [0, 1), not {rate}")
+    return rate

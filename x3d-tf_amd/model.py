@@ -23,7 +23,7 @@ import torch
 
 from . import hip
 from .config import ensemble_method, multi_label
-from .arch import Arch, ParamSpec, block_prefix, build_arch, param_specs, summary_rows
+from .arch import Arch, ParamSpec, block_prefix, build_arch, drop_path_rates, param_specs, summary_rows
 from .params import init_params
 from .plan import PLAN_DEFAULTS, _FakeBuf, _Plan, _experiment_options, record_inference, record_training  # noqa: F401  (PLAN_DEFAULTS, _FakeBuf: re-exported)
 
@@ -149,6 +149,16 @@ class X3D:
         self._build_panels()
         self._build_layers()
         self._dropout_mask_override = None
+        # stochastic depth (NETWORK.DROP_PATH_RATE): per-block rates, and -- only with a rate > 0 -- their fp32 device copy, the
+        # scale 1 / (1 - rate) of a kept sample and the generator state (seed, step) of x3d_drop_path_draw
+        self.drop_path_rates = drop_path_rates(self.arch)
+        self._drop_path_mask_override = None
+        self._dp_rates = self._dp_scale = self._dp_state = None
+        if any(r > 0.0 for r in self.drop_path_rates) and not self.dry:
+            r32 = torch.tensor(self.drop_path_rates, dtype=torch.float32)
+            self._dp_rates = r32.to(self.device)
+            self._dp_scale = (1.0 / (1.0 - r32)).to(self.device)         # fp32 arithmetic, as the draw kernel's
+            self.set_drop_path_state(0)
         self.last_loss = None
         self._stats_r = int(hip.load().x3d_stats_replicas())
 
@@ -418,6 +428,44 @@ class X3D:
         """Fix the dropout keep-mask ([N, 2048] of 0/1) for reproducible parity tests; None = random."""
         self._dropout_mask_override = mask
 
+    def _draw_drop_path(self, pl: _Plan):
+        """The keep table of this replay: one x3d_drop_path_draw launch (it advances the step counter on the device: no host
+        synchronisation, nothing to patch), or the override scaled by 1 / (1 - rate_l) -- then no launch, and no step."""
+        if pl.dp_keep is None:
+            return
+        if self._drop_path_mask_override is not None:
+            mask = self._drop_path_mask_override.to(self.device, torch.float32)
+            if tuple(mask.shape) != tuple(pl.dp_keep.shape):
+                raise ValueError(f"drop-path mask must be [blocks, N] = {tuple(pl.dp_keep.shape)}, got {tuple(mask.shape)}")
+            torch.mul(mask, self._dp_scale.view(-1, 1), out=pl.dp_keep)
+        else:
+            hip.call("x3d_drop_path_draw", pl.dp_keep.data_ptr(), self._dp_rates.data_ptr(), self._dp_state.data_ptr(),
+                     pl.dp_keep.shape[0], pl.n)
+
+    def set_drop_path_mask(self, mask: Optional[torch.Tensor]):
+        """Fix the stochastic-depth keep flags ([blocks, N] of 0/1, every residual block in network order; rows of blocks with
+        rate 0 are ignored) for reproducible parity tests; the model scales them by 1 / (1 - rate_l).  None = drawn on the device."""
+        self._drop_path_mask_override = mask
+
+    def set_drop_path_state(self, seed: int, step: int = 0):
+        """Seed and 64-bit step counter of the stochastic-depth draw: the table of a training replay is a function of (seed,
+        step) alone, and every replay advances the step by one.  Without NETWORK.DROP_PATH_RATE there is no draw: a no-op."""
+        if self._dp_rates is None:
+            return
+        from .ops import drop_path_state
+        st = drop_path_state(seed, step, self.device)
+        if self._dp_state is None:
+            self._dp_state = st
+        else:
+            self._dp_state.copy_(st)
+
+    def drop_path_step(self) -> Optional[int]:
+        """The step the next draw will use (synchronises); None without NETWORK.DROP_PATH_RATE."""
+        if self._dp_state is None:
+            return None
+        from .ops import drop_path_step
+        return drop_path_step(self._dp_state)
+
     def __call__(self, input, training=False):
         return self.call(input, training)
 
@@ -432,6 +480,7 @@ class X3D:
         if training:
             pl.zero_buf.zero_()
             self._draw_dropout(pl)
+            self._draw_drop_path(pl)
             # forward only: stop before the loss kernel (labels unknown); softmax (sigmoid) without labels
             pl.run(pl.fwd, 0, pl.grad_scale_slot)
             self._head_probs_only(pl, n)
@@ -481,6 +530,7 @@ class X3D:
         pl.zero_buf.zero_()
         self.flat_grads.zero_()
         self._draw_dropout(pl)
+        self._draw_drop_path(pl)
         gb = float(global_batch or n)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
         if self.multi_label:

@@ -424,6 +424,52 @@ def tail_bwd(dy_g, y, c_raw, r_raw, sums_c, sums_r):
              y[0, 0].numel(), hip.dtype_code(y.dtype))
 
 
+def tail_fwd_dp(c_raw, c_ss, shortcut, r_ss, keep, y):
+    """tail_fwd with stochastic depth: y = relu(keep[n] * bn_c(c_raw) + shortcut); keep [N] fp32 (x3d_tail_fwd_dp)."""
+    _chk(c_raw, c_ss, shortcut, r_ss, keep, y)
+    n, c = c_raw.shape[:2]
+    if keep.dtype != torch.float32 or keep.numel() != n:
+        raise ValueError(f"tail_fwd_dp: keep must be {n} float32, got {keep.numel()} {keep.dtype}")
+    hip.call("x3d_tail_fwd_dp", ptr(c_raw), ptr(c_ss), ptr(shortcut), ptr(r_ss), ptr(keep), ptr(y), n, c,
+             c_raw[0, 0].numel(), hip.dtype_code(c_raw.dtype))
+    return y
+
+
+def tail_bwd_dp(dy_g, g_branch, y, c_raw, r_raw, keep, sums_c, sums_r):
+    """tail_bwd with stochastic depth: g = dy * [y > 0] in place, g_branch = keep[n] * g (x3d_tail_bwd_dp)."""
+    _chk(dy_g, g_branch, y, c_raw, r_raw, keep, sums_c, sums_r)
+    n, c = y.shape[:2]
+    if keep.dtype != torch.float32 or keep.numel() != n:
+        raise ValueError(f"tail_bwd_dp: keep must be {n} float32, got {keep.numel()} {keep.dtype}")
+    hip.call("x3d_tail_bwd_dp", ptr(dy_g), ptr(g_branch), ptr(y), ptr(c_raw), ptr(r_raw), ptr(keep), ptr(sums_c), ptr(sums_r),
+             n, c, y[0, 0].numel(), hip.dtype_code(y.dtype))
+
+
+def drop_path_state(seed, step=0, device="cuda"):
+    """The device state of x3d_drop_path_draw: int32 [4] holding the uint32 words (seed_lo, seed_hi, step_lo, step_hi)."""
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    words = [seed & 0xFFFFFFFF, seed >> 32, step & 0xFFFFFFFF, step >> 32]
+    return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32, device=device)
+
+
+def drop_path_step(state):
+    """The 64-bit step counter a drop-path state holds (synchronises)."""
+    w = [int(v) & 0xFFFFFFFF for v in state.tolist()]
+    return w[2] | (w[3] << 32)
+
+
+def drop_path_draw(keep, rates, state):
+    """keep [L][N] fp32 <- the table of the step `state` holds; the step advances by one on the device (x3d_drop_path_draw)."""
+    _chk(keep, rates, state)
+    nl, n = keep.shape
+    if keep.dtype != torch.float32 or rates.dtype != torch.float32 or rates.numel() != nl:
+        raise ValueError(f"drop_path_draw: keep [L][N] and rates [L] must be float32, got {keep.dtype} / {rates.numel()} {rates.dtype}")
+    if state.dtype != torch.int32 or state.numel() != 4:
+        raise ValueError("drop_path_draw: state must be the int32 [4] tensor of drop_path_state()")
+    hip.call("x3d_drop_path_draw", ptr(keep), ptr(rates), ptr(state), nl, n)
+    return keep
+
+
 def relu_bn_bwd_reduce(dy, dpool, yraw, ss, g, sums):
     _chk(dy, dpool, yraw, ss, g, sums)
     n, c = yraw.shape[:2]

@@ -129,6 +129,7 @@ class BlockBackward:
     r_bwd_rc: bool = False
     db: Any = None                # Dw3dBwdArgs of the depthwise backward
     nc_sums: Optional[int] = None
+    g_branch: Any = None          # stochastic depth: keep * g, what the `c` backward reads (a view of Backward.gbr); None: g itself
 
 
 @dataclass
@@ -158,6 +159,7 @@ class Block(BlockBackward):
     sc: Any = None
     sr: Any = None
     tail_fwd_folded: bool = False     # the residual tail was built on load by the consumer of y
+    dp_keep: Optional[int] = None     # stochastic depth: address of this block's row [N] of the plan's keep table; None: never dropped
 
 
 @dataclass
@@ -174,6 +176,7 @@ class Backward:
     dv: Any = None
     ga: Any = None
     rtmp: Any = None
+    gbr: Any = None               # stochastic depth: the branch gradient keep * g of the block at hand (absent with the feature off)
     coef_nc: Any = None
     se_scratch: Any = None
     g5: Any = None
@@ -209,6 +212,7 @@ class _Plan:
         self.bn_eval_items: List = []
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
         self._head_hard = self._head_soft = None   # the two loss launches of a single-label training plan (use_soft_targets)
+        self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
 
     # -- allocation ------------------------------------------------------------------------------
     def act(self, *shape):
@@ -544,7 +548,8 @@ def _rec_infer_block(model, pl, B, dt):
 # forward, training ----------------------------------------
 # A residual tail y = relu(bn_c(c_raw) + shortcut) (shortcut raw with its own BatchNorm r_ss, or activated) that no launch
 # has built yet
-_Tail = collections.namedtuple("_Tail", "c_raw c_ss shortcut r_ss y cout p_out")
+# (keep: the block's row of the stochastic-depth table -- such a tail is never folded, x3d_tail_fwd_dp builds it)
+_Tail = collections.namedtuple("_Tail", "c_raw c_ss shortcut r_ss y cout p_out keep", defaults=(None,))
 
 
 def record_training(model, n, t, h, w) -> _Plan:
@@ -572,8 +577,18 @@ def record_training(model, n, t, h, w) -> _Plan:
     # that form exists and does not cost the layer its weights-stationary kernel; otherwise x3d_tail_fwd runs first.
     tail = _Tail(pl.t_raw, pl.bn1.ss, None, None, pl.y0, a.c1, t * h1 * w1)     # the stem's BatchNorm + ReLU (no Add)
     x_cur = pl.y0
-    for b, (hh, ww, ho, wo) in zip(a.blocks, geo):
+    # Stochastic depth (NETWORK.DROP_PATH_RATE): blocks with a rate > 0 scale bn_c's output by keep[l][n] -- 0, or 1 / (1 - rate_l)
+    # -- in their residual tail.  The table [blocks][N] is drawn anew on the device before every replay (x3d_drop_path_draw,
+    # model._draw_drop_path), so the lists themselves never change.  With every rate 0 nothing below differs from before.
+    rates = model.drop_path_rates
+    if any(r > 0.0 for r in rates):
+        pl.dp_keep = pl.f32(len(a.blocks), n)
+        if not model.dry:
+            pl.dp_keep.fill_(1.0)
+    for (l, b), (hh, ww, ho, wo) in zip(enumerate(a.blocks), geo):
         B = Block(b, x_cur, hh, ww, ho, wo)
+        if rates[l] > 0.0:
+            B.dp_keep = pl.dp_keep.data_ptr() + 4 * n * l
         tail = _rec_train_block(model, pl, B, tail, dt)
         pl.blocks.append(B)
         x_cur = B.y
@@ -616,6 +631,11 @@ def _rec_bn_finalize(model, pl, b: BNBuf, count):
 def _fold_pending_tail(model, pl, st, tl: _Tail, dt):
     """st: the x3d_pw_fwd arguments of the conv that reads the pending block output first.  Returns the arguments to record:
     the form that builds the tail on load, or st behind an x3d_tail_fwd launch."""
+    if tl.keep is not None:
+        # a block that may be dropped: the folded prologue does not carry keep (nor, backward, the tail epilogue of x3d_pw_bwd),
+        # so its tail is a pass of its own, which skips the c_raw of the dropped samples
+        pl.rec(pl.fwd, "x3d_tail_fwd_dp", tl.c_raw, tl.c_ss, tl.shortcut, tl.r_ss, tl.keep, tl.y, pl.n, tl.cout, tl.p_out, dt)
+        return st
     ft = hip.PwFwdArgs(_p(tl.c_raw), st.w, st.y, None, _p(tl.c_ss), None, ACT_RELU, st.N, st.Cin, st.Cout, st.T, st.H, st.W,
                        1, st.dtype, st.w_panel, in_add=_p(tl.shortcut), in_add_scale_shift=_p(tl.r_ss), in_store=_p(tl.y))
     # (the fold must not cost a layer its stationary kernel: stages 4 / 5 fold where the weights-stationary kernel carries
@@ -667,11 +687,11 @@ def _rec_train_block(model, pl, B, tail: _Tail, dt) -> _Tail:
     pl.rec(F, "x3d_pw_fwd", B.sc)
     _rec_bn_finalize(model, pl, B.bn_c, n * P_out)
     if not b.has_shortcut_conv:
-        return _Tail(B.c_raw, B.bn_c.ss, B.x, None, B.y, b.cout, P_out)
+        return _Tail(B.c_raw, B.bn_c.ss, B.x, None, B.y, b.cout, P_out, B.dp_keep)
     B.r_raw = pl.act(n, b.cout, t, B.ho, B.wo)
     _rec_shortcut_conv(model, pl, B, dt)
     _rec_bn_finalize(model, pl, B.bn_r, n * P_out)
-    return _Tail(B.c_raw, B.bn_c.ss, B.r_raw, B.bn_r.ss, B.y, b.cout, P_out)
+    return _Tail(B.c_raw, B.bn_c.ss, B.r_raw, B.bn_r.ss, B.y, b.cout, P_out, B.dp_keep)
 
 
 # backward: written out explicitly (the reference relies on Keras autodiff) ----------------------------------------
@@ -705,6 +725,8 @@ def record_backward(model, pl: _Plan, opt: dict) -> Backward:
     out.dv = pl.act(max_inner_out)
     out.ga = pl.act(max_inner_in)
     out.rtmp = pl.act(max_r)
+    max_dp = max([0] + [B.y.numel() for B in pl.blocks if B.dp_keep is not None])
+    out.gbr = pl.act(max_dp) if max_dp else None
     out.coef_nc = pl.f32(max_nc * 4)
     out.se_scratch = pl.f32(max([1] + [n * (2 * B.spec.inner + B.spec.se_width) for B in pl.blocks if B.spec.has_se]))
     out.g5 = pl.act(*pl.c5_raw.shape)
@@ -823,7 +845,14 @@ def _bwd_block(model, pl, s, bi):
     # PRODUCES dy -- the `a`-conv backward of the next block, whose conv input is this block's y -- wherever the fused
     # x3d_pw_bwd covers that layer with its tail epilogue; x3d_tail_bwd remains for the other blocks (and tail_bwd_fold = False)
     R.tail_folded, s.tail_folded = s.tail_folded, False
-    if not R.tail_folded:
+    if B.dp_keep is not None:
+        # stochastic depth: g in place as below (the shortcut path's gradient), and g_branch = keep * g for the `c` backward;
+        # the BN_c sums are taken over g_branch as stored, so bn_c's backward coefficients belong to the tensor `c` reads
+        assert not R.tail_folded
+        R.g_branch = s.out.gbr[:B.y.numel()]
+        pl.rec(Bk, "x3d_tail_bwd_dp", s.dy, R.g_branch, B.y, B.c_raw, B.r_raw, B.dp_keep, pl.acc(B.bn_c.bsums),
+               pl.acc(B.bn_r.bsums) if B.bn_r else None, pl.n, b.cout, pl.t * B.ho * B.wo, s.dt)
+    elif not R.tail_folded:
         # dy -> g = dy*[y>0] in place, with the BN_c (and BN_r) backward sums
         pl.rec(Bk, "x3d_tail_bwd", s.dy, B.y, B.c_raw, B.r_raw, pl.acc(B.bn_c.bsums),
                pl.acc(B.bn_r.bsums) if B.bn_r else None, pl.n, b.cout, pl.t * B.ho * B.wo, s.dt)
@@ -858,7 +887,7 @@ def _bwd_c(model, pl, s, B, R, dvv):
     """The `c` conv: data gradient with the swish backward in its epilogue (into dvv, with the per-(n, c) sums the SE / BN_b
     backward needs) + weight gradient.  Returns the reduce job of its weight-gradient slab, or None."""
     b, p, g, n, t, dt = B.spec, model.params, model.grads, pl.n, pl.t, s.dt
-    q, Bk, gten = f"{block_prefix(b)}/bottleneck", s.out.launches, s.dy
+    q, Bk, gten = f"{block_prefix(b)}/bottleneck", s.out.launches, (s.dy if R.g_branch is None else R.g_branch)
     wc = hip.PwWgradArgs(_p(gten), _p(B.c_raw), _p(B.bn_c.coef), _p(B.b_raw), _p(B.bn_b.ss), _p(B.gate),
                          ACT_SWISH, _p(g[f"{q}/c/kernel"]), n, b.inner, b.cout, t, B.ho, B.wo, 1, dt)
     R.nc_sums = pl.acc64(n, b.inner, 2)
@@ -1003,7 +1032,8 @@ def _bwd_a(model, pl, s, bi, gaa, nxt, rt):
         rc, fa = None, a_bwd_args(use_rc=False)
     fold_tail = opt["fused_pw_bwd"] and opt["tail_bwd_fold"]
     ft = None
-    if fold_tail and prev is not None:   # B.x is prev.y: this launch can apply prev's Add + ReLU backward to its dx
+    # B.x is prev.y: this launch can apply prev's Add + ReLU backward to its dx (not with stochastic depth: x3d_tail_bwd_dp)
+    if fold_tail and prev is not None and prev.dp_keep is None:
         ft = a_bwd_args(_p(prev.c_raw), _p(prev.r_raw))
         if not supported(ft):
             ft = None

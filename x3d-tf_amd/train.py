@@ -90,7 +90,7 @@ class Trainer:
     """
 
     def __init__(self, model, cfg, momentum: Optional[float] = None, sync_moving_stats: bool = True, group=None,
-                 loss_scale="auto", mix_seed: int = 0):
+                 loss_scale="auto", mix_seed: int = 0, drop_path_seed: int = 0):
         self.optimizer = cfg.TRAIN.OPTIMIZER.lower()
         if self.optimizer not in ("sgd", "adam"):   # reference train.py:88-97: SGD(nesterov) / Adam / NotImplementedError
             raise NotImplementedError(f"{cfg.TRAIN.OPTIMIZER} not supported")
@@ -144,6 +144,12 @@ class Trainer:
         self.last_grad_norm = None            # device scalar: global L2 norm of the unscaled gradient of the last update
         # weight EMA: trainable block + moving statistics, laid out as flat_params; starts from the (broadcast) weights
         self.ema = model.flat_params.clone() if self.solver.ema_decay > 0.0 else None
+        # stochastic depth (NETWORK.DROP_PATH_RATE): the tables are drawn on the device from (seed, step); rank r seeds with
+        # drop_path_seed + r, so data-parallel ranks drop different samples.  A no-op for a model without the rate.
+        rank = torch.distributed.get_rank(group) if torch.distributed.is_initialized() else xdist.env_world()[0]
+        self._drop_path_seed = int(drop_path_seed) + rank
+        if hasattr(model, "set_drop_path_state"):
+            model.set_drop_path_state(self._drop_path_seed, 0)
 
     def step(self, clips, labels, lr: Optional[float] = None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
@@ -510,6 +516,10 @@ class Trainer:
             return 0
         self._load(path)
         self.epoch = int(os.path.basename(path).split("-")[1])
+        if hasattr(self.model, "set_drop_path_state"):
+            # the stochastic-depth step counts forward_backward calls: ACCUM_STEPS per optimizer update (`iter`), so a resumed
+            # run goes on with new tables instead of replaying those of step 0
+            self.model.set_drop_path_state(self._drop_path_seed, self.opt_step * self._accum)
         if self.ema is not None:              # the EMA of that epoch (save_checkpoint: <model_dir>/ema/ckpt-<epoch>), if there
             ema_prefix = os.path.join(model_dir, "ema", os.path.basename(path))
             if os.path.exists(ema_prefix + ".index"):
