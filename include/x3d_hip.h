@@ -53,7 +53,8 @@ extern "C" {
  *   136 x3d_sigmoid_bce / x3d_view_max / x3d_multilabel_ap (multi-label head and mAP);
  *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing);
  *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing);
- *   138 (additions only, no bump) x3d_drop_path_draw / x3d_tail_fwd_dp / x3d_tail_bwd_dp (stochastic depth). */
+ *   138 (additions only, no bump) x3d_drop_path_draw / x3d_tail_fwd_dp / x3d_tail_bwd_dp (stochastic depth);
+ *   138 (additions only, no bump) x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb (layer-wise optimizers). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -642,6 +643,63 @@ int x3d_adam_ex(float* w, float* m, float* v, const float* g, const unsigned cha
                 float* ema, float ema_decay, long long n, void* stream);
 int x3d_ema_update(float* ema, const float* w, float decay, const double* norm, long long n, void* stream);
 int x3d_grad_accum(float* acc, const float* g, long long n, int first, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Layer-wise optimizers on the flat buffers: LARS, AdamW, LAMB (TRAIN.OPTIMIZER = lars | adamw | lamb, OPTIM.* of the config,
+ * INTEGRATION.md).  Added under ABI 138 without a version bump: new symbols only.  No floating-point atomics; a fixed number
+ * of launches whatever the number of tensors; nothing allocates or synchronises.
+ *
+ * SEGMENTS AND THE CHUNK TABLE.  A segment t is one trainable tensor of the flat buffers (offset, length); what lies between
+ * segments is padding and is never read or written, in w, the slots or ema.  The walk is driven by two int32 tables in DEVICE
+ * memory, built once on the host (x3d_tf_amd/segments.py):
+ *     chunks [nchunk][3] = (segment, first element, count): X3D_SEG_CHUNK elements at most, inside ONE segment, the chunks of a
+ *                          segment adjacent and ascending; first % 4 == 0 (segment offsets are 16-byte aligned); every element
+ *                          of every segment in exactly one chunk.  Elements are indexed with int: buffers under 2^31 elements.
+ *     segs   [nseg][3]   = (first chunk, number of chunks, l2 flag) -- l2_t = ParamSpec.l2: conv / dense kernels.
+ * One wave takes one chunk: count / 4 vectors of 16 bytes 64 lanes wide (base pointers that are not 16-byte aligned: the same
+ * elements by the same lanes, loaded one by one), then the count % 4 last elements by lanes 0..2.  Sums: a lane adds its
+ * elements in ascending order in fp64, the 64 lanes by a fixed butterfly -> one partial per chunk; a segment's partials are then
+ * added by one wave in a fixed order.  The same inputs give the same bits on every run and on either alignment path.
+ *
+ * x3d_seg_sumsq: out[t] = sum over the segment of (double)a[i]^2.  partials: nchunk doubles of scratch.  Two launches.
+ *
+ * c below = the coefficient of the _ex launches: grad_scale, or with norm grad_scale * min(1, max_norm / (sqrt(norm[0]) *
+ * grad_scale + 1e-6)); norm[1] != 0: EVERY launch of the call writes nothing -- w, the slots, ema and q stay bit for bit.
+ * ||.|| = sqrt of the fp64 segment sum.  q [nseg] fp32 is written to device memory: computed in fp64 from the fp64 sums and
+ * the fp32 arguments, rounded to fp32 once.  g is read-only.  ema / ema_decay as in the _ex launches, written by the last pass.
+ *
+ * x3d_lars (slot v): lambda = 2 * weight_decay, eta = trust_coef
+ *     l2_t and ||w_t|| > 0 and ||g_t|| > 0: q_t = eta ||w_t|| / (c ||g_t|| + lambda ||w_t|| + eps); clip != 0: q_t = min(q_t / lr, 1)
+ *     otherwise q_t = 1
+ *     g' = q_t (c g + [l2_t] lambda w) ; v = mom v - lr g' ; w = w + mom v - lr g'
+ *     roundings: c g | FMA (2 wd) w + . (where l2_t) | . * q_t | then x3d_sgd_nesterov's sequence on g' (lr g', FMA mom v - .,
+ *     FMA mom v' + w, FMA -lr g' + .).  q_t = 1: bit-identical to x3d_sgd_nesterov_ex on the segment (its mask = l2_t).
+ *     Launches: partial sums of w and g (partials: 2 * nchunk doubles), q, apply.
+ * x3d_adamw (slots m, v): x3d_adam_ex's step with the coupled L2 term off, then, where l2_t and decay > 0,
+ *     w = FMA(-(lr * decay), w_old, w_adam) (lr * decay rounded once; w_old = w before the step).  decay = 0: bit-identical to
+ *     x3d_adam_ex with weight_decay = 0 on every segment.  One launch.
+ * x3d_lamb (slots m, v): r = (float)(sqrt(1 - beta2^step) / (1 - beta1^step)) (fp64 on the host)
+ *     m = b1 m + (1 - b1) c g ; v = b2 v + (1 - b2) (c g)^2                     (x3d_adam's expressions and roundings)
+ *     u = r m / (sqrt(v) + eps) + [l2_t] decay w
+ *     l2_t and ||w_t|| > 0 and ||u_t|| > 0: q_t = ||w_t|| / ||u_t||, otherwise q_t = 1 ;  w = w - lr q_t u
+ *     roundings of u: r m | sqrt v | . + eps | the quotient | FMA decay w + . (where l2_t); of w: lr q_t | FMA -(lr q_t) u + w.
+ *     Launches: m, v and the partial sums of w and u (partials: 2 * nchunk doubles); q; apply, which recomputes u from the
+ *     m, v the first pass wrote (u is never stored).
+ * Refused before any launch (X3D_ERR_INVALID): a null required pointer, nchunk <= 0, nseg <= 0, a float pointer that is not
+ * 4-byte or a double pointer that is not 8-byte aligned, trust_coef <= 0, eps < 0 (x3d_lamb: <= 0), decay < 0, any of them not
+ * finite, step < 1, and what the _ex launches refuse of norm / max_norm / ema_decay.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_SEG_CHUNK 1024
+int x3d_seg_sumsq(const float* a, const int* chunks, int nchunk, const int* segs, int nseg, double* partials, double* out,
+                  void* stream);
+int x3d_lars(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg, float lr,
+             float momentum, float weight_decay, float grad_scale, float trust_coef, float eps, int clip, const double* norm,
+             float max_norm, float* ema, float ema_decay, double* partials, float* q, void* stream);
+int x3d_adamw(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg, float lr,
+              float beta1, float beta2, float eps, float decay, float grad_scale, long long step, const double* norm,
+              float max_norm, float* ema, float ema_decay, void* stream);
+int x3d_lamb(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg, float lr,
+             float beta1, float beta2, float eps, float decay, float grad_scale, long long step, const double* norm,
+             float max_norm, float* ema, float ema_decay, double* partials, float* q, void* stream);
 /* LossScaleOptimizer support (Keras mixed_float16, train.py:99-100): *flag (device int the caller set to 1) is cleared
  * when any of the n values is inf / nan -- the step is then skipped and the loss scale halved. */
 int x3d_all_finite(const float* g, long long n, int* flag, void* stream);

@@ -120,7 +120,7 @@ def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA),
-    NETWORK.DROP_PATH_RATE (stochastic depth)."""
+    NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -159,6 +159,10 @@ def get_default_config():
     # L2 norm of the unscaled, all-reduced gradient (0 = off), micro-batches per optimizer update, the decay of the weight EMA
     # (0 = off) and whether fit's validation runs on the EMA weights
     c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True))
+    # the layer-wise optimizers (TRAIN.OPTIMIZER = lars | adamw | lamb; inert for sgd / adam).  LARS (PySlowFast's SOLVER.LARS_ON):
+    # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
+    # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
+    c.OPTIM = CfgNode(dict(LARS_TRUST_COEF=0.001, LARS_EPS=1e-8, LARS_CLIP=False, WEIGHT_DECAY=0.0, LAMB_EPS=1e-6))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -183,6 +187,7 @@ def get_config(name, overrides=None, freeze=True):
     aug_settings(cfg)
     randaug_settings(cfg)
     solver_settings(cfg)
+    optim_settings(cfg)
     drop_path_settings(cfg)
     if freeze:
         cfg.freeze()
@@ -363,6 +368,36 @@ def solver_settings(cfg) -> SolverSettings:
     if not 0.0 <= decay < 1.0:
         raise ValueError(f"SOLVER.EMA_DECAY must lie in [0, 1), not {decay}")
     return SolverSettings(clip, accum, decay, bool(getattr(sv, "EMA_EVAL", d.ema_eval)))
+
+
+OptimSettings = collections.namedtuple("OptimSettings", "lars_trust_coef lars_eps lars_clip weight_decay lamb_eps")
+_OPTIM_DEFAULTS = OptimSettings(0.001, 1e-8, False, 0.0, 1e-6)
+OPTIMIZERS = ("sgd", "adam", "lars", "adamw", "lamb")       # TRAIN.OPTIMIZER, case-insensitive
+SLOT_KIND = dict(sgd="sgd", lars="sgd", adam="adam", adamw="adam", lamb="adam")   # whose slot / checkpoint layout a branch uses
+
+
+def optim_settings(cfg) -> OptimSettings:
+    """cfg.OPTIM.* as one tuple (a config tree without the section: the defaults).  ValueError for a LARS_TRUST_COEF that is
+    not positive and finite, a negative LARS_EPS, a WEIGHT_DECAY that is negative or not finite, a LAMB_EPS that is not
+    positive (NaN fails all of them)."""
+    import math
+    ov = getattr(cfg, "OPTIM", None)
+    d = _OPTIM_DEFAULTS
+    if ov is None:
+        return d
+    eta = float(getattr(ov, "LARS_TRUST_COEF", d.lars_trust_coef))
+    if not (eta > 0.0 and math.isfinite(eta)):
+        raise ValueError(f"OPTIM.LARS_TRUST_COEF must be positive and finite, not {eta}")
+    eps = float(getattr(ov, "LARS_EPS", d.lars_eps))
+    if not (eps >= 0.0 and math.isfinite(eps)):
+        raise ValueError(f"OPTIM.LARS_EPS must be finite and >= 0, not {eps}")
+    decay = float(getattr(ov, "WEIGHT_DECAY", d.weight_decay))
+    if not (decay >= 0.0 and math.isfinite(decay)):
+        raise ValueError(f"OPTIM.WEIGHT_DECAY must be finite and >= 0, not {decay}")
+    lamb_eps = float(getattr(ov, "LAMB_EPS", d.lamb_eps))
+    if not (lamb_eps > 0.0 and math.isfinite(lamb_eps)):
+        raise ValueError(f"OPTIM.LAMB_EPS must be positive and finite, not {lamb_eps}")
+    return OptimSettings(eta, eps, bool(getattr(ov, "LARS_CLIP", d.lars_clip)), decay, lamb_eps)
 
 
 def drop_path_settings(cfg) -> float:

@@ -8,6 +8,8 @@
 //   x3d_adam(_ex)           x3d_grad_sumsq left in device memory and writes the weight EMA in the same pass.
 //   x3d_ema_update          the same EMA rule for buffers the optimizer does not own (BatchNorm moving statistics)
 //   x3d_grad_accum          acc = g / acc += g
+//   x3d_seg_sumsq           per-tensor sums of squares and the layer-wise optimizers built on them (LARS, AdamW, LAMB): a chunk
+//   x3d_lars / _adamw / _lamb   table instead of one flat range, a fixed number of launches (at the end of this file)
 //
 // Shape.  Plain streaming kernels: a thread moves 16 bytes per array and iteration, the grid is capped at SOLVER_MAX_BLOCKS
 // workgroups and strides over the rest.  The vector kernels need every array 16-byte aligned (the l2 mask 4-byte); the n % 4
@@ -15,7 +17,8 @@
 // instantiation of the same kernel.  The plain entry points keep their one-element-per-thread launch: their results and
 // their speed are what they were.
 //
-// The update arithmetic exists once: sgd_nesterov_step / adam_step below, called by the old and the new kernels.
+// The update arithmetic exists once: sgd_nesterov_step / adam_step below, called by the old and the new kernels; the layer-wise
+// rules (lars_step, adamw_step, lamb_moments / lamb_u) are built on them.
 #include "common.h"
 
 #define SOLVER_BLOCK 256
@@ -450,5 +453,459 @@ extern "C" int x3d_grad_accum(float* acc, const float* g, long long n, int first
     else hipLaunchKernelGGL((grad_accum_kernel<1, false>), grid, dim3(SOLVER_BLOCK), 0, st, acc, g, n);
   }
   X3D_LAUNCH_CHECK("grad_accum");
+  return X3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// layer-wise optimizers: x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb
+// ------------------------------------------------------------------------------------------------
+// Driven by the chunk table (include/x3d_hip.h): chunks [nchunk][3] = (segment, first element, count), segs [nseg][3] =
+// (first chunk, chunks, l2).  ONE WAVE takes one chunk, the waves of the grid stride over the table: no workgroup barrier, no
+// LDS, a tensor of 24 floats costs one wave and not a workgroup.  Lane l takes the vectors l, l + 64, ... of the chunk (16
+// bytes each; SEG_CHUNK = 1024 elements = 4 per lane, all in flight), lanes 0..2 then the count % 4 last elements.  The
+// element -> lane map and the order a lane adds in do not depend on the alignment path (AL = false loads the same four floats
+// one by one), so the sums have the same bits on both.  Padding is in no chunk: it is never touched.
+#define SEG_CHUNK X3D_SEG_CHUNK
+#define SEG_WAVES (SOLVER_BLOCK / 64)
+static_assert(SEG_CHUNK % 4 == 0, "a chunk is whole vectors unless its segment ends");
+
+static inline unsigned seg_grid(int nchunk) {
+  long long b = ceil_div_ll(nchunk, SEG_WAVES);
+  if (b > SOLVER_MAX_BLOCKS) b = SOLVER_MAX_BLOCKS;
+  return (unsigned)(b < 1 ? 1 : b);
+}
+static inline bool seg_aligned(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr, const void* p3 = nullptr,
+                               const void* p4 = nullptr) {
+  return solver_vec(nullptr, p0, p1, p2, p3, p4) == 4;
+}
+
+template <bool AL> __device__ __forceinline__ void seg_load4(const float* p, float (&o)[4]) {
+  if constexpr (AL) VecIO<float, 4>::load(p, o);
+  else {
+#pragma unroll
+    for (int e = 0; e < 4; e++) o[e] = p[e];
+  }
+}
+template <bool AL> __device__ __forceinline__ void seg_store4(float* p, const float (&o)[4]) {
+  if constexpr (AL) VecIO<float, 4>::store(p, o);
+  else {
+#pragma unroll
+    for (int e = 0; e < 4; e++) p[e] = o[e];
+  }
+}
+
+// the chunk of this wave's turn `ch` (wave-uniform: kept in scalar registers)
+__device__ __forceinline__ void seg_chunk(const int* __restrict__ chunks, int ch, int& seg, int& first, int& cnt) {
+  seg = __builtin_amdgcn_readfirstlane(chunks[3 * ch]);
+  first = __builtin_amdgcn_readfirstlane(chunks[3 * ch + 1]);
+  cnt = __builtin_amdgcn_readfirstlane(chunks[3 * ch + 2]);
+}
+#define SEG_FOR_CHUNKS(ch)                                                                                           \
+  const int lane = threadIdx.x & 63;                                                                                 \
+  for (int ch = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6); ch < nchunk; ch += gridDim.x * SEG_WAVES)
+
+__device__ __forceinline__ void sq_add(float x, double& s) {
+  const double d = (double)x;
+  s += d * d;
+}
+
+// ---- the one definition of the per-element arithmetic (contraction off: every rounding is written out) ----
+// LARS: g' = q (c g + [l2] 2 wd w), then the Nesterov step of x3d_sgd_nesterov on g' (q = 1: that step's bits)
+__device__ __forceinline__ void lars_step(float& w, float& v, float g, bool l2, float q, float lr, float mom, float wd, float c) {
+#pragma clang fp contract(off)
+  float gi = g * c;
+  if (l2) gi = __builtin_fmaf(wd + wd, w, gi);
+  gi = gi * q;
+  sgd_nesterov_step(w, v, gi, false, lr, mom, 0.f, 1.f);
+}
+// AdamW: adam_step without the coupled L2 term, then the decoupled decay of the weight the step started from (ld = lr * decay)
+__device__ __forceinline__ void adamw_step(float& w, float& m, float& v, float g, bool l2, float lr_t, float b1, float b2,
+                                           float eps, float ld, float c) {
+#pragma clang fp contract(off)
+  const float w0 = w;
+  adam_step(w, m, v, g, false, lr_t, b1, b2, eps, 0.f, c);
+  if (l2 && ld > 0.f) w = __builtin_fmaf(-ld, w0, w);
+}
+// LAMB: the moments as adam_step forms them (L2 off), and u = r m / (sqrt(v) + eps) + [l2] decay w
+__device__ __forceinline__ void lamb_moments(float& m, float& v, float g, float b1, float b2, float c) {
+#pragma clang fp contract(off)
+  const float gi = g * c;
+  const float mi = __builtin_fmaf(1.f - b1, gi, b1 * m);
+  const float vi = __builtin_fmaf(gi, (1.f - b2) * gi, b2 * v);
+  m = mi;
+  v = vi;
+}
+__device__ __forceinline__ float lamb_u(float w, float m, float v, bool l2, float r, float eps, float decay) {
+#pragma clang fp contract(off)
+  float u = (r * m) / (sqrtf(v) + eps);
+  if (l2) u = __builtin_fmaf(decay, w, u);
+  return u;
+}
+__device__ __forceinline__ float lamb_apply(float w, float u, float lq) { return __builtin_fmaf(-lq, u, w); }
+
+// ---- partial sums: partials[ch] (and partials[nchunk + ch]) of chunk ch ----
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __restrict__ a, const int* __restrict__ chunks,
+                                                                 int nchunk, double* __restrict__ partials) {
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const int nv = cnt >> 2, rem = cnt & 3;
+    double s = 0.0;
+    for (int i = lane; i < nv; i += 64) {
+      float x[4];
+      seg_load4<AL>(a + first + 4 * i, x);
+#pragma unroll
+      for (int e = 0; e < 4; e++) sq_add(x[e], s);
+    }
+    if (lane < rem) sq_add(a[first + 4 * nv + lane], s);
+    s = wave_sum_d(s);
+    if (lane == 0) partials[ch] = s;
+  }
+}
+
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void lars_sums_kernel(const float* __restrict__ w, const float* __restrict__ g,
+                                                                 const int* __restrict__ chunks, int nchunk,
+                                                                 const double* __restrict__ norm, double* __restrict__ partials) {
+  if (norm && norm[1] != 0.0) return;
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const int nv = cnt >> 2, rem = cnt & 3;
+    double sw = 0.0, sg = 0.0;
+    for (int i = lane; i < nv; i += 64) {
+      float x[4], y[4];
+      seg_load4<AL>(w + first + 4 * i, x);
+      seg_load4<AL>(g + first + 4 * i, y);
+#pragma unroll
+      for (int e = 0; e < 4; e++) { sq_add(x[e], sw); sq_add(y[e], sg); }
+    }
+    if (lane < rem) { sq_add(w[first + 4 * nv + lane], sw); sq_add(g[first + 4 * nv + lane], sg); }
+    sw = wave_sum_d(sw);
+    sg = wave_sum_d(sg);
+    if (lane == 0) { partials[ch] = sw; partials[nchunk + ch] = sg; }
+  }
+}
+
+// LAMB's first pass: m, v are updated and stored; partial sums of w (not yet updated) and of u
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m,
+                                                                    float* __restrict__ v, const float* __restrict__ g,
+                                                                    const int* __restrict__ chunks, int nchunk,
+                                                                    const int* __restrict__ segs, float r, float b1, float b2,
+                                                                    float eps, float decay, float gscale,
+                                                                    const double* __restrict__ norm, float max_norm,
+                                                                    double* __restrict__ partials) {
+  float c;
+  if (!solver_coef(norm, gscale, max_norm, c)) return;
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
+    const int nv = cnt >> 2, rem = cnt & 3;
+    double sw = 0.0, su = 0.0;
+    for (int i = lane; i < nv; i += 64) {
+      const int at = first + 4 * i;
+      float wi[4], mi[4], vi[4], gi[4];
+      seg_load4<AL>(w + at, wi);
+      seg_load4<AL>(m + at, mi);
+      seg_load4<AL>(v + at, vi);
+      seg_load4<AL>(g + at, gi);
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        lamb_moments(mi[e], vi[e], gi[e], b1, b2, c);
+        sq_add(wi[e], sw);
+        sq_add(lamb_u(wi[e], mi[e], vi[e], l2, r, eps, decay), su);
+      }
+      seg_store4<AL>(m + at, mi);
+      seg_store4<AL>(v + at, vi);
+    }
+    if (lane < rem) {
+      const int at = first + 4 * nv + lane;
+      float mi = m[at], vi = v[at];
+      const float wi = w[at];
+      lamb_moments(mi, vi, g[at], b1, b2, c);
+      sq_add(wi, sw);
+      sq_add(lamb_u(wi, mi, vi, l2, r, eps, decay), su);
+      m[at] = mi;
+      v[at] = vi;
+    }
+    sw = wave_sum_d(sw);
+    su = wave_sum_d(su);
+    if (lane == 0) { partials[ch] = sw; partials[nchunk + ch] = su; }
+  }
+}
+
+// ---- per segment: one wave adds the segment's partials -- lane l those of chunks l, l + 64, ... in ascending order, the
+// lanes by the butterfly -- and lane 0 writes the sum (SEG_SUM) or q (SEG_LARS / SEG_LAMB: fp64, rounded once) ----
+enum { SEG_SUM = 0, SEG_LARS = 1, SEG_LAMB = 2 };
+template <int MODE>
+__global__ __launch_bounds__(SOLVER_BLOCK) void seg_final_kernel(const double* __restrict__ partials, int nchunk,
+                                                                 const int* __restrict__ segs, int nseg, float lr, float wd,
+                                                                 float gscale, float eta, float eps, int clip,
+                                                                 const double* __restrict__ norm, float max_norm,
+                                                                 double* __restrict__ out, float* __restrict__ q) {
+  float c = gscale;
+  if constexpr (MODE != SEG_SUM) {
+    if (!solver_coef(norm, gscale, max_norm, c)) return;
+  }
+  const int lane = threadIdx.x & 63;
+  const int seg = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const int c0 = segs[3 * seg], nc = segs[3 * seg + 1];
+  const bool l2 = segs[3 * seg + 2] != 0;
+  double s0 = 0.0, s1 = 0.0;
+  for (int k = lane; k < nc; k += 64) {
+    s0 += partials[c0 + k];
+    if constexpr (MODE != SEG_SUM) s1 += partials[nchunk + c0 + k];
+  }
+  s0 = wave_sum_d(s0);
+  if constexpr (MODE != SEG_SUM) s1 = wave_sum_d(s1);
+  if (lane != 0) return;
+  if constexpr (MODE == SEG_SUM) {
+    out[seg] = s0;
+  } else {
+    double t = 1.0;
+    if (l2 && s0 > 0.0 && s1 > 0.0) {
+      const double nw = sqrt(s0), nx = sqrt(s1);
+      if constexpr (MODE == SEG_LARS) {
+        t = (double)eta * nw / ((double)c * nx + 2.0 * (double)wd * nw + (double)eps);
+        if (clip) t = fmin(t / (double)lr, 1.0);
+      } else {
+        t = nw / nx;
+      }
+    }
+    q[seg] = (float)t;
+  }
+}
+
+// ---- apply passes ----
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restrict__ w, float* __restrict__ v,
+                                                                  const float* __restrict__ g, const int* __restrict__ chunks,
+                                                                  int nchunk, const int* __restrict__ segs,
+                                                                  const float* __restrict__ q, float lr, float mom, float wd,
+                                                                  float gscale, const double* __restrict__ norm, float max_norm,
+                                                                  float* __restrict__ ema, float omd) {
+  float c;
+  if (!solver_coef(norm, gscale, max_norm, c)) return;
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
+    const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
+    const int nv = cnt >> 2, rem = cnt & 3;
+    for (int i = lane; i < nv; i += 64) {
+      const int at = first + 4 * i;
+      float wi[4], vi[4], gi[4], ei[4];
+      seg_load4<AL>(w + at, wi);
+      seg_load4<AL>(v + at, vi);
+      seg_load4<AL>(g + at, gi);
+      if (ema) seg_load4<AL>(ema + at, ei);
+#pragma unroll
+      for (int e = 0; e < 4; e++) lars_step(wi[e], vi[e], gi[e], l2, qt, lr, mom, wd, c);
+      seg_store4<AL>(v + at, vi);
+      seg_store4<AL>(w + at, wi);
+      if (ema) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
+        seg_store4<AL>(ema + at, ei);
+      }
+    }
+    if (lane < rem) {
+      const int at = first + 4 * nv + lane;
+      float wi = w[at], vi = v[at];
+      lars_step(wi, vi, g[at], l2, qt, lr, mom, wd, c);
+      v[at] = vi;
+      w[at] = wi;
+      if (ema) ema[at] = ema_step(ema[at], wi, omd);
+    }
+  }
+}
+
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                                             const float* __restrict__ g, const int* __restrict__ chunks,
+                                                             int nchunk, const int* __restrict__ segs, float lr_t, float b1,
+                                                             float b2, float eps, float ld, float gscale,
+                                                             const double* __restrict__ norm, float max_norm,
+                                                             float* __restrict__ ema, float omd) {
+  float c;
+  if (!solver_coef(norm, gscale, max_norm, c)) return;
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
+    const int nv = cnt >> 2, rem = cnt & 3;
+    for (int i = lane; i < nv; i += 64) {
+      const int at = first + 4 * i;
+      float wi[4], mi[4], vi[4], gi[4], ei[4];
+      seg_load4<AL>(w + at, wi);
+      seg_load4<AL>(m + at, mi);
+      seg_load4<AL>(v + at, vi);
+      seg_load4<AL>(g + at, gi);
+      if (ema) seg_load4<AL>(ema + at, ei);
+#pragma unroll
+      for (int e = 0; e < 4; e++) adamw_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, ld, c);
+      seg_store4<AL>(m + at, mi);
+      seg_store4<AL>(v + at, vi);
+      seg_store4<AL>(w + at, wi);
+      if (ema) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
+        seg_store4<AL>(ema + at, ei);
+      }
+    }
+    if (lane < rem) {
+      const int at = first + 4 * nv + lane;
+      float wi = w[at], mi = m[at], vi = v[at];
+      adamw_step(wi, mi, vi, g[at], l2, lr_t, b1, b2, eps, ld, c);
+      m[at] = mi;
+      v[at] = vi;
+      w[at] = wi;
+      if (ema) ema[at] = ema_step(ema[at], wi, omd);
+    }
+  }
+}
+
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m,
+                                                                  const float* __restrict__ v, const int* __restrict__ chunks,
+                                                                  int nchunk, const int* __restrict__ segs,
+                                                                  const float* __restrict__ q, float lr, float r, float eps,
+                                                                  float decay, const double* __restrict__ norm,
+                                                                  float* __restrict__ ema, float omd) {
+  if (norm && norm[1] != 0.0) return;
+  SEG_FOR_CHUNKS(ch) {
+    int seg, first, cnt;
+    seg_chunk(chunks, ch, seg, first, cnt);
+    const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
+    const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
+    const float lq = lr * qt;
+    const int nv = cnt >> 2, rem = cnt & 3;
+    for (int i = lane; i < nv; i += 64) {
+      const int at = first + 4 * i;
+      float wi[4], mi[4], vi[4], ei[4];
+      seg_load4<AL>(w + at, wi);
+      seg_load4<AL>(m + at, mi);
+      seg_load4<AL>(v + at, vi);
+      if (ema) seg_load4<AL>(ema + at, ei);
+#pragma unroll
+      for (int e = 0; e < 4; e++) wi[e] = lamb_apply(wi[e], lamb_u(wi[e], mi[e], vi[e], l2, r, eps, decay), lq);
+      seg_store4<AL>(w + at, wi);
+      if (ema) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
+        seg_store4<AL>(ema + at, ei);
+      }
+    }
+    if (lane < rem) {
+      const int at = first + 4 * nv + lane;
+      const float wi = lamb_apply(w[at], lamb_u(w[at], m[at], v[at], l2, r, eps, decay), lq);
+      w[at] = wi;
+      if (ema) ema[at] = ema_step(ema[at], wi, omd);
+    }
+  }
+}
+
+// ---- entry points ----
+#define SEG_REQUIRE_TABLE(name)                                                                                               \
+  X3D_REQUIRE(chunks && segs && nchunk > 0 && nseg > 0 && nseg <= nchunk, name ": bad chunk table (null, or nseg / nchunk <= 0)"); \
+  X3D_REQUIRE((((uintptr_t)chunks | (uintptr_t)segs) & 3) == 0, name ": misaligned table")
+static inline bool seg_finite_ge0(float x) { return x >= 0.f && x <= 3.0e38f; }
+
+extern "C" int x3d_seg_sumsq(const float* a, const int* chunks, int nchunk, const int* segs, int nseg, double* partials,
+                             double* out, void* stream) {
+  X3D_REQUIRE(a && partials && out, "seg_sumsq: bad args");
+  SEG_REQUIRE_TABLE("seg_sumsq");
+  X3D_REQUIRE(((uintptr_t)a & 3) == 0 && (((uintptr_t)partials | (uintptr_t)out) & 7) == 0, "seg_sumsq: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
+  if (seg_aligned(a)) hipLaunchKernelGGL((seg_sumsq_kernel<true>), grid, block, 0, st, a, chunks, nchunk, partials);
+  else hipLaunchKernelGGL((seg_sumsq_kernel<false>), grid, block, 0, st, a, chunks, nchunk, partials);
+  hipLaunchKernelGGL((seg_final_kernel<SEG_SUM>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
+                     (const double*)partials, nchunk, segs, nseg, 0.f, 0.f, 1.f, 0.f, 0.f, 0, (const double*)nullptr, 0.f, out,
+                     (float*)nullptr);
+  X3D_LAUNCH_CHECK("seg_sumsq");
+  return X3D_OK;
+}
+
+extern "C" int x3d_lars(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg, float lr,
+                        float momentum, float weight_decay, float grad_scale, float trust_coef, float eps, int clip,
+                        const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
+                        void* stream) {
+  X3D_REQUIRE(w && v && g && partials && q, "lars: bad args");
+  SEG_REQUIRE_TABLE("lars");
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
+              ((uintptr_t)partials & 7) == 0, "lars: misaligned pointer");
+  X3D_REQUIRE(trust_coef > 0.f && trust_coef <= 3.0e38f, "lars: trust_coef must be positive and finite");
+  X3D_REQUIRE(seg_finite_ge0(eps) && seg_finite_ge0(weight_decay), "lars: eps and weight_decay must be >= 0 and finite");
+  X3D_REQUIRE(!clip || lr > 0.f, "lars: clip needs lr > 0");
+  SOLVER_REQUIRE_EXTRAS("lars");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
+  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
+  const bool al = seg_aligned(w, v, g, ema);
+  if (al) hipLaunchKernelGGL((lars_sums_kernel<true>), grid, block, 0, st, (const float*)w, g, chunks, nchunk, norm, partials);
+  else hipLaunchKernelGGL((lars_sums_kernel<false>), grid, block, 0, st, (const float*)w, g, chunks, nchunk, norm, partials);
+  hipLaunchKernelGGL((seg_final_kernel<SEG_LARS>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
+                     (const double*)partials, nchunk, segs, nseg, lr, weight_decay, grad_scale, trust_coef, eps, clip, norm, nm,
+                     (double*)nullptr, q);
+#define ARGS w, v, g, chunks, nchunk, segs, (const float*)q, lr, momentum, weight_decay, grad_scale, norm, nm, ema, omd
+  if (al) hipLaunchKernelGGL((lars_apply_kernel<true>), grid, block, 0, st, ARGS);
+  else hipLaunchKernelGGL((lars_apply_kernel<false>), grid, block, 0, st, ARGS);
+#undef ARGS
+  X3D_LAUNCH_CHECK("lars");
+  return X3D_OK;
+}
+
+extern "C" int x3d_adamw(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                         float lr, float beta1, float beta2, float eps, float decay, float grad_scale, long long step,
+                         const double* norm, float max_norm, float* ema, float ema_decay, void* stream) {
+  X3D_REQUIRE(w && m && v && g && step >= 1, "adamw: bad args (step counts from 1)");
+  SEG_REQUIRE_TABLE("adamw");
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "adamw: misaligned pointer");
+  X3D_REQUIRE(seg_finite_ge0(decay), "adamw: decay must be >= 0 and finite");
+  SOLVER_REQUIRE_EXTRAS("adamw");
+  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
+  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
+  const float lr_t = (float)adam_lr_t(lr, beta1, beta2, step);
+  const float ld = lr * decay;
+#define ARGS w, m, v, g, chunks, nchunk, segs, lr_t, beta1, beta2, eps, ld, grad_scale, norm, nm, ema, omd
+  if (seg_aligned(w, m, v, g, ema)) hipLaunchKernelGGL((adamw_kernel<true>), grid, block, 0, (hipStream_t)stream, ARGS);
+  else hipLaunchKernelGGL((adamw_kernel<false>), grid, block, 0, (hipStream_t)stream, ARGS);
+#undef ARGS
+  X3D_LAUNCH_CHECK("adamw");
+  return X3D_OK;
+}
+
+extern "C" int x3d_lamb(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                        float lr, float beta1, float beta2, float eps, float decay, float grad_scale, long long step,
+                        const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
+                        void* stream) {
+  X3D_REQUIRE(w && m && v && g && partials && q && step >= 1, "lamb: bad args (step counts from 1)");
+  SEG_REQUIRE_TABLE("lamb");
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
+              ((uintptr_t)partials & 7) == 0, "lamb: misaligned pointer");
+  X3D_REQUIRE(eps > 0.f && eps <= 3.0e38f, "lamb: eps must be positive and finite");
+  X3D_REQUIRE(seg_finite_ge0(decay), "lamb: decay must be >= 0 and finite");
+  SOLVER_REQUIRE_EXTRAS("lamb");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
+  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
+  const float r = (float)adam_lr_t(1.f, beta1, beta2, step);
+  const bool al = seg_aligned(w, m, v, g, ema);
+#define ARGS (const float*)w, m, v, g, chunks, nchunk, segs, r, beta1, beta2, eps, decay, grad_scale, norm, nm, partials
+  if (al) hipLaunchKernelGGL((lamb_moments_kernel<true>), grid, block, 0, st, ARGS);
+  else hipLaunchKernelGGL((lamb_moments_kernel<false>), grid, block, 0, st, ARGS);
+#undef ARGS
+  hipLaunchKernelGGL((seg_final_kernel<SEG_LAMB>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
+                     (const double*)partials, nchunk, segs, nseg, lr, 0.f, grad_scale, 0.f, 0.f, 0, norm, nm, (double*)nullptr, q);
+#define ARGS w, (const float*)m, (const float*)v, chunks, nchunk, segs, (const float*)q, lr, r, eps, decay, norm, ema, omd
+  if (al) hipLaunchKernelGGL((lamb_apply_kernel<true>), grid, block, 0, st, ARGS);
+  else hipLaunchKernelGGL((lamb_apply_kernel<false>), grid, block, 0, st, ARGS);
+#undef ARGS
+  X3D_LAUNCH_CHECK("lamb");
   return X3D_OK;
 }

@@ -205,6 +205,11 @@ class X3D:
         self.param_order = [s.name for s in order]
         self.n_params = sum(numel(s) for s in order)
         self.n_trainable = sum(numel(s) for s in order if s.trainable)
+        # the trainable tensors as segments of the flat buffers, in param_order: what the layer-wise optimizers (lars, adamw,
+        # lamb) walk.  Their chunk table goes to the device with the first use (`seg_table`), once.
+        from .segments import Segment
+        self.segments = [Segment(s.name, self._offsets[s.name], numel(s), bool(s.l2)) for s in order if s.trainable]
+        self._seg_table = None
 
     def _build_panels(self):
         """bf16 LDS-image panels of every pointwise-conv weight (x3d_pw_pack_weights): refreshed by one launch
@@ -639,6 +644,58 @@ class X3D:
                  self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
                  float(self.arch.weight_decay), float(grad_scale), int(step), pn, float(max_norm), pe, float(ema_decay),
                  self.n_trainable_flat)
+
+    # -- the layer-wise optimizers: a fixed number of launches over the chunk table, per-tensor trust ratios on the device --
+    @property
+    def seg_table(self):
+        """segments.SegTable of `self.segments`, on the model's device (built and copied once)."""
+        if self._seg_table is None:
+            from .segments import SegTable
+            self._seg_table = SegTable(self.segments).to(self.device)
+            self._seg_partials = torch.empty(2 * self._seg_table.nchunk, dtype=torch.float64, device=self.device)
+            self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
+        return self._seg_table
+
+    def _adam_slots(self):
+        self._claim_slots("adam")
+        if getattr(self, "flat_second", None) is None:
+            self.flat_second = torch.zeros_like(self.flat_velocity)
+
+    def apply_lars(self, lr, momentum=0.9, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None, max_norm=0.0,
+                   ema=None, ema_decay=0.0):
+        """LARS: SGD(momentum, nesterov=True) + L2 with the update of every conv / dense kernel scaled by its trust ratio
+        q_t = trust_coef ||w_t|| / (c ||g_t|| + 2 wd ||w_t|| + eps) (clip: min(q_t / lr, 1)); BatchNorm and bias tensors take
+        q_t = 1 (x3d_lars, the rule is in include/x3d_hip.h).  Slot and checkpoint layout: SGD's.  Three launches, no
+        synchronisation.  norm / max_norm / ema / ema_decay: as apply_sgd.  Returns the device [nseg] fp32 trust ratios (in
+        `segments` order), overwritten by the next call."""
+        from . import ops
+        self._claim_slots("sgd")
+        tb = self.seg_table
+        self._solver_extras(norm, max_norm, ema)
+        return ops.lars(self.flat_params, self.flat_velocity, self.flat_grads, tb, lr, momentum, self.arch.weight_decay,
+                        trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
+
+    def apply_adamw(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+                    ema=None, ema_decay=0.0):
+        """Adam with DECOUPLED weight decay: apply_adam's step without the coupled L2 term (NETWORK.WEIGHT_DECAY plays no part),
+        then w -= lr * decay * w_old on the conv / dense kernels (x3d_adamw).  Slots and checkpoint layout: Adam's.  One launch."""
+        from . import ops
+        self._adam_slots()
+        self._solver_extras(norm, max_norm, ema)
+        ops.adamw(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self.seg_table, lr, step, beta1,
+                  beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
+
+    def apply_lamb(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+                   ema=None, ema_decay=0.0):
+        """LAMB: Adam's moments, u = r_k m / (sqrt(v) + eps) + decay w, and w -= lr q_t u with q_t = ||w_t|| / ||u_t|| on the conv
+        / dense kernels, 1 elsewhere (x3d_lamb).  NETWORK.WEIGHT_DECAY plays no part.  Slots and checkpoint layout: Adam's.
+        Three launches, no synchronisation.  Returns the device [nseg] fp32 trust ratios, overwritten by the next call."""
+        from . import ops
+        self._adam_slots()
+        tb = self.seg_table
+        self._solver_extras(norm, max_norm, ema)
+        return ops.lamb(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, tb, lr, step, beta1, beta2, eps,
+                        decay, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
 
     def grads_finite(self) -> bool:
         """True when every entry of the flat gradient buffer is finite (x3d_all_finite; synchronises)."""

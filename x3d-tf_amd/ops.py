@@ -739,6 +739,103 @@ def grad_accum(acc, g, first=False):
     return acc
 
 
+# ---- layer-wise optimizers: driven by a segments.SegTable (chunk table on the device) ------------------------------------
+def _seg_table(op, table, *buffers):
+    """the table is on the device and covers nothing outside any of `buffers` (contiguous float32, same device)"""
+    if table.d_chunks is None:
+        raise ValueError(f"{op}: the chunk table is not on a device yet (SegTable.to(device))")
+    for name, t in buffers:
+        if t is None:
+            continue
+        _f32_flat(op, name, t)
+        if t.numel() < table.end:
+            raise ValueError(f"{op}: {name} holds {t.numel()} elements, the chunk table covers up to {table.end}")
+    _chk(table.d_chunks, table.d_segs, *[t for _, t in buffers])
+
+
+def _seg_scratch(op, table, partials, q, device):
+    """partials [2 * nchunk] fp64 and q [nseg] fp32: checked, or allocated when None"""
+    need = 2 * table.nchunk
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float64, device=device)
+    elif partials.dtype != torch.float64 or partials.numel() < need or not partials.is_contiguous():
+        raise ValueError(f"{op}: partials must hold {need} float64, got {partials.numel()} {partials.dtype}")
+    if q is None:
+        q = torch.ones(table.nseg, dtype=torch.float32, device=device)
+    elif q.dtype != torch.float32 or q.numel() != table.nseg or not q.is_contiguous():
+        raise ValueError(f"{op}: q must be {table.nseg} float32, got {q.numel()} {q.dtype}")
+    _chk(partials, q)
+    return partials, q
+
+
+def _seg_extras(op, norm, max_norm, ema_decay, ema):
+    if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2):
+        raise ValueError(f"{op}: norm must be the [2] float64 result of grad_sumsq")
+    if norm is not None and not float(max_norm) > 0.0:
+        raise ValueError(f"{op}: max_norm must be positive with norm, not {max_norm}")
+    if ema is not None and not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"{op}: ema_decay must lie in [0, 1), not {ema_decay}")
+
+
+def seg_sumsq(a, table, out=None, partials=None):
+    """out [nseg] fp64 = per-segment sum of squares of `a` (squared and added in fp64, a fixed order: the same bits on every
+    run; x3d_seg_sumsq).  table: segments.SegTable on a's device.  Two launches, does not synchronise."""
+    _seg_table("seg_sumsq", table, ("a", a))
+    if partials is None:
+        partials = torch.empty(table.nchunk, dtype=torch.float64, device=a.device)
+    elif partials.dtype != torch.float64 or partials.numel() < table.nchunk:
+        raise ValueError(f"seg_sumsq: partials must hold {table.nchunk} float64, got {partials.numel()} {partials.dtype}")
+    if out is None:
+        out = torch.empty(table.nseg, dtype=torch.float64, device=a.device)
+    elif out.dtype != torch.float64 or out.numel() != table.nseg:
+        raise ValueError(f"seg_sumsq: out must be {table.nseg} float64, got {out.numel()} {out.dtype}")
+    _chk(a, partials, out)
+    hip.call("x3d_seg_sumsq", ptr(a), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials), ptr(out))
+    return out
+
+
+def lars(w, v, g, table, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None,
+         max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
+    """LARS on the segments of `table` (x3d_lars: the rule is in include/x3d_hip.h); returns q [nseg] fp32, the trust ratios,
+    on the device.  Three launches, does not synchronise; g is not written."""
+    _seg_table("lars", table, ("w", w), ("v", v), ("g", g), ("ema", ema))
+    _seg_extras("lars", norm, max_norm, ema_decay, ema)
+    if not float(trust_coef) > 0.0 or float(eps) < 0.0:
+        raise ValueError(f"lars: trust_coef must be positive and eps >= 0, not {trust_coef}, {eps}")
+    partials, q = _seg_scratch("lars", table, partials, q, w.device)
+    hip.call("x3d_lars", ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, float(lr),
+             float(momentum), float(weight_decay), float(grad_scale), float(trust_coef), float(eps), 1 if clip else 0,
+             ptr(norm), float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
+    return q
+
+
+def adamw(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+          ema=None, ema_decay=0.0):
+    """Adam with decoupled weight decay on the l2 segments of `table` (x3d_adamw).  One launch, does not synchronise."""
+    _seg_table("adamw", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
+    _seg_extras("adamw", norm, max_norm, ema_decay, ema)
+    if float(decay) < 0.0 or int(step) < 1:
+        raise ValueError(f"adamw: decay must be >= 0 and step >= 1, not {decay}, {step}")
+    hip.call("x3d_adamw", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
+             float(max_norm), ptr(ema), float(ema_decay))
+
+
+def lamb(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+         ema=None, ema_decay=0.0, partials=None, q=None):
+    """LAMB on the segments of `table` (x3d_lamb); returns q [nseg] fp32, the trust ratios, on the device.  Three launches, does
+    not synchronise; g is not written."""
+    _seg_table("lamb", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
+    _seg_extras("lamb", norm, max_norm, ema_decay, ema)
+    if float(decay) < 0.0 or not float(eps) > 0.0 or int(step) < 1:
+        raise ValueError(f"lamb: decay must be >= 0, eps > 0 and step >= 1, not {decay}, {eps}, {step}")
+    partials, q = _seg_scratch("lamb", table, partials, q, w.device)
+    hip.call("x3d_lamb", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
+             float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
+    return q
+
+
 def l2_sumsq(w, l2_mask, out):
     _chk(w, l2_mask, out)
     hip.call("x3d_l2_sumsq", ptr(w), ptr(l2_mask), ptr(out), w.numel())

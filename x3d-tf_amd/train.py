@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
-from .config import mix_settings, solver_settings
+from .config import OPTIMIZERS, SLOT_KIND, mix_settings, optim_settings, solver_settings
 from .mix import NO_MIX, draw_mix_params
 
 
@@ -92,9 +92,13 @@ class Trainer:
     def __init__(self, model, cfg, momentum: Optional[float] = None, sync_moving_stats: bool = True, group=None,
                  loss_scale="auto", mix_seed: int = 0, drop_path_seed: int = 0):
         self.optimizer = cfg.TRAIN.OPTIMIZER.lower()
-        if self.optimizer not in ("sgd", "adam"):   # reference train.py:88-97: SGD(nesterov) / Adam / NotImplementedError
+        if self.optimizer not in OPTIMIZERS:   # reference train.py:88-97: SGD(nesterov) / Adam / NotImplementedError; + lars, adamw, lamb
             raise NotImplementedError(f"{cfg.TRAIN.OPTIMIZER} not supported")
         self.model, self.cfg, self.group = model, cfg, group
+        # lars keeps SGD's slot (momentum) and checkpoint layout, adamw and lamb keep Adam's (m, v, `iter`)
+        self.slot_kind = SLOT_KIND[self.optimizer]
+        self.optim = optim_settings(cfg)      # OPTIM.*: read by the lars / adamw / lamb branches only
+        self.last_trust_ratios = None         # lars / lamb: device [nseg] fp32 trust ratios of the last update (model.segments order)
         self.opt_step = 0                     # optimizer steps applied (Adam's bias correction counts them)
         # Loss scaling = tf.keras.mixed_precision.LossScaleOptimizer(opt) with its defaults (train.py:99-100): dynamic,
         # initial scale 2^15, doubled after 2000 consecutive finite steps, halved (and the step skipped) when a gradient
@@ -199,10 +203,19 @@ class Trainer:
             extras.update(norm=norm, max_norm=self.solver.clip_grad_l2norm)
         if self.ema is not None:
             extras.update(ema=self.ema, ema_decay=self.solver.ema_decay)
+        o = self.optim
         if self.optimizer == "adam":
             m.apply_adam(lr, self.opt_step, grad_scale=grad_scale, **extras)
-        else:
+        elif self.optimizer == "sgd":
             m.apply_sgd(lr, self.momentum, grad_scale=grad_scale, **extras)
+        elif self.optimizer == "lars":        # trust ratios of the all-reduced, accumulated gradient: the same on every rank
+            self.last_trust_ratios = m.apply_lars(lr, self.momentum, o.lars_trust_coef, o.lars_eps, o.lars_clip,
+                                                  grad_scale=grad_scale, **extras)
+        elif self.optimizer == "adamw":
+            m.apply_adamw(lr, self.opt_step, decay=o.weight_decay, grad_scale=grad_scale, **extras)
+        else:
+            self.last_trust_ratios = m.apply_lamb(lr, self.opt_step, eps=o.lamb_eps, decay=o.weight_decay,
+                                                  grad_scale=grad_scale, **extras)
         if self.ema is not None:              # the moving statistics behind the trainable block: skipped together with the step
             from . import ops
             ops.ema_update(self.ema[m.n_trainable_flat:], m.moving_stats_flat(), self.solver.ema_decay, extras.get("norm"))
@@ -477,18 +490,18 @@ class Trainer:
         os.makedirs(model_dir, exist_ok=True)
         prefix = os.path.join(model_dir, f"ckpt-{int(epoch)}")
         hyper = dict(iter=self.opt_step, learning_rate=lr_schedule(self.epoch, self.cfg), decay=0.0)
-        if self.optimizer == "adam":
+        if self.slot_kind == "adam":
             hyper.update(beta_1=0.9, beta_2=0.999)
         else:
             hyper.update(momentum=self.momentum)
-        self.model.save_weights(prefix, optimizer_hyper=hyper, optimizer=self.optimizer)
+        self.model.save_weights(prefix, optimizer_hyper=hyper, optimizer=self.slot_kind)
         if self.ema is not None:
             # the EMA model as a bundle of its own, in its own directory: `<model_dir>/checkpoint` still names ckpt-<epoch>,
             # and model.load_weights("<model_dir>/ema") loads the EMA weights for evaluation
             os.makedirs(os.path.join(model_dir, "ema"), exist_ok=True)
             with self.ema_scope():
                 self.model.save_weights(os.path.join(model_dir, "ema", f"ckpt-{int(epoch)}"), optimizer_hyper=hyper,
-                                        optimizer=self.optimizer)
+                                        optimizer=self.slot_kind)
         return prefix
 
     def resume(self, model_dir: str, pretrained_ckpt: Optional[str] = None, skip_mismatch: bool = False) -> int:
@@ -533,12 +546,12 @@ class Trainer:
         """Weights + this optimizer branch's slots from the checkpoint prefix `path`; sets `opt_step` from its `iter`."""
         m = self.model
         if skip_mismatch:
-            self.skipped_keys = m.load_weights(path, optimizer=self.optimizer, skip_mismatch=True)
+            self.skipped_keys = m.load_weights(path, optimizer=self.slot_kind, skip_mismatch=True)
         else:
-            m.load_weights(path, optimizer=self.optimizer)   # weights + this branch's optimizer slots; unknown keys tolerated as Keras does
+            m.load_weights(path, optimizer=self.slot_kind)   # weights + this branch's optimizer slots; unknown keys tolerated as Keras does
         st = getattr(m, "optimizer_state", None) or {}
         kind = st.get("kind")
-        if kind is not None and kind != self.optimizer:
+        if kind is not None and kind != self.slot_kind:
             # a checkpoint written by the other optimizer branch: Keras restores the variables and leaves the new
             # optimizer's slots at their initial value -- never reuse SGD momentum as Adam's first moment or vice versa
             m.flat_velocity.zero_()
@@ -548,15 +561,18 @@ class Trainer:
         else:
             # optimizer/iter: Adam's bias correction continues from the saved step count
             self.opt_step = int(st.get("hyper", {}).get("iter", 0))
-            if self.optimizer == "adam" and kind is None:
+            if self.slot_kind == "adam" and kind is None:
                 m.flat_velocity.zero_()
                 self.opt_step = 0
         if self.ema is not None:              # restart the EMA from the loaded weights (resume replaces it by a saved one)
             self.ema.copy_(m.flat_params)
 
     def loss(self, pl):
-        """global-batch mean cross-entropy + L2 term (what Keras reports as `loss`)."""
+        """global-batch mean cross-entropy + L2 term (what Keras reports as `loss`).  adamw / lamb decay the weights outside
+        the loss (OPTIM.WEIGHT_DECAY) and ignore NETWORK.WEIGHT_DECAY: for them this is the cross-entropy alone."""
         ce = pl.loss_rows.sum() / (pl.n * self.world)
         if self.collectives:
             torch.distributed.all_reduce(ce, group=self.group)
+        if self.optimizer in ("adamw", "lamb"):
+            return ce
         return ce + self.model.regularization_loss().float().squeeze()
