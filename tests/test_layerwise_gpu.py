@@ -21,84 +21,8 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-U = 2.0 ** -24
-F32 = np.float32
-CHUNK = 1024                                   # X3D_SEG_CHUNK (asserted against the header in _fix)
-SWEEP = 1024 * 4 * CHUNK                       # elements the largest grid takes before it strides
-LENGTHS = [1, 3, 4, 5, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 5 * CHUNK + 77, 37, 41, 2 * SWEEP + 4099]
-L2 = [True, False, True, True, False, True, True, True, False, True, True, True, True, True]
-ZERO_W, ZERO_G = 11, 12                        # the all-zero w segment and the all-zero g (LAMB: m, v too) segment, both l2
-LARS = dict(lr=F32(0.1), mom=F32(0.9), wd=F32(5e-5), eta=F32(0.02), eps=F32(1e-8))
-ADAM = dict(lr=F32(1e-3), b1=F32(0.9), b2=F32(0.999), eps=F32(1e-7), step=3)
-LAMB = dict(lr=F32(0.01), b1=F32(0.9), b2=F32(0.999), eps=F32(1e-6), step=3)
-GS = F32(1.0 / 1024.0)                         # grad_scale of a loss-scaled gradient, as test_solver_gpu.py
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32 if a.dtype == F32 else np.int64)
-
-
-class _Fix:
-    pass
-
-
-_FIX = {}
-
-
-def _fix(gpu):
-    """the segment layout and the host arrays, built once: clean copies (padding 0) for the fp64 references, `dirty` ones
-    (padding NaN) for the device"""
-    if _FIX:
-        return _FIX["f"]
-    from x3d_tf_amd import hip
-    from x3d_tf_amd.segments import SegTable
-    assert hip.SEG_CHUNK == CHUNK
-    f = _Fix()
-    rng = np.random.default_rng(7)
-    segs, off = [], 4
-    for t, (n, l2) in enumerate(zip(LENGTHS, L2)):
-        segs.append((off, n, l2))
-        off += (n + 3) // 4 * 4 + (4 if t % 2 else 0)          # the model's padding, and a whole vector of it now and then
-    f.segs, f.n = segs, off + 8
-    f.table = SegTable(segs).to(gpu)
-    f.covered = np.zeros(f.n, bool)
-    f.l2e = np.zeros(f.n, bool)
-    for o, n, l2 in segs:
-        f.covered[o:o + n] = True
-        f.l2e[o:o + n] = l2
-    f.w = rng.standard_normal(f.n).astype(F32)
-    for t, (o, n, _) in enumerate(segs):
-        if t % 3 == 0:
-            f.w[o:o + n] *= F32(10.0)                          # (trust ratios on both sides of lr: LARS_CLIP clips some)
-    f.v = (0.1 * rng.standard_normal(f.n)).astype(F32)         # SGD momentum / Adam's first moment
-    f.v2 = (np.abs(f.v) * F32(0.01)).astype(F32)               # Adam's second moment (>= 0)
-    f.g = (1024.0 * rng.standard_normal(f.n)).astype(F32)
-    f.e = (0.5 * f.w + 0.1).astype(F32)
-    o, n, _ = segs[ZERO_W]
-    f.w[o:o + n] = 0
-    o, n, _ = segs[ZERO_G]
-    f.g[o:o + n] = 0
-    f.v[o:o + n] = 0
-    f.v2[o:o + n] = 0
-    for a in (f.w, f.v, f.v2, f.g, f.e):
-        a[~f.covered] = 0
-    f.norm_total = float(np.sqrt(np.sum(f.g.astype(np.float64) ** 2)) * float(GS))     # the unscaled global norm
-    _FIX["f"] = f
-    return f
-
-
-def _dirty(f, a, gpu, off=0):
-    """`a` with NaN padding on the device; off = 1: the first element one float behind a 16-byte boundary"""
-    d = a.copy()
-    d[~f.covered] = np.nan
-    buf = torch.full((f.n + off + 8,), float("nan"), dtype=torch.float32, device=gpu)
-    t = buf[off:off + f.n]
-    t.copy_(torch.from_numpy(d))
-    return t, d
+from tests.solver_cases import (CHUNK, F32, GS, L2, LAMB, LARS, LENGTHS, SEG_ADAM as ADAM, SWEEP, U, ZERO_G, ZERO_W,  # noqa: E402,F401
+                                _bits, _coef, _dirty, _fix, _norm_of, _np)
 
 
 def _check_untouched_and_finite(f, named):
@@ -118,19 +42,6 @@ def _expand(q, segs, n):
     for (o, k, _), qt in zip(segs, q):
         e[o:o + k] = qt
     return e
-
-
-def _coef(norm0, gs, max_norm):
-    """the documented clip rule in fp64 (gs, max_norm: the fp32 values the ABI passes)"""
-    gs, max_norm = float(F32(gs)), float(F32(max_norm))
-    return gs * min(1.0, max_norm / (np.sqrt(norm0) * gs + 1e-6))
-
-
-def _norm_of(g_clean, gpu):
-    """x3d_grad_sumsq over the gradient with ZERO padding, as the model's flat_grads has it (NaN padding would count as a
-    non-finite gradient): the two doubles the launches read"""
-    from x3d_tf_amd import ops
-    return ops.grad_sumsq(torch.from_numpy(g_clean).to(gpu))
 
 
 MODES = ["plain", "clip_active_ema", "clip_inactive"]

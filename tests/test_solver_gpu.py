@@ -16,59 +16,8 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-U = 2.0 ** -24
-F32 = np.float32
-
-# (n, offset of every pointer in elements, with l2 mask): the edges of the vector / one-element paths (n % 4, n < 4), the
-# workgroup boundary (256), more than one workgroup, the grid-stride wrap (1024 workgroups x 256 threads x 4 elements =
-# 1 048 576 elements per sweep), every pointer misaligned by one float (mask: one byte), and no mask at all
-CASES = [(1, 0, True), (3, 0, True), (255, 0, True), (256, 0, True), (257, 0, True), (4100, 0, True), (2_500_003, 0, True),
-         (4099, 1, True), (4100, 0, False)]
-IDS = [f"n{n}" + ("_misaligned" if off else "") + ("" if mask else "_nomask") for n, off, mask in CASES]
-WRAP = 2_000_001                     # an index of the largest case that only a second sweep of the grid reaches
-
-
-def _host(n, seed, gscale_inv=1024.0):
-    """w, v (second slot: >= 0), g (a loss-scaled gradient), l2 mask"""
-    rng = np.random.default_rng(seed)
-    w = rng.standard_normal(n).astype(F32)
-    v = (0.1 * rng.standard_normal(n)).astype(F32)
-    g = (gscale_inv * rng.standard_normal(n)).astype(F32)
-    mask = (rng.random(n) < 0.7).astype(np.uint8)
-    return w, v, g, mask
-
-
-def _dev(a, gpu, off=0):
-    """a copy of `a` on the device whose first element sits `off` elements behind an aligned allocation"""
-    if a is None:
-        return None
-    buf = torch.zeros(a.size + off + 8, dtype=torch.from_numpy(a[:1]).dtype, device=gpu)
-    t = buf[off:off + a.size]
-    t.copy_(torch.from_numpy(a))
-    return t
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32 if a.dtype == F32 else np.int64)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _sumsq(g_dev):
-    from x3d_tf_amd import ops
-    return ops.grad_sumsq(g_dev)
-
-
-def _coef(norm0, gs, max_norm):
-    """the documented clip rule in fp64 (gs, max_norm: the fp32 values the ABI passes)"""
-    gs, max_norm = float(F32(gs)), float(F32(max_norm))
-    return gs * min(1.0, max_norm / (np.sqrt(norm0) * gs + 1e-6))
+from tests.solver_cases import (ADAM, CASES, F32, IDS, SGD, U, WRAP, _adam_ex, _adam_plain, _bits, _coef, _dev, _host,  # noqa: E402,F401
+                                _np, _p, _sgd_ex, _sgd_plain, _sumsq)
 
 
 # ---- x3d_grad_sumsq ---------------------------------------------------------------------------------------------------
@@ -107,36 +56,6 @@ def test_grad_sumsq(gpu, n, off, _mask):
 
 
 # ---- the optimizers ---------------------------------------------------------------------------------------------------
-SGD = dict(lr=F32(0.1), mom=F32(0.9), wd=F32(5e-5))
-ADAM = dict(lr=F32(1e-3), b1=F32(0.9), b2=F32(0.999), eps=F32(1e-7), wd=F32(5e-5), step=3)
-
-
-def _sgd_plain(w, v, g, mask, gs):
-    from x3d_tf_amd import hip
-    hip.call("x3d_sgd_nesterov", _p(w), _p(v), _p(g), _p(mask), float(SGD["lr"]), float(SGD["mom"]), float(SGD["wd"]),
-             float(gs), w.numel())
-
-
-def _sgd_ex(w, v, g, mask, gs, norm=None, max_norm=0.0, ema=None, decay=0.0):
-    from x3d_tf_amd import hip
-    hip.call("x3d_sgd_nesterov_ex", _p(w), _p(v), _p(g), _p(mask), float(SGD["lr"]), float(SGD["mom"]), float(SGD["wd"]),
-             float(gs), _p(norm), float(max_norm), _p(ema), float(decay), w.numel())
-
-
-def _adam_plain(w, m, v, g, mask, gs):
-    from x3d_tf_amd import hip
-    a = ADAM
-    hip.call("x3d_adam", _p(w), _p(m), _p(v), _p(g), _p(mask), float(a["lr"]), float(a["b1"]), float(a["b2"]),
-             float(a["eps"]), float(a["wd"]), float(gs), a["step"], w.numel())
-
-
-def _adam_ex(w, m, v, g, mask, gs, norm=None, max_norm=0.0, ema=None, decay=0.0):
-    from x3d_tf_amd import hip
-    a = ADAM
-    hip.call("x3d_adam_ex", _p(w), _p(m), _p(v), _p(g), _p(mask), float(a["lr"]), float(a["b1"]), float(a["b2"]),
-             float(a["eps"]), float(a["wd"]), float(gs), a["step"], _p(norm), float(max_norm), _p(ema), float(decay),
-             w.numel())
-
 
 def _sgd_ref(w, v, g, mask, c, hp=None):
     """fp64 of the documented rule with the fp32 hyper-parameters the ABI passes; returns w', v' and the limit.

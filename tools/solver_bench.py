@@ -1,13 +1,19 @@
-"""What the solver step costs on the device (writes profiles/solver_mi355x.txt; no run has been recorded yet).
+"""What the solver step costs on the device (prints; --out FILE keeps the lines.  profiles/solver_mi355x.txt holds recorded runs).
 
-    python tools/solver_bench.py [--out FILE] [--spread]          (FILE defaults to profiles/solver_mi355x.txt)
+    python tools/solver_bench.py [--out FILE] [--spread]
 
 At the X3D-M and X3D-XL parameter counts (the flat trainable block, from dry models), HIP events around 50 launches after 10
-warm-ups, the arms alternating over 3 rounds in one process:
+warm-ups, the arms alternating over 10 rounds in one process:
     plain            x3d_sgd_nesterov                                 5 streams of 4n bytes (w, v, g in; w, v out)
     clip             x3d_grad_sumsq + x3d_sgd_nesterov_ex(norm)       6 streams (+ g once more)
     clip + ema       x3d_grad_sumsq + x3d_sgd_nesterov_ex(norm, ema)  8 streams (+ ema in and out)
-(the l2 mask adds n bytes to each update).  The buffers (15 - 60 MB) fit the 256 MiB Infinity Cache, so the GB/s are
+    adam_ex          x3d_adam_ex(norm, ema)                           9 streams (w, m, v, g, ema in; w, m, v, ema out)
+    ema_update       x3d_ema_update                                   3 streams
+    grad_accum       x3d_grad_accum, first = 1 / 0                    2 / 3 streams
+    seg_sumsq, lars, adamw, lamb                                      the layer-wise entry points with norm and ema over
+                     SegTable(model.segments) of the dry model: 1 / 9 / 9 / 12 streams (tools/layerwise_bench.py: their
+                     passes; + ema in and out)
+(the l2 mask adds n bytes to each flat update).  The buffers (15 - 60 MB) fit the 256 MiB Infinity Cache, so the GB/s are
 cache-resident rates, as they are in a train step, where the backward pass has just written the gradient.
 --spread: also the run-to-run spread of the backward pass at the shapes of tests/test_solver_gpu.py (two twin models, same
 seed, same batch, max |g_a - g_b| / max |g|), the figure the accumulation tests take their limit from."""
@@ -20,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solver_mi355x.txt"), help="the lines are written here at the end")
+ap.add_argument("--out", help="the lines are also written here at the end")
 ap.add_argument("--spread", action="store_true", help="measure the backward's run-to-run spread at the test shapes too")
 args = ap.parse_args()
 lines = []
@@ -34,11 +40,13 @@ def say(s):
 import x3d_tf_amd as x  # noqa: E402
 from x3d_tf_amd import hip, ops  # noqa: E402
 from x3d_tf_amd.model import X3D  # noqa: E402
+from x3d_tf_amd.segments import SegTable  # noqa: E402
 
 assert torch.cuda.is_available(), "solver_bench.py measures on the GPU: there is nothing to time without one"
 dev = torch.device("cuda:0")
-say(f"device: {torch.cuda.get_device_name(0)}; HIP events, 50 launches after 10 warm-ups, 3 alternating rounds, best and median")
-WARM, REPS, ROUNDS = 10, 50, 3
+say(f"device: {torch.cuda.get_device_name(0)}; library {hip.LIB_PATH}")
+say("HIP events, 50 launches after 10 warm-ups, 10 alternating rounds, best and median")
+WARM, REPS, ROUNDS = 10, 50, 10
 LR, MOM, WD, GS = 0.1, 0.9, 5e-5, 1.0 / 1024.0
 
 
@@ -56,16 +64,24 @@ def timed(fn):
 
 
 for name in ("M", "XL"):
-    n = X3D(x.get_config(name), device="dry").n_trainable_flat
+    dry = X3D(x.get_config(name), device="dry")
+    n = dry.n_trainable_flat
+    tb = SegTable(dry.segments).to(dev)
     gen = torch.Generator(device=dev).manual_seed(1)
     w = torch.randn(n, generator=gen, device=dev)
     v = torch.zeros(n, device=dev)
     g = torch.randn(n, generator=gen, device=dev) * 1024.0
+    v2 = v.clone()
     ema = w.clone()
+    acc = torch.zeros(n, device=dev)
+    partials = torch.empty(2 * tb.nchunk, dtype=torch.float64, device=dev)
+    q = torch.ones(tb.nseg, device=dev)
+    seg_out = torch.empty(tb.nseg, dtype=torch.float64, device=dev)
     mask = (torch.rand(n, generator=gen, device=dev) < 0.9).to(torch.uint8)
     norm = torch.zeros(2, dtype=torch.float64, device=dev)
     scratch = torch.zeros(int(hip.load().x3d_grad_sumsq_scratch(n)), dtype=torch.float64, device=dev)
     p = [t.data_ptr() for t in (w, v, g, mask)]
+    extras = dict(grad_scale=GS, norm=norm, max_norm=1.0, ema=ema, ema_decay=0.9999)
 
     def plain():
         hip.call("x3d_sgd_nesterov", *p, LR, MOM, WD, GS, n)
@@ -81,8 +97,22 @@ for name in ("M", "XL"):
         sumsq()
         hip.call("x3d_sgd_nesterov_ex", *p, LR, MOM, WD, GS, norm.data_ptr(), 1.0, ema.data_ptr(), 0.9999, n)
 
+    def adam_ex():
+        hip.call("x3d_adam_ex", p[0], p[1], v2.data_ptr(), p[2], p[3], 1e-3, 0.9, 0.999, 1e-7, WD, GS, 3, norm.data_ptr(), 1.0,
+                 ema.data_ptr(), 0.9999, n)
+
     arms = [("plain: x3d_sgd_nesterov", plain, 5 * 4 * n + n), ("x3d_grad_sumsq alone", sumsq, 4 * n),
-            ("clip: sumsq + _ex", clip, 6 * 4 * n + n), ("clip + ema: sumsq + _ex", clip_ema, 8 * 4 * n + n)]
+            ("clip: sumsq + _ex", clip, 6 * 4 * n + n), ("clip + ema: sumsq + _ex", clip_ema, 8 * 4 * n + n),
+            ("x3d_adam_ex(norm, ema)", adam_ex, 9 * 4 * n + n),
+            ("x3d_ema_update", lambda: ops.ema_update(ema, w, 0.9999), 3 * 4 * n),
+            ("x3d_grad_accum first", lambda: ops.grad_accum(acc, g, first=True), 2 * 4 * n),
+            ("x3d_grad_accum add", lambda: ops.grad_accum(acc, g), 3 * 4 * n),
+            ("x3d_seg_sumsq", lambda: ops.seg_sumsq(g, tb, seg_out, partials), 4 * n),
+            ("x3d_lars(norm, ema)", lambda: ops.lars(w, v, g, tb, LR, MOM, WD, 0.001, 1e-8, False, partials=partials, q=q,
+                                                     **extras), 9 * 4 * n),
+            ("x3d_adamw(norm, ema)", lambda: ops.adamw(w, v, v2, g, tb, 1e-4, 3, decay=0.01, **extras), 9 * 4 * n),
+            ("x3d_lamb(norm, ema)", lambda: ops.lamb(w, v, v2, g, tb, 1e-4, 3, decay=0.01, partials=partials, q=q, **extras),
+             12 * 4 * n)]
     got = {a[0]: [] for a in arms}
     for _ in range(ROUNDS):
         for label, fn, _b in arms:
@@ -91,9 +121,9 @@ for name in ("M", "XL"):
     base = min(got[arms[0][0]])
     for label, _fn, nbytes in arms:
         t = sorted(got[label])
-        say(f"  {label:<28} best {t[0]:8.1f} us  median {t[len(t) // 2]:8.1f} us   {nbytes / 1e6:7.1f} MB   "
+        say(f"  {label:<28} best {t[0]:8.2f} us  median {t[len(t) // 2]:8.2f} us   {nbytes / 1e6:7.1f} MB   "
             f"{nbytes / t[0] / 1e3:6.2f} GB/s at best   {t[0] / base:5.2f} x plain")
-    del w, v, g, ema, mask
+    del w, v, v2, g, ema, acc, mask
 
 if args.spread:
     # the shapes of the trainer tests in tests/test_solver_gpu.py: XS, 10 classes, no dropout, 2 clips of 4 x 32 x 32, fp32 storage
@@ -113,5 +143,7 @@ if args.spread:
         say(f"backward run-to-run spread, XS 2 x 4 x 32 x 32 fp32, pair {rep}: max |g_a - g_b| / max |g| = {s:.3e}")
     say(f"worst of the three pairs: {worst:.3e}")
 
-with open(args.out, "w") as f:
-    f.write("\n".join(lines) + "\n")
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")

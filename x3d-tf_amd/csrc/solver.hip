@@ -11,15 +11,25 @@
 //   x3d_seg_sumsq           per-tensor sums of squares and the layer-wise optimizers built on them (LARS, AdamW, LAMB): a chunk
 //   x3d_lars / _adamw / _lamb   table instead of one flat range, a fixed number of launches (at the end of this file)
 //
-// Shape.  Plain streaming kernels: a thread moves 16 bytes per array and iteration, the grid is capped at SOLVER_MAX_BLOCKS
-// workgroups and strides over the rest.  The vector kernels need every array 16-byte aligned (the l2 mask 4-byte); the n % 4
-// elements at the end are further one-element work items of the same grid-stride walk.  Any other pointer takes the one-element
-// instantiation of the same kernel.  The plain entry points keep their one-element-per-thread launch: their results and
-// their speed are what they were.
+// Every streaming kernel is ONE BODY handed to one of two walkers.  A body is a generic lambda body(N, at): it loads N
+// elements at `at` (vec_load), applies the rule to each (solver_each) and stores N elements (vec_store); N is a
+// std::integral_constant, so the vector and the one-element form of a kernel are two instantiations of the same text and
+// agree to the bit by construction.
+//   solver_for_items<VEC>   the flat walk: a thread moves 16 bytes per array and iteration, the grid is capped at
+//                           SOLVER_MAX_BLOCKS workgroups and strides over the rest.  VEC = 4 needs every array 16-byte aligned
+//                           (the l2 mask 4-byte); the n % 4 elements at the end are further work items of the same walk, with
+//                           N = 1.  Any other pointer takes VEC = 1.
+//   seg_for_items           the walk over one chunk of the chunk table by one wave (the layer-wise kernels; the loop over the
+//                           chunks stays in the kernel: SEG_FOR_CHUNKS): lane l takes the vectors l, l + 64, ..., lanes 0..2
+//                           then the count % 4 last elements with N = 1.
+// The EMA written in the same pass is EmaPass in every kernel that takes an `ema` pointer; solver_launch picks the
+// instantiation on the host.  The plain entry points keep their one-element-per-thread kernels: their results and their
+// speed are what they were.
 //
 // The update arithmetic exists once: sgd_nesterov_step / adam_step below, called by the old and the new kernels; the layer-wise
 // rules (lars_step, adamw_step, lamb_moments / lamb_u) are built on them.
 #include "common.h"
+#include <type_traits>
 
 #define SOLVER_BLOCK 256
 #define SOLVER_MAX_BLOCKS 1024          // = the largest partial count of x3d_grad_sumsq
@@ -154,6 +164,43 @@ static inline int solver_vec(const void* mask, const void* p0, const void* p1 = 
   return 4;
 }
 
+// the flat walk: the items of this thread's grid-stride turns, each handed to body(N, first element) with N = VEC or 1
+template <int VEC, class Body> __device__ __forceinline__ void solver_for_items(long long n, Body&& body) {
+  const long long items = n / VEC + n % VEC;
+  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
+    long long i;
+    int cnt;
+    solver_item<VEC>(it, n, i, cnt);
+    if (cnt == VEC) body(std::integral_constant<int, VEC>{}, i);
+    else body(std::integral_constant<int, 1>{}, i);
+  }
+}
+
+// f(e) for the N elements of an item: what a body writes instead of a loop over e.  N = 1 is a plain call -- behind a one-trip
+// loop the compiler stops sharing code between the vector and the one-element path of a walk (grad_sumsq_kernel<4>: three more
+// VALU instructions per vector item in a kernel that is bound by them).
+template <int N, class F> __device__ __forceinline__ void solver_each(F&& f) {
+  if constexpr (N == 1) f(0);
+  else {
+#pragma unroll
+    for (int e = 0; e < N; e++) f(e);
+  }
+}
+
+// N floats at p.  AL: one access (16 bytes for N = 4); else the same floats one by one, for a p that is only 4-byte aligned
+template <int N, bool AL = true> __device__ __forceinline__ void vec_load(const float* p, float (&o)[N]) {
+  if constexpr (AL || N == 1) VecIO<float, N>::load(p, o);
+  else {
+    solver_each<N>([&](int e) { o[e] = p[e]; });
+  }
+}
+template <int N, bool AL = true> __device__ __forceinline__ void vec_store(float* p, const float (&o)[N]) {
+  if constexpr (AL || N == 1) VecIO<float, N>::store(p, o);
+  else {
+    solver_each<N>([&](int e) { p[e] = o[e]; });
+  }
+}
+
 template <int VEC> __device__ __forceinline__ void load_mask(const unsigned char* l2, long long i, bool (&o)[VEC]) {
   if (!l2) {
 #pragma unroll
@@ -167,6 +214,32 @@ template <int VEC> __device__ __forceinline__ void load_mask(const unsigned char
   }
 }
 
+// The EMA written in the same pass, in two halves: load() goes out with the kernel's other loads (one memory round trip per
+// item, not two), apply() takes the w the kernel has just computed.  The caller puts both behind `if (ema)`: the same answer
+// in every lane.
+template <int N, bool AL = true> struct EmaPass {
+  float e[N];
+  __device__ __forceinline__ void load(const float* p) { vec_load<N, AL>(p, e); }
+  __device__ __forceinline__ void apply(float* p, const float (&w)[N], float omd) {
+#pragma unroll
+    for (int k = 0; k < N; k++) e[k] = ema_step(e[k], w[k], omd);
+    vec_store<N, AL>(p, e);
+  }
+};
+
+// One launch of a streaming kernel: the instantiation `yes` or `no` of it, SOLVER_BLOCK threads.
+template <class... P, class... A>
+static inline void solver_launch(bool pick, void (*yes)(P...), void (*no)(P...), unsigned grid, void* stream, A... args) {
+  void (*kernel)(P...) = pick ? yes : no;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, static_cast<P>(args)...);
+}
+// what the kernels get of max_norm and ema_decay: 0 where the pointer they belong to is null
+struct SolverExtras {
+  float nm, omd;
+  SolverExtras(const double* norm, float max_norm, const float* ema, float ema_decay)
+      : nm(norm ? max_norm : 0.f), omd(ema ? 1.f - ema_decay : 0.f) {}
+};
+
 // ------------------------------------------------------------------------------------------------
 // x3d_grad_sumsq
 // ------------------------------------------------------------------------------------------------
@@ -175,7 +248,9 @@ static inline long long sumsq_parts(long long n) { return n > 0 ? (long long)sol
 __device__ __forceinline__ void sumsq_add(float x, double& s, unsigned& bad) {
   const bool fin = (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;   // exponent all ones: inf or nan
   const double d = fin ? (double)x : 0.0;
-  s += d * d;                                                            // the square in fp64: 1e-30 and 1e18 are fine
+  // the square in fp64: 1e-30 and 1e18 are fine.  The FMA is the fusion the compiler always made of s += d * d, spelled out:
+  // with it the two paths of the flat walk end in the same instruction and share it, as they did when they were written apart
+  s = __builtin_fma(d, d, s);
   bad += fin ? 0u : 1u;
 }
 
@@ -185,22 +260,14 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void grad_sumsq_kernel(const float* _
                                                                   double* __restrict__ scratch) {
   __shared__ double sh_s[SOLVER_BLOCK / 64];
   __shared__ unsigned sh_b[SOLVER_BLOCK / 64];
-  const long long items = n / VEC + n % VEC;
   double s = 0.0;
   unsigned bad = 0;
-  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
-    long long i;
-    int cnt;
-    solver_item<VEC>(it, n, i, cnt);
-    if (cnt == VEC) {
-      float x[VEC];
-      VecIO<float, VEC>::load(g + i, x);
-#pragma unroll
-      for (int e = 0; e < VEC; e++) sumsq_add(x[e], s, bad);
-    } else {
-      sumsq_add(g[i], s, bad);
-    }
-  }
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float x[N];
+    vec_load<N>(g + i, x);
+    solver_each<N>([&](int e) { sumsq_add(x[e], s, bad); });
+  });
   // lanes by xor butterfly, then the waves in ascending order: a fixed tree
   s = wave_sum_d(s);
 #pragma unroll
@@ -241,12 +308,8 @@ extern "C" int x3d_grad_sumsq(const float* g, long long n, double* scratch, doub
   X3D_REQUIRE(g && scratch && out && n > 0, "grad_sumsq: bad args");
   X3D_REQUIRE(((uintptr_t)scratch & 7) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)g & 3) == 0, "grad_sumsq: misaligned pointer");
   const unsigned parts = (unsigned)sumsq_parts(n);      // the grid: a function of n alone, whatever path the pointer takes
-  hipStream_t st = (hipStream_t)stream;
-  if (solver_vec(nullptr, g) == 4)
-    hipLaunchKernelGGL((grad_sumsq_kernel<4>), dim3(parts), dim3(SOLVER_BLOCK), 0, st, g, n, scratch);
-  else
-    hipLaunchKernelGGL((grad_sumsq_kernel<1>), dim3(parts), dim3(SOLVER_BLOCK), 0, st, g, n, scratch);
-  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, st, (const double*)scratch, (int)parts, out);
+  solver_launch(solver_vec(nullptr, g) == 4, grad_sumsq_kernel<4>, grad_sumsq_kernel<1>, parts, stream, g, n, scratch);
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, (int)parts, out);
   X3D_LAUNCH_CHECK("grad_sumsq");
   return X3D_OK;
 }
@@ -263,36 +326,21 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void sgd_nesterov_ex_kernel(float* __
                                                                        long long n) {
   float c;
   if (!solver_coef(norm, gscale, max_norm, c)) return;
-  const long long items = n / VEC + n % VEC;
-  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
-    long long i;
-    int cnt;
-    solver_item<VEC>(it, n, i, cnt);
-    if (cnt == VEC) {
-      float wi[VEC], vi[VEC], gi[VEC], ei[VEC];
-      bool m[VEC];
-      VecIO<float, VEC>::load(w + i, wi);
-      VecIO<float, VEC>::load(v + i, vi);
-      VecIO<float, VEC>::load(g + i, gi);
-      load_mask<VEC>(l2, i, m);
-      if (ema) VecIO<float, VEC>::load(ema + i, ei);
-#pragma unroll
-      for (int e = 0; e < VEC; e++) sgd_nesterov_step(wi[e], vi[e], gi[e], m[e], lr, mom, wd, c);
-      VecIO<float, VEC>::store(v + i, vi);
-      VecIO<float, VEC>::store(w + i, wi);
-      if (ema) {
-#pragma unroll
-        for (int e = 0; e < VEC; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-        VecIO<float, VEC>::store(ema + i, ei);
-      }
-    } else {
-      float wi = w[i], vi = v[i];
-      sgd_nesterov_step(wi, vi, g[i], l2 && l2[i], lr, mom, wd, c);
-      v[i] = vi;
-      w[i] = wi;
-      if (ema) ema[i] = ema_step(ema[i], wi, omd);
-    }
-  }
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float wi[N], vi[N], gi[N];
+    bool k[N];
+    vec_load<N>(w + i, wi);
+    vec_load<N>(v + i, vi);
+    vec_load<N>(g + i, gi);
+    load_mask<N>(l2, i, k);
+    EmaPass<N> ea;
+    if (ema) ea.load(ema + i);
+    solver_each<N>([&](int e) { sgd_nesterov_step(wi[e], vi[e], gi[e], k[e], lr, mom, wd, c); });
+    vec_store<N>(v + i, vi);
+    vec_store<N>(w + i, wi);
+    if (ema) ea.apply(ema + i, wi, omd);
+  });
 }
 
 template <int VEC>
@@ -303,39 +351,23 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adam_ex_kernel(float* __restrict
                                                                float* __restrict__ ema, float omd, long long n) {
   float c;
   if (!solver_coef(norm, gscale, max_norm, c)) return;
-  const long long items = n / VEC + n % VEC;
-  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
-    long long i;
-    int cnt;
-    solver_item<VEC>(it, n, i, cnt);
-    if (cnt == VEC) {
-      float wi[VEC], mi[VEC], vi[VEC], gi[VEC], ei[VEC];
-      bool k[VEC];
-      VecIO<float, VEC>::load(w + i, wi);
-      VecIO<float, VEC>::load(m + i, mi);
-      VecIO<float, VEC>::load(v + i, vi);
-      VecIO<float, VEC>::load(g + i, gi);
-      load_mask<VEC>(l2, i, k);
-      if (ema) VecIO<float, VEC>::load(ema + i, ei);
-#pragma unroll
-      for (int e = 0; e < VEC; e++) adam_step(wi[e], mi[e], vi[e], gi[e], k[e], lr_t, b1, b2, eps, wd, c);
-      VecIO<float, VEC>::store(m + i, mi);
-      VecIO<float, VEC>::store(v + i, vi);
-      VecIO<float, VEC>::store(w + i, wi);
-      if (ema) {
-#pragma unroll
-        for (int e = 0; e < VEC; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-        VecIO<float, VEC>::store(ema + i, ei);
-      }
-    } else {
-      float wi = w[i], mi = m[i], vi = v[i];
-      adam_step(wi, mi, vi, g[i], l2 && l2[i], lr_t, b1, b2, eps, wd, c);
-      m[i] = mi;
-      v[i] = vi;
-      w[i] = wi;
-      if (ema) ema[i] = ema_step(ema[i], wi, omd);
-    }
-  }
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float wi[N], mi[N], vi[N], gi[N];
+    bool k[N];
+    vec_load<N>(w + i, wi);
+    vec_load<N>(m + i, mi);
+    vec_load<N>(v + i, vi);
+    vec_load<N>(g + i, gi);
+    load_mask<N>(l2, i, k);
+    EmaPass<N> ea;
+    if (ema) ea.load(ema + i);
+    solver_each<N>([&](int e) { adam_step(wi[e], mi[e], vi[e], gi[e], k[e], lr_t, b1, b2, eps, wd, c); });
+    vec_store<N>(m + i, mi);
+    vec_store<N>(v + i, vi);
+    vec_store<N>(w + i, wi);
+    if (ema) ea.apply(ema + i, wi, omd);
+  });
 }
 
 // what the two _ex entry points and x3d_ema_update refuse alike
@@ -351,12 +383,9 @@ extern "C" int x3d_sgd_nesterov_ex(float* w, float* v, const float* g, const uns
   X3D_REQUIRE((((uintptr_t)w | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "sgd_nesterov_ex: misaligned pointer");
   SOLVER_REQUIRE_EXTRAS("sgd_nesterov_ex");
   const int vec = solver_vec(l2_mask, w, v, g, ema);
-  const dim3 grid(solver_grid(solver_items(n, vec)));
-  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
-#define ARGS w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale, norm, nm, ema, omd, n
-  if (vec == 4) hipLaunchKernelGGL((sgd_nesterov_ex_kernel<4>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ARGS);
-  else hipLaunchKernelGGL((sgd_nesterov_ex_kernel<1>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ARGS);
-#undef ARGS
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
+  solver_launch(vec == 4, sgd_nesterov_ex_kernel<4>, sgd_nesterov_ex_kernel<1>, solver_grid(solver_items(n, vec)), stream, w, v,
+                g, l2_mask, lr, momentum, weight_decay, grad_scale, norm, x.nm, ema, x.omd, n);
   X3D_LAUNCH_CHECK("sgd_nesterov_ex");
   return X3D_OK;
 }
@@ -368,13 +397,9 @@ extern "C" int x3d_adam_ex(float* w, float* m, float* v, const float* g, const u
   X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "adam_ex: misaligned pointer");
   SOLVER_REQUIRE_EXTRAS("adam_ex");
   const int vec = solver_vec(l2_mask, w, m, v, g, ema);
-  const dim3 grid(solver_grid(solver_items(n, vec)));
-  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
-  const float lr_t = (float)adam_lr_t(lr, beta1, beta2, step);
-#define ARGS w, m, v, g, l2_mask, lr_t, beta1, beta2, eps, weight_decay, grad_scale, norm, nm, ema, omd, n
-  if (vec == 4) hipLaunchKernelGGL((adam_ex_kernel<4>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ARGS);
-  else hipLaunchKernelGGL((adam_ex_kernel<1>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ARGS);
-#undef ARGS
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
+  solver_launch(vec == 4, adam_ex_kernel<4>, adam_ex_kernel<1>, solver_grid(solver_items(n, vec)), stream, w, m, v, g, l2_mask,
+                (float)adam_lr_t(lr, beta1, beta2, step), beta1, beta2, eps, weight_decay, grad_scale, norm, x.nm, ema, x.omd, n);
   X3D_LAUNCH_CHECK("adam_ex");
   return X3D_OK;
 }
@@ -386,22 +411,14 @@ template <int VEC>
 __global__ __launch_bounds__(SOLVER_BLOCK) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ w, float omd,
                                                                   const double* __restrict__ norm, long long n) {
   if (norm && norm[1] != 0.0) return;
-  const long long items = n / VEC + n % VEC;
-  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
-    long long i;
-    int cnt;
-    solver_item<VEC>(it, n, i, cnt);
-    if (cnt == VEC) {
-      float ei[VEC], wi[VEC];
-      VecIO<float, VEC>::load(ema + i, ei);
-      VecIO<float, VEC>::load(w + i, wi);
-#pragma unroll
-      for (int e = 0; e < VEC; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-      VecIO<float, VEC>::store(ema + i, ei);
-    } else {
-      ema[i] = ema_step(ema[i], w[i], omd);
-    }
-  }
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float wi[N];
+    EmaPass<N> ea;
+    ea.load(ema + i);
+    vec_load<N>(w + i, wi);
+    ea.apply(ema + i, wi, omd);
+  });
 }
 
 extern "C" int x3d_ema_update(float* ema, const float* w, float decay, const double* norm, long long n, void* stream) {
@@ -409,9 +426,8 @@ extern "C" int x3d_ema_update(float* ema, const float* w, float decay, const dou
   X3D_REQUIRE((((uintptr_t)ema | (uintptr_t)w) & 3) == 0 && ((uintptr_t)norm & 7) == 0, "ema_update: misaligned pointer");
   X3D_REQUIRE(decay >= 0.f && decay < 1.f, "ema_update: decay must lie in [0, 1)");
   const int vec = solver_vec(nullptr, ema, w);
-  const dim3 grid(solver_grid(solver_items(n, vec)));
-  if (vec == 4) hipLaunchKernelGGL((ema_update_kernel<4>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ema, w, 1.f - decay, norm, n);
-  else hipLaunchKernelGGL((ema_update_kernel<1>), grid, dim3(SOLVER_BLOCK), 0, (hipStream_t)stream, ema, w, 1.f - decay, norm, n);
+  solver_launch(vec == 4, ema_update_kernel<4>, ema_update_kernel<1>, solver_grid(solver_items(n, vec)), stream, ema, w,
+                1.f - decay, norm, n);
   X3D_LAUNCH_CHECK("ema_update");
   return X3D_OK;
 }
@@ -419,39 +435,25 @@ extern "C" int x3d_ema_update(float* ema, const float* w, float decay, const dou
 // acc and g may be the same array (acc = 2 g): no __restrict__; an element is read and written by one thread
 template <int VEC, bool FIRST>
 __global__ __launch_bounds__(SOLVER_BLOCK) void grad_accum_kernel(float* acc, const float* g, long long n) {
-  const long long items = n / VEC + n % VEC;
-  for (long long it = (long long)blockIdx.x * SOLVER_BLOCK + threadIdx.x; it < items; it += (long long)gridDim.x * SOLVER_BLOCK) {
-    long long i;
-    int cnt;
-    solver_item<VEC>(it, n, i, cnt);
-    if (cnt == VEC) {
-      float a[VEC], b[VEC];
-      VecIO<float, VEC>::load(g + i, b);
-      if constexpr (!FIRST) {
-        VecIO<float, VEC>::load(acc + i, a);
-#pragma unroll
-        for (int e = 0; e < VEC; e++) b[e] = a[e] + b[e];
-      }
-      VecIO<float, VEC>::store(acc + i, b);
-    } else {
-      acc[i] = FIRST ? g[i] : acc[i] + g[i];
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float a[N], b[N];
+    vec_load<N>(g + i, b);
+    if constexpr (!FIRST) {
+      vec_load<N>(acc + i, a);
+      solver_each<N>([&](int e) { b[e] = a[e] + b[e]; });
     }
-  }
+    vec_store<N>(acc + i, b);
+  });
 }
 
 extern "C" int x3d_grad_accum(float* acc, const float* g, long long n, int first, void* stream) {
   X3D_REQUIRE(acc && g && n > 0, "grad_accum: bad args");
   X3D_REQUIRE((((uintptr_t)acc | (uintptr_t)g) & 3) == 0, "grad_accum: misaligned pointer");
   const int vec = solver_vec(nullptr, acc, g);
-  const dim3 grid(solver_grid(solver_items(n, vec)));
-  hipStream_t st = (hipStream_t)stream;
-  if (vec == 4) {
-    if (first) hipLaunchKernelGGL((grad_accum_kernel<4, true>), grid, dim3(SOLVER_BLOCK), 0, st, acc, g, n);
-    else hipLaunchKernelGGL((grad_accum_kernel<4, false>), grid, dim3(SOLVER_BLOCK), 0, st, acc, g, n);
-  } else {
-    if (first) hipLaunchKernelGGL((grad_accum_kernel<1, true>), grid, dim3(SOLVER_BLOCK), 0, st, acc, g, n);
-    else hipLaunchKernelGGL((grad_accum_kernel<1, false>), grid, dim3(SOLVER_BLOCK), 0, st, acc, g, n);
-  }
+  solver_launch(vec == 4, first ? grad_accum_kernel<4, true> : grad_accum_kernel<4, false>,
+                first ? grad_accum_kernel<1, true> : grad_accum_kernel<1, false>, solver_grid(solver_items(n, vec)), stream, acc,
+                g, n);
   X3D_LAUNCH_CHECK("grad_accum");
   return X3D_OK;
 }
@@ -479,21 +481,6 @@ static inline bool seg_aligned(const void* p0, const void* p1 = nullptr, const v
   return solver_vec(nullptr, p0, p1, p2, p3, p4) == 4;
 }
 
-template <bool AL> __device__ __forceinline__ void seg_load4(const float* p, float (&o)[4]) {
-  if constexpr (AL) VecIO<float, 4>::load(p, o);
-  else {
-#pragma unroll
-    for (int e = 0; e < 4; e++) o[e] = p[e];
-  }
-}
-template <bool AL> __device__ __forceinline__ void seg_store4(float* p, const float (&o)[4]) {
-  if constexpr (AL) VecIO<float, 4>::store(p, o);
-  else {
-#pragma unroll
-    for (int e = 0; e < 4; e++) p[e] = o[e];
-  }
-}
-
 // the chunk of this wave's turn `ch` (wave-uniform: kept in scalar registers)
 __device__ __forceinline__ void seg_chunk(const int* __restrict__ chunks, int ch, int& seg, int& first, int& cnt) {
   seg = __builtin_amdgcn_readfirstlane(chunks[3 * ch]);
@@ -503,6 +490,14 @@ __device__ __forceinline__ void seg_chunk(const int* __restrict__ chunks, int ch
 #define SEG_FOR_CHUNKS(ch)                                                                                           \
   const int lane = threadIdx.x & 63;                                                                                 \
   for (int ch = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6); ch < nchunk; ch += gridDim.x * SEG_WAVES)
+
+// the walk of one wave over one chunk [first, first + cnt): body(N, element) with N = 4 for the vectors, then N = 1 for the
+// cnt % 4 last elements
+template <class Body> __device__ __forceinline__ void seg_for_items(int first, int cnt, int lane, Body&& body) {
+  const int nv = cnt >> 2, rem = cnt & 3;
+  for (int i = lane; i < nv; i += 64) body(std::integral_constant<int, 4>{}, first + 4 * i);
+  if (lane < rem) body(std::integral_constant<int, 1>{}, first + 4 * nv + lane);
+}
 
 __device__ __forceinline__ void sq_add(float x, double& s) {
   const double d = (double)x;
@@ -550,15 +545,13 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __
   SEG_FOR_CHUNKS(ch) {
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
-    const int nv = cnt >> 2, rem = cnt & 3;
     double s = 0.0;
-    for (int i = lane; i < nv; i += 64) {
-      float x[4];
-      seg_load4<AL>(a + first + 4 * i, x);
-#pragma unroll
-      for (int e = 0; e < 4; e++) sq_add(x[e], s);
-    }
-    if (lane < rem) sq_add(a[first + 4 * nv + lane], s);
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float x[N];
+      vec_load<N, AL>(a + at, x);
+      solver_each<N>([&](int e) { sq_add(x[e], s); });
+    });
     s = wave_sum_d(s);
     if (lane == 0) partials[ch] = s;
   }
@@ -572,16 +565,14 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lars_sums_kernel(const float* __
   SEG_FOR_CHUNKS(ch) {
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
-    const int nv = cnt >> 2, rem = cnt & 3;
     double sw = 0.0, sg = 0.0;
-    for (int i = lane; i < nv; i += 64) {
-      float x[4], y[4];
-      seg_load4<AL>(w + first + 4 * i, x);
-      seg_load4<AL>(g + first + 4 * i, y);
-#pragma unroll
-      for (int e = 0; e < 4; e++) { sq_add(x[e], sw); sq_add(y[e], sg); }
-    }
-    if (lane < rem) { sq_add(w[first + 4 * nv + lane], sw); sq_add(g[first + 4 * nv + lane], sg); }
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float x[N], y[N];
+      vec_load<N, AL>(w + at, x);
+      vec_load<N, AL>(g + at, y);
+      solver_each<N>([&](int e) { sq_add(x[e], sw); sq_add(y[e], sg); });
+    });
     sw = wave_sum_d(sw);
     sg = wave_sum_d(sg);
     if (lane == 0) { partials[ch] = sw; partials[nchunk + ch] = sg; }
@@ -603,34 +594,22 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_moments_kernel(const float*
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
-    const int nv = cnt >> 2, rem = cnt & 3;
     double sw = 0.0, su = 0.0;
-    for (int i = lane; i < nv; i += 64) {
-      const int at = first + 4 * i;
-      float wi[4], mi[4], vi[4], gi[4];
-      seg_load4<AL>(w + at, wi);
-      seg_load4<AL>(m + at, mi);
-      seg_load4<AL>(v + at, vi);
-      seg_load4<AL>(g + at, gi);
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float wi[N], mi[N], vi[N], gi[N];
+      vec_load<N, AL>(w + at, wi);
+      vec_load<N, AL>(m + at, mi);
+      vec_load<N, AL>(v + at, vi);
+      vec_load<N, AL>(g + at, gi);
+      solver_each<N>([&](int e) {
         lamb_moments(mi[e], vi[e], gi[e], b1, b2, c);
         sq_add(wi[e], sw);
         sq_add(lamb_u(wi[e], mi[e], vi[e], l2, r, eps, decay), su);
-      }
-      seg_store4<AL>(m + at, mi);
-      seg_store4<AL>(v + at, vi);
-    }
-    if (lane < rem) {
-      const int at = first + 4 * nv + lane;
-      float mi = m[at], vi = v[at];
-      const float wi = w[at];
-      lamb_moments(mi, vi, g[at], b1, b2, c);
-      sq_add(wi, sw);
-      sq_add(lamb_u(wi, mi, vi, l2, r, eps, decay), su);
-      m[at] = mi;
-      v[at] = vi;
-    }
+      });
+      vec_store<N, AL>(m + at, mi);
+      vec_store<N, AL>(v + at, vi);
+    });
     sw = wave_sum_d(sw);
     su = wave_sum_d(su);
     if (lane == 0) { partials[ch] = sw; partials[nchunk + ch] = su; }
@@ -679,6 +658,11 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_final_kernel(const double* _
     q[seg] = (float)t;
   }
 }
+// its launch: one wave per segment
+template <int MODE, class... A> static inline void seg_final_launch(int nseg, void* stream, A... args) {
+  hipLaunchKernelGGL((seg_final_kernel<MODE>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), dim3(SOLVER_BLOCK), 0,
+                     (hipStream_t)stream, args...);
+}
 
 // ---- apply passes ----
 template <bool AL>
@@ -695,32 +679,19 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restr
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
     const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
-    const int nv = cnt >> 2, rem = cnt & 3;
-    for (int i = lane; i < nv; i += 64) {
-      const int at = first + 4 * i;
-      float wi[4], vi[4], gi[4], ei[4];
-      seg_load4<AL>(w + at, wi);
-      seg_load4<AL>(v + at, vi);
-      seg_load4<AL>(g + at, gi);
-      if (ema) seg_load4<AL>(ema + at, ei);
-#pragma unroll
-      for (int e = 0; e < 4; e++) lars_step(wi[e], vi[e], gi[e], l2, qt, lr, mom, wd, c);
-      seg_store4<AL>(v + at, vi);
-      seg_store4<AL>(w + at, wi);
-      if (ema) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-        seg_store4<AL>(ema + at, ei);
-      }
-    }
-    if (lane < rem) {
-      const int at = first + 4 * nv + lane;
-      float wi = w[at], vi = v[at];
-      lars_step(wi, vi, g[at], l2, qt, lr, mom, wd, c);
-      v[at] = vi;
-      w[at] = wi;
-      if (ema) ema[at] = ema_step(ema[at], wi, omd);
-    }
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float wi[N], vi[N], gi[N];
+      vec_load<N, AL>(w + at, wi);
+      vec_load<N, AL>(v + at, vi);
+      vec_load<N, AL>(g + at, gi);
+      EmaPass<N, AL> ea;
+      if (ema) ea.load(ema + at);
+      solver_each<N>([&](int e) { lars_step(wi[e], vi[e], gi[e], l2, qt, lr, mom, wd, c); });
+      vec_store<N, AL>(v + at, vi);
+      vec_store<N, AL>(w + at, wi);
+      if (ema) ea.apply(ema + at, wi, omd);
+    });
   }
 }
 
@@ -737,35 +708,21 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
-    const int nv = cnt >> 2, rem = cnt & 3;
-    for (int i = lane; i < nv; i += 64) {
-      const int at = first + 4 * i;
-      float wi[4], mi[4], vi[4], gi[4], ei[4];
-      seg_load4<AL>(w + at, wi);
-      seg_load4<AL>(m + at, mi);
-      seg_load4<AL>(v + at, vi);
-      seg_load4<AL>(g + at, gi);
-      if (ema) seg_load4<AL>(ema + at, ei);
-#pragma unroll
-      for (int e = 0; e < 4; e++) adamw_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, ld, c);
-      seg_store4<AL>(m + at, mi);
-      seg_store4<AL>(v + at, vi);
-      seg_store4<AL>(w + at, wi);
-      if (ema) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-        seg_store4<AL>(ema + at, ei);
-      }
-    }
-    if (lane < rem) {
-      const int at = first + 4 * nv + lane;
-      float wi = w[at], mi = m[at], vi = v[at];
-      adamw_step(wi, mi, vi, g[at], l2, lr_t, b1, b2, eps, ld, c);
-      m[at] = mi;
-      v[at] = vi;
-      w[at] = wi;
-      if (ema) ema[at] = ema_step(ema[at], wi, omd);
-    }
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float wi[N], mi[N], vi[N], gi[N];
+      vec_load<N, AL>(w + at, wi);
+      vec_load<N, AL>(m + at, mi);
+      vec_load<N, AL>(v + at, vi);
+      vec_load<N, AL>(g + at, gi);
+      EmaPass<N, AL> ea;
+      if (ema) ea.load(ema + at);
+      solver_each<N>([&](int e) { adamw_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, ld, c); });
+      vec_store<N, AL>(m + at, mi);
+      vec_store<N, AL>(v + at, vi);
+      vec_store<N, AL>(w + at, wi);
+      if (ema) ea.apply(ema + at, wi, omd);
+    });
   }
 }
 
@@ -783,29 +740,18 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_apply_kernel(float* __restr
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
     const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
     const float lq = lr * qt;
-    const int nv = cnt >> 2, rem = cnt & 3;
-    for (int i = lane; i < nv; i += 64) {
-      const int at = first + 4 * i;
-      float wi[4], mi[4], vi[4], ei[4];
-      seg_load4<AL>(w + at, wi);
-      seg_load4<AL>(m + at, mi);
-      seg_load4<AL>(v + at, vi);
-      if (ema) seg_load4<AL>(ema + at, ei);
-#pragma unroll
-      for (int e = 0; e < 4; e++) wi[e] = lamb_apply(wi[e], lamb_u(wi[e], mi[e], vi[e], l2, r, eps, decay), lq);
-      seg_store4<AL>(w + at, wi);
-      if (ema) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) ei[e] = ema_step(ei[e], wi[e], omd);
-        seg_store4<AL>(ema + at, ei);
-      }
-    }
-    if (lane < rem) {
-      const int at = first + 4 * nv + lane;
-      const float wi = lamb_apply(w[at], lamb_u(w[at], m[at], v[at], l2, r, eps, decay), lq);
-      w[at] = wi;
-      if (ema) ema[at] = ema_step(ema[at], wi, omd);
-    }
+    seg_for_items(first, cnt, lane, [&](auto nc, int at) {
+      constexpr int N = decltype(nc)::value;
+      float wi[N], mi[N], vi[N];
+      vec_load<N, AL>(w + at, wi);
+      vec_load<N, AL>(m + at, mi);
+      vec_load<N, AL>(v + at, vi);
+      EmaPass<N, AL> ea;
+      if (ema) ea.load(ema + at);
+      solver_each<N>([&](int e) { wi[e] = lamb_apply(wi[e], lamb_u(wi[e], mi[e], vi[e], l2, r, eps, decay), lq); });
+      vec_store<N, AL>(w + at, wi);
+      if (ema) ea.apply(ema + at, wi, omd);
+    });
   }
 }
 
@@ -820,13 +766,10 @@ extern "C" int x3d_seg_sumsq(const float* a, const int* chunks, int nchunk, cons
   X3D_REQUIRE(a && partials && out, "seg_sumsq: bad args");
   SEG_REQUIRE_TABLE("seg_sumsq");
   X3D_REQUIRE(((uintptr_t)a & 3) == 0 && (((uintptr_t)partials | (uintptr_t)out) & 7) == 0, "seg_sumsq: misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
-  if (seg_aligned(a)) hipLaunchKernelGGL((seg_sumsq_kernel<true>), grid, block, 0, st, a, chunks, nchunk, partials);
-  else hipLaunchKernelGGL((seg_sumsq_kernel<false>), grid, block, 0, st, a, chunks, nchunk, partials);
-  hipLaunchKernelGGL((seg_final_kernel<SEG_SUM>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
-                     (const double*)partials, nchunk, segs, nseg, 0.f, 0.f, 1.f, 0.f, 0.f, 0, (const double*)nullptr, 0.f, out,
-                     (float*)nullptr);
+  solver_launch(seg_aligned(a), seg_sumsq_kernel<true>, seg_sumsq_kernel<false>, seg_grid(nchunk), stream, a, chunks, nchunk,
+                partials);
+  seg_final_launch<SEG_SUM>(nseg, stream, (const double*)partials, nchunk, segs, nseg, 0.f, 0.f, 1.f, 0.f, 0.f, 0,
+                            (const double*)nullptr, 0.f, out, (float*)nullptr);
   X3D_LAUNCH_CHECK("seg_sumsq");
   return X3D_OK;
 }
@@ -843,19 +786,14 @@ extern "C" int x3d_lars(float* w, float* v, const float* g, const int* chunks, i
   X3D_REQUIRE(seg_finite_ge0(eps) && seg_finite_ge0(weight_decay), "lars: eps and weight_decay must be >= 0 and finite");
   X3D_REQUIRE(!clip || lr > 0.f, "lars: clip needs lr > 0");
   SOLVER_REQUIRE_EXTRAS("lars");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
-  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
+  const unsigned grid = seg_grid(nchunk);
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
   const bool al = seg_aligned(w, v, g, ema);
-  if (al) hipLaunchKernelGGL((lars_sums_kernel<true>), grid, block, 0, st, (const float*)w, g, chunks, nchunk, norm, partials);
-  else hipLaunchKernelGGL((lars_sums_kernel<false>), grid, block, 0, st, (const float*)w, g, chunks, nchunk, norm, partials);
-  hipLaunchKernelGGL((seg_final_kernel<SEG_LARS>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
-                     (const double*)partials, nchunk, segs, nseg, lr, weight_decay, grad_scale, trust_coef, eps, clip, norm, nm,
-                     (double*)nullptr, q);
-#define ARGS w, v, g, chunks, nchunk, segs, (const float*)q, lr, momentum, weight_decay, grad_scale, norm, nm, ema, omd
-  if (al) hipLaunchKernelGGL((lars_apply_kernel<true>), grid, block, 0, st, ARGS);
-  else hipLaunchKernelGGL((lars_apply_kernel<false>), grid, block, 0, st, ARGS);
-#undef ARGS
+  solver_launch(al, lars_sums_kernel<true>, lars_sums_kernel<false>, grid, stream, w, g, chunks, nchunk, norm, partials);
+  seg_final_launch<SEG_LARS>(nseg, stream, (const double*)partials, nchunk, segs, nseg, lr, weight_decay, grad_scale, trust_coef,
+                             eps, clip, norm, x.nm, (double*)nullptr, q);
+  solver_launch(al, lars_apply_kernel<true>, lars_apply_kernel<false>, grid, stream, w, v, g, chunks, nchunk, segs, q, lr,
+                momentum, weight_decay, grad_scale, norm, x.nm, ema, x.omd);
   X3D_LAUNCH_CHECK("lars");
   return X3D_OK;
 }
@@ -868,14 +806,10 @@ extern "C" int x3d_adamw(float* w, float* m, float* v, const float* g, const int
   X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "adamw: misaligned pointer");
   X3D_REQUIRE(seg_finite_ge0(decay), "adamw: decay must be >= 0 and finite");
   SOLVER_REQUIRE_EXTRAS("adamw");
-  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
-  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
-  const float lr_t = (float)adam_lr_t(lr, beta1, beta2, step);
-  const float ld = lr * decay;
-#define ARGS w, m, v, g, chunks, nchunk, segs, lr_t, beta1, beta2, eps, ld, grad_scale, norm, nm, ema, omd
-  if (seg_aligned(w, m, v, g, ema)) hipLaunchKernelGGL((adamw_kernel<true>), grid, block, 0, (hipStream_t)stream, ARGS);
-  else hipLaunchKernelGGL((adamw_kernel<false>), grid, block, 0, (hipStream_t)stream, ARGS);
-#undef ARGS
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
+  solver_launch(seg_aligned(w, m, v, g, ema), adamw_kernel<true>, adamw_kernel<false>, seg_grid(nchunk), stream, w, m, v, g,
+                chunks, nchunk, segs, (float)adam_lr_t(lr, beta1, beta2, step), beta1, beta2, eps, lr * decay, grad_scale, norm,
+                x.nm, ema, x.omd);
   X3D_LAUNCH_CHECK("adamw");
   return X3D_OK;
 }
@@ -891,21 +825,16 @@ extern "C" int x3d_lamb(float* w, float* m, float* v, const float* g, const int*
   X3D_REQUIRE(eps > 0.f && eps <= 3.0e38f, "lamb: eps must be positive and finite");
   X3D_REQUIRE(seg_finite_ge0(decay), "lamb: decay must be >= 0 and finite");
   SOLVER_REQUIRE_EXTRAS("lamb");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(seg_grid(nchunk)), block(SOLVER_BLOCK);
-  const float nm = norm ? max_norm : 0.f, omd = ema ? 1.f - ema_decay : 0.f;
+  const unsigned grid = seg_grid(nchunk);
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
   const float r = (float)adam_lr_t(1.f, beta1, beta2, step);
   const bool al = seg_aligned(w, m, v, g, ema);
-#define ARGS (const float*)w, m, v, g, chunks, nchunk, segs, r, beta1, beta2, eps, decay, grad_scale, norm, nm, partials
-  if (al) hipLaunchKernelGGL((lamb_moments_kernel<true>), grid, block, 0, st, ARGS);
-  else hipLaunchKernelGGL((lamb_moments_kernel<false>), grid, block, 0, st, ARGS);
-#undef ARGS
-  hipLaunchKernelGGL((seg_final_kernel<SEG_LAMB>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), block, 0, st,
-                     (const double*)partials, nchunk, segs, nseg, lr, 0.f, grad_scale, 0.f, 0.f, 0, norm, nm, (double*)nullptr, q);
-#define ARGS w, (const float*)m, (const float*)v, chunks, nchunk, segs, (const float*)q, lr, r, eps, decay, norm, ema, omd
-  if (al) hipLaunchKernelGGL((lamb_apply_kernel<true>), grid, block, 0, st, ARGS);
-  else hipLaunchKernelGGL((lamb_apply_kernel<false>), grid, block, 0, st, ARGS);
-#undef ARGS
+  solver_launch(al, lamb_moments_kernel<true>, lamb_moments_kernel<false>, grid, stream, w, m, v, g, chunks, nchunk, segs, r,
+                beta1, beta2, eps, decay, grad_scale, norm, x.nm, partials);
+  seg_final_launch<SEG_LAMB>(nseg, stream, (const double*)partials, nchunk, segs, nseg, lr, 0.f, grad_scale, 0.f, 0.f, 0, norm,
+                             x.nm, (double*)nullptr, q);
+  solver_launch(al, lamb_apply_kernel<true>, lamb_apply_kernel<false>, grid, stream, w, m, v, chunks, nchunk, segs, q, lr, r, eps,
+                decay, norm, ema, x.omd);
   X3D_LAUNCH_CHECK("lamb");
   return X3D_OK;
 }

@@ -598,17 +598,6 @@ class X3D:
                  self._norm_out.data_ptr())
         return self._norm_out
 
-    def _solver_extras(self, norm, max_norm, ema):
-        """(norm pointer, ema pointer) of an _ex launch, checked: `ema` covers at least the trainable block."""
-        if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2 or not norm.is_cuda):
-            raise ValueError("norm must be the device [2] float64 tensor of grad_norm_sq()")
-        if norm is not None and not float(max_norm) > 0.0:
-            raise ValueError(f"max_norm must be positive with norm, not {max_norm}")
-        if ema is not None and (ema.dtype != torch.float32 or ema.numel() < self.n_trainable_flat or not ema.is_cuda
-                                or not ema.is_contiguous()):
-            raise ValueError(f"ema must be a contiguous device float32 buffer of at least {self.n_trainable_flat} elements")
-        return (None if norm is None else norm.data_ptr()), (None if ema is None else ema.data_ptr())
-
     def apply_sgd(self, lr, momentum=0.9, grad_scale=1.0, norm=None, max_norm=0.0, ema=None, ema_decay=0.0):
         """SGD(momentum, nesterov=True) + L2 (reference train.py:89-92, model.py:47), one launch.
         norm (grad_norm_sq()) + max_norm: the gradient is clipped to that global L2 norm and a non-finite gradient skips
@@ -620,30 +609,30 @@ class X3D:
                      self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
                      float(self.arch.weight_decay), float(grad_scale), self.n_trainable_flat)
             return
-        pn, pe = self._solver_extras(norm, max_norm, ema)
+        from . import ops
+        ops.solver_extras("apply_sgd", norm, max_norm, ema, ema_decay, self.n_trainable_flat)
         hip.call("x3d_sgd_nesterov_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
                  self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
-                 float(self.arch.weight_decay), float(grad_scale), pn, float(max_norm), pe, float(ema_decay),
-                 self.n_trainable_flat)
+                 float(self.arch.weight_decay), float(grad_scale), hip.ptr(norm), float(max_norm), hip.ptr(ema),
+                 float(ema_decay), self.n_trainable_flat)
 
     def apply_adam(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, norm=None, max_norm=0.0, ema=None,
                    ema_decay=0.0):
         """Adam + L2 (reference train.py:93-95: tf.optimizers.Adam(learning_rate), Keras defaults), one launch.  The first
         moment lives in `flat_velocity` (the slot the SGD branch uses for momentum), the second in `flat_second`.
         norm / max_norm / ema / ema_decay: as apply_sgd (x3d_adam_ex)."""
-        self._claim_slots("adam")
-        if getattr(self, "flat_second", None) is None:
-            self.flat_second = torch.zeros_like(self.flat_velocity)
+        self._adam_slots()
         if norm is None and ema is None:
             hip.call("x3d_adam", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
                      self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
                      float(self.arch.weight_decay), float(grad_scale), int(step), self.n_trainable_flat)
             return
-        pn, pe = self._solver_extras(norm, max_norm, ema)
+        from . import ops
+        ops.solver_extras("apply_adam", norm, max_norm, ema, ema_decay, self.n_trainable_flat)
         hip.call("x3d_adam_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
                  self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
-                 float(self.arch.weight_decay), float(grad_scale), int(step), pn, float(max_norm), pe, float(ema_decay),
-                 self.n_trainable_flat)
+                 float(self.arch.weight_decay), float(grad_scale), int(step), hip.ptr(norm), float(max_norm), hip.ptr(ema),
+                 float(ema_decay), self.n_trainable_flat)
 
     # -- the layer-wise optimizers: a fixed number of launches over the chunk table, per-tensor trust ratios on the device --
     @property
@@ -655,6 +644,12 @@ class X3D:
             self._seg_partials = torch.empty(2 * self._seg_table.nchunk, dtype=torch.float64, device=self.device)
             self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
         return self._seg_table
+
+    def _ema_covers_block(self, op, ema):
+        """ops.lars / adamw / lamb check norm, max_norm, ema and ema_decay (ops.solver_extras) against the chunk table, which ends
+        at the last tensor's last element; the model's EMA buffer also has to hold the padding behind it."""
+        if ema is not None and ema.numel() < self.n_trainable_flat:
+            raise ValueError(f"{op}: ema must hold at least {self.n_trainable_flat} elements, got {ema.numel()}")
 
     def _adam_slots(self):
         self._claim_slots("adam")
@@ -671,7 +666,7 @@ class X3D:
         from . import ops
         self._claim_slots("sgd")
         tb = self.seg_table
-        self._solver_extras(norm, max_norm, ema)
+        self._ema_covers_block("apply_lars", ema)
         return ops.lars(self.flat_params, self.flat_velocity, self.flat_grads, tb, lr, momentum, self.arch.weight_decay,
                         trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
 
@@ -681,7 +676,7 @@ class X3D:
         then w -= lr * decay * w_old on the conv / dense kernels (x3d_adamw).  Slots and checkpoint layout: Adam's.  One launch."""
         from . import ops
         self._adam_slots()
-        self._solver_extras(norm, max_norm, ema)
+        self._ema_covers_block("apply_adamw", ema)
         ops.adamw(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self.seg_table, lr, step, beta1,
                   beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
 
@@ -693,7 +688,7 @@ class X3D:
         from . import ops
         self._adam_slots()
         tb = self.seg_table
-        self._solver_extras(norm, max_norm, ema)
+        self._ema_covers_block("apply_lamb", ema)
         return ops.lamb(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, tb, lr, step, beta1, beta2, eps,
                         decay, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
 

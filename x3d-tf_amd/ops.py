@@ -768,11 +768,16 @@ def _seg_scratch(op, table, partials, q, device):
     return partials, q
 
 
-def _seg_extras(op, norm, max_norm, ema_decay, ema):
-    if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2):
-        raise ValueError(f"{op}: norm must be the [2] float64 result of grad_sumsq")
+def solver_extras(op, norm, max_norm, ema, ema_decay, n):
+    """The norm / max_norm / ema / ema_decay arguments of the _ex and the layer-wise launches, checked in one place for lars /
+    adamw / lamb here and X3D.apply_sgd / apply_adam: norm is grad_sumsq's device result and brings a positive max_norm, ema is a
+    flat device buffer of at least n elements and brings a decay in [0, 1)."""
+    if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2 or not norm.is_cuda):
+        raise ValueError(f"{op}: norm must be the device [2] float64 result of grad_sumsq")
     if norm is not None and not float(max_norm) > 0.0:
         raise ValueError(f"{op}: max_norm must be positive with norm, not {max_norm}")
+    if ema is not None and (ema.dtype != torch.float32 or ema.numel() < n or not ema.is_cuda or not ema.is_contiguous()):
+        raise ValueError(f"{op}: ema must be a contiguous device float32 buffer of at least {n} elements")
     if ema is not None and not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"{op}: ema_decay must lie in [0, 1), not {ema_decay}")
 
@@ -799,7 +804,7 @@ def lars(w, v, g, table, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8,
     """LARS on the segments of `table` (x3d_lars: the rule is in include/x3d_hip.h); returns q [nseg] fp32, the trust ratios,
     on the device.  Three launches, does not synchronise; g is not written."""
     _seg_table("lars", table, ("w", w), ("v", v), ("g", g), ("ema", ema))
-    _seg_extras("lars", norm, max_norm, ema_decay, ema)
+    solver_extras("lars", norm, max_norm, ema, ema_decay, table.end)
     if not float(trust_coef) > 0.0 or float(eps) < 0.0:
         raise ValueError(f"lars: trust_coef must be positive and eps >= 0, not {trust_coef}, {eps}")
     partials, q = _seg_scratch("lars", table, partials, q, w.device)
@@ -813,7 +818,7 @@ def adamw(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0
           ema=None, ema_decay=0.0):
     """Adam with decoupled weight decay on the l2 segments of `table` (x3d_adamw).  One launch, does not synchronise."""
     _seg_table("adamw", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    _seg_extras("adamw", norm, max_norm, ema_decay, ema)
+    solver_extras("adamw", norm, max_norm, ema, ema_decay, table.end)
     if float(decay) < 0.0 or int(step) < 1:
         raise ValueError(f"adamw: decay must be >= 0 and step >= 1, not {decay}, {step}")
     hip.call("x3d_adamw", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
@@ -826,7 +831,7 @@ def lamb(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.
     """LAMB on the segments of `table` (x3d_lamb); returns q [nseg] fp32, the trust ratios, on the device.  Three launches, does
     not synchronise; g is not written."""
     _seg_table("lamb", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    _seg_extras("lamb", norm, max_norm, ema_decay, ema)
+    solver_extras("lamb", norm, max_norm, ema, ema_decay, table.end)
     if float(decay) < 0.0 or not float(eps) > 0.0 or int(step) < 1:
         raise ValueError(f"lamb: decay must be >= 0, eps > 0 and step >= 1, not {decay}, {eps}, {step}")
     partials, q = _seg_scratch("lamb", table, partials, q, w.device)
