@@ -54,7 +54,8 @@ extern "C" {
  *   137 x3d_mix_clips / x3d_mix_targets / x3d_softmax_xent_soft (mixup, CutMix and label smoothing);
  *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing);
  *   138 (additions only, no bump) x3d_drop_path_draw / x3d_tail_fwd_dp / x3d_tail_bwd_dp (stochastic depth);
- *   138 (additions only, no bump) x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb (layer-wise optimizers). */
+ *   138 (additions only, no bump) x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb (layer-wise optimizers);
+ *   138 (additions only, no bump) x3d_precise_bn_accum / x3d_precise_bn_final (precise BatchNorm statistics). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -169,6 +170,46 @@ int x3d_bn_eval_coef_batched(const x3d_bn_eval_item* items, int n_items, float e
 int x3d_bn_bwd_finalize(const double* sums, double count, const float* mean_invstd,
                         const float* gamma, float* coef, float* dgamma, float* dbeta, int C,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K3p precise BatchNorm (NETWORK.BN.USE_PRECISE_STATS; PySlowFast BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE, fvcore
+ *     update_bn_stats): the moving statistics recomputed exactly from K training-mode forward passes instead of trusted to
+ *     the momentum blend.  Added under ABI 138 without a version bump: new symbols and constants only.
+ *     The raw fp64 sums are already on the device: every training plan keeps, per BatchNorm layer, the replicated `stats`
+ *     accumulator its producer added into (REPLICATED STATISTICS above), intact after a forward pass.  So pooling K batches is
+ *     one small launch per batch and one at the end; no second pass over activations, nothing returns to the host.
+ *   table  [nlayers][X3D_PBN_COLS] int64 in DEVICE memory, one row per BatchNorm layer:
+ *            X3D_PBN_STATS   address of the layer's `stats` accumulator (x3d_stats_replicas() copies, x3d_stats_stride(C) apart)
+ *            X3D_PBN_C       channels
+ *            X3D_PBN_COUNT   elements per channel the producer summed in one forward pass (N*T*H*W of the layer's output)
+ *            X3D_PBN_MEAN    element offset of the layer's moving mean [C] in `params`
+ *            X3D_PBN_VAR     element offset of its moving variance [C] in `params`
+ *            X3D_PBN_POOLED  element offset of its [C][2] (sum, sum of squares) in `pooled`
+ *          The kernels trust the table: the caller builds and checks it (x3d_tf_amd/plan.py).  Tables of different batch
+ *          shapes differ in X3D_PBN_STATS and X3D_PBN_COUNT only and may feed the same `pooled`.
+ *   pooled one fp64 buffer, the caller's, zeroed before the first batch: nlayers pooled counts, then every layer's [C][2] sums
+ *          at its X3D_PBN_POOLED offset (>= nlayers).  One buffer, so that ONE all-reduce (sum) pools data-parallel ranks.
+ *   x3d_precise_bn_accum: per channel, the copies of `stats` are added in the pairwise tree of x3d_bn_finalize / x3d_bn_fold
+ *          (eights as ((0+1)+(2+3))+((4+5)+(6+7)), then (q0+q1)+(q2+q3)) and the totals added to `pooled`; one thread per
+ *          layer adds X3D_PBN_COUNT to the layer's count slot.  One thread per channel, no atomics, a fixed order: the same
+ *          inputs give the same bits on every run.  `stats` is read only.
+ *   x3d_precise_bn_final: with n = the pooled count, per channel  mean = S1 / n ; var = max(S2 / n - mean^2, 0) ;
+ *          unb = n > 1 ? var * (n / (n - 1)) : var ;  params[X3D_PBN_MEAN + c] = (float)mean, params[X3D_PBN_VAR + c] =
+ *          (float)unb -- what x3d_bn_finalize hands to its moving update: after ONE accum the result equals, bit for bit, what
+ *          x3d_bn_finalize(momentum = 0, update_moving = 1) writes from the same accumulator.  Whatever the moving statistics
+ *          held is overwritten.  A layer whose pooled count is 0 gets NaN: run at least one accum first.
+ *   One launch each, all layers at once.  Refused before the launch (X3D_ERR_INVALID): a null pointer, nlayers < 1, a table
+ *   or pooled pointer that is not 8-byte, a params pointer that is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_PBN_COLS 6
+#define X3D_PBN_STATS 0
+#define X3D_PBN_C 1
+#define X3D_PBN_COUNT 2
+#define X3D_PBN_MEAN 3
+#define X3D_PBN_VAR 4
+#define X3D_PBN_POOLED 5
+int x3d_precise_bn_accum(const long long* table, int nlayers, double* pooled, void* stream);
+int x3d_precise_bn_final(const long long* table, int nlayers, const double* pooled, float* params, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K5  pointwise Conv3D(k=1, no bias) as a GEMM over points on MFMA: bottleneck a / c, shortcut

@@ -120,7 +120,8 @@ def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA),
-    NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb)."""
+    NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
+    NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -128,7 +129,9 @@ def get_default_config():
         # stochastic depth (PySlowFast's DROPCONNECT_RATE): the chance that the bottleneck branch of the LAST residual block is
         # dropped for a sample of a training step; linear in depth from 0 at the first block (0 = off)
         DROP_PATH_RATE=0.0,
-        BN=dict(MOMENTUM=0.9, EPS=1e-5)))
+        # USE_PRECISE_STATS (PySlowFast's BN section): Trainer.fit recomputes every layer's moving statistics exactly, from
+        # NUM_BATCHES_PRECISE training batches, after each epoch's steps -- before its validation and its checkpoint
+        BN=dict(MOMENTUM=0.9, EPS=1e-5, USE_PRECISE_STATS=False, NUM_BATCHES_PRECISE=200)))
     c.DATA = CfgNode(dict(
         FRAME_RATE=1, TEMP_DURATION=1, NUM_INPUT_CHANNELS=3, TRAIN_JITTER_SCALES=[182, 228],
         TRAIN_CROP_SIZE=112, TEST_CROP_SIZE=160, MEAN=[0.45, 0.45, 0.45],
@@ -189,6 +192,7 @@ def get_config(name, overrides=None, freeze=True):
     solver_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
+    precise_bn_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -406,3 +410,16 @@ def drop_path_settings(cfg) -> float:
     if not 0.0 <= rate < 1.0:           # (NaN fails too)
         raise ValueError(f"NETWORK.DROP_PATH_RATE must lie in [0, 1), not {rate}")
     return rate
+
+
+PreciseBNSettings = collections.namedtuple("PreciseBNSettings", "enable num_batches")
+
+
+def precise_bn_settings(cfg) -> PreciseBNSettings:
+    """cfg.NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE as one tuple (a config tree without the keys: off, 200 batches).
+    ValueError for a NUM_BATCHES_PRECISE that is not an integer >= 1 -- checked whether the switch is on or not."""
+    bn = getattr(cfg.NETWORK, "BN", None)
+    num = getattr(bn, "NUM_BATCHES_PRECISE", 200)
+    if isinstance(num, bool) or not isinstance(num, int) or num < 1:
+        raise ValueError(f"NETWORK.BN.NUM_BATCHES_PRECISE must be an integer >= 1, not {num!r}")
+    return PreciseBNSettings(bool(getattr(bn, "USE_PRECISE_STATS", False)), num)

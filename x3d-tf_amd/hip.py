@@ -148,6 +148,9 @@ RA_OPS = {name: _CONSTS["RA_" + const] for name, const in dict(
 RA_CLIP_COLS, RA_OP_COLS, RA_X_COLS, RA_FRAC_BITS = _consts("RA_CLIP_COLS", "RA_OP_COLS", "RA_X_COLS", "RA_FRAC_BITS")
 RA_O_OP, RA_O_IARG, RA_O_FARG, RA_X_A, RA_X_SRC, RA_X_DST = _consts("RA_O_OP", "RA_O_IARG", "RA_O_FARG", "RA_X_A", "RA_X_SRC",
                                                                     "RA_X_DST")
+# columns of the int64 layer table of x3d_precise_bn_accum / x3d_precise_bn_final (plan._Plan.precise_bn_table)
+PBN_COLS, PBN_STATS, PBN_C, PBN_COUNT, PBN_MEAN, PBN_VAR, PBN_POOLED = _consts("PBN_COLS", "PBN_STATS", "PBN_C", "PBN_COUNT",
+                                                                               "PBN_MEAN", "PBN_VAR", "PBN_POOLED")
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_MALFORMED, JPEG_CORRUPT, JPEG_SKIPPED = _consts(
     "JPEG_OK", "JPEG_UNSUPPORTED", "JPEG_MALFORMED", "JPEG_CORRUPT", "JPEG_SKIPPED")
 

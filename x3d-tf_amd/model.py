@@ -17,6 +17,7 @@ AND backward -- `stem_s_wgrad` reads them again, so the caller must not overwrit
 captured graph would bake that pointer in.  `options={"stem_nthwc": False}` restores the static planar input
 buffer (one conversion pass per step) for graph capture; replaying as a hipGraph measured no gain.
 """
+import collections
 from typing import Dict, Optional
 
 import torch
@@ -100,6 +101,9 @@ class _Sequential(list):
     """K.Sequential stand-in: an indexable list of layers (``layer_with_weights-i`` order)."""
     pass
 
+
+
+PreciseBNLayout = collections.namedtuple("PreciseBNLayout", "prefixes channels mean_offsets var_offsets pooled_offsets pooled_size")
 
 
 class X3D:
@@ -717,3 +721,21 @@ class X3D:
 
     def moving_stats_flat(self):
         return self.flat_params[self.n_trainable_flat:]
+
+    def precise_bn_layout(self):
+        """Where precise BatchNorm (precise_bn.update_bn_stats) keeps and writes each layer's statistics: a PreciseBNLayout of
+        parallel tuples over the BatchNorm layers, in `param_order` of their moving means -- `prefixes`, `channels`,
+        `mean_offsets` / `var_offsets` (elements into `flat_params`), `pooled_offsets` (elements into the fp64 pooled buffer:
+        the layer's [C][2] sums, behind one count slot per layer) -- and `pooled_size`, that buffer's length.  A function of
+        the architecture alone: plans of different (N, T, H, W) share one pooled buffer (_Plan.precise_bn_table)."""
+        if getattr(self, "_pbn_layout", None) is None:
+            prefixes = [k[:-len("/moving_mean")] for k in self.param_order if k.endswith("/moving_mean")]
+            channels = [self.params[f"{q}/moving_mean"].numel() for q in prefixes]
+            pooled, off = [], len(prefixes)
+            for c in channels:
+                pooled.append(off)
+                off += 2 * c
+            self._pbn_layout = PreciseBNLayout(tuple(prefixes), tuple(channels),
+                                               tuple(self._offsets[f"{q}/moving_mean"] for q in prefixes),
+                                               tuple(self._offsets[f"{q}/moving_variance"] for q in prefixes), tuple(pooled), off)
+        return self._pbn_layout

@@ -105,8 +105,9 @@ def _view(buf, *shape):
 @dataclass
 class BNBuf:
     """The buffers of one BatchNorm layer.  ss / mi: scale-shift and mean-invstd tables [C][2]; training plans add the fp64
-    statistics (`stats`: forward sums, the library's replicated layout; `bsums`: backward sums) as accumulator handles and the
-    backward coefficient table `coef` [C][4]."""
+    statistics (`stats`: forward sums, the library's replicated layout; `bsums`: backward sums) as accumulator handles, the
+    backward coefficient table `coef` [C][4] and `count`, the elements per channel behind `stats` (set where the layer's
+    finalize is recorded; read by precise_bn_table)."""
     prefix: str
     c: int
     ss: Any = None
@@ -114,6 +115,7 @@ class BNBuf:
     stats: Optional[int] = None
     bsums: Optional[int] = None
     coef: Any = None
+    count: Optional[int] = None
 
 
 @dataclass(kw_only=True)
@@ -213,6 +215,8 @@ class _Plan:
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
         self._head_hard = self._head_soft = None   # the two loss launches of a single-label training plan (use_soft_targets)
         self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
+        self.bn_layers: List[BNBuf] = []   # every BatchNorm layer of a training plan, as recorded (precise_bn_table)
+        self._pbn_table = None
 
     # -- allocation ------------------------------------------------------------------------------
     def act(self, *shape):
@@ -250,6 +254,7 @@ class _Plan:
             b.stats = self.acc64(self.model._stats_r * int(self.lib.x3d_stats_stride(c)))
             b.bsums = self.acc64(c, 2)
             b.coef = self.f32(c, 4)
+            self.bn_layers.append(b)
         else:
             p = self.model.params
             self.bn_eval_items.append(hip.BnEvalItem(_p(p[f"{prefix}/gamma"]), _p(p[f"{prefix}/beta"]),
@@ -300,6 +305,44 @@ class _Plan:
         for setter, handle in self._deferred:
             setter(self._zero_views[handle].data_ptr())
         self._deferred = []
+
+    def precise_bn_table(self):
+        """The int64 layer table [layers][PBN_COLS] of x3d_precise_bn_accum / x3d_precise_bn_final (include/x3d_hip.h) for
+        this training plan, built with the first call and kept on the model's device (a dry plan: on the host, with the
+        addresses of its stand-in accumulators).  Rows follow model.precise_bn_layout() -- the same for every plan of the
+        model -- and add what belongs to this plan: where each layer's `stats` lies and how many elements per channel one
+        forward pass sums into it.  The kernels trust the table, so it is checked here: ValueError for a layer the plan did
+        not register exactly once, or registered without `stats` or `count`, and for a channel count or an accumulator size
+        that disagrees with the layout."""
+        if self._pbn_table is not None:
+            return self._pbn_table
+        if not self.training:
+            raise ValueError("precise_bn_table: only a training plan accumulates BatchNorm statistics")
+        lay = self.model.precise_bn_layout()
+        by_prefix = {}
+        for b in self.bn_layers:
+            if b.prefix in by_prefix:
+                raise ValueError(f"precise_bn_table: BatchNorm layer {b.prefix} registered twice")
+            by_prefix[b.prefix] = b
+        if sorted(by_prefix) != sorted(lay.prefixes):
+            odd = sorted(set(by_prefix) ^ set(lay.prefixes))
+            raise ValueError(f"precise_bn_table: the plan's BatchNorm layers are not the model's: {odd}")
+        rows = []
+        for l, prefix in enumerate(lay.prefixes):
+            b = by_prefix[prefix]
+            if b.stats is None or b.count is None:
+                raise ValueError(f"precise_bn_table: {prefix} has no {'stats' if b.stats is None else 'count'}")
+            view = self._zero_views[b.stats] if b.stats < len(self._zero_views) else None
+            want = self.model._stats_r * int(self.lib.x3d_stats_stride(b.c))
+            if b.c != lay.channels[l] or b.count < 1 or view is None or view.numel() != want:
+                raise ValueError(f"precise_bn_table: {prefix}: C = {b.c} (layout {lay.channels[l]}), count = {b.count}, "
+                                 f"accumulator of {None if view is None else view.numel()} doubles (needs {want})")
+            row = [0] * hip.PBN_COLS
+            row[hip.PBN_STATS], row[hip.PBN_C], row[hip.PBN_COUNT] = view.data_ptr(), b.c, b.count
+            row[hip.PBN_MEAN], row[hip.PBN_VAR], row[hip.PBN_POOLED] = lay.mean_offsets[l], lay.var_offsets[l], lay.pooled_offsets[l]
+            rows.append(row)
+        self._pbn_table = torch.tensor(rows, dtype=torch.int64).to(self.model.device)
+        return self._pbn_table
 
     def install_backward(self, bw: Backward):
         self.backward, self.bwd, self.bwd_stage_marks = bw, bw.launches, bw.stage_marks
@@ -623,6 +666,7 @@ def record_training(model, n, t, h, w) -> _Plan:
 def _rec_bn_finalize(model, pl, b: BNBuf, count):
     """after the producer kernel: turn the batch statistics into scale / shift (and update the moving statistics)"""
     p, a = model.params, model.arch
+    b.count = int(count)
     pl.rec(pl.fwd, "x3d_bn_finalize", pl.acc(b.stats), float(count), p[f"{b.prefix}/gamma"], p[f"{b.prefix}/beta"],
            p[f"{b.prefix}/moving_mean"], p[f"{b.prefix}/moving_variance"], float(a.bn_eps), float(a.bn_momentum), 1,
            b.ss, b.mi, b.c)

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
-from .config import OPTIMIZERS, SLOT_KIND, mix_settings, optim_settings, solver_settings
+from .config import OPTIMIZERS, SLOT_KIND, mix_settings, optim_settings, precise_bn_settings, solver_settings
 from .mix import NO_MIX, draw_mix_params
 
 
@@ -154,6 +154,8 @@ class Trainer:
         self._drop_path_seed = int(drop_path_seed) + rank
         if hasattr(model, "set_drop_path_state"):
             model.set_drop_path_state(self._drop_path_seed, 0)
+        # precise BatchNorm (NETWORK.BN.USE_PRECISE_STATS; off by default: `fit` then draws the batches it always drew)
+        self.precise = precise_bn_settings(cfg)
 
     def step(self, clips, labels, lr: Optional[float] = None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
@@ -301,7 +303,7 @@ class Trainer:
 
     def fit(self, dataset, epochs: Optional[int] = None, steps_per_epoch: Optional[int] = None, model_dir: Optional[str] = None,
             initial_epoch: Optional[int] = None, on_step=None, validation_data=None, validation_steps: Optional[int] = None,
-            metrics=_DEFAULT_METRICS, save_freq="epoch"):
+            metrics=_DEFAULT_METRICS, save_freq="epoch", precise_bn_data=None):
         """The loop `model.fit(dataset, epochs, steps_per_epoch, initial_epoch, validation_data, callbacks)` runs in reference
         train.py:145-152, with the metrics it was compiled with (train.py:102-108), its LearningRateScheduler (per-epoch
         `lr_schedule`, train.py:114-125) and ModelCheckpoint (utils.py:128-132) callbacks -- nothing else of the Keras harness
@@ -329,7 +331,16 @@ class Trainer:
 
         SOLVER.* (INTEGRATION.md): with CLIP_GRAD_L2NORM `history["grad_norm"]` is the epoch's mean gradient norm before
         clipping; with ACCUM_STEPS = A every batch is a micro-batch, steps_per_epoch and an integer save_freq must be multiples
-        of A (ValueError); with EMA_DECAY and EMA_EVAL validation runs on the EMA weights (`ema_scope`)."""
+        of A (ValueError); with EMA_DECAY and EMA_EVAL validation runs on the EMA weights (`ema_scope`).
+
+        NETWORK.BN.USE_PRECISE_STATS: after an epoch's training steps, before its validation and its end-of-epoch checkpoint,
+        `precise_bn` recomputes the moving statistics of the raw weights from NUM_BATCHES_PRECISE batches and, with
+        EMA_DECAY, those of the EMA weights (inside `ema_scope`) from the NEXT NUM_BATCHES_PRECISE batches of the same source.
+        precise_bn_data: None -- the batches are drawn from `dataset`, which then has to yield steps + NUM_BATCHES_PRECISE
+            (with EMA: + 2 * NUM_BATCHES_PRECISE) batches per epoch -- or a zero-argument callable returning a fresh iterable,
+            called once per epoch.  Mixup / CutMix are not applied to these batches (PySlowFast's precise-BN loop does not
+            either).  A checkpoint an integer save_freq writes in the middle of an epoch carries whatever statistics exist
+            at that moment: the momentum blend of the steps since the last recomputation."""
         from .evaluate import DeviceMAP, DeviceMetrics
         tr = self.cfg.TRAIN
         epochs = int(tr.EPOCHS if epochs is None else epochs)
@@ -351,6 +362,8 @@ class Trainer:
         if initial_epoch is not None:
             self.epoch = int(initial_epoch)
         val_source = _validation_source(validation_data, epochs - self.epoch)
+        if precise_bn_data is not None and not callable(precise_bn_data):
+            raise ValueError("precise_bn_data must be None or a zero-argument callable returning a fresh iterable of batches")
         it = iter(dataset)
         history = []
         self.history = {"loss": [], "lr": []}
@@ -391,6 +404,11 @@ class Trainer:
                 r = train_m.all_reduce_(self.group).result()
                 for k in metrics:
                     self.history[k].append(r[k])
+            if self.precise.enable:
+                if precise_bn_data is None:
+                    self._fit_precise_bn(it, close=False)          # the training iterator goes on into the next epoch
+                else:
+                    self._fit_precise_bn(iter(precise_bn_data()), close=True)
             if val_source is not None:
                 with (self.ema_scope() if self.ema is not None and self.solver.ema_eval else contextlib.nullcontext()):
                     r = self.validate(val_source(), validation_steps)
@@ -399,6 +417,27 @@ class Trainer:
             if ckpt is not None and writer:
                 self.save_checkpoint(model_dir, ckpt)
         return history
+
+    def precise_bn(self, batches, num_batches: Optional[int] = None) -> int:
+        """precise_bn.update_bn_stats on this replica's model and process group: the moving statistics of the weights in
+        `flat_params` recomputed exactly from the first `num_batches` (default NETWORK.BN.NUM_BATCHES_PRECISE) items of
+        `batches`, pooled over the ranks; returns the batches used.  Inside `ema_scope()` the model is the EMA model, so this
+        computes the EMA weights' statistics, and the swap on exit carries them into `self.ema`."""
+        from .precise_bn import update_bn_stats
+        return update_bn_stats(self.model, batches, self.precise.num_batches if num_batches is None else num_batches,
+                               group=self.group)
+
+    def _fit_precise_bn(self, src, close: bool):
+        """`fit`, end of an epoch: the raw weights' statistics, then the EMA weights' from the batches that follow in the
+        iterator `src`; close: `src` is a fresh reader of this epoch's own (precise_bn_data)"""
+        try:
+            self.precise_bn(src)
+            if self.ema is not None:
+                with self.ema_scope():
+                    self.precise_bn(src)
+        finally:
+            if close and getattr(src, "close", None) is not None:
+                src.close()   # a reader's generator: stops its prefetch thread
 
     def validate(self, batches, steps: Optional[int] = None):
         """`model.evaluate` inside `fit` (reference train.py:148-151): `model(clips, training=False)` over `batches` (the
