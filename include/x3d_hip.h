@@ -341,7 +341,8 @@ typedef struct {
    * a 85-105 us launch), as plain stores into a slab per workgroup at the store rate.  With dw_slab the launch writes
    * x3d_pw_bwd_dw_parts(a) slabs of Cout * Cin floats (dw is not touched) and a LATER launch adds them up in a fixed order:
    * x3d_dw_slab_reduce, or the two reduce slots of x3d_se_bnb_bwd (a small launch that is on the critical path anyway).
-   * x3d_pw_bwd_dw_parts() == 0: the kernel behind this call has no slab form (leave dw_slab NULL). */
+   * x3d_pw_bwd_dw_parts() == 0: the kernel behind this call has no slab form (leave dw_slab NULL) -- also where Cout * Cin is
+   * not a multiple of 4: the reduce adds the slabs up in aligned float4s. */
   float* dw_slab;              /* x3d_pw_bwd_dw_parts(a) * Cout * Cin floats, 16-byte aligned */
   int dw_slab_parts;           /* (ABI 132) the number of slabs dw_slab holds = what x3d_pw_bwd_dw_parts(a) returned when the buffer was
                                 * sized: a launch whose grid differs (another device, another build switch between recording and

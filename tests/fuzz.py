@@ -1,7 +1,9 @@
 """Randomised kernel-parity cases: the kernel-level tests of tests/test_kernels_gpu.py (depthwise forward / fused backward,
 pointwise forward / data gradient / weight gradient, strided shortcut) on RANDOM shapes -- odd widths, ragged rows, point
 counts that are not a multiple of 8, strips cut by row ends, channel counts off the 32-grid -- in all three storage types.
-One generator for the in-suite slice (tests/test_fuzz_gpu.py) and the long sweep (tools/fuzz_parity.py)."""
+One generator for the in-suite slice (tests/test_fuzz_gpu.py) and the long sweep (tools/fuzz_parity.py).
+The fused pointwise backward (x3d_pw_bwd) is not drawn here: its kernels are discrete tile classes that uniform sampling keeps
+missing -- tests/pw_bwd_classes.py enumerates them and draws shapes class by class (tests/test_pw_bwd_classes_gpu.py)."""
 import random
 
 import torch

@@ -335,7 +335,9 @@ def test_pw_bwd_rc(gpu, dtype, shape):
     # the algebraic fold IS the definition up to that operand rounding (2^-9 relative per panel entry for bf16)
     fold_err = (dx_ref - dx_def).abs().max().item() / dx_def.abs().max().item()
     assert fold_err < (2e-2 if dtype == torch.bfloat16 else 3e-3), fold_err
-    if epi == "add":
+    if epi == "store":         # the dense shortcut form (no epilogue operand): the class sweep of tests/pw_bwd_classes.py
+        add, e = None, ops.EPI_STORE
+    elif epi == "add":
         add, addd = rnd((n, cin, t, h, w), dtype, g_)
         dx_ref = dx_ref + addd
         e = ops.EPI_ADD

@@ -648,6 +648,9 @@ extern "C" int x3d_pw_bwd_supported(const x3d_pw_bwd_args* b) { return (b && fb_
 // partial-slab form of the weight-gradient flush (x3d_hip.h dw_slab): the persistent weights-stationary kernels only
 extern "C" int x3d_pw_bwd_dw_parts(const x3d_pw_bwd_args* b) {
   if (!b || b->rc_panel || b->N <= 0 || b->T <= 0 || b->H <= 0 || b->W <= 0) return 0;
+  // a slab is Cout * Cin floats and the slabs lie back to back: the reduce (x3d_dw_slab_reduce, x3d_se_bnb_bwd) adds them up in
+  // aligned float4s and refuses a job whose element count is not a multiple of 4 -- such a layer has no slab form (fp32 atomics)
+  if (((long long)b->Cout * b->Cin) % 4) return 0;
   if (pw_bwd_wst_applies(b)) return pw_bwd_wst_dw_parts(b);
   if (pw_bwd_wsta_applies(b)) return pw_bwd_wsta_dw_parts(b);
   return 0;

@@ -293,6 +293,7 @@ extern "C" int x3d_pw_wgrad(const x3d_pw_wgrad_args* w, void* stream) {
 // in query mode -- the launcher reports its grid instead of launching
 extern "C" int x3d_pw_wgrad_dw_parts(const x3d_pw_wgrad_args* w) {
   if (!w || !w->g || !w->x || x3d_describe.out) return 0;
+  if (((long long)w->Cout * w->Cin) % 4) return 0;      // (the reduce adds aligned float4s: see x3d_pw_bwd_dw_parts)
   int parts = 0;
   int* saved = x3d_parts_query;
   x3d_parts_query = &parts;
