@@ -55,7 +55,9 @@ extern "C" {
  *   138 x3d_train_clips_aug (batched training augmentation: random-resized crop, colour jitter, random erasing);
  *   138 (additions only, no bump) x3d_drop_path_draw / x3d_tail_fwd_dp / x3d_tail_bwd_dp (stochastic depth);
  *   138 (additions only, no bump) x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb (layer-wise optimizers);
- *   138 (additions only, no bump) x3d_precise_bn_accum / x3d_precise_bn_final (precise BatchNorm statistics). */
+ *   138 (additions only, no bump) x3d_precise_bn_accum / x3d_precise_bn_final (precise BatchNorm statistics);
+ *   138 (additions only, no bump) x3d_seg_grad_sumsq / x3d_sgd_pt / x3d_adam_pt / x3d_lars_pt / x3d_adamw_pt / x3d_lamb_pt
+ *       (fine-tuning: frozen tensors and per-tensor learning rates). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -742,6 +744,54 @@ int x3d_adamw(float* w, float* m, float* v, const float* g, const int* chunks, i
 int x3d_lamb(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg, float lr,
              float beta1, float beta2, float eps, float decay, float grad_scale, long long step, const double* norm,
              float max_norm, float* ema, float ema_decay, double* partials, float* q, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Fine-tuning: frozen tensors and per-tensor learning rates (SOLVER.FREEZE / LR_MULT / LAYER_DECAY of the config,
+ * x3d_tf_amd/finetune.py).  Added under ABI 138 without a version bump: new symbols only; every entry point
+ * above keeps its signature and its bits.  All five rules and the gradient reduction walk a chunk table (above) built from the
+ * TUNED tensors only: a frozen tensor is in no chunk, so its weights, slots and ema are never read and never written -- whatever
+ * its gradient holds -- and its gradient is in neither the norm nor the finite count.  (A learning rate of 0 would not do that:
+ * Nesterov momentum still moves w, and 0 * inf is NaN.)
+ *
+ *     lr_scale: NULL (every scale 1), or [nseg] fp32 in device memory, > 0 and finite (the caller's to see to).  The learning
+ *               rate of segment t is lr_t = lr * lr_scale[t], ONE fp32 product, read once per chunk, and it stands wherever the
+ *               rule has lr: both uses in the Nesterov step and the LARC clip min(q_t / lr_t, 1) (sgd, lars); the bias-corrected
+ *               (float)((double)lr_t * sqrt(1 - beta2^step) / (1 - beta1^step)) and ld = lr_t * decay (adam, adamw); lr_t q_t
+ *               (lamb).  The update of segment t therefore has the bits of the plain update at the learning rate fl32(lr *
+ *               lr_scale[t]).
+ *     norm / max_norm / ema / ema_decay: as in the entry point of the same rule, and refused alike.
+ *
+ * x3d_seg_grad_sumsq: x3d_grad_sumsq over the table's chunks -- out[0] = the fp64 sum of squares of the finite g[i] inside
+ *     them, out[1] = the number of non-finite ones (as a double); every `norm` above can be this out[2].  One partial sum and
+ *     one count per chunk (partials: 2 * nchunk doubles; a lane adds its elements in ascending order, the lanes by a fixed
+ *     butterfly), then one launch that adds them in ascending order: no atomics, the same bits on every run and on either
+ *     alignment path.  Two launches.
+ * x3d_sgd_pt / x3d_adam_pt: x3d_sgd_nesterov_ex / x3d_adam_ex on the chunk walk; the l2 flag is segs[t][2], not a byte mask.
+ *     One launch each.
+ * x3d_lars_pt / x3d_adamw_pt / x3d_lamb_pt: x3d_lars / x3d_adamw / x3d_lamb -- the same three / one / three launches of the
+ *     same kernels, instantiated with lr_t per segment.  q [nseg] is in the order of the table's segments.
+ * lr_scale == NULL (or all 1) and a table over all segments: bit-identical to the entry point of the same rule (for sgd / adam:
+ *     on every segment, with its mask = l2_t).  Refused before any launch: what that entry point refuses, and an lr_scale that
+ *     is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int x3d_seg_grad_sumsq(const float* g, const int* chunks, int nchunk, const int* segs, int nseg, double* partials, double* out,
+                       void* stream);
+int x3d_sgd_pt(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+               const float* lr_scale, float lr, float momentum, float weight_decay, float grad_scale, const double* norm,
+               float max_norm, float* ema, float ema_decay, void* stream);
+int x3d_adam_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                const float* lr_scale, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                long long step, const double* norm, float max_norm, float* ema, float ema_decay, void* stream);
+int x3d_lars_pt(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                const float* lr_scale, float lr, float momentum, float weight_decay, float grad_scale, float trust_coef,
+                float eps, int clip, const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
+                void* stream);
+int x3d_adamw_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                 const float* lr_scale, float lr, float beta1, float beta2, float eps, float decay, float grad_scale,
+                 long long step, const double* norm, float max_norm, float* ema, float ema_decay, void* stream);
+int x3d_lamb_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                const float* lr_scale, float lr, float beta1, float beta2, float eps, float decay, float grad_scale,
+                long long step, const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
+                void* stream);
 /* LossScaleOptimizer support (Keras mixed_float16, train.py:99-100): *flag (device int the caller set to 1) is cleared
  * when any of the n values is inf / nan -- the step is then skipped and the loss scale halved. */
 int x3d_all_finite(const float* g, long long n, int* flag, void* stream);

@@ -18,19 +18,32 @@ _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs"
 
 
 class CfgNode(dict):
-    """Attribute-access dict with freeze, in the shape of yacs.config.CfgNode."""
+    """Attribute-access dict with freeze, in the shape of yacs.config.CfgNode.
+
+    optional: {key: default} of keys the section KNOWS but does not hold until a config file or an override sets them.  Reading
+    one as an attribute gives its default, merging one is allowed (and type-checked against the default), and the section's
+    items -- what `dict(node)`, iteration and a saved config show -- are what they were without them."""
 
     _FROZEN = "__frozen__"
+    _OPTIONAL = "__optional__"
 
-    def __init__(self, init=None):
+    def __init__(self, init=None, optional=None):
         super().__init__()
         object.__setattr__(self, CfgNode._FROZEN, False)
+        object.__setattr__(self, CfgNode._OPTIONAL, copy.deepcopy(dict(optional or {})))
         for k, v in (init or {}).items():
             self[k] = CfgNode(v) if isinstance(v, dict) and not isinstance(v, CfgNode) else v
+
+    def optional_keys(self):
+        return object.__getattribute__(self, CfgNode._OPTIONAL)
 
     def __getattr__(self, name):
         try:
             return self[name]
+        except KeyError:
+            pass
+        try:
+            return copy.deepcopy(self.optional_keys()[name])
         except KeyError:
             raise AttributeError(name)
 
@@ -63,7 +76,7 @@ class CfgNode(dict):
         return copy.deepcopy(self)
 
     def __deepcopy__(self, memo):
-        out = CfgNode()
+        out = CfgNode(optional=self.optional_keys())
         for k, v in self.items():
             dict.__setitem__(out, k, copy.deepcopy(v, memo))
         return out
@@ -82,7 +95,7 @@ class CfgNode(dict):
     def merge_from_dict(self, other, _path=""):
         for k, v in other.items():
             full = f"{_path}.{k}" if _path else k
-            if k not in self:
+            if k not in self and k not in self.optional_keys():
                 raise KeyError(f"Non-existent config key: {full}")
             if isinstance(v, dict):
                 if not isinstance(self[k], CfgNode):
@@ -90,7 +103,7 @@ class CfgNode(dict):
                 self[k].merge_from_dict(v, full)
             else:
                 v = CfgNode._decode(v)
-                old = self[k]
+                old = self[k] if k in self else self.optional_keys()[k]
                 if isinstance(old, float) and isinstance(v, int) and not isinstance(v, bool):
                     v = float(v)
                 if isinstance(old, tuple) and isinstance(v, list):
@@ -119,7 +132,8 @@ class CfgNode(dict):
 def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
-    AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA),
+    AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA;
+    LAYER_DECAY / LR_MULT / FREEZE: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save)."""
     c = CfgNode()
@@ -161,7 +175,12 @@ def get_default_config():
     # the solver step around the optimizer (all off by default; CLIP_GRAD_L2NORM as PySlowFast's SOLVER section): the max global
     # L2 norm of the unscaled, all-reduced gradient (0 = off), micro-batches per optimizer update, the decay of the weight EMA
     # (0 = off) and whether fit's validation runs on the EMA weights
-    c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True))
+    # Fine-tuning (finetune_settings; all off by default).  LAYER_DECAY: tensor of depth group d gets the learning-rate scale
+    # LAYER_DECAY ** (D - d) (timm's layer decay: stem 0, the residual blocks 1..L, head D = L + 1); LR_MULT: [[name prefix,
+    # factor], ...] on top of it, the longest matching prefix wins; FREEZE: name prefixes of the tensors the solver step leaves
+    # alone.  The section knows the three keys without holding them: its items stay the four above until one is set.
+    c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True),
+                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[]))
     # the layer-wise optimizers (TRAIN.OPTIMIZER = lars | adamw | lamb; inert for sgd / adam).  LARS (PySlowFast's SOLVER.LARS_ON):
     # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
     # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
@@ -190,6 +209,7 @@ def get_config(name, overrides=None, freeze=True):
     aug_settings(cfg)
     randaug_settings(cfg)
     solver_settings(cfg)
+    finetune_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
     precise_bn_settings(cfg)
@@ -372,6 +392,40 @@ def solver_settings(cfg) -> SolverSettings:
     if not 0.0 <= decay < 1.0:
         raise ValueError(f"SOLVER.EMA_DECAY must lie in [0, 1), not {decay}")
     return SolverSettings(clip, accum, decay, bool(getattr(sv, "EMA_EVAL", d.ema_eval)))
+
+
+FinetuneSettings = collections.namedtuple("FinetuneSettings", "layer_decay lr_mult freeze")
+_FINETUNE_OFF = FinetuneSettings(1.0, (), ())
+
+
+def finetune_settings(cfg) -> FinetuneSettings:
+    """cfg.SOLVER.LAYER_DECAY / LR_MULT / FREEZE as one tuple: (layer_decay, ((prefix, factor), ...), (prefix, ...)).  A config
+    tree without the keys (or without the section): everything off = (1.0, (), ()).  ValueError for a LAYER_DECAY outside
+    (0, 1], an LR_MULT entry that is not [str, finite float > 0] and a FREEZE entry that is not a string (NaN fails too).
+    Freezing is FREEZE's alone: a factor of 0 is refused, it would not freeze anything (finetune.py).  Whether the prefixes
+    match a tensor is finetune.lr_scales' to check: it needs the architecture."""
+    import math
+    sv = getattr(cfg, "SOLVER", None)
+    if sv is None:
+        return _FINETUNE_OFF
+    d = _FINETUNE_OFF
+    decay = getattr(sv, "LAYER_DECAY", d.layer_decay)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) <= 1.0:
+        raise ValueError(f"SOLVER.LAYER_DECAY must lie in (0, 1], not {decay!r}")
+    mult = getattr(sv, "LR_MULT", d.lr_mult)
+    if not isinstance(mult, (list, tuple)):
+        raise ValueError(f"SOLVER.LR_MULT must be a list of [name prefix, factor], not {mult!r}")
+    pairs = []
+    for e in mult:
+        ok = isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], str) and not isinstance(e[1], bool) \
+            and isinstance(e[1], (int, float)) and math.isfinite(e[1]) and e[1] > 0
+        if not ok:
+            raise ValueError(f"SOLVER.LR_MULT entries must be [name prefix (str), finite factor > 0], not {e!r}")
+        pairs.append((e[0], float(e[1])))
+    freeze = getattr(sv, "FREEZE", d.freeze)
+    if not isinstance(freeze, (list, tuple)) or not all(isinstance(f, str) for f in freeze):
+        raise ValueError(f"SOLVER.FREEZE must be a list of name prefixes (str), not {freeze!r}")
+    return FinetuneSettings(float(decay), tuple(pairs), tuple(freeze))
 
 
 OptimSettings = collections.namedtuple("OptimSettings", "lars_trust_coef lars_eps lars_clip weight_decay lamb_eps")

@@ -10,6 +10,10 @@
 //   x3d_grad_accum          acc = g / acc += g
 //   x3d_seg_sumsq           per-tensor sums of squares and the layer-wise optimizers built on them (LARS, AdamW, LAMB): a chunk
 //   x3d_lars / _adamw / _lamb   table instead of one flat range, a fixed number of launches (at the end of this file)
+//   x3d_seg_grad_sumsq      fine-tuning (frozen tensors, per-tensor learning rates): the chunk table holds the tuned tensors only,
+//   x3d_*_pt                the gradient reduction and all five rules walk it, and the learning rate of a chunk is lr *
+//                           lr_scale[segment].  The same kernels: the learning rate is a policy (LrOne / LrSeg) they are
+//                           instantiated with
 //
 // Every streaming kernel is ONE BODY handed to one of two walkers.  A body is a generic lambda body(N, at): it loads N
 // elements at `at` (vec_load), applies the rule to each (solver_each) and stores N elements (vec_store); N is a
@@ -372,9 +376,9 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adam_ex_kernel(float* __restrict
 
 // what the two _ex entry points and x3d_ema_update refuse alike
 #define SOLVER_REQUIRE_EXTRAS(name)                                                                                           \
-  X3D_REQUIRE(!norm || (max_norm > 0.f && max_norm <= 3.0e38f), name ": max_norm must be positive and finite with norm");     \
-  X3D_REQUIRE(!norm || ((uintptr_t)norm & 7) == 0, name ": misaligned norm");                                                 \
-  X3D_REQUIRE(!ema || (ema_decay >= 0.f && ema_decay < 1.f), name ": ema_decay must lie in [0, 1)")
+  X3D_REQUIRE(!norm || (max_norm > 0.f && max_norm <= 3.0e38f), "%s: max_norm must be positive and finite with norm", name);  \
+  X3D_REQUIRE(!norm || ((uintptr_t)norm & 7) == 0, "%s: misaligned norm", name);                                              \
+  X3D_REQUIRE(!ema || (ema_decay >= 0.f && ema_decay < 1.f), "%s: ema_decay must lie in [0, 1)", name)
 
 extern "C" int x3d_sgd_nesterov_ex(float* w, float* v, const float* g, const unsigned char* l2_mask, float lr, float momentum,
                                    float weight_decay, float grad_scale, const double* norm, float max_norm, float* ema,
@@ -538,22 +542,75 @@ __device__ __forceinline__ float lamb_u(float w, float m, float v, bool l2, floa
 }
 __device__ __forceinline__ float lamb_apply(float w, float u, float lq) { return __builtin_fmaf(-lq, u, w); }
 
+// ---- the learning rate of a segment: what the kernels below are instantiated with (wave-uniform, read once per chunk) ----
+// LrOne: the one value of the launch -- x3d_lars / x3d_adamw / x3d_lamb, whose kernels are what they were.
+// LrSeg: lr_t = lr * lr_scale[t], one fp32 product (lr_scale NULL: lr itself) -- the _pt entry points.  A tensor's update at
+// (lr, lr_scale[t]) then has the bits of the plain update at fl32(lr * lr_scale[t]).
+__device__ __forceinline__ float seg_uniform(const float* __restrict__ p, int seg) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p[seg])));
+}
+struct LrOne {
+  float lr;
+  __device__ __forceinline__ float at(int) const { return lr; }
+};
+struct LrSeg {
+  float lr;
+  const float* s;
+  __device__ __forceinline__ float at(int seg) const {
+#pragma clang fp contract(off)
+    return s ? lr * seg_uniform(s, seg) : lr;
+  }
+};
+// Adam's two uses of it: the bias-corrected lr_t and AdamW's ld = lr * decay.  AdamLrOne: both formed on the host, as ever.
+// AdamLrSeg: the host's expressions on the device -- (float)((double)lr_t * num / den) with num = sqrt(1 - b2^step), den = 1 -
+// b1^step from the host (adam_lr_t's order of operations; an fp64 quotient is correctly rounded on both sides) and lr_t * decay.
+struct AdamLrOne {
+  float lr_t, ld;
+  __device__ __forceinline__ void at(int, float& lt, float& d) const { lt = lr_t; d = ld; }
+};
+struct AdamLrSeg {
+  LrSeg lr;
+  double num, den;
+  float decay;
+  __device__ __forceinline__ void at(int seg, float& lt, float& d) const {
+#pragma clang fp contract(off)
+    const float l = lr.at(seg);
+    lt = (float)((double)l * num / den);
+    d = l * decay;
+  }
+};
+static inline AdamLrSeg adam_lr_seg(float lr, const float* lr_scale, float beta1, float beta2, long long step, float decay) {
+  return AdamLrSeg{LrSeg{lr, lr_scale}, sqrt(1.0 - pow((double)beta2, (double)step)), 1.0 - pow((double)beta1, (double)step), decay};
+}
+
 // ---- partial sums: partials[ch] (and partials[nchunk + ch]) of chunk ch ----
-template <bool AL>
+// FINITE (x3d_seg_grad_sumsq): x3d_grad_sumsq's rule -- a non-finite entry adds nothing to the sum and one to the chunk's count
+template <bool AL, bool FINITE>
 __global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __restrict__ a, const int* __restrict__ chunks,
                                                                  int nchunk, double* __restrict__ partials) {
   SEG_FOR_CHUNKS(ch) {
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     double s = 0.0;
+    unsigned bad = 0;
     seg_for_items(first, cnt, lane, [&](auto nc, int at) {
       constexpr int N = decltype(nc)::value;
       float x[N];
       vec_load<N, AL>(a + at, x);
-      solver_each<N>([&](int e) { sq_add(x[e], s); });
+      solver_each<N>([&](int e) {
+        if constexpr (FINITE) sumsq_add(x[e], s, bad);
+        else sq_add(x[e], s);
+      });
     });
     s = wave_sum_d(s);
-    if (lane == 0) partials[ch] = s;
+    if constexpr (FINITE) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    }
+    if (lane == 0) {
+      partials[ch] = s;
+      if constexpr (FINITE) partials[nchunk + ch] = (double)bad;
+    }
   }
 }
 
@@ -619,9 +676,9 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_moments_kernel(const float*
 // ---- per segment: one wave adds the segment's partials -- lane l those of chunks l, l + 64, ... in ascending order, the
 // lanes by the butterfly -- and lane 0 writes the sum (SEG_SUM) or q (SEG_LARS / SEG_LAMB: fp64, rounded once) ----
 enum { SEG_SUM = 0, SEG_LARS = 1, SEG_LAMB = 2 };
-template <int MODE>
+template <int MODE, class LR>
 __global__ __launch_bounds__(SOLVER_BLOCK) void seg_final_kernel(const double* __restrict__ partials, int nchunk,
-                                                                 const int* __restrict__ segs, int nseg, float lr, float wd,
+                                                                 const int* __restrict__ segs, int nseg, LR lrp, float wd,
                                                                  float gscale, float eta, float eps, int clip,
                                                                  const double* __restrict__ norm, float max_norm,
                                                                  double* __restrict__ out, float* __restrict__ q) {
@@ -650,7 +707,7 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_final_kernel(const double* _
       const double nw = sqrt(s0), nx = sqrt(s1);
       if constexpr (MODE == SEG_LARS) {
         t = (double)eta * nw / ((double)c * nx + 2.0 * (double)wd * nw + (double)eps);
-        if (clip) t = fmin(t / (double)lr, 1.0);
+        if (clip) t = fmin(t / (double)lrp.at(seg), 1.0);
       } else {
         t = nw / nx;
       }
@@ -659,17 +716,19 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_final_kernel(const double* _
   }
 }
 // its launch: one wave per segment
-template <int MODE, class... A> static inline void seg_final_launch(int nseg, void* stream, A... args) {
-  hipLaunchKernelGGL((seg_final_kernel<MODE>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), dim3(SOLVER_BLOCK), 0,
-                     (hipStream_t)stream, args...);
+template <int MODE, class LR, class... A>
+static inline void seg_final_launch(int nseg, void* stream, const double* partials, int nchunk, const int* segs, LR lrp, A... args) {
+  hipLaunchKernelGGL((seg_final_kernel<MODE, LR>), dim3((unsigned)ceil_div_ll(nseg, SEG_WAVES)), dim3(SOLVER_BLOCK), 0,
+                     (hipStream_t)stream, partials, nchunk, segs, nseg, lrp, args...);
 }
 
 // ---- apply passes ----
-template <bool AL>
+// LARS = false (x3d_sgd_pt): no q, the plain sgd_nesterov_step on the chunk -- x3d_sgd_nesterov_ex's rule on this walker
+template <bool AL, class LR, bool LARS>
 __global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restrict__ w, float* __restrict__ v,
                                                                   const float* __restrict__ g, const int* __restrict__ chunks,
                                                                   int nchunk, const int* __restrict__ segs,
-                                                                  const float* __restrict__ q, float lr, float mom, float wd,
+                                                                  const float* __restrict__ q, LR lrp, float mom, float wd,
                                                                   float gscale, const double* __restrict__ norm, float max_norm,
                                                                   float* __restrict__ ema, float omd) {
   float c;
@@ -678,7 +737,9 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restr
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
-    const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
+    float qt = 1.f;
+    if constexpr (LARS) qt = seg_uniform(q, seg);
+    const float lr = lrp.at(seg);
     seg_for_items(first, cnt, lane, [&](auto nc, int at) {
       constexpr int N = decltype(nc)::value;
       float wi[N], vi[N], gi[N];
@@ -687,7 +748,10 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restr
       vec_load<N, AL>(g + at, gi);
       EmaPass<N, AL> ea;
       if (ema) ea.load(ema + at);
-      solver_each<N>([&](int e) { lars_step(wi[e], vi[e], gi[e], l2, qt, lr, mom, wd, c); });
+      solver_each<N>([&](int e) {
+        if constexpr (LARS) lars_step(wi[e], vi[e], gi[e], l2, qt, lr, mom, wd, c);
+        else sgd_nesterov_step(wi[e], vi[e], gi[e], l2, lr, mom, wd, c);
+      });
       vec_store<N, AL>(v + at, vi);
       vec_store<N, AL>(w + at, wi);
       if (ema) ea.apply(ema + at, wi, omd);
@@ -695,11 +759,12 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lars_apply_kernel(float* __restr
   }
 }
 
-template <bool AL>
+// DECOUPLED = false (x3d_adam_pt): adam_step with the coupled L2 term (wd) -- x3d_adam_ex's rule on this walker
+template <bool AL, class LR, bool DECOUPLED>
 __global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                                              const float* __restrict__ g, const int* __restrict__ chunks,
-                                                             int nchunk, const int* __restrict__ segs, float lr_t, float b1,
-                                                             float b2, float eps, float ld, float gscale,
+                                                             int nchunk, const int* __restrict__ segs, LR lrp, float b1,
+                                                             float b2, float eps, float wd, float gscale,
                                                              const double* __restrict__ norm, float max_norm,
                                                              float* __restrict__ ema, float omd) {
   float c;
@@ -708,6 +773,8 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
+    float lr_t, ld;
+    lrp.at(seg, lr_t, ld);
     seg_for_items(first, cnt, lane, [&](auto nc, int at) {
       constexpr int N = decltype(nc)::value;
       float wi[N], mi[N], vi[N], gi[N];
@@ -717,7 +784,10 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__
       vec_load<N, AL>(g + at, gi);
       EmaPass<N, AL> ea;
       if (ema) ea.load(ema + at);
-      solver_each<N>([&](int e) { adamw_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, ld, c); });
+      solver_each<N>([&](int e) {
+        if constexpr (DECOUPLED) adamw_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, ld, c);
+        else adam_step(wi[e], mi[e], vi[e], gi[e], l2, lr_t, b1, b2, eps, wd, c);
+      });
       vec_store<N, AL>(m + at, mi);
       vec_store<N, AL>(v + at, vi);
       vec_store<N, AL>(w + at, wi);
@@ -726,11 +796,11 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void adamw_kernel(float* __restrict__
   }
 }
 
-template <bool AL>
+template <bool AL, class LR>
 __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m,
                                                                   const float* __restrict__ v, const int* __restrict__ chunks,
                                                                   int nchunk, const int* __restrict__ segs,
-                                                                  const float* __restrict__ q, float lr, float r, float eps,
+                                                                  const float* __restrict__ q, LR lrp, float r, float eps,
                                                                   float decay, const double* __restrict__ norm,
                                                                   float* __restrict__ ema, float omd) {
   if (norm && norm[1] != 0.0) return;
@@ -738,8 +808,8 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_apply_kernel(float* __restr
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
     const bool l2 = __builtin_amdgcn_readfirstlane(segs[3 * seg + 2]) != 0;
-    const float qt = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q[seg])));
-    const float lq = lr * qt;
+    const float qt = seg_uniform(q, seg);
+    const float lq = lrp.at(seg) * qt;
     seg_for_items(first, cnt, lane, [&](auto nc, int at) {
       constexpr int N = decltype(nc)::value;
       float wi[N], mi[N], vi[N];
@@ -756,21 +826,67 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void lamb_apply_kernel(float* __restr
 }
 
 // ---- entry points ----
+// Each rule has ONE host function, a template over the learning-rate policy; the plain entry point hands it LrOne and the _pt
+// entry point LrSeg.  What an entry point refuses is written once that way, under the caller's name.
 #define SEG_REQUIRE_TABLE(name)                                                                                               \
-  X3D_REQUIRE(chunks && segs && nchunk > 0 && nseg > 0 && nseg <= nchunk, name ": bad chunk table (null, or nseg / nchunk <= 0)"); \
-  X3D_REQUIRE((((uintptr_t)chunks | (uintptr_t)segs) & 3) == 0, name ": misaligned table")
+  X3D_REQUIRE(chunks && segs && nchunk > 0 && nseg > 0 && nseg <= nchunk, "%s: bad chunk table (null, or nseg / nchunk <= 0)", name); \
+  X3D_REQUIRE((((uintptr_t)chunks | (uintptr_t)segs) & 3) == 0, "%s: misaligned table", name)
+#define SEG_REQUIRE_LR_SCALE(name) X3D_REQUIRE(((uintptr_t)lr_scale & 3) == 0, "%s: misaligned lr_scale", name)
 static inline bool seg_finite_ge0(float x) { return x >= 0.f && x <= 3.0e38f; }
+
+template <bool FINITE>
+static int seg_sumsq_run(const char* name, const float* a, const int* chunks, int nchunk, const int* segs, int nseg,
+                         double* partials, double* out, void* stream) {
+  X3D_REQUIRE(a && partials && out, "%s: bad args", name);
+  SEG_REQUIRE_TABLE(name);
+  X3D_REQUIRE(((uintptr_t)a & 3) == 0 && (((uintptr_t)partials | (uintptr_t)out) & 7) == 0, "%s: misaligned pointer", name);
+  solver_launch(seg_aligned(a), seg_sumsq_kernel<true, FINITE>, seg_sumsq_kernel<false, FINITE>, seg_grid(nchunk), stream, a,
+                chunks, nchunk, partials);
+  if constexpr (FINITE)     // all chunks in ascending order, sums and counts: x3d_grad_sumsq's final launch on nchunk partials
+    hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, nchunk, out);
+  else
+    seg_final_launch<SEG_SUM>(nseg, stream, (const double*)partials, nchunk, segs, LrOne{0.f}, 0.f, 1.f, 0.f, 0.f, 0,
+                              (const double*)nullptr, 0.f, out, (float*)nullptr);
+  X3D_LAUNCH_CHECK(name);
+  return X3D_OK;
+}
 
 extern "C" int x3d_seg_sumsq(const float* a, const int* chunks, int nchunk, const int* segs, int nseg, double* partials,
                              double* out, void* stream) {
-  X3D_REQUIRE(a && partials && out, "seg_sumsq: bad args");
-  SEG_REQUIRE_TABLE("seg_sumsq");
-  X3D_REQUIRE(((uintptr_t)a & 3) == 0 && (((uintptr_t)partials | (uintptr_t)out) & 7) == 0, "seg_sumsq: misaligned pointer");
-  solver_launch(seg_aligned(a), seg_sumsq_kernel<true>, seg_sumsq_kernel<false>, seg_grid(nchunk), stream, a, chunks, nchunk,
-                partials);
-  seg_final_launch<SEG_SUM>(nseg, stream, (const double*)partials, nchunk, segs, nseg, 0.f, 0.f, 1.f, 0.f, 0.f, 0,
-                            (const double*)nullptr, 0.f, out, (float*)nullptr);
-  X3D_LAUNCH_CHECK("seg_sumsq");
+  return seg_sumsq_run<false>("seg_sumsq", a, chunks, nchunk, segs, nseg, partials, out, stream);
+}
+
+extern "C" int x3d_seg_grad_sumsq(const float* g, const int* chunks, int nchunk, const int* segs, int nseg, double* partials,
+                                  double* out, void* stream) {
+  return seg_sumsq_run<true>("seg_grad_sumsq", g, chunks, nchunk, segs, nseg, partials, out, stream);
+}
+
+// x3d_lars / x3d_lars_pt (LARS = true: sums, q, apply) and x3d_sgd_pt (LARS = false: the apply pass alone; partials, q unused)
+template <bool LARS, class LR>
+static int lars_run(const char* name, float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                    LR lrp, float momentum, float weight_decay, float grad_scale, float trust_coef, float eps, int clip,
+                    const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q, void* stream) {
+  X3D_REQUIRE(w && v && g && (!LARS || (partials && q)), "%s: bad args", name);
+  SEG_REQUIRE_TABLE(name);
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
+              ((uintptr_t)partials & 7) == 0, "%s: misaligned pointer", name);
+  if constexpr (LARS) {
+    X3D_REQUIRE(trust_coef > 0.f && trust_coef <= 3.0e38f, "%s: trust_coef must be positive and finite", name);
+    X3D_REQUIRE(seg_finite_ge0(eps) && seg_finite_ge0(weight_decay), "%s: eps and weight_decay must be >= 0 and finite", name);
+    X3D_REQUIRE(!clip || lrp.lr > 0.f, "%s: clip needs lr > 0", name);
+  }
+  SOLVER_REQUIRE_EXTRAS(name);
+  const unsigned grid = seg_grid(nchunk);
+  const SolverExtras x(norm, max_norm, ema, ema_decay);
+  const bool al = seg_aligned(w, v, g, ema);
+  if constexpr (LARS) {
+    solver_launch(al, lars_sums_kernel<true>, lars_sums_kernel<false>, grid, stream, w, g, chunks, nchunk, norm, partials);
+    seg_final_launch<SEG_LARS>(nseg, stream, (const double*)partials, nchunk, segs, lrp, weight_decay, grad_scale, trust_coef,
+                               eps, clip, norm, x.nm, (double*)nullptr, q);
+  }
+  solver_launch(al, lars_apply_kernel<true, LR, LARS>, lars_apply_kernel<false, LR, LARS>, grid, stream, w, v, g, chunks, nchunk,
+                segs, q, lrp, momentum, weight_decay, grad_scale, norm, x.nm, ema, x.omd);
+  X3D_LAUNCH_CHECK(name);
   return X3D_OK;
 }
 
@@ -778,39 +894,96 @@ extern "C" int x3d_lars(float* w, float* v, const float* g, const int* chunks, i
                         float momentum, float weight_decay, float grad_scale, float trust_coef, float eps, int clip,
                         const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
                         void* stream) {
-  X3D_REQUIRE(w && v && g && partials && q, "lars: bad args");
-  SEG_REQUIRE_TABLE("lars");
-  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
-              ((uintptr_t)partials & 7) == 0, "lars: misaligned pointer");
-  X3D_REQUIRE(trust_coef > 0.f && trust_coef <= 3.0e38f, "lars: trust_coef must be positive and finite");
-  X3D_REQUIRE(seg_finite_ge0(eps) && seg_finite_ge0(weight_decay), "lars: eps and weight_decay must be >= 0 and finite");
-  X3D_REQUIRE(!clip || lr > 0.f, "lars: clip needs lr > 0");
-  SOLVER_REQUIRE_EXTRAS("lars");
-  const unsigned grid = seg_grid(nchunk);
+  return lars_run<true>("lars", w, v, g, chunks, nchunk, segs, nseg, LrOne{lr}, momentum, weight_decay, grad_scale, trust_coef,
+                        eps, clip, norm, max_norm, ema, ema_decay, partials, q, stream);
+}
+
+extern "C" int x3d_lars_pt(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                           const float* lr_scale, float lr, float momentum, float weight_decay, float grad_scale,
+                           float trust_coef, float eps, int clip, const double* norm, float max_norm, float* ema,
+                           float ema_decay, double* partials, float* q, void* stream) {
+  SEG_REQUIRE_LR_SCALE("lars_pt");
+  return lars_run<true>("lars_pt", w, v, g, chunks, nchunk, segs, nseg, LrSeg{lr, lr_scale}, momentum, weight_decay, grad_scale,
+                        trust_coef, eps, clip, norm, max_norm, ema, ema_decay, partials, q, stream);
+}
+
+extern "C" int x3d_sgd_pt(float* w, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                          const float* lr_scale, float lr, float momentum, float weight_decay, float grad_scale,
+                          const double* norm, float max_norm, float* ema, float ema_decay, void* stream) {
+  SEG_REQUIRE_LR_SCALE("sgd_pt");
+  return lars_run<false>("sgd_pt", w, v, g, chunks, nchunk, segs, nseg, LrSeg{lr, lr_scale}, momentum, weight_decay, grad_scale,
+                         0.f, 0.f, 0, norm, max_norm, ema, ema_decay, (double*)nullptr, (float*)nullptr, stream);
+}
+
+// x3d_adamw / x3d_adamw_pt (DECOUPLED = true; weight_decay unused) and x3d_adam_pt (false: the coupled L2 term weight_decay)
+template <bool DECOUPLED, class LR>
+static int adamw_run(const char* name, float* w, float* m, float* v, const float* g, const int* chunks, int nchunk,
+                     const int* segs, int nseg, LR lrp, float beta1, float beta2, float eps, float decay, float weight_decay,
+                     float grad_scale, long long step, const double* norm, float max_norm, float* ema, float ema_decay,
+                     void* stream) {
+  X3D_REQUIRE(w && m && v && g && step >= 1, "%s: bad args (step counts from 1)", name);
+  SEG_REQUIRE_TABLE(name);
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "%s: misaligned pointer", name);
+  X3D_REQUIRE(seg_finite_ge0(decay), "%s: decay must be >= 0 and finite", name);
+  SOLVER_REQUIRE_EXTRAS(name);
   const SolverExtras x(norm, max_norm, ema, ema_decay);
-  const bool al = seg_aligned(w, v, g, ema);
-  solver_launch(al, lars_sums_kernel<true>, lars_sums_kernel<false>, grid, stream, w, g, chunks, nchunk, norm, partials);
-  seg_final_launch<SEG_LARS>(nseg, stream, (const double*)partials, nchunk, segs, nseg, lr, weight_decay, grad_scale, trust_coef,
-                             eps, clip, norm, x.nm, (double*)nullptr, q);
-  solver_launch(al, lars_apply_kernel<true>, lars_apply_kernel<false>, grid, stream, w, v, g, chunks, nchunk, segs, q, lr,
-                momentum, weight_decay, grad_scale, norm, x.nm, ema, x.omd);
-  X3D_LAUNCH_CHECK("lars");
+  solver_launch(seg_aligned(w, m, v, g, ema), adamw_kernel<true, LR, DECOUPLED>, adamw_kernel<false, LR, DECOUPLED>,
+                seg_grid(nchunk), stream, w, m, v, g, chunks, nchunk, segs, lrp, beta1, beta2, eps, weight_decay, grad_scale, norm,
+                x.nm, ema, x.omd);
+  X3D_LAUNCH_CHECK(name);
   return X3D_OK;
 }
 
 extern "C" int x3d_adamw(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
                          float lr, float beta1, float beta2, float eps, float decay, float grad_scale, long long step,
                          const double* norm, float max_norm, float* ema, float ema_decay, void* stream) {
-  X3D_REQUIRE(w && m && v && g && step >= 1, "adamw: bad args (step counts from 1)");
-  SEG_REQUIRE_TABLE("adamw");
-  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema) & 3) == 0, "adamw: misaligned pointer");
-  X3D_REQUIRE(seg_finite_ge0(decay), "adamw: decay must be >= 0 and finite");
-  SOLVER_REQUIRE_EXTRAS("adamw");
+  return adamw_run<true>("adamw", w, m, v, g, chunks, nchunk, segs, nseg,
+                         AdamLrOne{(float)adam_lr_t(lr, beta1, beta2, step > 0 ? step : 1), lr * decay}, beta1, beta2, eps, decay,
+                         0.f, grad_scale, step, norm, max_norm, ema, ema_decay, stream);
+}
+
+extern "C" int x3d_adamw_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs,
+                            int nseg, const float* lr_scale, float lr, float beta1, float beta2, float eps, float decay,
+                            float grad_scale, long long step, const double* norm, float max_norm, float* ema, float ema_decay,
+                            void* stream) {
+  SEG_REQUIRE_LR_SCALE("adamw_pt");
+  return adamw_run<true>("adamw_pt", w, m, v, g, chunks, nchunk, segs, nseg,
+                         adam_lr_seg(lr, lr_scale, beta1, beta2, step > 0 ? step : 1, decay), beta1, beta2, eps, decay, 0.f,
+                         grad_scale, step, norm, max_norm, ema, ema_decay, stream);
+}
+
+extern "C" int x3d_adam_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                           const float* lr_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                           float grad_scale, long long step, const double* norm, float max_norm, float* ema, float ema_decay,
+                           void* stream) {
+  SEG_REQUIRE_LR_SCALE("adam_pt");
+  return adamw_run<false>("adam_pt", w, m, v, g, chunks, nchunk, segs, nseg,
+                          adam_lr_seg(lr, lr_scale, beta1, beta2, step > 0 ? step : 1, 0.f), beta1, beta2, eps, 0.f, weight_decay,
+                          grad_scale, step, norm, max_norm, ema, ema_decay, stream);
+}
+
+template <class LR>
+static int lamb_run(const char* name, float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs,
+                    int nseg, LR lrp, float beta1, float beta2, float eps, float decay, float grad_scale, long long step,
+                    const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q, void* stream) {
+  X3D_REQUIRE(w && m && v && g && partials && q && step >= 1, "%s: bad args (step counts from 1)", name);
+  SEG_REQUIRE_TABLE(name);
+  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
+              ((uintptr_t)partials & 7) == 0, "%s: misaligned pointer", name);
+  X3D_REQUIRE(eps > 0.f && eps <= 3.0e38f, "%s: eps must be positive and finite", name);
+  X3D_REQUIRE(seg_finite_ge0(decay), "%s: decay must be >= 0 and finite", name);
+  SOLVER_REQUIRE_EXTRAS(name);
+  const unsigned grid = seg_grid(nchunk);
   const SolverExtras x(norm, max_norm, ema, ema_decay);
-  solver_launch(seg_aligned(w, m, v, g, ema), adamw_kernel<true>, adamw_kernel<false>, seg_grid(nchunk), stream, w, m, v, g,
-                chunks, nchunk, segs, (float)adam_lr_t(lr, beta1, beta2, step), beta1, beta2, eps, lr * decay, grad_scale, norm,
-                x.nm, ema, x.omd);
-  X3D_LAUNCH_CHECK("adamw");
+  const float r = (float)adam_lr_t(1.f, beta1, beta2, step);
+  const bool al = seg_aligned(w, m, v, g, ema);
+  solver_launch(al, lamb_moments_kernel<true>, lamb_moments_kernel<false>, grid, stream, w, m, v, g, chunks, nchunk, segs, r,
+                beta1, beta2, eps, decay, grad_scale, norm, x.nm, partials);
+  seg_final_launch<SEG_LAMB>(nseg, stream, (const double*)partials, nchunk, segs, LrOne{0.f}, 0.f, grad_scale, 0.f, 0.f, 0, norm,
+                             x.nm, (double*)nullptr, q);
+  solver_launch(al, lamb_apply_kernel<true, LR>, lamb_apply_kernel<false, LR>, grid, stream, w, m, v, chunks, nchunk, segs, q,
+                lrp, r, eps, decay, norm, ema, x.omd);
+  X3D_LAUNCH_CHECK(name);
   return X3D_OK;
 }
 
@@ -818,23 +991,15 @@ extern "C" int x3d_lamb(float* w, float* m, float* v, const float* g, const int*
                         float lr, float beta1, float beta2, float eps, float decay, float grad_scale, long long step,
                         const double* norm, float max_norm, float* ema, float ema_decay, double* partials, float* q,
                         void* stream) {
-  X3D_REQUIRE(w && m && v && g && partials && q && step >= 1, "lamb: bad args (step counts from 1)");
-  SEG_REQUIRE_TABLE("lamb");
-  X3D_REQUIRE((((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)q) & 3) == 0 &&
-              ((uintptr_t)partials & 7) == 0, "lamb: misaligned pointer");
-  X3D_REQUIRE(eps > 0.f && eps <= 3.0e38f, "lamb: eps must be positive and finite");
-  X3D_REQUIRE(seg_finite_ge0(decay), "lamb: decay must be >= 0 and finite");
-  SOLVER_REQUIRE_EXTRAS("lamb");
-  const unsigned grid = seg_grid(nchunk);
-  const SolverExtras x(norm, max_norm, ema, ema_decay);
-  const float r = (float)adam_lr_t(1.f, beta1, beta2, step);
-  const bool al = seg_aligned(w, m, v, g, ema);
-  solver_launch(al, lamb_moments_kernel<true>, lamb_moments_kernel<false>, grid, stream, w, m, v, g, chunks, nchunk, segs, r,
-                beta1, beta2, eps, decay, grad_scale, norm, x.nm, partials);
-  seg_final_launch<SEG_LAMB>(nseg, stream, (const double*)partials, nchunk, segs, nseg, lr, 0.f, grad_scale, 0.f, 0.f, 0, norm,
-                             x.nm, (double*)nullptr, q);
-  solver_launch(al, lamb_apply_kernel<true>, lamb_apply_kernel<false>, grid, stream, w, m, v, chunks, nchunk, segs, q, lr, r, eps,
-                decay, norm, ema, x.omd);
-  X3D_LAUNCH_CHECK("lamb");
-  return X3D_OK;
+  return lamb_run("lamb", w, m, v, g, chunks, nchunk, segs, nseg, LrOne{lr}, beta1, beta2, eps, decay, grad_scale, step, norm,
+                  max_norm, ema, ema_decay, partials, q, stream);
+}
+
+extern "C" int x3d_lamb_pt(float* w, float* m, float* v, const float* g, const int* chunks, int nchunk, const int* segs, int nseg,
+                           const float* lr_scale, float lr, float beta1, float beta2, float eps, float decay, float grad_scale,
+                           long long step, const double* norm, float max_norm, float* ema, float ema_decay, double* partials,
+                           float* q, void* stream) {
+  SEG_REQUIRE_LR_SCALE("lamb_pt");
+  return lamb_run("lamb_pt", w, m, v, g, chunks, nchunk, segs, nseg, LrSeg{lr, lr_scale}, beta1, beta2, eps, decay, grad_scale,
+                  step, norm, max_norm, ema, ema_decay, partials, q, stream);
 }

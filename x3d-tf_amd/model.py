@@ -18,6 +18,7 @@ captured graph would bake that pointer in.  `options={"stem_nthwc": False}` rest
 buffer (one conversion pass per step) for graph capture; replaying as a hipGraph measured no gain.
 """
 import collections
+import types
 from typing import Dict, Optional
 
 import torch
@@ -214,6 +215,9 @@ class X3D:
         from .segments import Segment
         self.segments = [Segment(s.name, self._offsets[s.name], numel(s), bool(s.l2)) for s in order if s.trainable]
         self._seg_table = None
+        # fine-tuning (set_finetune): off -- every apply_* and the gradient reduction make the launches they always made
+        self._ft = None
+        self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
 
     def _build_panels(self):
         """bf16 LDS-image panels of every pointwise-conv weight (x3d_pw_pack_weights): refreshed by one launch
@@ -598,6 +602,9 @@ class X3D:
             n_scratch = int(hip.load().x3d_grad_sumsq_scratch(self.n_trainable_flat))
             self._norm_scratch = torch.empty(n_scratch, dtype=torch.float64, device=self.device)
             self._norm_out = torch.zeros(2, dtype=torch.float64, device=self.device)
+        if self._ft is not None:              # the tuned tensors only, as clip_grad_norm_ over the requires_grad parameters
+            from . import ops
+            return ops.seg_grad_sumsq(self.flat_grads, self._ft.table, self._norm_out, self._ft.partials)
         hip.call("x3d_grad_sumsq", self.flat_grads.data_ptr(), self.n_trainable_flat, self._norm_scratch.data_ptr(),
                  self._norm_out.data_ptr())
         return self._norm_out
@@ -608,6 +615,12 @@ class X3D:
         the update, both decided on the device; ema: a flat fp32 buffer that receives ema_decay * ema + (1 - ema_decay) * w
         in the same pass (x3d_sgd_nesterov_ex).  With neither this is the x3d_sgd_nesterov launch it always was."""
         self._claim_slots("sgd")
+        if self._ft is not None:
+            from . import ops
+            self._ema_covers_block("apply_sgd", ema)
+            ops.sgd_pt(self.flat_params, self.flat_velocity, self.flat_grads, self._ft.table, self._ft.scale, lr, momentum,
+                       self.arch.weight_decay, grad_scale, norm, max_norm, ema, ema_decay)
+            return
         if norm is None and ema is None:
             hip.call("x3d_sgd_nesterov", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
                      self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
@@ -626,6 +639,12 @@ class X3D:
         moment lives in `flat_velocity` (the slot the SGD branch uses for momentum), the second in `flat_second`.
         norm / max_norm / ema / ema_decay: as apply_sgd (x3d_adam_ex)."""
         self._adam_slots()
+        if self._ft is not None:
+            from . import ops
+            self._ema_covers_block("apply_adam", ema)
+            ops.adam_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self._ft.table, self._ft.scale,
+                        lr, step, beta1, beta2, eps, self.arch.weight_decay, grad_scale, norm, max_norm, ema, ema_decay)
+            return
         if norm is None and ema is None:
             hip.call("x3d_adam", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
                      self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
@@ -649,6 +668,41 @@ class X3D:
             self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
         return self._seg_table
 
+    def set_finetune(self, freeze=(), lr_mult=(), layer_decay=1.0):
+        """Fine-tuning (SOLVER.FREEZE / LR_MULT / LAYER_DECAY, finetune.py): freeze the trainable tensors whose names start with
+        a prefix of `freeze`, and give every other ("tuned") tensor the learning rate lr * scale, scale = layer_decay ** (D -
+        depth group) * factor of the longest `lr_mult` prefix ([(prefix, factor), ...]).  Builds and keeps the chunk table of
+        the tuned segments and their fp32 scales on the device, `tuned_segments`, `lr_scales` (name -> scale, frozen names
+        absent) and `frozen_names`.  While set, apply_sgd / adam / lars / adamw / lamb make the x3d_*_pt launches, grad_norm_sq
+        makes x3d_seg_grad_sumsq's and grads_finite reads its count: a frozen tensor's weights, slots and EMA are never read or
+        written and its gradient is in neither the norm nor the finite check; the trust ratios apply_lars / apply_lamb return
+        are [len(tuned_segments)], in that order.  Without arguments: cleared, every method makes the launches it always made.
+        The forward and backward passes are not changed: frozen tensors' gradients are still computed, BatchNorm in frozen
+        layers still uses batch statistics and updates its moving statistics."""
+        from .config import FinetuneSettings
+        from .finetune import lr_scales
+        from .segments import SegTable
+        st = FinetuneSettings(float(layer_decay), tuple((str(p), float(f)) for p, f in lr_mult), tuple(freeze))
+        if not 0.0 < st.layer_decay <= 1.0 or not all(f > 0.0 and f < float("inf") for _, f in st.lr_mult):
+            raise ValueError(f"set_finetune: layer_decay must lie in (0, 1] and every factor must be finite and > 0, not "
+                             f"{layer_decay}, {list(lr_mult)}")
+        if st == FinetuneSettings(1.0, (), ()):
+            self._ft = None
+            self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
+            return
+        tuned, scales, frozen = lr_scales(self.arch, [self.specs[n] for n in self.param_order], st)
+        if not set(tuned) <= set(self.segments):
+            raise RuntimeError("finetune.flat_segments and the model's parameter layout disagree")
+        ft = types.SimpleNamespace()
+        ft.table = SegTable(tuned)
+        if not self.dry:
+            ft.table.to(self.device)
+            ft.scale = torch.tensor(scales, dtype=torch.float32).to(self.device)
+            ft.partials = torch.empty(2 * ft.table.nchunk, dtype=torch.float64, device=self.device)
+            ft.trust_ratios = torch.ones(ft.table.nseg, dtype=torch.float32, device=self.device)
+        self._ft = ft
+        self.tuned_segments, self.lr_scales, self.frozen_names = tuned, {s.name: c for s, c in zip(tuned, scales)}, frozen
+
     def _ema_covers_block(self, op, ema):
         """ops.lars / adamw / lamb check norm, max_norm, ema and ema_decay (ops.solver_extras) against the chunk table, which ends
         at the last tensor's last element; the model's EMA buffer also has to hold the padding behind it."""
@@ -669,8 +723,13 @@ class X3D:
         `segments` order), overwritten by the next call."""
         from . import ops
         self._claim_slots("sgd")
-        tb = self.seg_table
         self._ema_covers_block("apply_lars", ema)
+        if self._ft is not None:
+            ft = self._ft
+            return ops.lars_pt(self.flat_params, self.flat_velocity, self.flat_grads, ft.table, ft.scale, lr, momentum,
+                               self.arch.weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay,
+                               ft.partials, ft.trust_ratios)
+        tb = self.seg_table
         return ops.lars(self.flat_params, self.flat_velocity, self.flat_grads, tb, lr, momentum, self.arch.weight_decay,
                         trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
 
@@ -681,6 +740,10 @@ class X3D:
         from . import ops
         self._adam_slots()
         self._ema_covers_block("apply_adamw", ema)
+        if self._ft is not None:
+            ops.adamw_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self._ft.table, self._ft.scale,
+                         lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
+            return
         ops.adamw(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self.seg_table, lr, step, beta1,
                   beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
 
@@ -691,13 +754,21 @@ class X3D:
         Three launches, no synchronisation.  Returns the device [nseg] fp32 trust ratios, overwritten by the next call."""
         from . import ops
         self._adam_slots()
-        tb = self.seg_table
         self._ema_covers_block("apply_lamb", ema)
+        if self._ft is not None:
+            ft = self._ft
+            return ops.lamb_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, ft.table, ft.scale, lr,
+                               step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay, ft.partials,
+                               ft.trust_ratios)
+        tb = self.seg_table
         return ops.lamb(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, tb, lr, step, beta1, beta2, eps,
                         decay, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
 
     def grads_finite(self) -> bool:
-        """True when every entry of the flat gradient buffer is finite (x3d_all_finite; synchronises)."""
+        """True when every entry of the flat gradient buffer is finite (x3d_all_finite; synchronises).  With set_finetune:
+        every entry of the TUNED tensors' gradients -- the count x3d_seg_grad_sumsq leaves in grad_norm_sq()'s result."""
+        if self._ft is not None:
+            return float(self.grad_norm_sq()[1].item()) == 0.0
         if getattr(self, "_finite_flag", None) is None:
             self._finite_flag = torch.ones(1, dtype=torch.int32, device=self.device)
         self._finite_flag.fill_(1)

@@ -799,46 +799,139 @@ def seg_sumsq(a, table, out=None, partials=None):
     return out
 
 
+def _lr_scale(op, table, lr_scale):
+    """the lr_scale argument of the _pt launches as a tuple to splice in behind nseg: None (every scale 1), or the device
+    [nseg] float32 of the table's segments"""
+    if lr_scale is not None:
+        if lr_scale.dtype != torch.float32 or lr_scale.numel() != table.nseg or not lr_scale.is_contiguous() \
+                or not lr_scale.is_cuda:
+            raise ValueError(f"{op}: lr_scale must be a contiguous device float32 tensor of {table.nseg} elements (one per "
+                             f"segment of the table), got {lr_scale.numel()} {lr_scale.dtype}")
+        _chk(table.d_chunks, lr_scale)
+    return (ptr(lr_scale),)
+
+
+def _lars(op, scale, w, v, g, table, lr, momentum, weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema,
+          ema_decay, partials, q):
+    _seg_table(op, table, ("w", w), ("v", v), ("g", g), ("ema", ema))
+    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
+    if not float(trust_coef) > 0.0 or float(eps) < 0.0:
+        raise ValueError(f"{op}: trust_coef must be positive and eps >= 0, not {trust_coef}, {eps}")
+    partials, q = _seg_scratch(op, table, partials, q, w.device)
+    hip.call("x3d_" + op, ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, *scale,
+             float(lr), float(momentum), float(weight_decay), float(grad_scale), float(trust_coef), float(eps), 1 if clip else 0,
+             ptr(norm), float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
+    return q
+
+
 def lars(w, v, g, table, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None,
          max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
     """LARS on the segments of `table` (x3d_lars: the rule is in include/x3d_hip.h); returns q [nseg] fp32, the trust ratios,
     on the device.  Three launches, does not synchronise; g is not written."""
-    _seg_table("lars", table, ("w", w), ("v", v), ("g", g), ("ema", ema))
-    solver_extras("lars", norm, max_norm, ema, ema_decay, table.end)
-    if not float(trust_coef) > 0.0 or float(eps) < 0.0:
-        raise ValueError(f"lars: trust_coef must be positive and eps >= 0, not {trust_coef}, {eps}")
-    partials, q = _seg_scratch("lars", table, partials, q, w.device)
-    hip.call("x3d_lars", ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, float(lr),
-             float(momentum), float(weight_decay), float(grad_scale), float(trust_coef), float(eps), 1 if clip else 0,
-             ptr(norm), float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
-    return q
+    return _lars("lars", (), w, v, g, table, lr, momentum, weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema,
+                 ema_decay, partials, q)
+
+
+def _adamw(op, scale, w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay):
+    _seg_table(op, table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
+    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
+    if float(decay) < 0.0 or int(step) < 1:
+        raise ValueError(f"{op}: decay must be >= 0 and step >= 1, not {decay}, {step}")
+    hip.call("x3d_" + op, ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             *scale, float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
+             float(max_norm), ptr(ema), float(ema_decay))
 
 
 def adamw(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
           ema=None, ema_decay=0.0):
     """Adam with decoupled weight decay on the l2 segments of `table` (x3d_adamw).  One launch, does not synchronise."""
-    _seg_table("adamw", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    solver_extras("adamw", norm, max_norm, ema, ema_decay, table.end)
-    if float(decay) < 0.0 or int(step) < 1:
-        raise ValueError(f"adamw: decay must be >= 0 and step >= 1, not {decay}, {step}")
-    hip.call("x3d_adamw", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
-             float(max_norm), ptr(ema), float(ema_decay))
+    _adamw("adamw", (), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
+
+
+def _lamb(op, scale, w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay,
+          partials, q):
+    _seg_table(op, table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
+    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
+    if float(decay) < 0.0 or not float(eps) > 0.0 or int(step) < 1:
+        raise ValueError(f"{op}: decay must be >= 0, eps > 0 and step >= 1, not {decay}, {eps}, {step}")
+    partials, q = _seg_scratch(op, table, partials, q, w.device)
+    hip.call("x3d_" + op, ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             *scale, float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
+             float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
+    return q
 
 
 def lamb(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
          ema=None, ema_decay=0.0, partials=None, q=None):
     """LAMB on the segments of `table` (x3d_lamb); returns q [nseg] fp32, the trust ratios, on the device.  Three launches, does
     not synchronise; g is not written."""
-    _seg_table("lamb", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    solver_extras("lamb", norm, max_norm, ema, ema_decay, table.end)
-    if float(decay) < 0.0 or not float(eps) > 0.0 or int(step) < 1:
-        raise ValueError(f"lamb: decay must be >= 0, eps > 0 and step >= 1, not {decay}, {eps}, {step}")
-    partials, q = _seg_scratch("lamb", table, partials, q, w.device)
-    hip.call("x3d_lamb", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
-             float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
-    return q
+    return _lamb("lamb", (), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay,
+                 partials, q)
+
+
+# ---- fine-tuning: the same rules on a table of the TUNED segments, lr * lr_scale[segment] per segment (finetune.py) ----------
+def seg_grad_sumsq(g, table, out=None, partials=None):
+    """out [2] fp64 = (sum of squares of the finite entries of g inside the table's chunks, number of non-finite ones):
+    grad_sumsq restricted to the segments of `table` (x3d_seg_grad_sumsq), the `norm=` of every launch here.  The same bits on
+    every run.  Two launches, does not synchronise."""
+    _seg_table("seg_grad_sumsq", table, ("g", g))
+    need = 2 * table.nchunk
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float64, device=g.device)
+    elif partials.dtype != torch.float64 or partials.numel() < need or not partials.is_contiguous():
+        raise ValueError(f"seg_grad_sumsq: partials must hold {need} float64, got {partials.numel()} {partials.dtype}")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=g.device)
+    elif out.dtype != torch.float64 or out.numel() != 2:
+        raise ValueError(f"seg_grad_sumsq: out must be 2 float64, got {out.numel()} {out.dtype}")
+    _chk(g, partials, out)
+    hip.call("x3d_seg_grad_sumsq", ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials),
+             ptr(out))
+    return out
+
+
+def sgd_pt(w, v, g, table, lr_scale, lr, momentum, weight_decay, grad_scale=1.0, norm=None, max_norm=0.0, ema=None,
+           ema_decay=0.0):
+    """SGD(momentum, nesterov) + L2 on the segments of `table` at lr * lr_scale[t] (x3d_sgd_pt; lr_scale None: all 1; the l2 flag
+    is the segment's).  One launch, does not synchronise."""
+    _seg_table("sgd_pt", table, ("w", w), ("v", v), ("g", g), ("ema", ema))
+    solver_extras("sgd_pt", norm, max_norm, ema, ema_decay, table.end)
+    hip.call("x3d_sgd_pt", ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             *_lr_scale("sgd_pt", table, lr_scale), float(lr), float(momentum), float(weight_decay), float(grad_scale), ptr(norm),
+             float(max_norm), ptr(ema), float(ema_decay))
+
+
+def adam_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=0.0, grad_scale=1.0, norm=None,
+            max_norm=0.0, ema=None, ema_decay=0.0):
+    """Adam + L2 on the segments of `table` at lr * lr_scale[t] (x3d_adam_pt).  One launch, does not synchronise."""
+    _seg_table("adam_pt", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
+    solver_extras("adam_pt", norm, max_norm, ema, ema_decay, table.end)
+    if int(step) < 1:
+        raise ValueError(f"adam_pt: step must be >= 1, not {step}")
+    hip.call("x3d_adam_pt", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
+             *_lr_scale("adam_pt", table, lr_scale), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+             float(grad_scale), int(step), ptr(norm), float(max_norm), ptr(ema), float(ema_decay))
+
+
+def lars_pt(w, v, g, table, lr_scale, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0,
+            norm=None, max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
+    """lars at lr * lr_scale[t] per segment (x3d_lars_pt); q [nseg] in the order of the table's segments."""
+    return _lars("lars_pt", _lr_scale("lars_pt", table, lr_scale), w, v, g, table, lr, momentum, weight_decay, trust_coef, eps,
+                 clip, grad_scale, norm, max_norm, ema, ema_decay, partials, q)
+
+
+def adamw_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None,
+             max_norm=0.0, ema=None, ema_decay=0.0):
+    """adamw at lr * lr_scale[t] per segment (x3d_adamw_pt)."""
+    _adamw("adamw_pt", _lr_scale("adamw_pt", table, lr_scale), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale,
+           norm, max_norm, ema, ema_decay)
+
+
+def lamb_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None,
+            max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
+    """lamb at lr * lr_scale[t] per segment (x3d_lamb_pt); q [nseg] in the order of the table's segments."""
+    return _lamb("lamb_pt", _lr_scale("lamb_pt", table, lr_scale), w, m, v, g, table, lr, step, beta1, beta2, eps, decay,
+                 grad_scale, norm, max_norm, ema, ema_decay, partials, q)
 
 
 def l2_sumsq(w, l2_mask, out):

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
-from .config import OPTIMIZERS, SLOT_KIND, mix_settings, optim_settings, precise_bn_settings, solver_settings
+from .config import OPTIMIZERS, SLOT_KIND, finetune_settings, mix_settings, optim_settings, precise_bn_settings, solver_settings
 from .mix import NO_MIX, draw_mix_params
 
 
@@ -98,7 +98,7 @@ class Trainer:
         # lars keeps SGD's slot (momentum) and checkpoint layout, adamw and lamb keep Adam's (m, v, `iter`)
         self.slot_kind = SLOT_KIND[self.optimizer]
         self.optim = optim_settings(cfg)      # OPTIM.*: read by the lars / adamw / lamb branches only
-        self.last_trust_ratios = None         # lars / lamb: device [nseg] fp32 trust ratios of the last update (model.segments order)
+        self.last_trust_ratios = None         # lars / lamb: device [nseg] fp32 trust ratios of the last update (model.segments order; fine-tuning: model.tuned_segments)
         self.opt_step = 0                     # optimizer steps applied (Adam's bias correction counts them)
         # Loss scaling = tf.keras.mixed_precision.LossScaleOptimizer(opt) with its defaults (train.py:99-100): dynamic,
         # initial scale 2^15, doubled after 2000 consecutive finite steps, halved (and the step skipped) when a gradient
@@ -146,6 +146,11 @@ class Trainer:
         self._micro = 0                       # micro-batches gathered of the running accumulation
         self._grad_acc = None                 # their summed local gradients (allocated by the first accumulation)
         self.last_grad_norm = None            # device scalar: global L2 norm of the unscaled gradient of the last update
+        # fine-tuning (SOLVER.FREEZE / LR_MULT / LAYER_DECAY; off by default: the model is then not told anything).  The update,
+        # the clip norm and the finite check then cover the tuned tensors only, at lr * scale per tensor (X3D.set_finetune)
+        self.finetune = finetune_settings(cfg)
+        if self.finetune != (1.0, (), ()):
+            model.set_finetune(freeze=self.finetune.freeze, lr_mult=self.finetune.lr_mult, layer_decay=self.finetune.layer_decay)
         # weight EMA: trainable block + moving statistics, laid out as flat_params; starts from the (broadcast) weights
         self.ema = model.flat_params.clone() if self.solver.ema_decay > 0.0 else None
         # stochastic depth (NETWORK.DROP_PATH_RATE): the tables are drawn on the device from (seed, step); rank r seeds with
