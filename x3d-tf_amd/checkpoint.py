@@ -628,7 +628,7 @@ def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None, skip_mi
     optimizer: the optimizer branch that will USE the slots ("sgd" | "adam" | None = whatever the bundle holds).  Slots of
     the other branch are not installed (Keras restores the variables and leaves a new optimizer's slots at zero): Adam's first
     moment is never SGD momentum or vice versa.  Whatever is installed is recorded in `model.slot_kind`, which
-    `apply_sgd` / `apply_adam` check before their first use of the buffers.
+    every `apply_*` checks before its first use of the buffers (X3D._claim_slots).
 
     skip_mismatch: variables whose bundle shape differs from the model's (fine-tuning a Kinetics-400 checkpoint into a
     157-class model: fc2) are not loaded -- they keep their current values and their optimizer slots stay zero -- and
@@ -642,20 +642,15 @@ def load_tf_checkpoint(model, path, expect_partial=True, optimizer=None, skip_mi
         warnings.warn(f"{len(skipped)} variables of {path} do not match the model's shapes and were not loaded: {skipped}")
     model.load_state_dict(sd, strict=not skipped)
     kind = "adam" if slots["m"] or slots["v"] else "sgd" if slots["momentum"] else None
-    model.flat_velocity.zero_()
-    if getattr(model, "flat_second", None) is not None:
-        model.flat_second.zero_()
+    model.zero_slots()
     install = kind is not None and optimizer in (None, kind)
     if install:
         for k, v in (slots["m"] or slots["momentum"]).items():
             if k in model.grads:
                 _flat_slot(model, model.flat_velocity, k).copy_(v)
-        if slots["v"]:
-            if getattr(model, "flat_second", None) is None:
-                model.flat_second = torch.zeros_like(model.flat_velocity)
-            for k, v in slots["v"].items():
-                if k in model.grads:
-                    _flat_slot(model, model.flat_second, k).copy_(v)
+        for k, v in slots["v"].items():
+            if k in model.grads:
+                _flat_slot(model, model.second_slot(), k).copy_(v)
     model.slot_kind = kind if install else None
     model.optimizer_state = dict(hyper=hyper, kind=kind)
     return skipped if skip_mismatch else model
@@ -666,9 +661,7 @@ def save_tf_checkpoint(model, prefix, optimizer_hyper=None, optimizer="sgd"):
     "adam": both moments as Keras Adam's `m` / `v` slots with Adam's hyper variables."""
     first = {k: _flat_slot(model, model.flat_velocity, k) for k in model.grads}
     if optimizer == "adam":
-        second = getattr(model, "flat_second", None)
-        if second is None:
-            second = torch.zeros_like(model.flat_velocity)
+        second = model.flat_second if model.flat_second is not None else torch.zeros_like(model.flat_velocity)   # (not kept)
         return write_checkpoint(prefix, model.state_dict(), model.specs, optimizer_hyper=optimizer_hyper,
                                 slots={"m": first, "v": {k: _flat_slot(model, second, k) for k in model.grads}})
     return write_checkpoint(prefix, model.state_dict(), model.specs, momentum=first, optimizer_hyper=optimizer_hyper)

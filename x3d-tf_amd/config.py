@@ -14,6 +14,8 @@ import re
 
 import yaml
 
+from .solver import RULES
+
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
 
 
@@ -430,8 +432,8 @@ def finetune_settings(cfg) -> FinetuneSettings:
 
 OptimSettings = collections.namedtuple("OptimSettings", "lars_trust_coef lars_eps lars_clip weight_decay lamb_eps")
 _OPTIM_DEFAULTS = OptimSettings(0.001, 1e-8, False, 0.0, 1e-6)
-OPTIMIZERS = ("sgd", "adam", "lars", "adamw", "lamb")       # TRAIN.OPTIMIZER, case-insensitive
-SLOT_KIND = dict(sgd="sgd", lars="sgd", adam="adam", adamw="adam", lamb="adam")   # whose slot / checkpoint layout a branch uses
+OPTIMIZERS = tuple(RULES)                                   # TRAIN.OPTIMIZER, case-insensitive
+SLOT_KIND = {name: rule.slot_kind for name, rule in RULES.items()}   # whose slot / checkpoint layout a branch uses
 
 
 def optim_settings(cfg) -> OptimSettings:

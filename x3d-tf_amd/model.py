@@ -23,10 +23,12 @@ from typing import Dict, Optional
 
 import torch
 
-from . import hip
-from .config import ensemble_method, multi_label
+from . import hip, ops
+from .config import FinetuneSettings, ensemble_method, multi_label
 from .arch import Arch, ParamSpec, block_prefix, build_arch, drop_path_rates, param_specs, summary_rows
 from .params import init_params
+from .segments import Segment, SegTable
+from .solver import RULES
 from .plan import PLAN_DEFAULTS, _FakeBuf, _Plan, _experiment_options, record_inference, record_training  # noqa: F401  (PLAN_DEFAULTS, _FakeBuf: re-exported)
 
 
@@ -195,6 +197,8 @@ class X3D:
         self.flat_params = torch.zeros(off, dtype=torch.float32, device=self.device)
         self.flat_grads = torch.zeros(self.n_trainable_flat, dtype=torch.float32, device=self.device)
         self.flat_velocity = torch.zeros(self.n_trainable_flat, dtype=torch.float32, device=self.device)
+        self.flat_second = None    # until an Adam-kind rule or an Adam checkpoint needs it (second_slot)
+        self.slot_kind = None      # whose state the slot buffers hold: set by load_weights, then by the first update (_claim_slots)
         l2 = torch.zeros(self.n_trainable_flat, dtype=torch.uint8)
         self.params: Dict[str, torch.Tensor] = {}
         self.grads: Dict[str, torch.Tensor] = {}
@@ -212,7 +216,6 @@ class X3D:
         self.n_trainable = sum(numel(s) for s in order if s.trainable)
         # the trainable tensors as segments of the flat buffers, in param_order: what the layer-wise optimizers (lars, adamw,
         # lamb) walk.  Their chunk table goes to the device with the first use (`seg_table`), once.
-        from .segments import Segment
         self.segments = [Segment(s.name, self._offsets[s.name], numel(s), bool(s.l2)) for s in order if s.trainable]
         self._seg_table = None
         # fine-tuning (set_finetune): off -- every apply_* and the gradient reduction make the launches they always made
@@ -360,12 +363,25 @@ class X3D:
     def _claim_slots(self, kind):
         """The slot buffers hold state of ONE optimizer branch (`slot_kind`: set by load_weights, then by the first update).
         An update of the other branch starts from zero slots, as a freshly built Keras optimizer does."""
-        have = getattr(self, "slot_kind", None)
-        if have is not None and have != kind:
-            self.flat_velocity.zero_()
-            if getattr(self, "flat_second", None) is not None:
-                self.flat_second.zero_()
+        if self.slot_kind is not None and self.slot_kind != kind:
+            self.zero_slots()
         self.slot_kind = kind
+
+    def zero_slots(self):
+        """Both slot buffers as a freshly built optimizer has them."""
+        self.flat_velocity.zero_()
+        if self.flat_second is not None:
+            self.flat_second.zero_()
+
+    def second_slot(self):
+        """`flat_second`, the second slot buffer of the Adam-kind rules (v), allocated -- as zeros -- with the first use."""
+        if self.flat_second is None:
+            self.flat_second = torch.zeros_like(self.flat_velocity)
+        return self.flat_second
+
+    def _adam_slots(self):
+        self._claim_slots("adam")
+        self.second_slot()
 
     def save_weights(self, prefix, optimizer_hyper=None, optimizer="sgd"):
         from .checkpoint import save_tf_checkpoint
@@ -465,8 +481,7 @@ class X3D:
         step) alone, and every replay advances the step by one.  Without NETWORK.DROP_PATH_RATE there is no draw: a no-op."""
         if self._dp_rates is None:
             return
-        from .ops import drop_path_state
-        st = drop_path_state(seed, step, self.device)
+        st = ops.drop_path_state(seed, step, self.device)
         if self._dp_state is None:
             self._dp_state = st
         else:
@@ -476,8 +491,7 @@ class X3D:
         """The step the next draw will use (synchronises); None without NETWORK.DROP_PATH_RATE."""
         if self._dp_state is None:
             return None
-        from .ops import drop_path_step
-        return drop_path_step(self._dp_state)
+        return ops.drop_path_step(self._dp_state)
 
     def __call__(self, input, training=False):
         return self.call(input, training)
@@ -594,75 +608,93 @@ class X3D:
                  self.n_trainable_flat)
         return acc * self.arch.weight_decay
 
+    def _solver_form(self, rule=None):
+        """The one choice of where a solver launch goes, as ops.solver_launch's keywords.  set_finetune active: the tuned chunk
+        table, its scales and scratch -- the _pt entry points and x3d_seg_grad_sumsq.  Otherwise the whole flat block under the
+        byte mask for a rule with flat entry points and for the gradient reductions (rule None), the full `seg_table` for the
+        other rules."""
+        ft = self._ft
+        if ft is not None:
+            return dict(table=ft.table, pt=True, lr_scale=ft.scale, partials=ft.partials, q=ft.trust_ratios)
+        if rule is None or rule.flat:
+            return dict(mask=self.l2_mask, n=self.n_trainable_flat)
+        return dict(table=self.seg_table, partials=self._seg_partials, q=self.trust_ratios)
+
     def grad_norm_sq(self):
         """x3d_grad_sumsq over `flat_grads` into buffers the model keeps: the device [2] fp64 tensor (sum of squares of the
-        raw gradient, number of non-finite entries) the `norm=` of apply_sgd / apply_adam reads.  Two launches, no
+        raw gradient, number of non-finite entries) the `norm=` of the apply_* methods reads.  Two launches, no
         synchronisation; the tensor is overwritten by the next call."""
         if getattr(self, "_norm_out", None) is None:
             n_scratch = int(hip.load().x3d_grad_sumsq_scratch(self.n_trainable_flat))
             self._norm_scratch = torch.empty(n_scratch, dtype=torch.float64, device=self.device)
             self._norm_out = torch.zeros(2, dtype=torch.float64, device=self.device)
-        if self._ft is not None:              # the tuned tensors only, as clip_grad_norm_ over the requires_grad parameters
-            from . import ops
-            return ops.seg_grad_sumsq(self.flat_grads, self._ft.table, self._norm_out, self._ft.partials)
-        hip.call("x3d_grad_sumsq", self.flat_grads.data_ptr(), self.n_trainable_flat, self._norm_scratch.data_ptr(),
+        form = self._solver_form()
+        if "table" in form:                   # the tuned tensors only, as clip_grad_norm_ over the requires_grad parameters
+            return ops.seg_grad_sumsq(self.flat_grads, form["table"], self._norm_out, form["partials"])
+        hip.call("x3d_grad_sumsq", self.flat_grads.data_ptr(), form["n"], self._norm_scratch.data_ptr(),
                  self._norm_out.data_ptr())
         return self._norm_out
+
+    def _apply(self, rule, norm, max_norm, ema, ema_decay, **scalars):
+        """One update of solver.RULES[rule], for every apply_*: claims the slot buffers for the rule's slot kind (zeroed when the
+        other kind held them), checks that `ema` also holds the padding behind the last tensor -- the chunk tables end before
+        it, so ops.solver_launch cannot know -- and makes the launch in the form `_solver_form` chooses.  Returns the device
+        trust ratios of a rule that computes them."""
+        r = RULES[rule]
+        self._claim_slots(r.slot_kind)
+        slots = (self.flat_velocity, self.second_slot()) if r.slot_kind == "adam" else (self.flat_velocity,)
+        if ema is not None and ema.numel() < self.n_trainable_flat:
+            raise ValueError(f"apply_{rule}: ema must hold at least {self.n_trainable_flat} elements, got {ema.numel()}")
+        if "weight_decay" in r.scalars:       # the coupled L2 term is the architecture's (NETWORK.WEIGHT_DECAY)
+            scalars["weight_decay"] = self.arch.weight_decay
+        return ops.solver_launch("apply_" + rule, rule, self.flat_params, slots, self.flat_grads, norm=norm, max_norm=max_norm,
+                                 ema=ema, ema_decay=ema_decay, **self._solver_form(r), **scalars)
 
     def apply_sgd(self, lr, momentum=0.9, grad_scale=1.0, norm=None, max_norm=0.0, ema=None, ema_decay=0.0):
         """SGD(momentum, nesterov=True) + L2 (reference train.py:89-92, model.py:47), one launch.
         norm (grad_norm_sq()) + max_norm: the gradient is clipped to that global L2 norm and a non-finite gradient skips
         the update, both decided on the device; ema: a flat fp32 buffer that receives ema_decay * ema + (1 - ema_decay) * w
         in the same pass (x3d_sgd_nesterov_ex).  With neither this is the x3d_sgd_nesterov launch it always was."""
-        self._claim_slots("sgd")
-        if self._ft is not None:
-            from . import ops
-            self._ema_covers_block("apply_sgd", ema)
-            ops.sgd_pt(self.flat_params, self.flat_velocity, self.flat_grads, self._ft.table, self._ft.scale, lr, momentum,
-                       self.arch.weight_decay, grad_scale, norm, max_norm, ema, ema_decay)
-            return
-        if norm is None and ema is None:
-            hip.call("x3d_sgd_nesterov", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
-                     self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
-                     float(self.arch.weight_decay), float(grad_scale), self.n_trainable_flat)
-            return
-        from . import ops
-        ops.solver_extras("apply_sgd", norm, max_norm, ema, ema_decay, self.n_trainable_flat)
-        hip.call("x3d_sgd_nesterov_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(),
-                 self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(momentum),
-                 float(self.arch.weight_decay), float(grad_scale), hip.ptr(norm), float(max_norm), hip.ptr(ema),
-                 float(ema_decay), self.n_trainable_flat)
+        self._apply("sgd", norm, max_norm, ema, ema_decay, lr=lr, momentum=momentum, grad_scale=grad_scale)
 
     def apply_adam(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, norm=None, max_norm=0.0, ema=None,
                    ema_decay=0.0):
         """Adam + L2 (reference train.py:93-95: tf.optimizers.Adam(learning_rate), Keras defaults), one launch.  The first
         moment lives in `flat_velocity` (the slot the SGD branch uses for momentum), the second in `flat_second`.
         norm / max_norm / ema / ema_decay: as apply_sgd (x3d_adam_ex)."""
-        self._adam_slots()
-        if self._ft is not None:
-            from . import ops
-            self._ema_covers_block("apply_adam", ema)
-            ops.adam_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self._ft.table, self._ft.scale,
-                        lr, step, beta1, beta2, eps, self.arch.weight_decay, grad_scale, norm, max_norm, ema, ema_decay)
-            return
-        if norm is None and ema is None:
-            hip.call("x3d_adam", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
-                     self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
-                     float(self.arch.weight_decay), float(grad_scale), int(step), self.n_trainable_flat)
-            return
-        from . import ops
-        ops.solver_extras("apply_adam", norm, max_norm, ema, ema_decay, self.n_trainable_flat)
-        hip.call("x3d_adam_ex", self.flat_params.data_ptr(), self.flat_velocity.data_ptr(), self.flat_second.data_ptr(),
-                 self.flat_grads.data_ptr(), self.l2_mask.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
-                 float(self.arch.weight_decay), float(grad_scale), int(step), hip.ptr(norm), float(max_norm), hip.ptr(ema),
-                 float(ema_decay), self.n_trainable_flat)
+        self._apply("adam", norm, max_norm, ema, ema_decay, lr=lr, step=step, beta1=beta1, beta2=beta2, eps=eps,
+                    grad_scale=grad_scale)
 
     # -- the layer-wise optimizers: a fixed number of launches over the chunk table, per-tensor trust ratios on the device --
+    def apply_lars(self, lr, momentum=0.9, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None, max_norm=0.0,
+                   ema=None, ema_decay=0.0):
+        """LARS: SGD(momentum, nesterov=True) + L2 with the update of every conv / dense kernel scaled by its trust ratio
+        q_t = trust_coef ||w_t|| / (c ||g_t|| + 2 wd ||w_t|| + eps) (clip: min(q_t / lr, 1)); BatchNorm and bias tensors take
+        q_t = 1 (x3d_lars, the rule is in include/x3d_hip.h).  Slot and checkpoint layout: SGD's.  Three launches, no
+        synchronisation.  norm / max_norm / ema / ema_decay: as apply_sgd.  Returns the device [nseg] fp32 trust ratios (in
+        `segments` order), overwritten by the next call."""
+        return self._apply("lars", norm, max_norm, ema, ema_decay, lr=lr, momentum=momentum, trust_coef=trust_coef, eps=eps,
+                           clip=clip, grad_scale=grad_scale)
+
+    def apply_adamw(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+                    ema=None, ema_decay=0.0):
+        """Adam with DECOUPLED weight decay: apply_adam's step without the coupled L2 term (NETWORK.WEIGHT_DECAY plays no part),
+        then w -= lr * decay * w_old on the conv / dense kernels (x3d_adamw).  Slots and checkpoint layout: Adam's.  One launch."""
+        self._apply("adamw", norm, max_norm, ema, ema_decay, lr=lr, step=step, beta1=beta1, beta2=beta2, eps=eps, decay=decay,
+                    grad_scale=grad_scale)
+
+    def apply_lamb(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
+                   ema=None, ema_decay=0.0):
+        """LAMB: Adam's moments, u = r_k m / (sqrt(v) + eps) + decay w, and w -= lr q_t u with q_t = ||w_t|| / ||u_t|| on the conv
+        / dense kernels, 1 elsewhere (x3d_lamb).  NETWORK.WEIGHT_DECAY plays no part.  Slots and checkpoint layout: Adam's.
+        Three launches, no synchronisation.  Returns the device [nseg] fp32 trust ratios, overwritten by the next call."""
+        return self._apply("lamb", norm, max_norm, ema, ema_decay, lr=lr, step=step, beta1=beta1, beta2=beta2, eps=eps,
+                           decay=decay, grad_scale=grad_scale)
+
     @property
     def seg_table(self):
         """segments.SegTable of `self.segments`, on the model's device (built and copied once)."""
         if self._seg_table is None:
-            from .segments import SegTable
             self._seg_table = SegTable(self.segments).to(self.device)
             self._seg_partials = torch.empty(2 * self._seg_table.nchunk, dtype=torch.float64, device=self.device)
             self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
@@ -679,9 +711,7 @@ class X3D:
         are [len(tuned_segments)], in that order.  Without arguments: cleared, every method makes the launches it always made.
         The forward and backward passes are not changed: frozen tensors' gradients are still computed, BatchNorm in frozen
         layers still uses batch statistics and updates its moving statistics."""
-        from .config import FinetuneSettings
         from .finetune import lr_scales
-        from .segments import SegTable
         st = FinetuneSettings(float(layer_decay), tuple((str(p), float(f)) for p, f in lr_mult), tuple(freeze))
         if not 0.0 < st.layer_decay <= 1.0 or not all(f > 0.0 and f < float("inf") for _, f in st.lr_mult):
             raise ValueError(f"set_finetune: layer_decay must lie in (0, 1] and every factor must be finite and > 0, not "
@@ -703,71 +733,10 @@ class X3D:
         self._ft = ft
         self.tuned_segments, self.lr_scales, self.frozen_names = tuned, {s.name: c for s, c in zip(tuned, scales)}, frozen
 
-    def _ema_covers_block(self, op, ema):
-        """ops.lars / adamw / lamb check norm, max_norm, ema and ema_decay (ops.solver_extras) against the chunk table, which ends
-        at the last tensor's last element; the model's EMA buffer also has to hold the padding behind it."""
-        if ema is not None and ema.numel() < self.n_trainable_flat:
-            raise ValueError(f"{op}: ema must hold at least {self.n_trainable_flat} elements, got {ema.numel()}")
-
-    def _adam_slots(self):
-        self._claim_slots("adam")
-        if getattr(self, "flat_second", None) is None:
-            self.flat_second = torch.zeros_like(self.flat_velocity)
-
-    def apply_lars(self, lr, momentum=0.9, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None, max_norm=0.0,
-                   ema=None, ema_decay=0.0):
-        """LARS: SGD(momentum, nesterov=True) + L2 with the update of every conv / dense kernel scaled by its trust ratio
-        q_t = trust_coef ||w_t|| / (c ||g_t|| + 2 wd ||w_t|| + eps) (clip: min(q_t / lr, 1)); BatchNorm and bias tensors take
-        q_t = 1 (x3d_lars, the rule is in include/x3d_hip.h).  Slot and checkpoint layout: SGD's.  Three launches, no
-        synchronisation.  norm / max_norm / ema / ema_decay: as apply_sgd.  Returns the device [nseg] fp32 trust ratios (in
-        `segments` order), overwritten by the next call."""
-        from . import ops
-        self._claim_slots("sgd")
-        self._ema_covers_block("apply_lars", ema)
-        if self._ft is not None:
-            ft = self._ft
-            return ops.lars_pt(self.flat_params, self.flat_velocity, self.flat_grads, ft.table, ft.scale, lr, momentum,
-                               self.arch.weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay,
-                               ft.partials, ft.trust_ratios)
-        tb = self.seg_table
-        return ops.lars(self.flat_params, self.flat_velocity, self.flat_grads, tb, lr, momentum, self.arch.weight_decay,
-                        trust_coef, eps, clip, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
-
-    def apply_adamw(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
-                    ema=None, ema_decay=0.0):
-        """Adam with DECOUPLED weight decay: apply_adam's step without the coupled L2 term (NETWORK.WEIGHT_DECAY plays no part),
-        then w -= lr * decay * w_old on the conv / dense kernels (x3d_adamw).  Slots and checkpoint layout: Adam's.  One launch."""
-        from . import ops
-        self._adam_slots()
-        self._ema_covers_block("apply_adamw", ema)
-        if self._ft is not None:
-            ops.adamw_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self._ft.table, self._ft.scale,
-                         lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
-            return
-        ops.adamw(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, self.seg_table, lr, step, beta1,
-                  beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
-
-    def apply_lamb(self, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
-                   ema=None, ema_decay=0.0):
-        """LAMB: Adam's moments, u = r_k m / (sqrt(v) + eps) + decay w, and w -= lr q_t u with q_t = ||w_t|| / ||u_t|| on the conv
-        / dense kernels, 1 elsewhere (x3d_lamb).  NETWORK.WEIGHT_DECAY plays no part.  Slots and checkpoint layout: Adam's.
-        Three launches, no synchronisation.  Returns the device [nseg] fp32 trust ratios, overwritten by the next call."""
-        from . import ops
-        self._adam_slots()
-        self._ema_covers_block("apply_lamb", ema)
-        if self._ft is not None:
-            ft = self._ft
-            return ops.lamb_pt(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, ft.table, ft.scale, lr,
-                               step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay, ft.partials,
-                               ft.trust_ratios)
-        tb = self.seg_table
-        return ops.lamb(self.flat_params, self.flat_velocity, self.flat_second, self.flat_grads, tb, lr, step, beta1, beta2, eps,
-                        decay, grad_scale, norm, max_norm, ema, ema_decay, self._seg_partials, self.trust_ratios)
-
     def grads_finite(self) -> bool:
         """True when every entry of the flat gradient buffer is finite (x3d_all_finite; synchronises).  With set_finetune:
         every entry of the TUNED tensors' gradients -- the count x3d_seg_grad_sumsq leaves in grad_norm_sq()'s result."""
-        if self._ft is not None:
+        if "table" in self._solver_form():
             return float(self.grad_norm_sq()[1].item()) == 0.0
         if getattr(self, "_finite_flag", None) is None:
             self._finite_flag = torch.ones(1, dtype=torch.int32, device=self.device)

@@ -10,6 +10,7 @@ import torch
 from . import hip
 from .hip import (ACT_NONE, ACT_RELU, ACT_SWISH, EPI_ADD, EPI_ADD_STRIDED, EPI_STORE,  # noqa: F401
                   EPI_SWISH_BWD, ptr)
+from .solver import RULES, SLOT_NAMES
 
 
 def _chk(*ts):
@@ -687,16 +688,20 @@ def randaug_clips(videos, randaug_list, t, rate=1, starts=None, fill=(0, 0, 0)):
     return views.randaug_clips(videos, randaug_list, int(t), int(rate), starts, fill)[0]
 
 
-def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
-    _chk(w, v, g, l2_mask)
-    hip.call("x3d_sgd_nesterov", ptr(w), ptr(v), ptr(g), ptr(l2_mask), float(lr), float(momentum),
-             float(weight_decay), float(grad_scale), w.numel())
-
-
 def _f32_flat(op, name, t, n=None):
     if t.dtype != torch.float32 or not t.is_contiguous() or (n is not None and t.numel() != n):
         raise ValueError(f"{op}: {name} must be contiguous float32" + (f" of {n} elements" if n is not None else "")
                          + f", got {t.numel()} {t.dtype}")
+
+
+def _f64_scratch(op, name, t, need, device, exact=False):
+    """the `out` / `partials` / `scratch` of the sum-of-squares launches: checked (contiguous float64 of `need` elements when
+    `exact`, of at least that many otherwise), or allocated when None"""
+    if t is None:
+        return torch.empty(need, dtype=torch.float64, device=device)
+    if t.dtype != torch.float64 or not t.is_contiguous() or (t.numel() != need if exact else t.numel() < need):
+        raise ValueError(f"{op}: {name} must {'be' if exact else 'hold'} {need} float64, got {t.numel()} {t.dtype}")
+    return t
 
 
 def grad_sumsq(g, out=None, scratch=None):
@@ -705,15 +710,8 @@ def grad_sumsq(g, out=None, scratch=None):
     _chk(g, out, scratch)
     _f32_flat("grad_sumsq", "g", g)
     n = g.numel()
-    need = int(hip.load().x3d_grad_sumsq_scratch(n))
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.float64, device=g.device)
-    elif scratch.dtype != torch.float64 or scratch.numel() < need:
-        raise ValueError(f"grad_sumsq: scratch must hold {need} float64, got {scratch.numel()} {scratch.dtype}")
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=g.device)
-    elif out.dtype != torch.float64 or out.numel() != 2:
-        raise ValueError(f"grad_sumsq: out must be 2 float64, got {out.numel()} {out.dtype}")
+    scratch = _f64_scratch("grad_sumsq", "scratch", scratch, int(hip.load().x3d_grad_sumsq_scratch(n)), g.device)
+    out = _f64_scratch("grad_sumsq", "out", out, 2, g.device, exact=True)
     hip.call("x3d_grad_sumsq", ptr(g), n, ptr(scratch), ptr(out))
     return out
 
@@ -739,39 +737,51 @@ def grad_accum(acc, g, first=False):
     return acc
 
 
-# ---- layer-wise optimizers: driven by a segments.SegTable (chunk table on the device) ------------------------------------
+def _covered(op, end, what, *buffers):
+    """every (name, tensor) of `buffers` is contiguous float32 and holds the first `end` elements"""
+    for name, t in buffers:
+        if t is not None:
+            _f32_flat(op, name, t)
+            if t.numel() < end:
+                raise ValueError(f"{op}: {name} holds {t.numel()} elements, {what} {end}")
+
+
 def _seg_table(op, table, *buffers):
     """the table is on the device and covers nothing outside any of `buffers` (contiguous float32, same device)"""
     if table.d_chunks is None:
         raise ValueError(f"{op}: the chunk table is not on a device yet (SegTable.to(device))")
-    for name, t in buffers:
-        if t is None:
-            continue
-        _f32_flat(op, name, t)
-        if t.numel() < table.end:
-            raise ValueError(f"{op}: {name} holds {t.numel()} elements, the chunk table covers up to {table.end}")
+    _covered(op, table.end, "the chunk table covers up to", *buffers)
     _chk(table.d_chunks, table.d_segs, *[t for _, t in buffers])
 
 
-def _seg_scratch(op, table, partials, q, device):
-    """partials [2 * nchunk] fp64 and q [nseg] fp32: checked, or allocated when None"""
-    need = 2 * table.nchunk
-    if partials is None:
-        partials = torch.empty(need, dtype=torch.float64, device=device)
-    elif partials.dtype != torch.float64 or partials.numel() < need or not partials.is_contiguous():
-        raise ValueError(f"{op}: partials must hold {need} float64, got {partials.numel()} {partials.dtype}")
-    if q is None:
-        q = torch.ones(table.nseg, dtype=torch.float32, device=device)
-    elif q.dtype != torch.float32 or q.numel() != table.nseg or not q.is_contiguous():
-        raise ValueError(f"{op}: q must be {table.nseg} float32, got {q.numel()} {q.dtype}")
-    _chk(partials, q)
-    return partials, q
+def seg_sumsq(a, table, out=None, partials=None):
+    """out [nseg] fp64 = per-segment sum of squares of `a` (squared and added in fp64, a fixed order: the same bits on every
+    run; x3d_seg_sumsq).  table: segments.SegTable on a's device.  Two launches, does not synchronise."""
+    _seg_table("seg_sumsq", table, ("a", a))
+    _chk(partials, out)
+    partials = _f64_scratch("seg_sumsq", "partials", partials, table.nchunk, a.device)
+    out = _f64_scratch("seg_sumsq", "out", out, table.nseg, a.device, exact=True)
+    hip.call("x3d_seg_sumsq", ptr(a), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials), ptr(out))
+    return out
 
 
+def seg_grad_sumsq(g, table, out=None, partials=None):
+    """out [2] fp64 = (sum of squares of the finite entries of g inside the table's chunks, number of non-finite ones):
+    grad_sumsq restricted to the segments of `table` (x3d_seg_grad_sumsq), the `norm=` of the launches over a table of tuned
+    segments.  The same bits on every run.  Two launches, does not synchronise."""
+    _seg_table("seg_grad_sumsq", table, ("g", g))
+    partials = _f64_scratch("seg_grad_sumsq", "partials", partials, 2 * table.nchunk, g.device)
+    out = _f64_scratch("seg_grad_sumsq", "out", out, 2, g.device, exact=True)
+    _chk(partials, out)
+    hip.call("x3d_seg_grad_sumsq", ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials),
+             ptr(out))
+    return out
+
+
+# ---- the update rules (solver.RULES): one assembler makes every launch, the public wrappers bind their arguments to it -------
 def solver_extras(op, norm, max_norm, ema, ema_decay, n):
-    """The norm / max_norm / ema / ema_decay arguments of the _ex and the layer-wise launches, checked in one place for lars /
-    adamw / lamb here and X3D.apply_sgd / apply_adam: norm is grad_sumsq's device result and brings a positive max_norm, ema is a
-    flat device buffer of at least n elements and brings a decay in [0, 1)."""
+    """The norm / max_norm / ema / ema_decay arguments of the _ex and the chunk-table launches: norm is grad_sumsq's device result
+    and brings a positive max_norm, ema is a flat device buffer of at least n elements and brings a decay in [0, 1)."""
     if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 2 or not norm.is_cuda):
         raise ValueError(f"{op}: norm must be the device [2] float64 result of grad_sumsq")
     if norm is not None and not float(max_norm) > 0.0:
@@ -782,156 +792,137 @@ def solver_extras(op, norm, max_norm, ema, ema_decay, n):
         raise ValueError(f"{op}: ema_decay must lie in [0, 1), not {ema_decay}")
 
 
-def seg_sumsq(a, table, out=None, partials=None):
-    """out [nseg] fp64 = per-segment sum of squares of `a` (squared and added in fp64, a fixed order: the same bits on every
-    run; x3d_seg_sumsq).  table: segments.SegTable on a's device.  Two launches, does not synchronise."""
-    _seg_table("seg_sumsq", table, ("a", a))
-    if partials is None:
-        partials = torch.empty(table.nchunk, dtype=torch.float64, device=a.device)
-    elif partials.dtype != torch.float64 or partials.numel() < table.nchunk:
-        raise ValueError(f"seg_sumsq: partials must hold {table.nchunk} float64, got {partials.numel()} {partials.dtype}")
-    if out is None:
-        out = torch.empty(table.nseg, dtype=torch.float64, device=a.device)
-    elif out.dtype != torch.float64 or out.numel() != table.nseg:
-        raise ValueError(f"seg_sumsq: out must be {table.nseg} float64, got {out.numel()} {out.dtype}")
-    _chk(a, partials, out)
-    hip.call("x3d_seg_sumsq", ptr(a), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials), ptr(out))
-    return out
+_AS_C = {float: float, int: int, bool: lambda flag: 1 if flag else 0}
+_OUTSIDE = {"> 0": lambda v: not v > 0, ">= 0": lambda v: v < 0, ">= 1": lambda v: v < 1}      # the bounds solver.RULES names
 
 
-def _lr_scale(op, table, lr_scale):
-    """the lr_scale argument of the _pt launches as a tuple to splice in behind nseg: None (every scale 1), or the device
-    [nseg] float32 of the table's segments"""
-    if lr_scale is not None:
-        if lr_scale.dtype != torch.float32 or lr_scale.numel() != table.nseg or not lr_scale.is_contiguous() \
-                or not lr_scale.is_cuda:
-            raise ValueError(f"{op}: lr_scale must be a contiguous device float32 tensor of {table.nseg} elements (one per "
-                             f"segment of the table), got {lr_scale.numel()} {lr_scale.dtype}")
-        _chk(table.d_chunks, lr_scale)
-    return (ptr(lr_scale),)
+def solver_launch(op, rule, w, slots, g, *, mask=None, n=None, table=None, pt=False, lr_scale=None, norm=None, max_norm=0.0,
+                  ema=None, ema_decay=0.0, partials=None, q=None, **scalars):
+    """One update of rule `rule` (a key of solver.RULES) on the weights w, its slot buffers `slots` and the gradient g: every
+    argument checked, then exactly one hip.call.  `op` is the caller's name, for the messages.
+      where     mask (byte mask of the L2-regularised elements, or None) and n: the first n elements, by the rule's flat entry
+                point -- the plain one when neither norm nor ema is given, else _ex.  table (a segments.SegTable on the device):
+                its segments, by the chunk-table entry point; pt: its _pt form, at lr * lr_scale[segment] (lr_scale None: all 1)
+      scalars   by the names of RULES[rule].scalars; the record's defaults for those not given
+      extras    norm (grad_sumsq's / seg_grad_sumsq's result) + max_norm: clip to that global L2 norm, skip the update on a
+                non-finite gradient; ema + ema_decay: the weight average kept in the same pass (solver_extras)
+      scratch   partials [2 * nchunk] fp64 and q [nseg] fp32 of a rule with trust ratios, allocated when None (ignored by the
+                other rules).  Returns q for such a rule, else None."""
+    r = RULES[rule]
+    buffers = (("w", w), *zip(SLOT_NAMES[r.slot_kind], slots, strict=True), ("g", g))
+    ex = table is not None or norm is not None or ema is not None          # the entry point takes the extras
+    entry = r.table[bool(pt)] if table is not None else r.flat and r.flat[ex]
+    if not entry:
+        raise ValueError(f"{op}: {rule} has no {'chunk-table entry point without lr_scale' if table is not None else 'flat form'}")
+    if table is None:
+        n = int(n)
+        _chk(mask, *[t for _, t in buffers])
+        _covered(op, n, "the update covers", *buffers)
+        if mask is not None and mask.numel() < n:
+            raise ValueError(f"{op}: l2_mask holds {mask.numel()} elements, the update covers {n}")
+        where = (ptr(mask),)
+    else:
+        _seg_table(op, table, *buffers, ("ema", ema))
+        n = table.end
+        where = (ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg)
+    solver_extras(op, norm, max_norm, ema, ema_decay, n)
+    values = {}
+    for name, default in r.scalars.items():
+        v = scalars.pop(name, default)
+        if isinstance(v, type):
+            raise TypeError(f"{op}: {rule} needs {name}")
+        values[name] = _AS_C[default if isinstance(default, type) else type(default)](v)
+    if scalars:
+        raise TypeError(f"{op}: {rule} takes no {sorted(scalars)}")
+    if table is not None and any(_OUTSIDE[b](values[k]) for k, b in r.bounds.items()):    # (the flat forms take what they are given)
+        raise ValueError(f"{op}: " + ", ".join(f"{k} must be {b}" for k, b in r.bounds.items()) + ", not "
+                         + ", ".join(str(values[k]) for k in r.bounds))
+    if pt:
+        if lr_scale is not None:
+            if lr_scale.dtype != torch.float32 or lr_scale.numel() != table.nseg or not lr_scale.is_contiguous() \
+                    or not lr_scale.is_cuda:
+                raise ValueError(f"{op}: lr_scale must be a contiguous device float32 tensor of {table.nseg} elements (one per "
+                                 f"segment of the table), got {lr_scale.numel()} {lr_scale.dtype}")
+            _chk(table.d_chunks, lr_scale)
+        where += (ptr(lr_scale),)
+    tail = (ptr(norm), float(max_norm), ptr(ema), float(ema_decay)) if ex else ()
+    if table is None:
+        tail += (n,)
+    if r.trust:
+        partials = _f64_scratch(op, "partials", partials, 2 * table.nchunk, w.device)
+        if q is None:
+            q = torch.ones(table.nseg, dtype=torch.float32, device=w.device)
+        elif q.dtype != torch.float32 or q.numel() != table.nseg or not q.is_contiguous():
+            raise ValueError(f"{op}: q must be {table.nseg} float32, got {q.numel()} {q.dtype}")
+        _chk(partials, q)
+        tail += (ptr(partials), ptr(q))
+    hip.call(entry, *map(ptr, (w, *slots, g)), *where, *values.values(), *tail)
+    return q if r.trust else None
 
 
-def _lars(op, scale, w, v, g, table, lr, momentum, weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema,
-          ema_decay, partials, q):
-    _seg_table(op, table, ("w", w), ("v", v), ("g", g), ("ema", ema))
-    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
-    if not float(trust_coef) > 0.0 or float(eps) < 0.0:
-        raise ValueError(f"{op}: trust_coef must be positive and eps >= 0, not {trust_coef}, {eps}")
-    partials, q = _seg_scratch(op, table, partials, q, w.device)
-    hip.call("x3d_" + op, ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, *scale,
-             float(lr), float(momentum), float(weight_decay), float(grad_scale), float(trust_coef), float(eps), 1 if clip else 0,
-             ptr(norm), float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
-    return q
+def _bound(op, rule, a):
+    """The launch of a public wrapper from its locals(): the wrappers' parameter names are those of the rule's slots (v | m, v)
+    and scalars and solver_launch's keywords; a wrapper with an lr_scale parameter is the _pt form."""
+    keys = ("table", "lr_scale", "norm", "max_norm", "ema", "ema_decay", "partials", "q", *RULES[rule].scalars)
+    return solver_launch(op, rule, a["w"], [a[k] for k in SLOT_NAMES[RULES[rule].slot_kind]], a["g"], pt="lr_scale" in a,
+                         **{k: a[k] for k in keys if k in a})
+
+
+def sgd_nesterov(w, v, g, l2_mask, lr, momentum, weight_decay, grad_scale=1.0):
+    solver_launch("sgd_nesterov", "sgd", w, (v,), g, mask=l2_mask, n=w.numel(), lr=lr, momentum=momentum,
+                  weight_decay=weight_decay, grad_scale=grad_scale)
 
 
 def lars(w, v, g, table, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0, norm=None,
          max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
     """LARS on the segments of `table` (x3d_lars: the rule is in include/x3d_hip.h); returns q [nseg] fp32, the trust ratios,
     on the device.  Three launches, does not synchronise; g is not written."""
-    return _lars("lars", (), w, v, g, table, lr, momentum, weight_decay, trust_coef, eps, clip, grad_scale, norm, max_norm, ema,
-                 ema_decay, partials, q)
-
-
-def _adamw(op, scale, w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay):
-    _seg_table(op, table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
-    if float(decay) < 0.0 or int(step) < 1:
-        raise ValueError(f"{op}: decay must be >= 0 and step >= 1, not {decay}, {step}")
-    hip.call("x3d_" + op, ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             *scale, float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
-             float(max_norm), ptr(ema), float(ema_decay))
+    return _bound("lars", "lars", locals())
 
 
 def adamw(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
           ema=None, ema_decay=0.0):
     """Adam with decoupled weight decay on the l2 segments of `table` (x3d_adamw).  One launch, does not synchronise."""
-    _adamw("adamw", (), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay)
-
-
-def _lamb(op, scale, w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay,
-          partials, q):
-    _seg_table(op, table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    solver_extras(op, norm, max_norm, ema, ema_decay, table.end)
-    if float(decay) < 0.0 or not float(eps) > 0.0 or int(step) < 1:
-        raise ValueError(f"{op}: decay must be >= 0, eps > 0 and step >= 1, not {decay}, {eps}, {step}")
-    partials, q = _seg_scratch(op, table, partials, q, w.device)
-    hip.call("x3d_" + op, ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             *scale, float(lr), float(beta1), float(beta2), float(eps), float(decay), float(grad_scale), int(step), ptr(norm),
-             float(max_norm), ptr(ema), float(ema_decay), ptr(partials), ptr(q))
-    return q
+    _bound("adamw", "adamw", locals())
 
 
 def lamb(w, m, v, g, table, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None, max_norm=0.0,
          ema=None, ema_decay=0.0, partials=None, q=None):
     """LAMB on the segments of `table` (x3d_lamb); returns q [nseg] fp32, the trust ratios, on the device.  Three launches, does
     not synchronise; g is not written."""
-    return _lamb("lamb", (), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale, norm, max_norm, ema, ema_decay,
-                 partials, q)
+    return _bound("lamb", "lamb", locals())
 
 
-# ---- fine-tuning: the same rules on a table of the TUNED segments, lr * lr_scale[segment] per segment (finetune.py) ----------
-def seg_grad_sumsq(g, table, out=None, partials=None):
-    """out [2] fp64 = (sum of squares of the finite entries of g inside the table's chunks, number of non-finite ones):
-    grad_sumsq restricted to the segments of `table` (x3d_seg_grad_sumsq), the `norm=` of every launch here.  The same bits on
-    every run.  Two launches, does not synchronise."""
-    _seg_table("seg_grad_sumsq", table, ("g", g))
-    need = 2 * table.nchunk
-    if partials is None:
-        partials = torch.empty(need, dtype=torch.float64, device=g.device)
-    elif partials.dtype != torch.float64 or partials.numel() < need or not partials.is_contiguous():
-        raise ValueError(f"seg_grad_sumsq: partials must hold {need} float64, got {partials.numel()} {partials.dtype}")
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=g.device)
-    elif out.dtype != torch.float64 or out.numel() != 2:
-        raise ValueError(f"seg_grad_sumsq: out must be 2 float64, got {out.numel()} {out.dtype}")
-    _chk(g, partials, out)
-    hip.call("x3d_seg_grad_sumsq", ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(partials),
-             ptr(out))
-    return out
-
-
+# fine-tuning: the same rules on a table of the TUNED segments, lr * lr_scale[segment] per segment (finetune.py; lr_scale None: all 1)
 def sgd_pt(w, v, g, table, lr_scale, lr, momentum, weight_decay, grad_scale=1.0, norm=None, max_norm=0.0, ema=None,
            ema_decay=0.0):
-    """SGD(momentum, nesterov) + L2 on the segments of `table` at lr * lr_scale[t] (x3d_sgd_pt; lr_scale None: all 1; the l2 flag
-    is the segment's).  One launch, does not synchronise."""
-    _seg_table("sgd_pt", table, ("w", w), ("v", v), ("g", g), ("ema", ema))
-    solver_extras("sgd_pt", norm, max_norm, ema, ema_decay, table.end)
-    hip.call("x3d_sgd_pt", ptr(w), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             *_lr_scale("sgd_pt", table, lr_scale), float(lr), float(momentum), float(weight_decay), float(grad_scale), ptr(norm),
-             float(max_norm), ptr(ema), float(ema_decay))
+    """SGD(momentum, nesterov) + L2 on the segments of `table` at lr * lr_scale[t] (x3d_sgd_pt; the l2 flag is the segment's).
+    One launch, does not synchronise."""
+    _bound("sgd_pt", "sgd", locals())
 
 
 def adam_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=0.0, grad_scale=1.0, norm=None,
             max_norm=0.0, ema=None, ema_decay=0.0):
     """Adam + L2 on the segments of `table` at lr * lr_scale[t] (x3d_adam_pt).  One launch, does not synchronise."""
-    _seg_table("adam_pt", table, ("w", w), ("m", m), ("v", v), ("g", g), ("ema", ema))
-    solver_extras("adam_pt", norm, max_norm, ema, ema_decay, table.end)
-    if int(step) < 1:
-        raise ValueError(f"adam_pt: step must be >= 1, not {step}")
-    hip.call("x3d_adam_pt", ptr(w), ptr(m), ptr(v), ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg,
-             *_lr_scale("adam_pt", table, lr_scale), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-             float(grad_scale), int(step), ptr(norm), float(max_norm), ptr(ema), float(ema_decay))
+    _bound("adam_pt", "adam", locals())
 
 
 def lars_pt(w, v, g, table, lr_scale, lr, momentum, weight_decay, trust_coef=0.001, eps=1e-8, clip=False, grad_scale=1.0,
             norm=None, max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
     """lars at lr * lr_scale[t] per segment (x3d_lars_pt); q [nseg] in the order of the table's segments."""
-    return _lars("lars_pt", _lr_scale("lars_pt", table, lr_scale), w, v, g, table, lr, momentum, weight_decay, trust_coef, eps,
-                 clip, grad_scale, norm, max_norm, ema, ema_decay, partials, q)
+    return _bound("lars_pt", "lars", locals())
 
 
 def adamw_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-7, decay=0.0, grad_scale=1.0, norm=None,
              max_norm=0.0, ema=None, ema_decay=0.0):
     """adamw at lr * lr_scale[t] per segment (x3d_adamw_pt)."""
-    _adamw("adamw_pt", _lr_scale("adamw_pt", table, lr_scale), w, m, v, g, table, lr, step, beta1, beta2, eps, decay, grad_scale,
-           norm, max_norm, ema, ema_decay)
+    _bound("adamw_pt", "adamw", locals())
 
 
 def lamb_pt(w, m, v, g, table, lr_scale, lr, step, beta1=0.9, beta2=0.999, eps=1e-6, decay=0.0, grad_scale=1.0, norm=None,
             max_norm=0.0, ema=None, ema_decay=0.0, partials=None, q=None):
     """lamb at lr * lr_scale[t] per segment (x3d_lamb_pt); q [nseg] in the order of the table's segments."""
-    return _lamb("lamb_pt", _lr_scale("lamb_pt", table, lr_scale), w, m, v, g, table, lr, step, beta1, beta2, eps, decay,
-                 grad_scale, norm, max_norm, ema, ema_decay, partials, q)
+    return _bound("lamb_pt", "lamb", locals())
 
 
 def l2_sumsq(w, l2_mask, out):

@@ -11,8 +11,10 @@ from typing import Optional
 import torch
 
 from . import dist as xdist
-from .config import OPTIMIZERS, SLOT_KIND, finetune_settings, mix_settings, optim_settings, precise_bn_settings, solver_settings
+from . import ops
+from .config import OPTIMIZERS, finetune_settings, mix_settings, optim_settings, precise_bn_settings, solver_settings
 from .mix import NO_MIX, draw_mix_params
+from .solver import RULES
 
 
 def lr_schedule(epoch, cfg):
@@ -96,7 +98,8 @@ class Trainer:
             raise NotImplementedError(f"{cfg.TRAIN.OPTIMIZER} not supported")
         self.model, self.cfg, self.group = model, cfg, group
         # lars keeps SGD's slot (momentum) and checkpoint layout, adamw and lamb keep Adam's (m, v, `iter`)
-        self.slot_kind = SLOT_KIND[self.optimizer]
+        self.rule = RULES[self.optimizer]
+        self.slot_kind = self.rule.slot_kind
         self.optim = optim_settings(cfg)      # OPTIM.*: read by the lars / adamw / lamb branches only
         self.last_trust_ratios = None         # lars / lamb: device [nseg] fp32 trust ratios of the last update (model.segments order; fine-tuning: model.tuned_segments)
         self.opt_step = 0                     # optimizer steps applied (Adam's bias correction counts them)
@@ -210,21 +213,14 @@ class Trainer:
             extras.update(norm=norm, max_norm=self.solver.clip_grad_l2norm)
         if self.ema is not None:
             extras.update(ema=self.ema, ema_decay=self.solver.ema_decay)
-        o = self.optim
-        if self.optimizer == "adam":
-            m.apply_adam(lr, self.opt_step, grad_scale=grad_scale, **extras)
-        elif self.optimizer == "sgd":
-            m.apply_sgd(lr, self.momentum, grad_scale=grad_scale, **extras)
-        elif self.optimizer == "lars":        # trust ratios of the all-reduced, accumulated gradient: the same on every rank
-            self.last_trust_ratios = m.apply_lars(lr, self.momentum, o.lars_trust_coef, o.lars_eps, o.lars_clip,
-                                                  grad_scale=grad_scale, **extras)
-        elif self.optimizer == "adamw":
-            m.apply_adamw(lr, self.opt_step, decay=o.weight_decay, grad_scale=grad_scale, **extras)
-        else:
-            self.last_trust_ratios = m.apply_lamb(lr, self.opt_step, eps=o.lamb_eps, decay=o.weight_decay,
-                                                  grad_scale=grad_scale, **extras)
+        # the rule's scalars (solver.RULES): the trainer's own state for those it has, OPTIM.* for those the record maps there
+        mine = dict(momentum=self.momentum, step=self.opt_step)
+        kw = {k: mine[k] for k in self.rule.scalars if k in mine}
+        kw.update({k: getattr(self.optim, field) for k, field in self.rule.settings.items()})
+        q = getattr(m, "apply_" + self.optimizer)(lr, grad_scale=grad_scale, **kw, **extras)
+        if self.rule.trust:                   # of the all-reduced, accumulated gradient: the same on every rank
+            self.last_trust_ratios = q
         if self.ema is not None:              # the moving statistics behind the trainable block: skipped together with the step
-            from . import ops
             ops.ema_update(self.ema[m.n_trainable_flat:], m.moving_stats_flat(), self.solver.ema_decay, extras.get("norm"))
         if self.dynamic_scale and self._good_steps >= self.growth_steps:
             self.loss_scale *= 2.0
@@ -237,7 +233,6 @@ class Trainer:
         Micro-batch A adds the accumulator back -- under data parallelism bucket by bucket in the backward hook, in front of
         that bucket's all-reduce, so the exchange still hides behind the backward pass -- and updates on the total, which
         `flat_grads` then holds.  The loss scale changes with an update only, so it is one value within an accumulation."""
-        from . import ops
         m = self.model
         self._micro += 1
         last = self._micro == self._accum
@@ -265,7 +260,6 @@ class Trainer:
         storage type -- which binding them would do anyway -- made a copy, else into a buffer the trainer keeps.  With
         smoothing only (mode "none") the clips are passed through and lam = 1.  Single-label models: `plan.labels` receives
         the hard labels the training metrics count against.  Launches only, no host synchronisation."""
-        from . import ops
         m = self.model
         n, t, h, w, _ = clips.shape
         p = draw_mix_params(self.cfg, h, w, self._mix_rng)
@@ -489,7 +483,6 @@ class Trainer:
         i = self._launch_at.get(stage)
         if i is not None:
             if self._accum > 1:               # the last micro-batch of an accumulation: the earlier ones join their bucket first
-                from . import ops
                 b = self.reducer.buckets[i]
                 lo = b.storage_offset() - self.model.flat_grads.storage_offset()
                 ops.grad_accum(b, self._grad_acc[lo:lo + b.numel()])
@@ -598,15 +591,13 @@ class Trainer:
         if kind is not None and kind != self.slot_kind:
             # a checkpoint written by the other optimizer branch: Keras restores the variables and leaves the new
             # optimizer's slots at their initial value -- never reuse SGD momentum as Adam's first moment or vice versa
-            m.flat_velocity.zero_()
-            if getattr(m, "flat_second", None) is not None:
-                m.flat_second.zero_()
+            m.zero_slots()
             self.opt_step = 0
         else:
             # optimizer/iter: Adam's bias correction continues from the saved step count
             self.opt_step = int(st.get("hyper", {}).get("iter", 0))
             if self.slot_kind == "adam" and kind is None:
-                m.flat_velocity.zero_()
+                m.zero_slots()
                 self.opt_step = 0
         if self.ema is not None:              # restart the EMA from the loaded weights (resume replaces it by a saved one)
             self.ema.copy_(m.flat_params)
@@ -617,6 +608,6 @@ class Trainer:
         ce = pl.loss_rows.sum() / (pl.n * self.world)
         if self.collectives:
             torch.distributed.all_reduce(ce, group=self.group)
-        if self.optimizer in ("adamw", "lamb"):
+        if not self.rule.l2_in_loss:
             return ce
         return ce + self.model.regularization_loss().float().squeeze()
