@@ -681,6 +681,146 @@ def aux_full_id(case):
     return "-".join([e] + [p if p else "none" for p in parts])
 
 
+# ---- the same runners (tests/aux_checks.py) at the edges of the kernels' tiles: tests/test_aux_edges_gpu.py runs every case,
+# tests/test_aux_edges.py keeps the table on the edges when a tile size is retuned.  Keys as AUX_FULL, the plane-wise ones with an
+# optional trailing element offset of every tensor into its allocation (a view that is not 16-byte aligned), and
+#   ("tail_fwd", dtype, N, C, P, None | "identity" | "conv"[, off])      ("dw_slab_reduce", ((parts, elems), ...))
+#   ("all_finite", n, kind, pos)     ("l2_sumsq", n, None | "random" | "zeros")     ("nthwc_to_ncthw", src, dst, N, C, P[, off])
+#   ("dense_bwd_refused", N, K, M)   ("se_fwd_refused", N, C, Wd)                   ("dw_slab_reduce_refused", parts, elems, off)
+# The tile sizes the table was built for: the #define lines of head.hip, se.hip and elem.hip (test_aux_edges.py reads them from the
+# sources and fails when one moved), and the literals of the kernels' loops:
+AUX_TILES = dict(DENSE_NT=8, DENSE_MT=4, DENSE_BN=4, DENSE_BM=8, SE_MAXC=1024, SE_MAXW=64, DWR_EPB=64, ELEM_BLOCK=256, ELEM_ITERS=4)
+AUX_TILE_SOURCES = {"head.hip": ("DENSE_NT", "DENSE_MT", "DENSE_BN", "DENSE_BM"), "se.hip": ("SE_MAXC", "SE_MAXW", "DWR_EPB"),
+                    "elem.hip": ("ELEM_BLOCK", "ELEM_ITERS")}
+AUX_LITERALS = dict(
+    LANES=64,            # head.hip dense_fwd_kernel: `k += 64`, dense_bwd_dx_kernel: 64 inputs k per workgroup (the lanes)
+    DX_BATCH=16 * 4,     # head.hip dense_bwd_dx_kernel: DXB = 16 loads per wave and round, four waves: `m += 4 * DXB`, then `m += 4`
+    DW_KBLOCK=256,       # head.hip dense_bwd_dw_kernel: `k = blockIdx.x * 256 + threadIdx.x`
+    DW_NBATCH=8,         # head.hip dense_bwd_dw_kernel: DWB = 8 samples per round, dzs rows rounded up to 8
+    SE_ROUND=32,         # se.hip se_fwd_kernel / se_bwd_kernel: `j0 += 32` (four waves of eight rows)
+    SE_BATCH=8,          # se.hip: the 8-wide batches of the fc2 / fc1^T loops, `j + 8 <= Wd`, then one row at a time
+    SLAB_GROUPS=16,      # se.hip dw_slab_reduce_block: sixteen part groups, `p += 16` in the tail loop
+    SLAB_STRIDE=64,      # se.hip dw_slab_reduce_block: four chains of 16 parts, `p += 64`
+    ALL_FINITE_CAP=2048,  # head.hip x3d_all_finite: `if (blocks > 2048)`, 256 * 8 elements per workgroup below the cap
+    L2_SUMSQ_CAP=1024,   # head.hip x3d_l2_sumsq: `if (blocks > 1024)`
+    GRID_Y=65535,        # the 16 bits of gridDim.y (elem.hip elem_grid: N * C planes in y)
+)
+
+
+def aux_tile_defines(csrc=None):
+    """{name: value} of AUX_TILE_SOURCES' #define lines, read from the kernel sources; KeyError names a missing one."""
+    import os
+    import re
+    csrc = csrc or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "x3d-tf_amd", "csrc")
+    out = {}
+    for fname, names in AUX_TILE_SOURCES.items():
+        text = open(os.path.join(csrc, fname)).read()
+        for nm in names:
+            m = re.search(rf"^#define\s+{nm}\s+(\d+)\b", text, re.M)
+            if not m:
+                raise KeyError(f"{fname}: no `#define {nm} <integer>` line")
+            out[nm] = int(m.group(1))
+    return out
+
+
+def aux_vec(dtype):
+    return 4 if dtype == F32 else 8
+
+
+def _aux_edge():
+    T, Lt = AUX_TILES, AUX_LITERALS
+    E = []
+    # dense_fwd (N, K, M, act, mask_scale, bias); dense_bwd (N, K, M, act, mask_scale, dx, db)
+    E += [("dense_fwd",) + c for c in [
+        (1, 1, 1, 0, None, False), (3, 63, 5, 1, None, True), (8, 64, 4, 0, 2.0, True), (9, 65, 157, 1, 2.0, False),
+        (5, 200, 101, 0, None, True), (17, 257, 174, 1, 2.0, True), (37, 630, 51, 0, 2.0, True), (70, 129, 259, 1, None, False),
+        (2, 256, 7, 0, None, True)]]
+    E += [("dense_bwd",) + c for c in [
+        (1, 1, 1, 0, None, True, True), (3, 63, 5, 1, None, True, False),
+        (4, 64, 64, 0, 2.0, True, True),        # M = 64: every wave runs its 16-batch exactly once and has no tail
+        (5, 65, 61, 1, 2.0, True, True),        # wave 0 takes the batch, waves 1 to 3 only the tail
+        (9, 255, 157, 0, 2.0, False, True), (8, 256, 101, 1, None, True, True), (17, 257, 174, 0, None, True, False),
+        (70, 300, 259, 1, 2.0, True, True), (130, 54, 400, 0, None, True, True)]]
+    # the host limits (64 KiB of LDS): dz [DENSE_BN][M] floats, dzs [N rounded up to 8][DENSE_BM] floats
+    E += [("dense_bwd_refused", 1, 1, 65536 // (4 * T["DENSE_BN"]) + 1), ("dense_bwd_refused", 65536 // (4 * T["DENSE_BM"]) + 1, 2, 3)]
+    for m in (1, 2, 8, 63, 255, 256, 257, 1000):
+        E += [("softmax_xent", n, m, 0.5, True) for n in (1, 3)]
+    E += [("softmax_xent", n, m, 1.0, False) for m in (1, 257) for n in (1, 3)]
+    E += [("view_mean",) + c for c in [(1, 1, 1), (3, 2, 127), (2, 3, 128), (2, 30, 129), (5, 10, 401)]]
+    # squeeze-excite
+    E += [("se_fwd",) + c for c in [
+        (1, 1, 1, 8), (3, 63, 7, 100), (2, 64, 8, 100), (2, 65, 9, 100), (5, 257, 33, 49), (3, 306, 24, 64), (2, 630, 40, 36),
+        (2, T["SE_MAXC"], T["SE_MAXW"], 10), (65, 72, 8, 100)]]
+    E += [("se_fwd_refused", 2, T["SE_MAXC"] + 1, 8), ("se_fwd_refused", 2, 24, T["SE_MAXW"] + 1)]
+    E += [("se_bnb_bwd",) + c for c in [
+        (2, 306, 24, 64, True, ()), (3, 630, 40, 36, True, ()),        # the XL training widths; 40: the second `j0 += 32` round
+        (65, 72, 8, 16, True, ()), (130, 24, 0, 16, False, ()), (1, 1, 1, 8, True, ()), (5, 257, 33, 8, True, ((1, 4),)),
+        (4, 63, 7, 12, True, ((15, 60), (17, 68))), (3, 40, T["SE_MAXW"], 12, True, ((16, 64), (65, 252))),
+        (4, 24, 0, 12, False, ((63, 4), (113, 128))),                  # the 256-thread launch without SE
+        (2, T["SE_MAXC"], 16, 8, True, ())]]
+    # slab reducer: every (parts, elems), alternately one and two jobs per launch
+    combos = [(p, e) for p in (1, 15, 16, 17, 48, 49, 63, 64, 65, 113) for e in (4, 60, 64, 68)]
+    i, two = 0, False
+    while i < len(combos):
+        k = 2 if two and i + 1 < len(combos) else 1
+        E.append(("dw_slab_reduce", tuple(combos[i:i + k])))
+        i, two = i + k, not two
+    E += [("dw_slab_reduce_refused", 3, 6, 0), ("dw_slab_reduce_refused", 3, 8, 1)]
+    # plane-wise kernels: every entry at every P edge of its storage type, the second option of each entry in turn
+    span = lambda dt: T["ELEM_BLOCK"] * aux_vec(dt) * T["ELEM_ITERS"]      # one workgroup's elements on the vector path
+    small = T["ELEM_BLOCK"] * 8                                          # tail_bwd: 16-bit planes below it take the small-plane kernel
+    rot = {"tail_bwd": (False, True), "tail_fwd": (None, "identity", "conv"),
+           "relu_bn_bwd_reduce": (("dy", True), ("dy", False), ("dpool", True)), "pool_fwd": ((),)}
+    cnt = {k: 0 for k in rot}
+
+    def plane(entry, dt, n, c, P, *off):
+        o = rot[entry][cnt[entry] % len(rot[entry])]
+        cnt[entry] += 1
+        E.append((entry, dt, n, c, P) + (o if isinstance(o, tuple) else (o,)) + off)
+    for entry in rot:
+        for dt in (BF16, F16):
+            for P in (8, small - 8, small, small + 8, span(dt) - 8, span(dt), span(dt) + 8):
+                plane(entry, dt, 3, 5, P)
+        for P in (4, span(F32) - 4, span(F32), span(F32) + 4):
+            plane(entry, F32, 3, 5, P)
+        s1 = T["ELEM_BLOCK"] * T["ELEM_ITERS"]                             # the scalar path's span
+        for dt in (BF16, F16, F32):
+            for P in (1, 7, s1 - 1, s1, s1 + 1):
+                plane(entry, dt, 3, 5, P)
+            plane(entry, dt, 3, 5, s1, 1)                                  # (s1 is a multiple of VEC: scalar only off alignment)
+        # views that are not 16-byte aligned although P % VEC == 0: pick_vec's 4 (16-bit) / 2 (fp32) collapse to the scalar kernel
+        for dt, P, off in ((BF16, small, 1), (F16, small, 4), (F32, span(F32), 2), (BF16, 8, 1)):
+            plane(entry, dt, 2, 3, P, off)
+        # N * C planes beyond the 16 bits of gridDim.y (pool_fwd: in gridDim.x)
+        plane(entry, BF16, 175, 400, 8)
+    E.append(("tail_bwd", F32, 175, 400, 4, True))     # (16-bit planes of 8 take the small-plane kernel, whose grid is (C, N / NB))
+    # small-plane groups of tail_bwd, NB = min(1024 // (P / 8), N, 16) samples per workgroup: 16 + 1, 4 + 1, 15 + 1 (the last with
+    # two rounds of the 512-vector loop)
+    for i, (n, P) in enumerate(((17, 8), (5, small - 8), (16, 520))):
+        E += [("tail_bwd", BF16, n, 3, P, i % 2 == 0), ("tail_bwd", F16, n, 3, P, i % 2 == 1)]
+    # layout converter: C = 3 and P % 8 == 0 on aligned tensors is the vector form
+    pairs = ((F32, F32), (F32, BF16), (BF16, BF16), (BF16, F32), (F32, F16), (F16, F16), (F16, F32))
+    E += [("nthwc_to_ncthw", s, d, 2, 3, P) for P in (8, small - 8, small, small + 8) for s, d in pairs]
+    E += [("nthwc_to_ncthw", s, d, 2, 3, small - 1) for s, d in pairs[:3]]
+    E += [("nthwc_to_ncthw", s, d, 2, 3, small, 1) for s, d in pairs[2:5]]
+    E += [("nthwc_to_ncthw",) + pairs[(i + 3) % 7] + (2, c, 300) for i, c in enumerate((1, 2, 4, 24))]
+    # grid-stride reductions, below and above their workgroup caps
+    kinds = ("+inf", "-inf", "nan", "-nan-payload")
+    big = 2048 * Lt["ALL_FINITE_CAP"] + 257
+    for n in (1, 63, 2047, 2048, 2049, big):
+        E.append(("all_finite", n, "none", "first"))
+        pos = ("first",) if n == 1 else ("first", "last", "mid") + (("trip2",) if n == big else ())
+        full = n in (2049, big)
+        for j, ps in enumerate(pos):
+            E += [("all_finite", n, k, ps) for i, k in enumerate(kinds) if full or i == (j + n) % 4]
+    E += [("l2_sumsq", n, m) for n in (1, 255, 2049, 2048 * Lt["L2_SUMSQ_CAP"] + 513) for m in (None, "random", "zeros")]
+    return E
+
+
+AUX_EDGE = _aux_edge()
+aux_edge_id = aux_full_id          # (defined below AUX_FULL: the same id scheme)
+
+
 # ---- whole-model cases (tests/test_model_gpu.py): variant, N, T, S --------------------------------------------------------
 MODEL_TRAIN_FP32 = [
     ("XS", 4, 4, 64), ("S", 2, 13, 64), ("M", 2, 4, 64), ("S", 3, 5, 96),

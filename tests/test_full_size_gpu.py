@@ -27,6 +27,8 @@ import pytest
 import torch
 
 from tests import shapes as S
+from tests.aux_checks import (_AUX_CASES, _AUX_ULPS, _LAM, _U, _aux_fp32_chain, _aux_raw, _aux_rn, _check, _elem_vec,  # noqa: F401
+                              _frac, _moment_checks, _project_out, _sum_lim, _within)
 from tests.util import bn_bwd_coef_sums as _bn_bwd_coef_sums, round_to, tie_slack_t, tol_gemm, tol_store
 
 pytestmark = pytest.mark.gpu
@@ -43,15 +45,6 @@ def _bn_bwd_coef(g, y, gamma):
     m = y.shape[0] * y.shape[2] * y.shape[3] * y.shape[4]
     return _bn_bwd_coef_sums(m, y.sum((0, 2, 3, 4)), (y * y).sum((0, 2, 3, 4)), g.sum((0, 2, 3, 4)), (g * y).sum((0, 2, 3, 4)), gamma)
 
-
-def _check(name, got, ref, rtol, atol):
-    got, ref = got.double(), ref.double()
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    assert torch.isfinite(got).all(), f"{name}: non-finite values"
-    assert not bad.any(), (f"{name}: {int(bad.sum())}/{bad.numel()} out of tolerance (rtol {rtol}, atol {atol:.3e}); max err "
-                           f"{err.max().item():.3e}, max |ref| {ref.abs().max().item():.3e}")
-    return (err.max() / (ref.abs().max() + 1e-300)).item()
 
 
 @pytest.mark.parametrize("dtype", HALF)
@@ -603,12 +596,6 @@ def test_stem_fp32_full_size(gpu):
 
 
 # ---- every depthwise launch of the full-size plans (tests/shapes.py DW_FULL: BASELINE configs 2 - 5, config 3 in fp16 too) ----
-def _frac(name, got, ref, rtol, atol):
-    """_check, returning the worst error as a fraction of its limit atol + rtol |ref|."""
-    _check(name, got, ref, rtol, atol)
-    got, ref = got.double(), ref.double()
-    return ((got - ref).abs() / (atol + rtol * ref.abs()).clamp_min(1e-300)).max().item()
-
 
 def _dw_chunk(case):
     """Samples per fp64 chunk: about 48 M input elements (0.4 GB in fp64) at a time."""
@@ -1219,555 +1206,7 @@ def test_pw_wgrad_generic_kernel_refuses_a_slab(gpu, dtype):
     assert float((dw - 0.5).abs().max()) == 0.0 and bool(slab.isnan().all())
 
 
-# ---- every other launch of the full-size plans (tests/shapes.py AUX_FULL: BatchNorm bookkeeping, residual-tail backward,
-# squeeze-excite and its slab reductions, head, loss) ----------------------------------------------------------------------
-# fp32 sums are held to the probabilistic bound of test_stem_fp32_full_size, lambda sqrt(L) u sum |terms| (lambda = 6,
-# u = 2^-24), plus 2^-50 sum |terms| for the fp64 atomics that combine the workgroups' partial sums.  BatchNorm finalize
-# arithmetic against fp64 of the same operands, to _AUX_ULPS fp32 roundings of the magnitude of each result's terms.
-_LAM, _U = 6.0, 2.0 ** -24
-_AUX_ULPS = 8
-
-
-def _sum_lim(L, absum):
-    import math
-    return _LAM * math.sqrt(L) * _U * absum + 2.0 ** -50 * absum
-
-
-def _within(name, got, ref, lim):
-    """|got - ref| <= lim element-wise; returns the worst error as a fraction of its limit."""
-    got, ref = got.double(), ref.double()
-    err = (got - ref).abs()
-    lim = torch.as_tensor(lim, dtype=torch.float64, device=err.device).expand_as(err)
-    assert torch.isfinite(got).all(), f"{name}: non-finite values"
-    bad = err > lim
-    assert not bad.any(), (f"{name}: {int(bad.sum())}/{bad.numel()} beyond the limit; worst err / limit "
-                           f"{(err / lim.clamp_min(1e-300)).max().item():.3e}, max err {err.max().item():.3e}, "
-                           f"max |ref| {ref.abs().max().item():.3e}")
-    return (err / lim.clamp_min(1e-300)).max().item()
-
-
-def _elem_vec(dtype, P):
-    """VEC of elem.hip's launchers: 16-byte vectors when P is a multiple of one (pick_vec; torch allocations are 256-byte
-    aligned, so P alone decides), else scalar loads."""
-    full = 4 if dtype == torch.float32 else 8
-    return full if P % full == 0 else 1
-
-
-def _aux_fp32_chain(entry, dtype, n, P):
-    """L, the longest chain of fp32 roundings a term of the launch's per-channel sum passes through (elem.hip):
-      tail_bwd_kernel / relu_bn_bwd_reduce_kernel: ELEM_ITERS = 4 rounds of VEC terms per thread, the product (1), the
-          256-thread block_sum (8 levels); one fp64 atomic per workgroup;
-      tail_bwd_small_kernel (16-bit, VEC 8, P / 8 < 256): NB samples of one channel per workgroup, NB = min(1024 / (P / 8),
-          N, 16), so ceil(NB P / 8 / 256) vectors of 8 terms per thread, the product, 8 levels;
-      pool_fwd_kernel: one workgroup per (n, c), ceil(P / (256 VEC)) vectors of VEC terms per thread, the fma and the max,
-          8 levels, the division by P."""
-    vec = _elem_vec(dtype, P)
-    if entry == "pool_fwd":
-        return -(-P // (256 * vec)) * vec + 2 + 8 + 1
-    if entry == "tail_bwd" and dtype != torch.float32 and vec == 8 and P // 8 < 256:
-        nb = min(1024 // (P // 8), n, 16)
-        return -(-(nb * (P // 8)) // 256) * 8 + 1 + 8
-    return 4 * vec + 1 + 8
-
-
-def _aux_rn(gpu, seed):
-    g_ = torch.Generator(device=gpu)
-    g_.manual_seed(seed)
-    return (lambda *s: torch.randn(*s, generator=g_, device=gpu, dtype=torch.float32)), g_
-
-
-def _aux_raw(rn, n, c, P, dtype):
-    """A raw conv output [N, C, P] with non-zero channel means, several standard deviations in some channels."""
-    mu, sd = 3 * rn(c), 0.5 + rn(c).abs()
-    return (rn(n, c, P) * sd.view(1, -1, 1) + mu.view(1, -1, 1)).to(dtype)
-
-
-def _project_out(d, mask, basis):
-    """d * mask minus its per-channel least-squares fit on mask * basis_k (fp64, [N, C, P]): the result's sums against each
-    basis tensor vanish per channel, as the BatchNorm-backward sums (sum g, sum g y) do in a training step."""
-    B = [mask * b for b in basis]
-    G = torch.stack([torch.stack([(bi * bj).sum((0, 2)) for bj in B], -1) for bi in B], -2)
-    r = torch.stack([(d * mask * b).sum((0, 2)) for b in B], -1)
-    a = torch.linalg.solve(G, r.unsqueeze(-1)).squeeze(-1)
-    return d * mask - sum(a[:, k].view(1, -1, 1) * B[k] for k in range(len(B)))
-
-
-def _moment_checks(tag, got, gd, vals, L, count, gpu, rn):
-    """The kernel's (sum g, sum g v) per channel against fp64, and what they do after the BatchNorm-backward finalize:
-    both sums through tests.util.bn_bwd_fold64 with v's own statistics, dgamma and B = coef[:, 1] against the same fold of the
-    fp64 sums, as a fraction of the bound the sum limits imply (|d dgamma| <= (lim1 + |mean| lim0) invstd, |d B| <=
-    |gamma| invstd^2 |d dgamma| / count)."""
-    from tests.util import bn_bwd_fold64
-    vd = vals.double()
-    ref = torch.stack([gd.sum((0, 2)), (gd * vd).sum((0, 2))], 1)
-    lim = torch.stack([_sum_lim(L, gd.abs().sum((0, 2))), _sum_lim(L, (gd * vd).abs().sum((0, 2)))], 1)
-    e = _within(f"{tag} sums", got, ref, lim)
-    mean = vd.sum((0, 2)) / count
-    inv = 1.0 / torch.sqrt((vd * vd).sum((0, 2)) / count - mean * mean + 1e-5)
-    mi = torch.stack([mean, inv], 1).float()
-    gamma = 1 + 0.3 * rn(got.shape[0])
-    c_got, dga_got, _ = bn_bwd_fold64(got, count, mi, gamma)
-    c_ref, dga_ref, _ = bn_bwd_fold64(ref, count, mi, gamma)
-    mi64 = mi.double()
-    lim_dg = (lim[:, 1] + mi64[:, 0].abs() * lim[:, 0]) * mi64[:, 1] * (1 + 1e-9) + 1e-300
-    lim_b = gamma.double().abs() * mi64[:, 1] ** 2 * lim_dg / count * (1 + 1e-9) + 1e-300
-    e_dg = _within(f"{tag} dgamma", dga_got, dga_ref, lim_dg)
-    e_b = _within(f"{tag} B", c_got[:, 1], c_ref[:, 1], lim_b)
-    return f"{tag} sums {e:.2e} (L {L}), dgamma {e_dg:.2e}, B {e_b:.2e}"
-
-
-def _aux_tail_bwd(gpu, case, rn, g_):
-    """g = dy [y > 0] bit for bit; (sum g, sum g c_raw) and (sum g, sum g r_raw) at the fp32 summation bound, with dy built so
-    that both sums cancel per channel."""
-    from x3d_tf_amd import ops
-    _, dtype, n, c, P, has_r = case
-    craw = _aux_raw(rn, n, c, P, dtype)
-    rraw = _aux_raw(rn, n, c, P, dtype) if has_r else None
-    y = torch.relu(rn(n, c, P)).to(dtype)
-    mask = (y > 0).double()
-    d0 = rn(n, c, P).double()
-    basis = [torch.ones_like(d0), craw.double()] + ([rraw.double()] if has_r else [])
-    g = _project_out(d0, mask, basis)
-    dy = torch.where(y > 0, g, d0).to(dtype)
-    del g, d0, basis
-    dyg = dy.clone()
-    sc = torch.zeros((c, 2), dtype=torch.float64, device=gpu)
-    sr = torch.zeros((c, 2), dtype=torch.float64, device=gpu) if has_r else None
-    ops.tail_bwd(dyg, y, craw, rraw, sc, sr)
-    torch.cuda.synchronize()
-    assert torch.equal(dyg, torch.where(y > 0, dy, torch.zeros_like(dy))), "tail_bwd: g differs from dy [y > 0]"
-    gd = dy.double() * mask
-    L = _aux_fp32_chain("tail_bwd", dtype, n, P)
-    msg = "g exact, " + _moment_checks("c", sc, gd, craw, L, n * P, gpu, rn)
-    if has_r:
-        msg += ", " + _moment_checks("r", sr, gd, rraw, L, n * P, gpu, rn)
-    return msg
-
-
-def _aux_relu_bn_bwd_reduce(gpu, case, rn, g_):
-    """g = (dy | dpool / P) [s yraw + t > 0]: the dy form (g not written in the plans: sums only) and the dpool form (g at
-    tol_store: the only arithmetic is dpool / P and the stored rounding).  Points whose z lies within 4 fp32 roundings of 0
-    may take either side of the mask; they are left out of the g check and their |terms| added to the sum limits.  The dpool
-    form's sums add the rounding of the stored g, which has one sign per (n, c): u_T sum |terms| on top of the fp32 bound."""
-    from x3d_tf_amd import ops
-    _, dtype, n, c, P, form, g_written = case
-    yraw = _aux_raw(rn, n, c, P, dtype)
-    yd = yraw.double()
-    mean = yd.mean((0, 2))
-    sd = (yd * yd).mean((0, 2)) - mean * mean
-    k = (1 + 0.3 * rn(c)).double() / torch.sqrt(sd + 1e-5)
-    ss = torch.stack([k, 0.3 * rn(c).double() - mean * k], 1).float()
-    s64, t64 = ss[:, 0].double().view(1, -1, 1), ss[:, 1].double().view(1, -1, 1)
-    z = s64 * yd + t64
-    amb = z.abs() <= 4 * _U * ((s64 * yd).abs() + t64.abs())
-    mask = (z > 0).double()
-    del z
-    if form == "dy":
-        d0 = rn(n, c, P).double()
-        dy = torch.where(mask > 0, _project_out(d0, mask, [torch.ones_like(d0), yd]), d0).to(dtype)
-        del d0
-        dpool, gd = None, dy.double() * mask
-    else:
-        d0 = rn(n, c).double()
-        A = torch.stack([mask.sum(2), (mask * yd).sum(2)], -1).transpose(0, 1)          # [C, N, 2]
-        coef = torch.linalg.solve(A.transpose(1, 2) @ A, A.transpose(1, 2) @ d0.t().unsqueeze(-1))
-        dpool = (d0.t() - (A @ coef).squeeze(-1)).t().float().contiguous()              # sum_n dpool cnt = sum_n dpool sy = 0
-        dy, gd = None, (dpool.double() / P).unsqueeze(-1) * mask
-    gbuf = torch.empty_like(yraw) if g_written else None
-    sums = torch.zeros((c, 2), dtype=torch.float64, device=gpu)
-    ops.relu_bn_bwd_reduce(dy, dpool, yraw, ss, gbuf, sums)
-    torch.cuda.synchronize()
-    msg = ""
-    if g_written:
-        keep = ~amb
-        rt, at = tol_store(dtype)
-        msg = f"g {_frac('g', gbuf[keep], gd[keep], rt, at * gd.abs().max().item()):.2e}, "
-    L = _aux_fp32_chain("relu_bn_bwd_reduce", dtype, n, P)
-    uT = {torch.float32: _U, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype] if form == "dpool" else 0.0
-    ref = torch.stack([gd.sum((0, 2)), (gd * yd).sum((0, 2))], 1)
-    ga = (dy.double().abs() if dy is not None else (dpool.double().abs() / P).unsqueeze(-1).expand_as(yd)) * amb
-    t0, t1 = gd.abs().sum((0, 2)), (gd * yd).abs().sum((0, 2))
-    lim = torch.stack([_sum_lim(L, t0) + uT * t0 + ga.sum((0, 2)), _sum_lim(L, t1) + uT * t1 + (ga * yd.abs()).sum((0, 2))], 1)
-    e = _within("sums", sums, ref, lim)
-    return msg + f"sums {e:.2e} (L {L}, {int(amb.sum())} points at the mask boundary)"
-
-
-def _aux_pool_fwd(gpu, case, rn, g_):
-    """pooled = mean_p relu(s x + t) at the fp32 summation bound over sum |relu| / P, and the rounding of the quotient."""
-    from x3d_tf_amd import ops
-    _, dtype, n, c, P = case
-    x = _aux_raw(rn, n, c, P, dtype)
-    xd = x.double()
-    mean = xd.mean((0, 2))
-    k = 1.0 / torch.sqrt((xd * xd).mean((0, 2)) - mean * mean + 1e-5)
-    ss = torch.stack([k, 0.2 * rn(c).double() - mean * k], 1).float()
-    a = torch.relu(ss[:, 0].double().view(1, -1, 1) * xd + ss[:, 1].double().view(1, -1, 1))
-    ref = a.mean(2)
-    pooled = torch.empty((n, c), device=gpu)
-    ops.pool_fwd(x, ss, pooled)
-    torch.cuda.synchronize()
-    L = _aux_fp32_chain("pool_fwd", dtype, n, P)
-    e = _within("pooled", pooled, ref, _sum_lim(L, a.sum(2)) / P + 2 * _U * ref.abs())
-    return f"pooled {e:.2e} (L {L})"
-
-
-def _aux_subsample2(gpu, case, rn, g_):
-    from x3d_tf_amd import ops
-    _, dtype, planes, h, w = case
-    x = rn(1, planes, 1, h, w).to(dtype)
-    out = ops.subsample2(x)
-    torch.cuda.synchronize()
-    assert torch.equal(out, x[..., ::2, ::2]), "subsample2: not the even-pixel copy"
-    return "exact"
-
-
-def _aux_se_params(rn, c, wd):
-    return (rn(wd, c) / c ** 0.5, 0.1 * rn(wd), rn(c, wd) / wd ** 0.5, 0.1 * rn(c))
-
-
-def _aux_se_fwd(gpu, case, rn, g_):
-    """hidden = relu(W1 pooled + b1), gate = sigmoid(W2 hidden + b2), pooled = s pool_sums / P + t.  Limits: pooled carries 4
-    fp32 roundings of |s pool_sums / P| + |t|; each GEMV the fp32 bound with L = K + 8 (any summation tree of K terms has
-    a chain of at most K - 1, plus the product, the bias and the lane reduction), hidden's error through |W2|, and the
-    sigmoid (slope <= 1/4) plus 4 roundings of the gate."""
-    from x3d_tf_amd import ops
-    _, n, c, wd, P = case
-    mu, sd = 3 * rn(c).double(), (0.5 + rn(c).abs()).double()
-    ps = P * mu.view(1, -1) + P ** 0.5 * sd.view(1, -1) * rn(n, c).double()
-    k = (1 + 0.3 * rn(c)).double() / torch.sqrt(sd * sd / P + 1e-5)
-    bss = torch.stack([k, 0.3 * rn(c).double() - mu * k], 1).float()
-    w1, b1, w2, b2 = _aux_se_params(rn, c, wd)
-    gate = torch.empty((n, c), device=gpu)
-    hidden = torch.empty((n, wd), device=gpu)
-    ops.se_fwd(ps, float(P), bss, w1, b1, w2, b2, gate, hidden)
-    torch.cuda.synchronize()
-    s64, t64 = bss[:, 0].double(), bss[:, 1].double()
-    pooled = s64 * ps / P + t64
-    e_p = 4 * _U * ((s64 * ps / P).abs() + t64.abs())
-    w1d, w2d = w1.double(), w2.double()
-    h = torch.relu(pooled @ w1d.t() + b1.double())
-    lim_h = e_p @ w1d.abs().t() + _sum_lim(c + 8, pooled.abs() @ w1d.abs().t() + b1.double().abs())
-    z2 = h @ w2d.t() + b2.double()
-    lim_z = lim_h @ w2d.abs().t() + _sum_lim(wd + 8, h.abs() @ w2d.abs().t() + b2.double().abs())
-    gref = torch.sigmoid(z2)
-    e_h = _within("hidden", hidden, h, lim_h)
-    e_g = _within("gate", gate, gref, 0.25 * lim_z + 4 * _U * gref)
-    return f"hidden {e_h:.2e}, gate {e_g:.2e}"
-
-
-def _aux_se_bnb_bwd(gpu, case, rn, g_):
-    """BN_b backward through the SE gate from per-(n, c) sums: the fp64 restatement is autograd over the SUM-level graph
-    L = sum_{n,c} gate (k (S2 - mean S1) + beta S1), with the batch statistics from pool_sums and Q = sum b_raw^2, so that
-    dL/db_raw = A dv + B b_raw + C with A = dL/dS2, B = 2 dL/dQ (the same for every sample), C = dL/dpool_sums: coef_nc must reproduce that gradient
-    (error of A rms(dv) + B rms(b_raw) + C within 2e-4 of its scale, test_se_bnb_bwd's tolerance) and the parameter
-    gradients fp64 autograd (2e-4 of each one's maximum).  The slab jobs: the same bits as x3d_dw_slab_reduce on the same
-    slabs, and the fp64 sum at the fp32 bound with L = parts + 8."""
-    from x3d_tf_amd import ops
-    _, n, c, wd, P, has_se, jobs = case
-    mu, sd = 3 * rn(c), 0.5 + rn(c).abs()
-    S1 = torch.empty((n, c), dtype=torch.float64, device=gpu)
-    S2, ps, Q, Qd = torch.empty_like(S1), torch.empty_like(S1), torch.empty_like(S1), torch.empty_like(S1)
-    for i in range(n):
-        b = (rn(c, P) * sd.view(-1, 1) + mu.view(-1, 1)).double()
-        dv = rn(c, P).double()
-        S1[i], S2[i], ps[i], Q[i], Qd[i] = dv.sum(1), (dv * b).sum(1), b.sum(1), (b * b).sum(1), (dv * dv).sum(1)
-    del b, dv
-    m = n * P
-    gam = (1 + 0.3 * rn(c)).double().requires_grad_(True)
-    bet = (0.3 * rn(c)).double().requires_grad_(True)
-    prm = [t.double().requires_grad_(True) for t in _aux_se_params(rn, c, wd)] if has_se else []
-    lv = [S2.clone().requires_grad_(True), ps.clone().requires_grad_(True), Q.clone().requires_grad_(True)]
-    mean = lv[1].sum(0) / m
-    inv = 1.0 / torch.sqrt(lv[2].sum(0) / m - mean * mean + 1e-5)
-    k = gam * inv
-    gate = hid = None
-    G = 1.0
-    if has_se:
-        pooled = k * (lv[1] / P - mean) + bet
-        hid = torch.relu(pooled @ prm[0].t() + prm[1])
-        gate = torch.sigmoid(hid @ prm[2].t() + prm[3])
-        G = gate
-    Lsum = (G * (k * (lv[0] - mean * S1) + bet * S1)).sum()
-    grads = torch.autograd.grad(Lsum, lv + [gam, bet] + prm)
-    A, Bq, Cp = grads[0], 2 * grads[2], grads[1]
-    f32 = lambda t: t.detach().float().contiguous()
-    bss = torch.stack([k, bet - mean * k], 1)
-    bmi = torch.stack([mean, inv], 1)
-    coef = torch.empty((n, c, 4), device=gpu)
-    dgam = torch.zeros(c, device=gpu)
-    dbet = torch.zeros(c, device=gpu)
-    kw = {}
-    if has_se:
-        kw = dict(w1=f32(prm[0]), b1=f32(prm[1]), w2=f32(prm[2]), b2=f32(prm[3]), gate=f32(gate), hidden=f32(hid),
-                  dw1=torch.zeros((wd, c), device=gpu), db1=torch.zeros(wd, device=gpu), dw2=torch.zeros((c, wd), device=gpu),
-                  db2=torch.zeros(c, device=gpu), scratch=torch.empty(n * (2 * c + wd), device=gpu))
-    red = []
-    for parts, elems in jobs:
-        red.append((rn(parts * elems), torch.full((elems,), 0.5, device=gpu), parts))
-    ops.se_bnb_bwd(torch.stack([S1, S2], -1).contiguous(), ps if has_se else None, float(P), f32(bss), f32(bmi), f32(gam), dgam,
-                   dbet, coef, n, c, reduce=red, **kw)
-    torch.cuda.synchronize()
-    msgs = []
-    for j, (slab, dwj, parts) in enumerate(red):
-        alone = torch.full_like(dwj, 0.5)
-        ops.dw_slab_reduce([(slab, alone, parts)])
-        torch.cuda.synchronize()
-        assert torch.equal(alone, dwj), "the reduce slots of x3d_se_bnb_bwd and x3d_dw_slab_reduce add in the same order"
-        sv = slab.double().view(parts, -1)
-        ref = sv.sum(0) + 0.5
-        msgs.append(f"slab{j} {_within(f'slab {j}', dwj, ref, _sum_lim(parts + 8, sv.abs().sum(0) + 0.5) + _U * ref.abs()):.2e}")
-    rdv, rb = (Qd / P).sqrt(), (Q / P).sqrt()
-    cf = coef.double()
-    scale = (A.abs() * rdv + Bq.abs() * rb + Cp.abs()).max()
-    err = (cf[:, :, 0] - A).abs() * rdv + (cf[:, :, 1] - Bq).abs() * rb + (cf[:, :, 2] - Cp).abs()
-    e_c = _within("coef_nc (dL/db_raw)", err, torch.zeros_like(err), 2e-4 * scale)
-    out = [("dgamma_b", dgam, grads[3]), ("dbeta_b", dbet, grads[4])]
-    if has_se:
-        out += [(nm, kw[nm], gr) for nm, gr in zip(("dw1", "db1", "dw2", "db2"), grads[5:])]
-    e_p = max(_within(nm, got, gr, 2e-4 * gr.abs().max() + 1e-300) for nm, got, gr in out)
-    return ", ".join([f"coef {e_c:.2e}", f"param grads {e_p:.2e}"] + msgs)
-
-
-def _aux_dense_fwd(gpu, case, rn, g_):
-    """y = act(sum_k x m s w + b) at the fp32 bound, L = K + 8 (see _aux_se_fwd); the dropout mask scale (2.0, keep 0 / 1)
-    is exact."""
-    from x3d_tf_amd import ops
-    _, n, kk, mm, act, mscale, bias = case
-    x = torch.relu(rn(n, kk)) + 0.05
-    w = rn(mm, kk) / kk ** 0.5
-    b = 0.1 * rn(mm) if bias else None
-    mask = (torch.rand((n, kk), generator=g_, device=gpu) >= 0.5).float() if mscale is not None else None
-    y = torch.empty((n, mm), device=gpu)
-    ops.dense_fwd(x, w, b, y, act=act, mask=mask, mask_scale=1.0 if mscale is None else mscale)
-    torch.cuda.synchronize()
-    xm = x.double() * (mask.double() * mscale if mask is not None else 1.0)
-    ref = xm @ w.double().t() + (b.double() if bias else 0.0)
-    lim = _sum_lim(kk + 8, xm.abs() @ w.double().abs().t() + (b.double().abs() if bias else 0.0))
-    if act == 1:
-        ref = torch.relu(ref)
-    return f"y {_within('y', y, ref, lim):.2e}"
-
-
-def _aux_dense_bwd(gpu, case, rn, g_):
-    """dz = dy [y > 0]; dx = (W^T dz) m s (L = M + 8), dw += dz^T (x m s) and db += sum_n dz (L = N + 8), at the fp32 bound
-    (+ the rounding of the pre-filled accumulators)."""
-    from x3d_tf_amd import ops
-    _, n, kk, mm, act, mscale, has_dx, has_db = case
-    x = torch.relu(rn(n, kk)) + 0.05
-    w = rn(mm, kk) / kk ** 0.5
-    dy = rn(n, mm) / n
-    y = torch.relu(rn(n, mm)) if act == 1 else None
-    mask = (torch.rand((n, kk), generator=g_, device=gpu) >= 0.5).float() if mscale is not None else None
-    dx = torch.empty((n, kk), device=gpu) if has_dx else None
-    dw = torch.full((mm, kk), 0.25, device=gpu)
-    db = torch.full((mm,), -0.5, device=gpu) if has_db else None
-    ops.dense_bwd(dy, y, act, x, w, dx, dw, db, mask=mask, mask_scale=1.0 if mscale is None else mscale)
-    torch.cuda.synchronize()
-    ms = mask.double() * mscale if mask is not None else torch.ones((n, kk), dtype=torch.float64, device=gpu)
-    dz = dy.double() * ((y > 0).double() if act == 1 else 1.0)
-    xm, wd = x.double() * ms, w.double()
-    msg = []
-    if has_dx:
-        ref = (dz @ wd) * ms
-        msg.append(f"dx {_within('dx', dx, ref, _sum_lim(mm + 8, dz.abs() @ wd.abs()) * ms + 1e-300):.2e}")
-    ref = dz.t() @ xm + 0.25
-    msg.append(f"dw {_within('dw', dw, ref, _sum_lim(n + 8, dz.abs().t() @ xm.abs() + 0.25) + _U * ref.abs()):.2e}")
-    if has_db:
-        ref = dz.sum(0) - 0.5
-        msg.append(f"db {_within('db', db, ref, _sum_lim(n + 8, dz.abs().sum(0) + 0.5) + _U * ref.abs()):.2e}")
-    return ", ".join(msg)
-
-
-def _aux_softmax_xent(gpu, case, rn, g_):
-    """probs, loss rows and dlogits = grad_scale d(sum loss)/dlogits (Keras' clipped cross-entropy on probabilities) against
-    fp64 autograd; row 0 is in the clipped regime (one logit 40 above the rest, the label elsewhere).  Limits: rho = (lambda
-    sqrt(M + 8) + 8) u relative on every probability (the exponentials, the fp32 row sum, the division); loss rows 2 rho +
-    4 u |loss|; dlogits grad_scale 4 rho (p_j + |ref| / grad_scale + 1e-7)."""
-    import math
-    from x3d_tf_amd import ops
-    _, n, mm, gs, train = case
-    logits = 3 * rn(n, mm)
-    logits[0, 3] = 40.0
-    labels = torch.randint(0, mm, (n,), generator=g_, device=gpu, dtype=torch.int32)
-    labels[0] = 7
-    probs = torch.empty((n, mm), device=gpu)
-    loss = torch.empty(n, device=gpu) if train else None
-    dl = torch.empty((n, mm), device=gpu) if train else None
-    ops.softmax_xent(logits, labels if train else None, probs, loss, dl, gs)
-    torch.cuda.synchronize()
-    ld = logits.double().requires_grad_(True)
-    p = torch.softmax(ld, -1)
-    q = p.clamp(1e-7, 1 - 1e-7)
-    rows = -torch.log(q.gather(1, labels.long().view(-1, 1)).squeeze(1)) + torch.log(q.sum(1))
-    rho = (_LAM * math.sqrt(mm + 8) + 8) * _U
-    pd = p.detach()
-    msg = f"probs {_within('probs', probs, pd, rho * pd + 1e-300):.2e}"
-    if train:
-        (g,) = torch.autograd.grad(rows.sum() * gs, [ld])
-        msg += f", loss {_within('loss rows', loss, rows.detach(), 2 * rho + 4 * _U * rows.detach().abs()):.2e}"
-        msg += f", dlogits {_within('dlogits', dl, g, gs * 4 * rho * (pd + g.abs() / gs + 1e-7)):.2e}"
-    return msg
-
-
-def _aux_view_mean(gpu, case, rn, g_):
-    from x3d_tf_amd import ops
-    _, videos, views, mm = case
-    probs = torch.softmax(3 * rn(videos * views, mm), -1)
-    out = torch.empty((videos, mm), device=gpu)
-    ops.view_mean(probs, out, views)
-    torch.cuda.synchronize()
-    pv = probs.double().view(videos, views, mm)
-    ref = pv.mean(1)
-    return f"out {_within('view mean', out, ref, _sum_lim(views + 8, pv.sum(1)) / views + 2 * _U * ref):.2e}"
-
-
-def _aux_bn_stats(rn, c, count):
-    """fp64 (sum, sum of squares) of `count` points per channel with means up to several standard deviations."""
-    mu, sd = 3 * rn(c).double(), (0.5 + rn(c).abs()).double()
-    mean = mu + sd * rn(c).double() / count ** 0.5
-    var = sd * sd * (1 + 0.01 * rn(c).double())
-    return count * mean, count * (var + mean * mean)
-
-
-def _aux_bn_finalize(gpu, case, rn, g_):
-    """x3d_bn_finalize reading the replicated statistics layout (every copy holds a random share of the totals) against fp64
-    of the same fp64 copies: scale / shift, mean / invstd and the moving statistics (momentum 0.9, unbiased variance), each to
-    _AUX_ULPS fp32 roundings of the magnitude of its terms."""
-    from x3d_tf_amd import hip, ops
-    _, c, count, upd = case
-    s1, s2 = _aux_bn_stats(rn, c, count)
-    r, stride = hip.stats_layout(c)
-    share = torch.rand((r, c), generator=g_, device=gpu).double()
-    share = share / share.sum(0, keepdim=True)
-    buf = torch.zeros(r * stride, dtype=torch.float64, device=gpu)
-    bv = buf.view(r, stride)[:, :2 * c].view(r, c, 2)
-    bv[:, :, 0], bv[:, :, 1] = share * s1, share * s2
-    gamma, beta = 1 + 0.3 * rn(c), 0.3 * rn(c)
-    mmv, mvv = rn(c), 0.5 + rn(c).abs()
-    mm_, mv_ = mmv.clone(), mvv.clone()
-    ss = torch.empty((c, 2), device=gpu)
-    mi = torch.empty((c, 2), device=gpu)
-    ops.bn_finalize(buf, count, gamma, beta, mm_, mv_, 1e-5, 0.9, upd, ss, mi)
-    torch.cuda.synchronize()
-    S1, S2 = bv[:, :, 0].sum(0), bv[:, :, 1].sum(0)
-    mean = S1 / count
-    var = S2 / count - mean * mean
-    inv = 1.0 / torch.sqrt(var + 1e-5)
-    g64, b64 = gamma.double(), beta.double()
-    sc = g64 * inv
-    u = _AUX_ULPS * _U
-    e = [_within("scale", ss[:, 0], sc, u * sc.abs()), _within("shift", ss[:, 1], b64 - mean * sc, u * (b64.abs() + (mean * sc).abs())),
-         _within("mean", mi[:, 0], mean, u * mean.abs()), _within("invstd", mi[:, 1], inv, u * inv)]
-    if upd:
-        a, b = 0.9 * mmv.double(), 0.1 * mean
-        e.append(_within("moving_mean", mm_, a + b, u * (a.abs() + b.abs())))
-        a, b = 0.9 * mvv.double(), 0.1 * var * count / (count - 1)
-        e.append(_within("moving_var", mv_, a + b, u * (a.abs() + b.abs())))
-    return f"worst {max(e):.2e}"
-
-
-def _aux_bwd_fin_inputs(rn, c, count):
-    """(sums [C][2] = (sum g, sum g y) of a training step -- sum g near 0, sum g y of sqrt(count) size --, mean_invstd, gamma)."""
-    s1, s2 = _aux_bn_stats(rn, c, count)
-    mean = s1 / count
-    inv = 1.0 / torch.sqrt(s2 / count - mean * mean + 1e-5)
-    sums = torch.stack([0.01 * count ** 0.5 * rn(c).double(), count ** 0.5 * rn(c).double() / inv], 1)
-    return sums, torch.stack([mean, inv], 1).float(), 1 + 0.3 * rn(c)
-
-
-def _aux_bwd_fin_check(sums, count, mi, gamma, coef, dg, db):
-    """coef, dgamma (+= onto 0.25), dbeta (+= onto -0.5) against tests.util.bn_bwd_fold64 of the same operands, to _AUX_ULPS
-    fp32 roundings of the magnitude of each result's terms."""
-    from tests.util import bn_bwd_fold64
-    ref, dga, dbe = bn_bwd_fold64(sums, count, mi, gamma)
-    mean, inv, g = mi[:, 0].double(), mi[:, 1].double(), gamma.double()
-    u = _AUX_ULPS * _U
-    mdg = (sums[:, 1].abs() + (mean * sums[:, 0]).abs()) * inv
-    k1 = g * inv
-    mb = k1.abs() * inv * mdg / count
-    mc = k1.abs() * sums[:, 0].abs() / count + mb * mean.abs()
-    return max(_within("coef A", coef[:, 0], ref[:, 0], u * k1.abs()), _within("coef B", coef[:, 1], ref[:, 1], u * mb),
-               _within("coef C", coef[:, 2], ref[:, 2], u * mc + 1e-300),
-               _within("dgamma", dg, dga + 0.25, u * (mdg + 0.25)), _within("dbeta", db, dbe - 0.5, u * (dbe.abs() + 0.5)))
-
-
-def _aux_bn_bwd_finalize(gpu, case, rn, g_):
-    from x3d_tf_amd import ops
-    _, c, count = case
-    sums, mi, gamma = _aux_bwd_fin_inputs(rn, c, count)
-    coef = torch.empty((c, 4), device=gpu)
-    dg, db = torch.full((c,), 0.25, device=gpu), torch.full((c,), -0.5, device=gpu)
-    ops.bn_bwd_finalize(sums, count, mi, gamma, coef, dg, db)
-    torch.cuda.synchronize()
-    return f"worst {_aux_bwd_fin_check(sums, count, mi, gamma, coef, dg, db):.2e}"
-
-
-def _aux_bn_bwd_finalize_rc(gpu, case, rn, g_):
-    """x3d_bn_bwd_finalize_rc in the plan's form writes the same bits as x3d_bn_bwd_finalize + x3d_pw_bwd_rc_prepare +
-    x3d_pw_bwd_rc_finish one after the other, and its finalize outputs match fp64 as in _aux_bn_bwd_finalize."""
-    from x3d_tf_amd import hip, ops
-    _, dtype, c, count, cin, fin = case
-    lib = hip.load()
-    sums, mi, gamma = _aux_bwd_fin_inputs(rn, c, count)
-    w = 0.2 * rn(c, cin) if cin else None
-    pe = int(lib.x3d_pw_bwd_rc_panel_elems(c, cin)) if cin else 0
-    if fin:
-        fco, fci = fin
-        fw, fcoef = 0.2 * rn(fco, fci), 0.5 * rn(fco, 4)
-        fsums = 30 * rn((fco + 1 + fci) * fci)
-
-    def fresh():
-        return (torch.zeros((c, 4), device=gpu), torch.full((c,), 0.25, device=gpu), torch.full((c,), -0.5, device=gpu),
-                torch.zeros(max(pe, 1), dtype=dtype, device=gpu), torch.zeros(max(cin, 1), device=gpu),
-                torch.full(fin or (1,), 0.5, device=gpu))
-    dt = hip.dtype_code(dtype)
-    coef0, dg0, db0, pan0, c00, dw0 = fresh()
-    ops.bn_bwd_finalize(sums, count, mi, gamma, coef0, dg0, db0)
-    if cin:
-        hip.call("x3d_pw_bwd_rc_prepare", w.data_ptr(), coef0.data_ptr(), pan0.data_ptr(), c00.data_ptr(), c, cin, dt)
-    if fin:
-        hip.call("x3d_pw_bwd_rc_finish", fsums.data_ptr(), fw.data_ptr(), fcoef.data_ptr(), dw0.data_ptr(), fco, fci, dt)
-    coef1, dg1, db1, pan1, c01, dw1 = fresh()
-    ops.bn_bwd_finalize_rc(sums, count, mi, gamma, coef1, dg1, db1, dtype, prep=(w, pan1, c01) if cin else None,
-                           fin=(fsums, fw, fcoef, dw1) if fin else None)
-    torch.cuda.synchronize()
-    assert torch.equal(coef0, coef1) and torch.equal(dg0, dg1) and torch.equal(db0, db1), "finalize outputs differ"
-    assert torch.equal(pan0, pan1) and torch.equal(c00, c01), "prepare outputs differ"
-    assert torch.equal(dw0, dw1), "finish output differs"
-    return f"same bits as the three launches; finalize worst {_aux_bwd_fin_check(sums, count, mi, gamma, coef1, dg1, db1):.2e}"
-
-
-def _aux_bn_eval_coef_batched(gpu, case, rn, g_):
-    """The whole X3D-XL inference BatchNorm table in one launch: scale = gamma invstd, shift = beta - mean scale, mean /
-    invstd from the moving statistics, every item against fp64 to _AUX_ULPS fp32 roundings of its terms' magnitude."""
-    from x3d_tf_amd import hip
-    _, chans = case
-    rows, items = [], []
-    for c in chans:
-        g, b, m_, v = 1 + 0.3 * rn(c), 0.3 * rn(c), 3 * rn(c), 0.05 + rn(c).abs()
-        ss, mi = torch.empty((c, 2), device=gpu), torch.empty((c, 2), device=gpu)
-        rows.append((g, b, m_, v, ss, mi))
-        items.append(hip.BnEvalItem(g.data_ptr(), b.data_ptr(), m_.data_ptr(), v.data_ptr(), ss.data_ptr(), mi.data_ptr(), c))
-    arr = (hip.BnEvalItem * len(items))(*items)
-    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(gpu)
-    hip.call("x3d_bn_eval_coef_batched", table.data_ptr(), len(items), 1e-5)
-    torch.cuda.synchronize()
-    u, worst = _AUX_ULPS * _U, 0.0
-    for i, (g, b, m_, v, ss, mi) in enumerate(rows):
-        inv = 1.0 / torch.sqrt(v.double() + 1e-5)
-        sc = g.double() * inv
-        worst = max(worst, _within(f"item {i} scale", ss[:, 0], sc, u * sc.abs()),
-                    _within(f"item {i} shift", ss[:, 1], b.double() - m_.double() * sc, u * (b.double().abs() + (m_.double() * sc).abs())),
-                    _within(f"item {i} mean", mi[:, 0], m_.double(), 0.0), _within(f"item {i} invstd", mi[:, 1], inv, u * inv))
-    return f"worst {worst:.2e}"
-
-
-_AUX_CASES = {"tail_bwd": _aux_tail_bwd, "relu_bn_bwd_reduce": _aux_relu_bn_bwd_reduce, "pool_fwd": _aux_pool_fwd,
-              "subsample2": _aux_subsample2, "se_fwd": _aux_se_fwd, "se_bnb_bwd": _aux_se_bnb_bwd, "dense_fwd": _aux_dense_fwd,
-              "dense_bwd": _aux_dense_bwd, "softmax_xent": _aux_softmax_xent, "view_mean": _aux_view_mean,
-              "bn_finalize": _aux_bn_finalize, "bn_bwd_finalize": _aux_bn_bwd_finalize,
-              "bn_bwd_finalize_rc": _aux_bn_bwd_finalize_rc, "bn_eval_coef_batched": _aux_bn_eval_coef_batched}
-
+# ---- every other launch of the full-size plans (tests/shapes.py AUX_FULL; the runners and their limits: tests/aux_checks.py) ----
 
 @pytest.mark.parametrize("case", S.AUX_FULL, ids=[S.aux_full_id(c) for c in S.AUX_FULL])
 def test_aux_full_size(gpu, case):

@@ -1498,8 +1498,14 @@ def test_bn_fold_dw3d_fwd(gpu, dtype, shape):
     assert ss1.abs().sum().item() > 0 and not torch.equal(mm1, torch.full((c,), 0.25, device=gpu))
 
 
+# the plane sizes on both sides of the tail kernels' tile edges (tests/shapes.py AUX_EDGE: the 16-bit and fp32 vector paths around the
+# small-plane threshold and one workgroup's span, the scalar path), the shortcut form in turn
+FOLD_TAIL_EDGES = [(2, 3, P, (True, False, None)[i % 3]) for i, P in enumerate(
+    (1, 4, 7, 8, 1023, 1024, 1025, 2040, 2048, 2056, 4092, 4096, 4100, 8184, 8192, 8200))]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [(2, 6, 3 * 14 * 14, True), (3, 4, 5 * 7 * 7, False), (1, 5, 1000, None)])
+@pytest.mark.parametrize("shape", [(2, 6, 3 * 14 * 14, True), (3, 4, 5 * 7 * 7, False), (1, 5, 1000, None)] + FOLD_TAIL_EDGES)
 def test_bn_fold_tail_fwd(gpu, dtype, shape):
     ops = _ops()
     n, c, pts, conv_shortcut = shape

@@ -208,14 +208,15 @@ extern "C" int x3d_dense_bwd(const float* dy, const float* y, int act, const flo
   X3D_REQUIRE(act == X3D_ACT_NONE || (act == X3D_ACT_RELU && y), "dense_bwd: relu needs y");
   const size_t dz_bytes = (size_t)DENSE_BN * (M > 256 ? M : 256) * sizeof(float);   // >= the [4][DENSE_BN][64] partial sums
   X3D_REQUIRE(dz_bytes <= 64 * 1024, "dense_bwd: M too large");
+  // (both limits before the first launch: a refused call leaves dx untouched as well)
+  const size_t dzs_bytes = (size_t)((N + 7) & ~7) * DENSE_BM * sizeof(float);
+  X3D_REQUIRE(dzs_bytes <= 64 * 1024, "dense_bwd: N too large");
   hipStream_t st = (hipStream_t)stream;
   if (dx) {
     hipLaunchKernelGGL(dense_bwd_dx_kernel, dim3(ceil_div(K, 64), ceil_div(N, DENSE_BN)), dim3(256), dz_bytes, st, dy, y, act,
                        mask, mask_scale, w, dx, N, K, M);
     X3D_LAUNCH_CHECK("dense_bwd_dx");
   }
-  const size_t dzs_bytes = (size_t)((N + 7) & ~7) * DENSE_BM * sizeof(float);
-  X3D_REQUIRE(dzs_bytes <= 64 * 1024, "dense_bwd: N too large");
   hipLaunchKernelGGL(dense_bwd_dw_kernel, dim3(ceil_div(K, 256), ceil_div(M, DENSE_BM)), dim3(256), dzs_bytes, st, dy, y, act, x, mask, mask_scale, dw, db, N, K, M);
   X3D_LAUNCH_CHECK("dense_bwd_dw");
   return X3D_OK;
