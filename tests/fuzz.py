@@ -12,6 +12,19 @@ DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 WIDTHS = [3, 5, 6, 7, 9, 10, 11, 12, 13, 14, 17, 19, 20, 21, 23, 26, 28, 31, 37, 39, 40, 45, 46, 53, 56, 57, 78, 91]
 CHANS = [24, 48, 54, 96, 108, 192, 216, 432, 40, 72, 200]
 
+# the seeded slice inside the `-m gpu` suite (tests/test_fuzz_gpu.py): chunk i runs SLICE_PER_CHUNK cases from seed SLICE_SEED + i
+SLICE_SEED, SLICE_CHUNKS, SLICE_PER_CHUNK = 7000, 20, 10
+
+
+def slice_calls():
+    """[(seed, test function name, positional args)] of every kernel-test call of the seeded slice, in run order."""
+    out = []
+    for chunk in range(SLICE_CHUNKS):
+        rng = random.Random(SLICE_SEED + chunk)
+        for _ in range(SLICE_PER_CHUNK):
+            out += [(SLICE_SEED + chunk, fn, args) for fn, args in case_calls(rng)]
+    return out
+
 
 def case_calls(rng: random.Random):
     """One fuzz case = 12 kernel-test calls: [(test function name, positional args after `gpu`)]."""

@@ -47,6 +47,10 @@ PW_FWD = [
     (1, 24, 24, 2, 40, 40, 1, None), (2, 24, 24, 1, 56, 56, 1, None), (1, 24, 48, 2, 28, 28, 1, None), (2, 48, 96, 2, 14, 14, 1, None),
     (2, 96, 192, 4, 7, 7, 1, None), (1, 24, 24, 2, 78, 78, 1, None), (1, 32, 32, 1, 78, 78, 1, None), (1, 24, 48, 2, 39, 39, 1, None),
     (1, 48, 96, 2, 20, 20, 1, None), (1, 96, 192, 2, 10, 10, 1, None),
+    # the shipped X3D-S yaml with 16-bit storage (13 frames, 160-pixel crops; tests/test_dispatch_coverage.py
+    # test_every_instantiation_of_a_shipped_config_is_covered), at the smallest N and T that keep the instantiation:
+    (1, 48, 96, 1, 20, 20, 2, None),       # stage-4 shortcut 20 -> 10: pw_gemm_bf16_kernel<T, 8, 3, 0, 100, 2, 8, 1>
+    (1, 96, 432, 1, 10, 10, 1, None),      # stage-5 `a` conv, inference (with a panel): pw_gemm_wst_kernel<T, 0, 100, 7, 2, 6, 2, 1>
 ]
 # ... with the residual tail of the block below folded into the prologue (16-bit storage; prologue "tail": identity shortcut,
 # "tail_conv": shortcut conv with its own BN): x = raw c output, in_add = shortcut, in_store = the block output y
@@ -55,6 +59,7 @@ PW_FWD_TAIL = [
     (1, 48, 216, 1, 16, 16, 1, "tail"), (1, 32, 72, 1, 16, 16, 1, "tail"), (1, 72, 162, 1, 8, 8, 1, "tail_conv"),     # stage-4 block 0; X3D-XL
     (1, 48, 108, 13, 5, 5, 1, "tail"), (2, 96, 216, 13, 10, 10, 1, "tail_conv"), (1, 24, 54, 1, 3, 4, 1, "tail"),     # odd / ragged point counts
     (3, 40, 72, 2, 7, 8, 1, "tail_conv"),
+    (1, 96, 432, 1, 10, 10, 1, "tail"),   # X3D-S stage-5 `a` conv, training, 16-bit (with a panel): pw_gemm_wst_kernel<T, 3, 100, 7, 2, 6, 2, 1>
     # stages 4 / 5: the weights-stationary kernel carries the fold (shapes 4, 5, 2 of pw_gemm_wst.h; with a weight panel), whole and
     # ragged rows (13 frames of 10 x 10 / 5 x 5), two samples, a partial last tile
     (2, 96, 216, 4, 14, 14, 1, "tail"), (1, 96, 432, 2, 14, 14, 1, "tail_conv"), (2, 192, 432, 4, 7, 7, 1, "tail"), (1, 192, 432, 8, 7, 7, 1, "tail_conv"),
@@ -117,7 +122,29 @@ PW_WGRAD = [
     (1, 24, 24, 2, 40, 40, 1, None), (2, 24, 24, 1, 56, 56, 1, None), (1, 24, 48, 2, 28, 28, 1, None), (2, 48, 96, 2, 14, 14, 1, None),
     (2, 96, 192, 4, 7, 7, 1, None), (1, 24, 48, 2, 39, 39, 1, None), (1, 48, 96, 2, 20, 20, 1, None), (1, 96, 192, 2, 10, 10, 1, None),
     (2, 48, 96, 13, 10, 10, 1, None), (2, 24, 24, 13, 40, 40, 1, None),
+    # the shipped yamls outside the BASELINE plans (tests/test_dispatch_coverage.py), smallest N and T that keep the instantiation
+    (1, 48, 96, 1, 20, 20, 2, None),          # X3D-S 16-bit, stage-4 shortcut: pw_wgrad_bf16_v2_kernel<T, 4, 2, 0, 2, 256, 1>
+    (1, 162, 72, 4, 39, 39, 1, "swish"),      # X3D-XL fp32 training: pw_wgrad_f32p_kernel<2, 3, 1, 0> (T = 4: below it another point split)
+    (1, 280, 630, 1, 10, 10, 1, None),        # ... pw_wgrad_f32p_kernel<2, 4, 0, 0>
+    (1, 72, 32, 1, 78, 78, 1, "swish"),       # ... pw_wgrad_f32p_kernel<1, 3, 1, 0>
+    (1, 72, 136, 1, 39, 39, 2, None),         # ... pw_wgrad_kernel<float, 1, 4, 0, 1>
 ]
+
+# ---- fp32 launches whose instantiation only exists at full size: the pipelined fp32 kernels hand tensors their 32-bit buffer
+# offsets cannot span (N max(Cin, Cout) + 256 rows of P floats reach 2 GB) to the resident-weights kernels (pw_gemm_f32r.h /
+# pw_wgrad_f32r.h), so no smaller N or T keeps the name.
+# tests/test_kernels_gpu.py test_pw_f32_past_buffer_offsets_fp64 checks them against fp64 on the GPU, sample by sample.
+#   entry, (N, Cin, Cout, T, H, W)
+PW_F32_FULL = [
+    ("fwd", (21, 24, 54, 16, 156, 156)),      # X3D-L fp32 inference, 24 clips (stage-2 `a` conv): pw_f32r_kernel<4, 2, 4, 0, 100>; N >= 21 at T = 16
+    ("wgrad", (16, 32, 72, 16, 156, 156)),    # X3D-XL fp32 training, 16 clips (stage-2 `a` conv): pw_wgrad_f32r_kernel<2, 1, 0>; N = 16 and T = 16 only
+]
+
+
+def pw_f32_full_struct(case):
+    entry, (n, cin, cout, t, h, w) = case
+    shape = (n, cin, cout, t, h, w, 1, None)
+    return pw_fwd_struct(shape, F32, False) if entry == "fwd" else pw_wgrad_struct(shape, F32)
 
 # ---- x3d_pw_bwd (fused dgrad + wgrad): N, Cin, Cout, T, H, W, epilogue ---------------------------------------------------
 PW_BWD = [

@@ -5,6 +5,8 @@ launched) which instantiation each launch of a full-size DRY plan runs (x3d_tf_a
 each registered parity case (tests/shapes.py: the lists tests/test_kernels_gpu.py and tests/test_model_gpu.py
 parametrise over) runs.  The first set must be contained in the second.
 """
+import functools
+
 import pytest
 import torch
 
@@ -40,6 +42,9 @@ def _kernel_case_names():
                     add(S.pw_dgrad_struct(shp, epi, dt, True), f"test_pw_dgrad[{shp}, {epi}, {dt}, panel]")
         for shp in S.PW_WGRAD:
             add(S.pw_wgrad_struct(shp, dt), f"test_pw_wgrad[{shp}, {dt}]")
+        if not half:
+            for case in S.PW_F32_FULL:
+                add(S.pw_f32_full_struct(case), f"test_pw_f32_past_buffer_offsets_fp64[{case}]")
         if half:
             for shp in S.PW_BWD:
                 st = S.pw_bwd_struct(shp, dt)
@@ -84,6 +89,57 @@ def test_every_instantiation_of_a_baseline_config_has_a_parity_case(parity_kerne
     missing = {k: v for k, v in need.items() if k not in parity_kernels}
     assert not missing, (f"BASELINE config {index} {D.BASELINE_CONFIGS[index][:5]} dispatches kernel instantiations that no "
                          f"-m gpu oracle-parity case runs:\n" + "\n".join(f"  {k}   <- {v}" for k, v in sorted(missing.items())))
+
+
+# ---- the shipped configurations (configs/kinetics/*.yaml) beyond the five BASELINE plans: every storage type, the yaml's global
+# training batch on 1, 2, 4 and 8 GPUs, inference on one video (views x crops clips) and on TEST.BATCH_SIZE videos; clip length
+# and crop from the yaml
+SHIPPED_VARIANTS = ("XS", "S", "M", "L", "XL")
+
+
+@functools.lru_cache(maxsize=None)
+def shipped_config_plans(variant):
+    """[(clips per GPU, T, crop, training)] of a shipped yaml."""
+    import x3d_tf_amd as x
+    cfg = x.get_config(variant)
+    t, views = cfg.DATA.TEMP_DURATION, cfg.TEST.NUM_TEMPORAL_VIEWS * cfg.TEST.NUM_SPATIAL_CROPS
+    return ([(cfg.TRAIN.BATCH_SIZE // d, t, cfg.DATA.TRAIN_CROP_SIZE, True) for d in (1, 2, 4, 8)]
+            + [(views, t, cfg.DATA.TEST_CROP_SIZE, False), (cfg.TEST.BATCH_SIZE * views, t, cfg.DATA.TEST_CROP_SIZE, False)])
+
+
+@functools.lru_cache(maxsize=None)
+def shipped_config_kernels(variant=None, dtype=None):
+    """{(entry point, instantiation): first launch that dispatches it} over the dry plans of a shipped yaml in one storage type
+    (variant None: over all of them, every storage type)."""
+    from x3d_tf_amd import dispatch as D
+    got = {}
+    if variant is None:
+        for v in SHIPPED_VARIANTS:
+            for dt in S.DTYPES:
+                for k, what in shipped_config_kernels(v, dt).items():
+                    got.setdefault(k, what)
+        return got
+    for n, t, s, training in shipped_config_plans(variant):
+        for entry, kern, shape in D.config_kernels(variant, n, t, s, dtype, training):
+            got.setdefault((entry, kern), f"X3D-{variant} {str(dtype)[6:]} {'training' if training else 'inference'}, {n} clips: {shape}")
+    return got
+
+
+@pytest.mark.parametrize("dtype", S.DTYPES, ids=lambda d: str(d)[6:])
+@pytest.mark.parametrize("variant", SHIPPED_VARIANTS)
+def test_every_instantiation_of_a_shipped_config_is_covered(parity_kernels, variant, dtype):
+    """Every conv instantiation a shipped yaml dispatches -- training at its global batch on 1, 2, 4, 8 GPUs, inference on one
+    video and on TEST.BATCH_SIZE videos -- is run by a registered kernel-level case, or is a class of the fused pointwise
+    backward sweep (tests/pw_bwd_classes.py) or of the depthwise sweep (tests/dw_classes.py)."""
+    from tests import dw_classes as DC
+    from tests import pw_bwd_classes as PC
+    need = shipped_config_kernels(variant, dtype)
+    assert need, "the dry plans recorded no conv launches"
+    pw_bwd, dw = PC.enumerate_classes(), DC.enumerate_classes()
+    missing = {k: v for k, v in need.items()
+               if k[1] not in parity_kernels and not (k[0] == "x3d_pw_bwd" and k[1] in pw_bwd) and k not in dw}
+    assert not missing, (f"X3D-{variant} ({dtype}) dispatches kernel instantiations that no -m gpu parity case runs:\n"
+                         + "\n".join(f"  {k[0]} {k[1]}   <- {v}" for k, v in sorted(missing.items())))
 
 
 def test_bench_workload_is_config_3(parity_kernels):

@@ -7,10 +7,10 @@ from tests import fuzz
 
 pytestmark = pytest.mark.gpu
 
-CHUNKS, PER_CHUNK = 20, 10
+CHUNKS, PER_CHUNK = fuzz.SLICE_CHUNKS, fuzz.SLICE_PER_CHUNK
 
 
 @pytest.mark.parametrize("chunk", range(CHUNKS))
 def test_random_shapes_match_the_fp64_restatement(gpu, chunk):
-    fails = fuzz.run_cases(gpu, PER_CHUNK, seed=7000 + chunk)
+    fails = fuzz.run_cases(gpu, PER_CHUNK, seed=fuzz.SLICE_SEED + chunk)
     assert not fails, f"{len(fails)} of {12 * PER_CHUNK} random kernel checks failed; first: {fails[0]}"

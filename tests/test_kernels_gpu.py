@@ -1678,3 +1678,60 @@ def test_pw_f32_full_size_fp64(gpu, shape):
     torch.cuda.synchronize()
     err = (dw.double() - ref_dw).abs().max().item() / ref_dw.abs().max().item()
     assert err <= 2e-5, f"weight gradient {err:.2e}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", S.PW_F32_FULL, ids=lambda c: f"{c[0]}-" + "x".join(map(str, c[1])))
+def test_pw_f32_past_buffer_offsets_fp64(gpu, case):
+    """The fp32 launches of the shipped X3D-L / X3D-XL yamls that only reach their instantiation at full size (shapes.PW_F32_FULL:
+    the resident-weights kernels behind the pipelined fp32 ones, pw_gemm_f32r.h / pw_wgrad_f32r.h), against fp64 arithmetic on the
+    GPU, sample by sample, at the limit of test_pw_f32_full_size_fp64 (2e-5 of the largest value: the kernel tests' fp32 tol_gemm).
+    The forward's output starts as NaN; the weight gradient keeps its `+=` on a pre-fill of 0.5."""
+    ops = _ops()
+    from x3d_tf_amd import hip
+    entry, (n, cin, cout, t, h, w) = case
+    want = {"fwd": "pw_f32r_kernel<4, 2, 4, 0, 100>", "wgrad": "pw_wgrad_f32r_kernel<2, 1, 0>"}[entry]
+    name = hip.kernel_name(S.pw_f32_full_struct(case))
+    assert name == want, name
+    g_ = torch.Generator(device=gpu).manual_seed(31)
+    x = torch.randn((n, cin, t, h, w), generator=g_, device=gpu)
+    wt = torch.randn((cout, cin), generator=g_, device=gpu) * (2.0 / cin) ** 0.5
+    wd = wt.double()
+    if entry == "fwd":
+        stats = torch.zeros((cout, 2), dtype=torch.float64, device=gpu)
+        y = torch.full((n, cout, t, h, w), float("nan"), device=gpu)
+        # (the launch itself: the dispatch asked over the real pointers, in the form ops.pw_fwd builds)
+        real = hip.PwFwdArgs(x.data_ptr(), wt.data_ptr(), y.data_ptr(), ops.stats_buffer(cout, gpu).data_ptr(), None, None, 0, n, cin, cout,
+                             t, h, w, 1, hip.dtype_code(x.dtype), None)
+        assert hip.kernel_name(real) == want
+        ops.pw_fwd(x, wt, y=y, stats=stats)
+        torch.cuda.synchronize()
+        assert torch.isfinite(y).all(), "forward: unwritten or non-finite outputs"
+        s_ref = torch.zeros((cout, 2), dtype=torch.float64, device=gpu)
+        err = scale = 0.0
+        for i in range(n):
+            ref = torch.einsum("oc,cp->op", wd, x[i].reshape(cin, -1).double())
+            err = max(err, (y[i].reshape(cout, -1).double() - ref).abs().max().item())
+            scale = max(scale, ref.abs().max().item())
+            s_ref += torch.stack([ref.sum(1), (ref * ref).sum(1)], 1)
+        print(f"forward {name}: err / scale {err / scale:.2e}")
+        assert err <= 2e-5 * scale, f"forward {err / scale:.2e}"
+        assert ((stats - s_ref).abs().max() / s_ref.abs().max()).item() <= 2e-5, "statistics"
+        return
+    gy = torch.randn((n, cout, t, h, w), generator=g_, device=gpu)
+    yraw = torch.randn((n, cout, t, h, w), generator=g_, device=gpu)
+    coef = torch.randn((cout, 4), generator=g_, device=gpu) * 0.5
+    dw = torch.full((cout, cin), 0.5, device=gpu)
+    real = hip.PwWgradArgs(gy.data_ptr(), yraw.data_ptr(), coef.data_ptr(), x.data_ptr(), None, None, 0, dw.data_ptr(), n, cin, cout,
+                           t, h, w, 1, hip.dtype_code(x.dtype))
+    assert hip.kernel_name(real) == want
+    ops.pw_wgrad(gy, yraw, coef, x, dw)
+    torch.cuda.synchronize()
+    cd = coef.double()
+    ref = torch.zeros((cout, cin), dtype=torch.float64, device=gpu)
+    for i in range(n):
+        dy = cd[:, 0:1] * gy[i].reshape(cout, -1).double() + cd[:, 1:2] * yraw[i].reshape(cout, -1).double() + cd[:, 2:3]
+        ref += dy @ x[i].reshape(cin, -1).double().t()
+    err = (dw.double() - (ref + 0.5)).abs().max().item() / ref.abs().max().item()
+    print(f"weight gradient {name}: err / scale {err:.2e}")
+    assert torch.isfinite(dw).all() and err <= 2e-5, f"weight gradient {err:.2e}"
