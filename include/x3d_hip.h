@@ -57,7 +57,8 @@ extern "C" {
  *   138 (additions only, no bump) x3d_seg_sumsq / x3d_lars / x3d_adamw / x3d_lamb (layer-wise optimizers);
  *   138 (additions only, no bump) x3d_precise_bn_accum / x3d_precise_bn_final (precise BatchNorm statistics);
  *   138 (additions only, no bump) x3d_seg_grad_sumsq / x3d_sgd_pt / x3d_adam_pt / x3d_lars_pt / x3d_adamw_pt / x3d_lamb_pt
- *       (fine-tuning: frozen tensors and per-tensor learning rates). */
+ *       (fine-tuning: frozen tensors and per-tensor learning rates);
+ *   138 (additions only, no bump) x3d_softmax_xent_kd / x3d_sigmoid_bce_kd (knowledge distillation). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -609,6 +610,42 @@ int x3d_view_max(const float* probs, float* out, int videos, int views, int M, v
  * never truncated: its ap is NaN and npos[c] = -P (only possible when N > X3D_AP_MAX_POSITIVES). */
 #define X3D_AP_MAX_POSITIVES 32768
 int x3d_multilabel_ap(const float* scores, const float* targets, int N, int M, double* ap, int* npos, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Knowledge distillation (DISTILL.* of the config): the three training losses with a second term against a teacher's
+ * logits at a temperature (Hinton, Vinyals, Dean 2015).  logits, teacher_logits [N][M] fp32.  With z = logits,
+ * t = teacher_logits, T = temperature, a = alpha, u = z / T and v = t / T:
+ *   loss_rows[n] = (1 - a) * hard + a * kd;   kd_rows[n] = kd (unweighted; may be NULL);
+ *   dlogits = grad_scale * ((1 - a) * d hard / dz + a * d kd / dz)      (grad_scale = loss_scale / global_batch).
+ * probs is the T = 1 output of the head the hard term belongs to, bit-identical to that kernel's (the training metrics
+ * read it); loss_rows / dlogits may be NULL.
+ * alpha == 0: the teacher is not read (teacher_logits may be NULL), loss_rows and dlogits are bit-identical to the hard
+ * kernel's and kd_rows is 0 -- a branch, not a product with 0.
+ * A teacher logit that is not finite (NaN, +-inf) anywhere in a row: loss_rows[n] and kd_rows[n] are NaN and the dlogits
+ * row is zero (an unusable sample, as for a label outside [0, M)); probs is written all the same.  The hard term's own
+ * rules for such samples (below) hold whatever the teacher says; kd_rows[n] is then still the row's KD term.
+ * Refused before any launch (X3D_ERR_INVALID, the message names the argument): logits or probs NULL; alpha outside [0, 1]
+ * or NaN; temperature not finite or <= 0; alpha > 0 with teacher_logits NULL; N <= 0 or M <= 0; N * M >= 2^31;
+ * teacher_logits or targets sharing a byte with probs, loss_rows, kd_rows or dlogits.
+ * One launch, one 256-thread workgroup per row, sums in a fixed order, no atomics.
+ * ------------------------------------------------------------------------------------------ */
+/* Softmax head.  Exactly one of labels ([N] int32: the hard term of x3d_softmax_xent, a label outside [0, M) gives a NaN
+ * loss row and a zero dlogits row) and targets ([N][M] fp32 dense rows: that of x3d_softmax_xent_soft, likewise for a NaN
+ * target) must be given; both or neither is refused.
+ *   kd = T^2 * sum_j p_t,j * (log p_t,j - log p_s,j),   log p_s = u - lse(u), log p_t = v - lse(v), p_t = exp(log p_t):
+ * evaluated in log space and in fp64, no clipping; a teacher probability that underflows to 0 contributes 0, never NaN.
+ *   d kd / dz = T * (softmax(u) - softmax(v)). */
+int x3d_softmax_xent_kd(const float* logits, const float* teacher_logits, const int* labels, const float* targets,
+                        float* probs, float* loss_rows, float* kd_rows, float* dlogits, float grad_scale, float alpha,
+                        float temperature, int N, int M, void* stream);
+/* Sigmoid head (DATA.MULTI_LABEL): the hard term of x3d_sigmoid_bce on targets [N][M] fp32 (required).  The KD term is the
+ * Bernoulli KL per class against sigmoid(v), >= 0 and 0 where z = t:
+ *   kd = T^2 * mean_j [ (softplus(u_j) - sigmoid(v_j) u_j) - (softplus(v_j) - sigmoid(v_j) v_j) ],
+ *   softplus(x) = max(x, 0) + log1p(exp(-|x|)); the terms and the row sum in fp64, as the hard term's.
+ *   d kd / dz_j = T * (sigmoid(u_j) - sigmoid(v_j)) / M. */
+int x3d_sigmoid_bce_kd(const float* logits, const float* teacher_logits, const float* targets, float* probs,
+                       float* loss_rows, float* kd_rows, float* dlogits, float grad_scale, float alpha, float temperature,
+                       int N, int M, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mixup / CutMix (ABI 137; MIXUP.* of the config): a batch mixed with its own reverse, clip i with clip N-1-i.

@@ -137,7 +137,8 @@ def get_default_config():
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA;
     LAYER_DECAY / LR_MULT / FREEZE: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
-    NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save)."""
+    NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
+    DISTILL.* (knowledge distillation against a teacher's logits)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -187,6 +188,10 @@ def get_default_config():
     # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
     # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
     c.OPTIM = CfgNode(dict(LARS_TRUST_COEF=0.001, LARS_EPS=1e-8, LARS_CLIP=False, WEIGHT_DECAY=0.0, LAMB_EPS=1e-6))
+    # knowledge distillation (distill_settings; off by default): the training loss becomes (1 - ALPHA) * hard + ALPHA * T^2 *
+    # KL(teacher || student) on logits softened by TEMPERATURE.  TEACHER: a shipped config name (XS .. XL) or a yaml path,
+    # TEACHER_CKPT its checkpoint prefix; both unused when the trainer is handed a teacher model
+    c.DISTILL = CfgNode(dict(ENABLE=False, TEACHER="", TEACHER_CKPT="", ALPHA=0.5, TEMPERATURE=1.0))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -215,6 +220,7 @@ def get_config(name, overrides=None, freeze=True):
     optim_settings(cfg)
     drop_path_settings(cfg)
     precise_bn_settings(cfg)
+    distill_settings(cfg, have_teacher=True)   # (whether a teacher exists is the trainer's to check)
     if freeze:
         cfg.freeze()
     return cfg
@@ -479,3 +485,31 @@ def precise_bn_settings(cfg) -> PreciseBNSettings:
     if isinstance(num, bool) or not isinstance(num, int) or num < 1:
         raise ValueError(f"NETWORK.BN.NUM_BATCHES_PRECISE must be an integer >= 1, not {num!r}")
     return PreciseBNSettings(bool(getattr(bn, "USE_PRECISE_STATS", False)), num)
+
+
+DistillSettings = collections.namedtuple("DistillSettings", "enable teacher teacher_ckpt alpha temperature")
+_DISTILL_OFF = DistillSettings(False, "", "", 0.5, 1.0)
+
+
+def distill_settings(cfg, have_teacher: bool = False) -> DistillSettings:
+    """cfg.DISTILL.* as one tuple (a config tree without the section: off).  ValueError for an ALPHA outside [0, 1], a
+    TEMPERATURE that is not finite and > 0 (NaN fails both) -- checked whether the switch is on or not -- and for ENABLE
+    with an empty TEACHER unless `have_teacher`: the trainer was handed a teacher model (get_config cannot know, it passes
+    True and leaves that check to the trainer)."""
+    import math
+    dv = getattr(cfg, "DISTILL", None)
+    if dv is None:
+        return _DISTILL_OFF
+    d = _DISTILL_OFF
+    alpha = float(getattr(dv, "ALPHA", d.alpha))
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"DISTILL.ALPHA must lie in [0, 1], not {alpha}")
+    temp = float(getattr(dv, "TEMPERATURE", d.temperature))
+    if not (temp > 0.0 and math.isfinite(temp)):
+        raise ValueError(f"DISTILL.TEMPERATURE must be finite and > 0, not {temp}")
+    s = DistillSettings(bool(getattr(dv, "ENABLE", False)), str(getattr(dv, "TEACHER", d.teacher)),
+                        str(getattr(dv, "TEACHER_CKPT", d.teacher_ckpt)), alpha, temp)
+    if s.enable and not s.teacher and not have_teacher:
+        raise ValueError("DISTILL.ENABLE needs DISTILL.TEACHER (a shipped config name or a yaml path) or a teacher model "
+                         "handed to the trainer")
+    return s

@@ -392,12 +392,16 @@ class X3D:
     # ---------------------------------------------------------------------------------------------
     MAX_PLANS = 3   # a plan owns every activation / gradient / scratch buffer of its shape (X3D-M, B = 64, bf16: ~16 GB)
 
-    def _plan(self, n, t, h, w, training) -> _Plan:
-        key = (n, t, h, w, bool(training))
+    def _plan(self, n, t, h, w, training, logits_only=False) -> _Plan:
+        """logits_only: the inference list that ends with fc2 (`logits`), a plan of its own beside the `call` one"""
+        key = (n, t, h, w, False, "logits") if logits_only else (n, t, h, w, bool(training))
         pl = self._plans.pop(key, None)
         if pl is None:
             self.release_plans(keep=self.MAX_PLANS - 1)
-            pl = (record_training if training else record_inference)(self, n, t, h, w)
+            if logits_only:
+                pl = record_inference(self, n, t, h, w, probs=False)
+            else:
+                pl = (record_training if training else record_inference)(self, n, t, h, w)
         self._plans[key] = pl           # most recently used last
         return pl
 
@@ -516,7 +520,21 @@ class X3D:
         pl.run(pl.fwd)
         return pl.out
 
-    def forward_backward(self, input, labels, global_batch=None, on_stage_done=None, loss_scale=1.0):
+    def logits(self, input):
+        """Per-clip logits at training=False (moving statistics, no dropout): the launches of `call(input)` up to, but not
+        including, the probabilities -- what a distillation teacher hands to the student's `forward_backward`.  Returns the
+        plan-owned fp32 ``[N, classes]`` buffer on the device (overwritten by the next call of the same shape); N need not be
+        a multiple of views * crops.  Nothing of the model's state is written."""
+        n, t, h, w, _ = input.shape
+        pl = self._plan(n, t, h, w, False, logits_only=True)
+        self._bind_input(pl, input)
+        self._pack_panels()
+        pl.zero_buf.zero_()
+        pl.run(pl.fwd)
+        return pl.logits
+
+    def forward_backward(self, input, labels, global_batch=None, on_stage_done=None, loss_scale=1.0, teacher_logits=None,
+                         distill=None):
         """One training forward + backward.  Fills ``self.grads`` (data gradients only; the L2 term is
         applied by the optimizer), updates BN moving statistics, returns the plan (loss_rows, probs).
 
@@ -533,19 +551,35 @@ class X3D:
         on_stage_done(stage): called with "fwd" once the forward pass is on the stream, then as soon as every
             gradient of ``stage`` (4 = head, 3..0 = stages, -1 = stem) is final on the stream -- the hook gradient
             all-reduce buckets attach to.
+        teacher_logits, distill=(alpha, temperature): knowledge distillation.  teacher_logits: a device fp32 [N, classes]
+            tensor (a teacher's `logits(input)`); the loss of whichever head applies becomes (1 - alpha) * that loss +
+            alpha * T^2 * KL(teacher || student) at temperature T (x3d_softmax_xent_kd / x3d_sigmoid_bce_kd), `plan.kd_rows`
+            holds the KD term per row and `plan.teacher` the logits.  The shape is checked here, the values by the kernel
+            (a non-finite teacher logit: NaN loss row, no gradient from the sample).  Without teacher_logits nothing changes.
         """
         n, t, h, w, _ = input.shape
         pl = self._plan(n, t, h, w, True)
         self._bind_input(pl, input)
         soft = (not self.multi_label and torch.is_tensor(labels) and labels.dim() == 2
                 and labels.dtype.is_floating_point)
+        kd = teacher_logits is not None
+        if kd:
+            if distill is None:
+                raise ValueError("teacher_logits needs distill=(alpha, temperature)")
+            kd_alpha, kd_temp = (float(v) for v in distill)
+            if not torch.is_tensor(teacher_logits) or not teacher_logits.is_cuda or teacher_logits.dtype != torch.float32 \
+                    or tuple(teacher_logits.shape) != (n, self.num_classes):
+                got = (tuple(teacher_logits.shape), teacher_logits.dtype, teacher_logits.device) \
+                    if torch.is_tensor(teacher_logits) else type(teacher_logits)
+                raise ValueError(f"teacher_logits must be a device float32 [{n}, {self.num_classes}] tensor, got {got}")
         if self.multi_label:
+            pl.use_soft_targets(False, distill=kd)
             self._bind_targets(pl, labels, n)
         elif soft:
-            pl.use_soft_targets(True)
+            pl.use_soft_targets(True, distill=kd)
             self._bind_targets(pl, labels, n, what="soft")
         else:
-            pl.use_soft_targets(False)
+            pl.use_soft_targets(False, distill=kd)
             if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
                 if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
                     raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
@@ -559,8 +593,18 @@ class X3D:
         self._draw_dropout(pl)
         self._draw_drop_path(pl)
         gb = float(global_batch or n)
+        if kd and teacher_logits.data_ptr() != pl.teacher.data_ptr():
+            pl.teacher.copy_(teacher_logits)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
-        if self.multi_label:
+        if kd:
+            tail = (pl.probs.data_ptr(), pl.loss_rows.data_ptr(), pl.kd_rows.data_ptr(), pl.dlogits.data_ptr(),
+                    float(loss_scale) / gb, kd_alpha, kd_temp, n, self.num_classes)
+            if self.multi_label:
+                hip.call("x3d_sigmoid_bce_kd", pl.logits.data_ptr(), pl.teacher.data_ptr(), pl.targets.data_ptr(), *tail)
+            else:
+                hip.call("x3d_softmax_xent_kd", pl.logits.data_ptr(), pl.teacher.data_ptr(),
+                         None if soft else pl.labels.data_ptr(), pl.targets.data_ptr() if soft else None, *tail)
+        elif self.multi_label:
             hip.call("x3d_sigmoid_bce", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
                      pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
         elif soft:

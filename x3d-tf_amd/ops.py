@@ -627,6 +627,53 @@ def softmax_xent_soft(logits, targets, probs, loss_rows=None, dlogits=None, grad
     return probs
 
 
+def _kd_args(name, logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits):
+    """the tensor checks softmax_xent_kd and sigmoid_bce_kd share (those of softmax_xent_soft); returns (N, M)"""
+    _f32_2d(name, "logits", logits)
+    n, m = logits.shape
+    _f32_2d(name, "probs", probs, (n, m))
+    for what, t in (("teacher_logits", teacher_logits), ("targets", targets), ("dlogits", dlogits)):
+        if t is not None:
+            _f32_2d(name, what, t, (n, m))
+    for what, t in (("loss_rows", loss_rows), ("kd_rows", kd_rows)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n):
+            raise ValueError(f"{name}: {what} must be {n} float32, got {t.numel()} {t.dtype}")
+    return n, m
+
+
+def softmax_xent_kd(logits, teacher_logits, probs, labels=None, targets=None, loss_rows=None, kd_rows=None, dlogits=None,
+                    grad_scale=1.0, alpha=0.5, temperature=1.0):
+    """Distillation loss of the softmax head (x3d_softmax_xent_kd: the rules are in include/x3d_hip.h): loss_rows [N] =
+    (1 - alpha) * hard + alpha * kd, with the hard term of softmax_xent on `labels` [N] int32 or of softmax_xent_soft on
+    `targets` [N, M] fp32 (exactly one of the two), kd = T^2 * KL(softmax(teacher / T) || softmax(logits / T)) in kd_rows,
+    and the gradient of the sum in dlogits.  probs is softmax(logits), as those kernels write it.  alpha = 0 does not read
+    the teacher (teacher_logits may be None).  The scalars are the library's to check.  One launch, does not synchronise."""
+    _chk(logits, teacher_logits, labels, targets, probs, loss_rows, kd_rows, dlogits)
+    n, m = _kd_args("softmax_xent_kd", logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
+    if (labels is None) == (targets is None):
+        raise ValueError("softmax_xent_kd: exactly one of labels / targets must be given")
+    if labels is not None and (labels.dtype != torch.int32 or labels.numel() != n):
+        raise ValueError(f"softmax_xent_kd: labels must be {n} int32, got {labels.numel()} {labels.dtype}")
+    hip.call("x3d_softmax_xent_kd", ptr(logits), ptr(teacher_logits), ptr(labels), ptr(targets), ptr(probs), ptr(loss_rows),
+             ptr(kd_rows), ptr(dlogits), float(grad_scale), float(alpha), float(temperature), n, m)
+    return probs
+
+
+def sigmoid_bce_kd(logits, teacher_logits, targets, probs, loss_rows=None, kd_rows=None, dlogits=None, grad_scale=1.0,
+                   alpha=0.5, temperature=1.0):
+    """Distillation loss of the multi-label head (x3d_sigmoid_bce_kd: the rules are in include/x3d_hip.h): loss_rows [N] =
+    (1 - alpha) * sigmoid_bce's row + alpha * kd, kd = T^2 * the mean Bernoulli KL of sigmoid(logits / T) from
+    sigmoid(teacher / T) in kd_rows, and the gradient of the sum in dlogits.  probs is sigmoid(logits).  alpha = 0 does not
+    read the teacher (teacher_logits may be None).  One launch, does not synchronise."""
+    _chk(logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
+    if targets is None:
+        raise ValueError("sigmoid_bce_kd: targets must be given")
+    n, m = _kd_args("sigmoid_bce_kd", logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
+    hip.call("x3d_sigmoid_bce_kd", ptr(logits), ptr(teacher_logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(kd_rows),
+             ptr(dlogits), float(grad_scale), float(alpha), float(temperature), n, m)
+    return probs
+
+
 MIX_MODES = {"mixup": hip.MIX_MIXUP, "cutmix": hip.MIX_CUTMIX}
 
 

@@ -214,6 +214,8 @@ class _Plan:
         self.bn_eval_items: List = []
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
         self._head_hard = self._head_soft = None   # the two loss launches of a single-label training plan (use_soft_targets)
+        self._head_kd: Dict = {}       # their distillation forms, and the multi-label head's: "labels" | "targets" | "multi" -> entry
+        self.teacher = self.kd_rows = None   # distillation: the teacher's logits [N][classes] and the KD term per row (first distilled call)
         self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
         self.bn_layers: List[BNBuf] = []   # every BatchNorm layer of a training plan, as recorded (precise_bn_table)
         self._pbn_table = None
@@ -351,24 +353,43 @@ class _Plan:
         for B, r in zip(self.blocks, bw.blocks):
             vars(B).update(vars(r))
 
-    def use_soft_targets(self, soft: bool):
-        """Single-label training plans: which loss the head slot (fwd[grad_scale_slot]) holds -- x3d_softmax_xent on
+    def use_soft_targets(self, soft: bool, distill: bool = False):
+        """Which loss the head slot (fwd[grad_scale_slot]) of a training plan holds.  Single-label plans: x3d_softmax_xent on
         `labels`, as recorded, or x3d_softmax_xent_soft on the dense rows in `targets`.  The targets buffer and the second
-        entry come into being with the first soft call, so a plan that never sees soft targets allocates nothing for them."""
-        slot = self.grad_scale_slot
-        if not soft:
-            if self._head_hard is not None:
-                self.fwd[slot] = self._head_hard
-            return
-        if self._head_soft is None:
-            m = self.model
+        entry come into being with the first soft call, so a plan that never sees soft targets allocates nothing for them.
+        distill: the knowledge-distillation form of that loss instead -- x3d_softmax_xent_kd on `labels` or on `targets`,
+        x3d_sigmoid_bce_kd for a multi-label plan (whose one hard head takes no `soft`) -- reading the teacher's logits from
+        `teacher` and writing the KD term per row to `kd_rows`; both buffers and the entries likewise come into being with
+        the first distilled call.  The scalars of a recorded entry (grad_scale, alpha, temperature) are placeholders: the
+        model launches the slot's entry point with the step's own."""
+        slot, m = self.grad_scale_slot, self.model
+        soft = bool(soft) and not m.multi_label
+        if (soft or distill) and self._head_hard is None:
             self._head_hard = self.fwd[slot]
+        if soft and self._head_soft is None:
             self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
             tmp = []
             self.rec(tmp, "x3d_softmax_xent_soft", self.logits, self.targets, self.probs, self.loss_rows, self.dlogits,
                      1.0 / self.n, self.n, m.num_classes)
             self._head_soft = tmp[0]
-        self.fwd[slot] = self._head_soft
+        if not distill:
+            entry = self._head_soft if soft else self._head_hard
+            if entry is not None:
+                self.fwd[slot] = entry
+            return
+        if self.teacher is None:
+            self.teacher, self.kd_rows = self.f32(self.n, m.num_classes), self.f32(self.n)
+        key = "multi" if m.multi_label else ("targets" if soft else "labels")
+        if key not in self._head_kd:
+            tmp = []
+            tail = (self.probs, self.loss_rows, self.kd_rows, self.dlogits, 1.0 / self.n, 0.5, 1.0, self.n, m.num_classes)
+            if m.multi_label:
+                self.rec(tmp, "x3d_sigmoid_bce_kd", self.logits, self.teacher, self.targets, *tail)
+            else:
+                self.rec(tmp, "x3d_softmax_xent_kd", self.logits, self.teacher, None if soft else self.labels,
+                         self.targets if soft else None, *tail)
+            self._head_kd[key] = tmp[0]
+        self.fwd[slot] = self._head_kd[key]
 
     def run(self, lst, start=0, stop=None):
         if self.model.dry:
@@ -498,8 +519,10 @@ def _rec_infer_head(model, pl):
 
 
 # forward, inference ----------------------------------------
-def record_inference(model, n, t, h, w) -> _Plan:
+def record_inference(model, n, t, h, w, probs=True) -> _Plan:
     """The forward pass at training=False (reference model.py:113-127; eval.py:83-89) as its own launch list.
+    probs=False (X3D.logits): the same list without its last two launches -- it ends with fc2, pl.logits [n, classes] is the
+    result, and n need not be a multiple of views * crops since no views are combined.
 
     With the moving statistics every BatchNorm is a per-channel affine known before the first kernel, so nothing
     waits for batch statistics and the training plan's materialised intermediates disappear:
@@ -516,7 +539,7 @@ def record_inference(model, n, t, h, w) -> _Plan:
     pl = _Plan(model, n, t, h, w, False)
     dt = hip.dtype_code(model.dtype)
     F = pl.fwd
-    if n % a.num_preds:
+    if probs and n % a.num_preds:
         raise ValueError(f"inference batch {n} is not a multiple of views*crops={a.num_preds} "
                          "(reference model.py:125)")
     F.append(None)   # slot 0: x3d_bn_eval_coef_batched, filled in once every BN layer is known
@@ -551,7 +574,9 @@ def record_inference(model, n, t, h, w) -> _Plan:
     pl.s5 = _conv5_args(model, pl, x_cur, hh, ww, dt)
     pl.rec(F, "x3d_pw_fwd", pl.s5)
     _rec_head_dense(model, pl, dt)
-    _rec_infer_head(model, pl)
+    pl.out = None
+    if probs:
+        _rec_infer_head(model, pl)
     items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
     pl.bn_eval_table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(model.device)
     F[0] = ("x3d_bn_eval_coef_batched", pl.lib.x3d_bn_eval_coef_batched,

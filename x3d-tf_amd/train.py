@@ -12,7 +12,8 @@ import torch
 
 from . import dist as xdist
 from . import ops
-from .config import OPTIMIZERS, finetune_settings, mix_settings, optim_settings, precise_bn_settings, solver_settings
+from .config import (OPTIMIZERS, distill_settings, finetune_settings, mix_settings, optim_settings, precise_bn_settings,
+                     solver_settings)
 from .mix import NO_MIX, draw_mix_params
 from .solver import RULES
 
@@ -92,7 +93,7 @@ class Trainer:
     """
 
     def __init__(self, model, cfg, momentum: Optional[float] = None, sync_moving_stats: bool = True, group=None,
-                 loss_scale="auto", mix_seed: int = 0, drop_path_seed: int = 0):
+                 loss_scale="auto", mix_seed: int = 0, drop_path_seed: int = 0, teacher=None):
         self.optimizer = cfg.TRAIN.OPTIMIZER.lower()
         if self.optimizer not in OPTIMIZERS:   # reference train.py:88-97: SGD(nesterov) / Adam / NotImplementedError; + lars, adamw, lamb
             raise NotImplementedError(f"{cfg.TRAIN.OPTIMIZER} not supported")
@@ -164,11 +165,60 @@ class Trainer:
             model.set_drop_path_state(self._drop_path_seed, 0)
         # precise BatchNorm (NETWORK.BN.USE_PRECISE_STATS; off by default: `fit` then draws the batches it always drew)
         self.precise = precise_bn_settings(cfg)
+        # knowledge distillation (DISTILL.*; off by default: `step` is then what it was, launch for launch).  `teacher`: an X3D
+        # model of the student's class layout, or built here from DISTILL.TEACHER / TEACHER_CKPT.  It only ever runs `logits`:
+        # never trained, in no bucket, no checkpoint and no EMA, not part of `validate` or `precise_bn`.
+        self.distill = distill_settings(cfg, have_teacher=teacher is not None)
+        self.teacher = None
+        if teacher is not None:
+            self._check_teacher(teacher)
+        if self.distill.enable:
+            self.teacher = teacher if teacher is not None else self._build_teacher()
+        self._kd = (self.distill.alpha, self.distill.temperature)
+
+    def _check_teacher(self, teacher):
+        m = self.model
+        if teacher.num_classes != m.num_classes:
+            raise ValueError(f"the teacher has {teacher.num_classes} classes, the student {m.num_classes}: distillation "
+                             "compares their logits class by class")
+        if bool(getattr(teacher, "multi_label", False)) != bool(getattr(m, "multi_label", False)):
+            raise ValueError("teacher and student must both be multi-label (DATA.MULTI_LABEL) or both single-label")
+
+    def _build_teacher(self):
+        """The teacher of DISTILL.TEACHER -- a shipped config name (XS .. XL) or a yaml path -- on the student's device and
+        storage type, NETWORK.NUM_CLASSES and DATA.MULTI_LABEL forced to the student's, with the weights of
+        DISTILL.TEACHER_CKPT.  Every rank loads its own copy: no collective."""
+        from .config import get_config, get_default_config
+        from .model import X3D
+        m, d = self.model, self.distill
+        if not d.teacher_ckpt:
+            raise ValueError("DISTILL.TEACHER_CKPT is empty: a teacher built from DISTILL.TEACHER needs its checkpoint (a "
+                             "randomly initialised teacher teaches nothing)")
+        over = ["NETWORK.NUM_CLASSES", int(m.num_classes), "DATA.MULTI_LABEL", bool(getattr(m, "multi_label", False))]
+        if d.teacher.endswith((".yaml", ".yml")) or os.sep in d.teacher:
+            cfg = get_default_config()
+            cfg.merge_from_file(d.teacher)
+            cfg.merge_from_list(over)
+            cfg.freeze()
+        else:
+            cfg = get_config(d.teacher, over)
+        teacher = X3D(cfg, dtype=m.dtype, device=m.device)
+        teacher.load_weights(d.teacher_ckpt)
+        self._check_teacher(teacher)
+        return teacher
+
+    def _teacher_kw(self, clips):
+        """forward_backward's distillation arguments: the teacher's logits of the clips the student sees (after mixing, as
+        DeiT / timm feed the teacher); {} with DISTILL off.  Launches only."""
+        if self.teacher is None:
+            return {}
+        return dict(teacher_logits=self.teacher.logits(clips), distill=self._kd)
 
     def step(self, clips, labels, lr: Optional[float] = None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
         plan (loss_rows, probs).  With MIXUP.ENABLE or TRAIN.LABEL_SMOOTHING the batch is mixed and the targets are built
-        first (`_mix_batch`; `last_mix` holds the parameters drawn)."""
+        first (`_mix_batch`; `last_mix` holds the parameters drawn).  With DISTILL.ENABLE the teacher's logits of the (mixed)
+        clips join the loss (`_teacher_kw`; `plan.kd_rows` holds the KD term per row)."""
         m = self.model
         n = clips.shape[0]
         if lr is None:
@@ -179,7 +229,7 @@ class Trainer:
             return self._accum_step(clips, labels, lr, n)
         pl = m.forward_backward(clips, labels, global_batch=n * self.world,
                                 on_stage_done=self._on_stage_done if self.collectives else None,
-                                loss_scale=self.loss_scale)
+                                loss_scale=self.loss_scale, **self._teacher_kw(clips))
         self.reducer.mark_backward_done()     # (an event on the compute stream: finish() measures the exposed exchange from it)
         self.reducer.finish()
         self._finish_stats()
@@ -240,7 +290,7 @@ class Trainer:
             self._grad_acc = torch.zeros_like(m.flat_grads)
         hook = (self._on_stage_done if last else self._on_stage_done_no_grads) if self.collectives else None
         pl = m.forward_backward(clips, labels, global_batch=n * self.world * self._accum, on_stage_done=hook,
-                                loss_scale=self.loss_scale)
+                                loss_scale=self.loss_scale, **self._teacher_kw(clips))
         if not last:
             ops.grad_accum(self._grad_acc, m.flat_grads, first=self._micro == 1)
             self._finish_stats()
@@ -328,6 +378,9 @@ class Trainer:
         self.history: per-epoch lists like keras.callbacks.History.history -- `loss` (= the returned list), `lr`, the
         requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating.
 
+        DISTILL.ENABLE: `history["kd_loss"]` is the epoch mean of the unweighted KD term (`kd_loss`); `loss` stays the combined
+        loss (+ L2).
+
         SOLVER.* (INTEGRATION.md): with CLIP_GRAD_L2NORM `history["grad_norm"]` is the epoch's mean gradient norm before
         clipping; with ACCUM_STEPS = A every batch is a micro-batch, steps_per_epoch and an integer save_freq must be multiples
         of A (ValueError); with EMA_DECAY and EMA_EVAL validation runs on the EMA weights (`ema_scope`).
@@ -369,6 +422,8 @@ class Trainer:
         self.history.update({k: [] for k in metrics})
         if self._clip:
             self.history["grad_norm"] = []
+        if self.teacher is not None:
+            self.history["kd_loss"] = []
         if val_source is not None:
             self.history.update({"val_" + k: [] for k in val_keys})
         writer = model_dir is not None and xdist.env_world()[0] == 0
@@ -377,11 +432,14 @@ class Trainer:
             tot = torch.zeros((), dtype=torch.float64, device=self.model.device)
             train_m = (DeviceMAP() if multi else DeviceMetrics()) if metrics else None
             gn_tot, updates = (torch.zeros((), dtype=torch.float64, device=self.model.device) if self._clip else None), 0
+            kd_tot = torch.zeros((), dtype=torch.float64, device=self.model.device) if self.teacher is not None else None
             for _ in range(steps):
                 clips, labels = next(it)
                 before = self.opt_step
                 pl = self.step(clips, labels, lr)
                 tot += self.loss(pl).double()
+                if kd_tot is not None:
+                    kd_tot += self.kd_loss(pl).double()
                 if gn_tot is not None and self.opt_step != before:     # an update ran (not inside an accumulation / fp16 skip)
                     gn_tot += self.last_grad_norm
                     updates += 1
@@ -397,6 +455,8 @@ class Trainer:
             history.append(float(tot.item()) / steps)
             self.history["loss"].append(history[-1])
             self.history["lr"].append(lr)
+            if kd_tot is not None:            # the epoch mean of the unweighted KD term; read once per epoch, like the loss
+                self.history["kd_loss"].append(float(kd_tot.item()) / steps)
             if gn_tot is not None:            # mean over the epoch's updates; read once per epoch, like the loss
                 self.history["grad_norm"].append(float(gn_tot.item()) / max(updates, 1))
             if train_m is not None:
@@ -611,3 +671,11 @@ class Trainer:
         if not self.rule.l2_in_loss:
             return ce
         return ce + self.model.regularization_loss().float().squeeze()
+
+    def kd_loss(self, pl):
+        """global-batch mean of the unweighted distillation term T^2 * KL(teacher || student) of the last distilled step
+        (`plan.kd_rows`), reduced as `loss` is"""
+        kd = pl.kd_rows.sum() / (pl.n * self.world)
+        if self.collectives:
+            torch.distributed.all_reduce(kd, group=self.group)
+        return kd
