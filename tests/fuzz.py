@@ -3,7 +3,10 @@ pointwise forward / data gradient / weight gradient, strided shortcut) on RANDOM
 counts that are not a multiple of 8, strips cut by row ends, channel counts off the 32-grid -- in all three storage types.
 One generator for the in-suite slice (tests/test_fuzz_gpu.py) and the long sweep (tools/fuzz_parity.py).
 The fused pointwise backward (x3d_pw_bwd) is not drawn here: its kernels are discrete tile classes that uniform sampling keeps
-missing -- tests/pw_bwd_classes.py enumerates them and draws shapes class by class (tests/test_pw_bwd_classes_gpu.py)."""
+missing -- tests/pw_bwd_classes.py enumerates them and draws shapes class by class (tests/test_pw_bwd_classes_gpu.py).
+The same holds for x3d_pw_fwd / x3d_pw_dgrad / x3d_pw_wgrad, which ARE drawn here: what this generator reaches of their
+instantiations is an accident of the seeds (100 of 676 were covered by the slice alone) -- tests/pw_classes.py enumerates them
+and commits cases class by class (tests/test_pw_classes_gpu.py)."""
 import random
 
 import torch

@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import shapes as S
-from tests.util import report, rnd, round_to, tie_slack, tol_gemm, tol_store
+from tests.util import dev_at, out_at, report, rnd, round_to, tie_slack, tol_gemm, tol_store
 
 pytestmark = pytest.mark.gpu
 
@@ -77,9 +77,10 @@ def _panels(ops, wt, dtype, gpu):
 @pytest.mark.parametrize("panel", [False, True])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", S.PW_FWD + S.PW_FWD_XL)
-def test_pw_fwd(gpu, dtype, shape, panel):
+def test_pw_fwd(gpu, dtype, shape, panel, off=0):
     """x3d_pw_fwd against the oracle's pointwise conv.  panel=True passes the packed weight panel, as model.py always does
-    for 16-bit storage: that is the production dispatch (weights-stationary / weights-streamed / resident-panel kernels)."""
+    for 16-bit storage: that is the production dispatch (weights-stationary / weights-streamed / resident-panel kernels).
+    off > 0 (tests/pw_classes.py): x and y are views `off` elements into larger allocations (util.dev_at)."""
     if panel and dtype == torch.float32:
         pytest.skip("weight panels exist for the 16-bit storage types only")
     ops, O = _ops(), _oracle()
@@ -101,7 +102,8 @@ def test_pw_fwd(gpu, dtype, shape, panel):
     ref = O.pointwise(round_to(xin, dtype), round_to(wt, dtype), stride)
     stats = torch.zeros((cout, 2), dtype=torch.float64, device=gpu)
     fp = _panels(ops, wt, dtype, gpu)[0] if panel else None
-    y = ops.pw_fwd(x.to(gpu), wt.to(gpu), stats=stats, in_ss=None if ss is None else ss.to(gpu),
+    yout = out_at((n, cout, t, -(-h // stride), -(-w // stride)), dtype, gpu, off) if off else None
+    y = ops.pw_fwd(dev_at(x, gpu, off), wt.to(gpu), y=yout, stats=stats, in_ss=None if ss is None else ss.to(gpu),
                    in_gate=None if gate is None else gate.to(gpu), in_act=act, stride=stride, w_panel=fp)
     torch.cuda.synchronize()
     rt, at = tol_gemm(dtype)
@@ -118,7 +120,7 @@ def test_pw_fwd(gpu, dtype, shape, panel):
 @pytest.mark.parametrize("panel", [False, True])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", S.PW_FWD_TAIL)
-def test_pw_fwd_tail(gpu, dtype, shape, panel):
+def test_pw_fwd_tail(gpu, dtype, shape, panel, off=0):
     """x3d_pw_fwd with the residual tail of the block below folded into its prologue (in_add / in_store): x is that block's
     raw `c` output, the conv input y = relu(bn_c(x) + shortcut) (reference model.py:381-392) is built on load, STORED (it is
     the block's output: the shortcut conv, the next tail and the backward pass read it) and multiplied.  y against the fp64
@@ -142,17 +144,22 @@ def test_pw_fwd_tail(gpu, dtype, shape, panel):
         sc_, short = None, 0.0
     y_ref = F.relu(_affine(cd, ss.double()) + short)
     dev = lambda v: None if v is None else v.to(gpu)
+    act = lambda v: dev_at(v, gpu, off)        # (the activation operands: `off` elements into a larger allocation)
     ystore = torch.full((n, cin, t, h, w), 7.0, dtype=dtype, device=gpu)
+    if off:
+        ystore = out_at((n, cin, t, h, w), dtype, gpu, off, fill=7.0)
     stats = torch.zeros((cout, 2), dtype=torch.float64, device=gpu)
     fp = _panels(ops, wt, dtype, gpu)[0] if panel else None
-    out = ops.pw_fwd(dev(c), dev(wt), stats=stats, in_ss=dev(ss), in_act=1, w_panel=fp, in_add=dev(sc_), in_add_ss=dev(ssr),
-                     in_store=ystore)
+    out = ops.pw_fwd(act(c), dev(wt), y=out_at((n, cout, t, h, w), dtype, gpu, off) if off else None, stats=stats, in_ss=dev(ss),
+                     in_act=1, w_panel=fp, in_add=act(sc_), in_add_ss=dev(ssr), in_store=ystore)
     torch.cuda.synchronize()
     rs, as_ = tol_store(dtype)
     report("y (stored conv input)", ystore, y_ref, rs, as_ * y_ref.abs().max().item())
     # the separate pass stores the same tensor (the two evaluate the affine sum in a different association: one ulp at most)
     y2 = torch.empty_like(ystore)
-    ops.tail_fwd(dev(c), dev(ss), dev(sc_), dev(ssr), y2)
+    if off:
+        y2 = out_at((n, cin, t, h, w), dtype, gpu, off)
+    ops.tail_fwd(act(c), dev(ss), act(sc_), dev(ssr), y2)
     torch.cuda.synchronize()
     report("y vs x3d_tail_fwd", ystore, y2.float().cpu(), 2 * rs, as_ * y_ref.abs().max().item())
     ref = O.pointwise(ystore.float().cpu().double(), round_to(wt, dtype), 1)      # the GEMM operand is the stored y
@@ -165,7 +172,7 @@ def test_pw_fwd_tail(gpu, dtype, shape, panel):
 @pytest.mark.parametrize("panel", [False, True])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", S.PW_FWD_INFER)
-def test_pw_fwd_infer(gpu, dtype, shape, panel):
+def test_pw_fwd_infer(gpu, dtype, shape, panel, off=0):
     """x3d_pw_fwd with the inference epilogue (out_scale_shift): y = act(s_o * conv(f(x)) + t_o [+ s_r * add + t_r]) -- the
     BatchNorm after the conv folded from the moving statistics and the residual Add + ReLU (reference model.py:300-303,
     368-371, 381-392 at training=False) -- against the oracle's pointwise conv + the same affine arithmetic in fp64."""
@@ -198,8 +205,9 @@ def test_pw_fwd_infer(gpu, dtype, shape, panel):
         ref = F.relu(ref)
     fp = _panels(ops, wt, dtype, gpu)[0] if panel else None
     dev = lambda v: None if v is None else v.to(gpu)
-    y = ops.pw_fwd(dev(x), dev(wt), in_ss=dev(ss), in_gate=dev(gate), in_act=act, w_panel=fp, out_ss=dev(oss),
-                   out_add=dev(add), out_add_ss=dev(ass), out_act=1 if oact == "relu" else 0)
+    y = ops.pw_fwd(dev_at(x, gpu, off), dev(wt), y=out_at((n, cout, t, h, w), dtype, gpu, off) if off else None, in_ss=dev(ss),
+                   in_gate=dev(gate), in_act=act, w_panel=fp, out_ss=dev(oss), out_add=dev_at(add, gpu, off), out_add_ss=dev(ass),
+                   out_act=1 if oact == "relu" else 0)
     torch.cuda.synchronize()
     rt, at = tol_gemm(dtype)
     slack = 0.0
@@ -807,7 +815,7 @@ def test_dw3d_fwd(gpu, dtype, shape):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", S.PW_DGRAD)   # N, Cin, Cout, T, H, W
 @pytest.mark.parametrize("epi", S.PW_DGRAD_EPI)
-def test_pw_dgrad(gpu, dtype, shape, epi, panel):
+def test_pw_dgrad(gpu, dtype, shape, epi, panel, off=0):
     if panel and dtype == torch.float32:
         pytest.skip("weight panels exist for the 16-bit storage types only")
     ops = _ops()
@@ -820,19 +828,21 @@ def test_pw_dgrad(gpu, dtype, shape, epi, panel):
     dyraw = _dyraw(coef, gd, yd, dtype)       # operands as the matrix cores see them (fp32 prologue, rounded to storage)
     ref = torch.einsum("oc,nothw->ncthw", round_to(wt, dtype), dyraw)
     dx = torch.empty((n, cin, t, h, w), dtype=dtype, device=gpu)
+    if off:
+        dx = out_at((n, cin, t, h, w), dtype, gpu, off)
     kw = {}
     rt, at = tol_gemm(dtype)
     if epi == "add":
         add, addd = rnd((n, cin, t, h, w), dtype, g_)
         ref = ref + addd
-        kw = dict(epi=ops.EPI_ADD, add=add.to(gpu))
+        kw = dict(epi=ops.EPI_ADD, add=dev_at(add, gpu, off))
     elif epi == "add_strided":
         hh, wh = (h + 1) // 2, (w + 1) // 2
         add, addd = rnd((n, cin, t, hh, wh), dtype, g_)
         up = torch.zeros_like(ref)
         up[:, :, :, ::2, ::2] = addd
         ref = ref + up
-        kw = dict(epi=ops.EPI_ADD_STRIDED, add=add.to(gpu))
+        kw = dict(epi=ops.EPI_ADD_STRIDED, add=dev_at(add, gpu, off))
     elif epi == "swish_bwd":
         braw, bd = rnd((n, cin, t, h, w), dtype, g_)
         bss = torch.stack([1 + 0.3 * torch.randn(cin, generator=g_), 0.3 * torch.randn(cin, generator=g_)], 1)
@@ -841,10 +851,10 @@ def test_pw_dgrad(gpu, dtype, shape, epi, panel):
         s = torch.sigmoid(v)
         ref = ref * (s * (1 + v * (1 - s)))
         ncs = torch.zeros((n, cin, 2), dtype=torch.float64, device=gpu)
-        kw = dict(epi=ops.EPI_SWISH_BWD, braw=braw.to(gpu), b_ss=bss.to(gpu), gate=gate.to(gpu), nc_sums=ncs)
+        kw = dict(epi=ops.EPI_SWISH_BWD, braw=dev_at(braw, gpu, off), b_ss=bss.to(gpu), gate=gate.to(gpu), nc_sums=ncs)
     if panel:
         kw["w_panel"] = _panels(ops, wt, dtype, gpu)[1]     # the production dispatch (model.py always passes the panel)
-    ops.pw_dgrad(g.to(gpu), yraw.to(gpu), coef.to(gpu), wt.to(gpu), dx, **kw)
+    ops.pw_dgrad(dev_at(g, gpu, off), dev_at(yraw, gpu, off), coef.to(gpu), wt.to(gpu), dx, **kw)
     torch.cuda.synchronize()
     report("dx", dx, ref, rt, at * ref.abs().max().item() + 1.1 * _dyraw_slack(coef, gd, yd, dtype, wt))
     if epi == "swish_bwd":
@@ -856,9 +866,9 @@ def test_pw_dgrad(gpu, dtype, shape, epi, panel):
 @pytest.mark.parametrize("slab", [False, True])
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", S.PW_WGRAD)   # N, Cin, Cout, T, H, W, stride, prologue
-def test_pw_wgrad(gpu, dtype, shape, slab):
+def test_pw_wgrad(gpu, dtype, shape, slab, off=0):
     """slab: through per-point-chunk partial slabs + x3d_dw_slab_reduce (x3d_hip.h dw_slab), where the kernel behind the call
-    has the form (the 12-tile groups: the stage-5 layers)."""
+    has the form (the 12-tile groups: the stage-5 layers).  off > 0: g, yraw and x `off` elements into larger allocations."""
     ops = _ops()
     n, cin, cout, t, h, w, stride, pro = shape
     if slab and not hip_lib().x3d_pw_wgrad_dw_parts(S.pw_wgrad_struct(shape, dtype)):
@@ -882,7 +892,7 @@ def test_pw_wgrad(gpu, dtype, shape, slab):
         xin = xin[:, :, :, ::stride, ::stride]
     ref = torch.einsum("nothw,ncthw->oc", dyraw, xin)
     dw = torch.full((cout, cin), 0.5, dtype=torch.float32, device=gpu)   # += semantics
-    assert ops.pw_wgrad(g.to(gpu), yraw.to(gpu), coef.to(gpu), x.to(gpu), dw, in_ss=None if ss is None else ss.to(gpu),
+    assert ops.pw_wgrad(dev_at(g, gpu, off), dev_at(yraw, gpu, off), coef.to(gpu), dev_at(x, gpu, off), dw, in_ss=None if ss is None else ss.to(gpu),
                         in_gate=None if gate is None else gate.to(gpu), in_act=act, stride=stride, slab=slab)
     torch.cuda.synchronize()
     tol = _wtol(dtype)

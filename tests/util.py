@@ -229,6 +229,24 @@ def rnd(shape, dtype, gen, scale=1.0):
     return t, t.double()
 
 
+def dev_at(t, gpu, off=0):
+    """t on the device; off > 0: as a contiguous view `off` elements into a larger allocation, so that the kernel sees an
+    operand `off` elements past a 16-byte boundary (torch's device allocations are aligned to far more).  None stays None."""
+    if t is None or not off:
+        return None if t is None else t.to(gpu)
+    v = torch.empty(t.numel() + off, dtype=t.dtype, device=gpu)[off:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == (off * v.element_size()) % 16
+    return v
+
+
+def out_at(shape, dtype, gpu, off=0, fill=None):
+    """A caller-provided output on the device, uninitialised or filled, placed like dev_at()."""
+    import math
+    v = torch.empty(math.prod(shape) + off, dtype=dtype, device=gpu)[off:].view(shape)
+    return v if fill is None else v.fill_(fill)
+
+
 class AltBackward:
     """A second backward pass (`rec`: x3d_tf_amd.plan.Backward) recorded over the SAME forward buffers of a training plan with
     other plan options (record_alternate_backward).  run() replays it from the forward state `snapshot` captured."""
