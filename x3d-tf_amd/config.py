@@ -135,7 +135,7 @@ def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA;
-    LAYER_DECAY / LR_MULT / FREEZE: fine-tuning),
+    LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
     DISTILL.* (knowledge distillation against a teacher's logits)."""
@@ -181,9 +181,12 @@ def get_default_config():
     # Fine-tuning (finetune_settings; all off by default).  LAYER_DECAY: tensor of depth group d gets the learning-rate scale
     # LAYER_DECAY ** (D - d) (timm's layer decay: stem 0, the residual blocks 1..L, head D = L + 1); LR_MULT: [[name prefix,
     # factor], ...] on top of it, the longest matching prefix wins; FREEZE: name prefixes of the tensors the solver step leaves
-    # alone.  The section knows the three keys without holding them: its items stay the four above until one is set.
+    # alone; FREEZE_EVAL (freeze_eval_settings): the frozen PREFIX of the network -- the stem and the residual blocks behind it,
+    # as far as every trainable tensor is frozen -- runs in inference form during training (moving statistics, nothing kept)
+    # and the backward pass ends above it.  The section knows the four keys without holding them: its items stay the four
+    # above until one is set.
     c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True),
-                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[]))
+                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[], FREEZE_EVAL=False))
     # the layer-wise optimizers (TRAIN.OPTIMIZER = lars | adamw | lamb; inert for sgd / adam).  LARS (PySlowFast's SOLVER.LARS_ON):
     # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
     # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
@@ -217,6 +220,7 @@ def get_config(name, overrides=None, freeze=True):
     randaug_settings(cfg)
     solver_settings(cfg)
     finetune_settings(cfg)
+    freeze_eval_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
     precise_bn_settings(cfg)
@@ -434,6 +438,18 @@ def finetune_settings(cfg) -> FinetuneSettings:
     if not isinstance(freeze, (list, tuple)) or not all(isinstance(f, str) for f in freeze):
         raise ValueError(f"SOLVER.FREEZE must be a list of name prefixes (str), not {freeze!r}")
     return FinetuneSettings(float(decay), tuple(pairs), tuple(freeze))
+
+
+def freeze_eval_settings(cfg) -> bool:
+    """cfg.SOLVER.FREEZE_EVAL (False for a config tree without the key or the section): the frozen prefix of SOLVER.FREEZE runs
+    in inference form and the backward pass is cut above it (finetune.frozen_prefix, X3D.set_finetune).  Kept apart from
+    FinetuneSettings, which stays the 3-tuple of the solver step.  ValueError for a value that is not a bool; whether FREEZE
+    freezes a prefix at all is the model's to check: it needs the architecture."""
+    sv = getattr(cfg, "SOLVER", None)
+    on = False if sv is None else getattr(sv, "FREEZE_EVAL", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"SOLVER.FREEZE_EVAL must be a bool, not {on!r}")
+    return on
 
 
 OptimSettings = collections.namedtuple("OptimSettings", "lars_trust_coef lars_eps lars_clip weight_decay lamb_eps")

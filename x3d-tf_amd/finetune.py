@@ -12,9 +12,18 @@ rounded to fp32 -- the value the kernels multiply the learning rate with (x3d_*_
 Frozen is not "scale 0".  Nesterov SGD with a velocity left over still moves a weight at lr = 0, and 0 * inf is NaN; so a
 frozen tensor is simply in no chunk of the table the solver step walks (segments.SegTable over the tuned segments): its
 weights, optimizer slots and EMA copy are never read or written, whatever its gradient holds, and its gradient is in neither
-the clip norm nor the finite check.  What freezing does NOT do: the backward pass still computes (and data parallelism still
-all-reduces) the frozen tensors' gradients, BatchNorm inside frozen layers still normalises with batch statistics and still
-updates its moving statistics, and the reported regularisation loss still sums over all regularised kernels."""
+the clip norm nor the finite check.  What freezing alone does NOT do: the backward pass still computes (and data parallelism
+still all-reduces) the frozen tensors' gradients, BatchNorm inside frozen layers still normalises with batch statistics and
+still updates its moving statistics, and the reported regularisation loss still sums over all regularised kernels.
+
+SOLVER.FREEZE_EVAL cuts the passes for the frozen PREFIX (`frozen_prefix`): units are numbered in network order, u0 the stem,
+u1..uL the residual blocks; the prefix is the longest run u0..u(k-1) whose every trainable tensor is frozen.  A training step
+then runs those units as `training=False` runs them -- BatchNorm on the moving statistics, which are not updated; no block
+dropped by NETWORK.DROP_PATH_RATE; nothing kept for a backward pass -- and the backward list ends at the seam, the first unit
+above the prefix, with that unit's weight gradients: no gradient of a prefix tensor is computed, its slice of `flat_grads`
+stays at the zero the step starts from (data parallelism reduces those zeros: the buckets and their order do not change).
+conv5, bn5 and the dense head are never part of the prefix.  Frozen tensors OUTSIDE the prefix keep the behaviour above
+(gradient computed, batch statistics), and the regularisation loss is unchanged either way."""
 import math
 
 import numpy as np
@@ -39,6 +48,28 @@ def depth_groups(arch):
         raise ValueError(f"{name}: not a tensor of the stem, a residual block or the head")
 
     return group, top
+
+
+def _prefix_break(arch, param_specs, frozen_names):
+    """(k, name): the frozen prefix length and the first trainable tensor, in network order, that is not frozen -- the one
+    that ends the prefix (None when the stem and every block are frozen)."""
+    group, top = depth_groups(arch)
+    frozen = set(frozen_names)
+    first = {}                                # unit -> its first trainable tensor that is not frozen
+    for s in param_specs:
+        if s.trainable and s.name not in frozen:
+            first.setdefault(group(s.name), s.name)
+    for d in range(top):
+        if d in first:
+            return d, first[d]
+    return top, None
+
+
+def frozen_prefix(arch, param_specs, frozen_names) -> int:
+    """k: the length of the longest run of units u0..u(k-1) -- u0 the stem (`conv1/`), u1..uL the residual blocks of
+    `arch.blocks` -- in which every trainable tensor of every unit is in `frozen_names`.  0: the stem is not fully frozen;
+    1: the stem only; L + 1: the stem and all blocks.  conv5, bn5 and the dense head are never part of it."""
+    return _prefix_break(arch, param_specs, frozen_names)[0]
 
 
 def flat_segments(param_specs):

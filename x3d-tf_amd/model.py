@@ -221,6 +221,7 @@ class X3D:
         # fine-tuning (set_finetune): off -- every apply_* and the gradient reduction make the launches they always made
         self._ft = None
         self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
+        self.frozen_prefix = 0     # units (stem, blocks) a training plan records in inference form (set_finetune freeze_eval)
 
     def _build_panels(self):
         """bf16 LDS-image panels of every pointwise-conv weight (x3d_pw_pack_weights): refreshed by one launch
@@ -394,14 +395,16 @@ class X3D:
 
     def _plan(self, n, t, h, w, training, logits_only=False) -> _Plan:
         """logits_only: the inference list that ends with fc2 (`logits`), a plan of its own beside the `call` one"""
-        key = (n, t, h, w, False, "logits") if logits_only else (n, t, h, w, bool(training))
+        # (a training plan is recorded for one frozen prefix: changing it never reuses a stale plan)
+        key = (n, t, h, w, False, "logits") if logits_only else ((n, t, h, w, True, self.frozen_prefix) if training and self.frozen_prefix
+                                                                  else (n, t, h, w, bool(training)))
         pl = self._plans.pop(key, None)
         if pl is None:
             self.release_plans(keep=self.MAX_PLANS - 1)
             if logits_only:
                 pl = record_inference(self, n, t, h, w, probs=False)
             else:
-                pl = (record_training if training else record_inference)(self, n, t, h, w)
+                pl = record_training(self, n, t, h, w, self.frozen_prefix) if training else record_inference(self, n, t, h, w)
         self._plans[key] = pl           # most recently used last
         return pl
 
@@ -744,7 +747,7 @@ class X3D:
             self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
         return self._seg_table
 
-    def set_finetune(self, freeze=(), lr_mult=(), layer_decay=1.0):
+    def set_finetune(self, freeze=(), lr_mult=(), layer_decay=1.0, freeze_eval=False):
         """Fine-tuning (SOLVER.FREEZE / LR_MULT / LAYER_DECAY, finetune.py): freeze the trainable tensors whose names start with
         a prefix of `freeze`, and give every other ("tuned") tensor the learning rate lr * scale, scale = layer_decay ** (D -
         depth group) * factor of the longest `lr_mult` prefix ([(prefix, factor), ...]).  Builds and keeps the chunk table of
@@ -753,20 +756,34 @@ class X3D:
         makes x3d_seg_grad_sumsq's and grads_finite reads its count: a frozen tensor's weights, slots and EMA are never read or
         written and its gradient is in neither the norm nor the finite check; the trust ratios apply_lars / apply_lamb return
         are [len(tuned_segments)], in that order.  Without arguments: cleared, every method makes the launches it always made.
-        The forward and backward passes are not changed: frozen tensors' gradients are still computed, BatchNorm in frozen
-        layers still uses batch statistics and updates its moving statistics."""
-        from .finetune import lr_scales
+        By itself this does not change the forward and backward passes: frozen tensors' gradients are still computed, BatchNorm
+        in frozen layers still uses batch statistics and updates its moving statistics.
+        freeze_eval (SOLVER.FREEZE_EVAL): the passes are cut for the frozen PREFIX, `frozen_prefix` = finetune.frozen_prefix --
+        the stem and the blocks behind it as far as every trainable tensor is frozen.  Training plans recorded from now on run
+        those units as training=False runs them (moving statistics, not updated; never dropped by NETWORK.DROP_PATH_RATE;
+        nothing kept) and end their backward list at the first unit above them: the prefix tensors' slices of `flat_grads`
+        stay at the zero forward_backward writes.  Frozen tensors outside the prefix behave as described above.  ValueError
+        when the stem is not fully frozen (an empty prefix), naming the first tensor that breaks the run."""
+        from .finetune import _prefix_break, lr_scales
         st = FinetuneSettings(float(layer_decay), tuple((str(p), float(f)) for p, f in lr_mult), tuple(freeze))
         if not 0.0 < st.layer_decay <= 1.0 or not all(f > 0.0 and f < float("inf") for _, f in st.lr_mult):
             raise ValueError(f"set_finetune: layer_decay must lie in (0, 1] and every factor must be finite and > 0, not "
                              f"{layer_decay}, {list(lr_mult)}")
         if st == FinetuneSettings(1.0, (), ()):
-            self._ft = None
+            if freeze_eval:
+                raise ValueError("set_finetune: freeze_eval needs a `freeze` list that freezes the stem (conv1/) at least")
+            self._ft, self.frozen_prefix = None, 0
             self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
             return
         tuned, scales, frozen = lr_scales(self.arch, [self.specs[n] for n in self.param_order], st)
         if not set(tuned) <= set(self.segments):
             raise RuntimeError("finetune.flat_segments and the model's parameter layout disagree")
+        k = 0
+        if freeze_eval:
+            k, broke = _prefix_break(self.arch, [self.specs[n] for n in self.param_order], frozen)
+            if k == 0:
+                raise ValueError(f"set_finetune: freeze_eval needs a frozen prefix, but {broke} (the stem) is not frozen by "
+                                 f"{list(st.freeze)}: nothing would run in inference form")
         ft = types.SimpleNamespace()
         ft.table = SegTable(tuned)
         if not self.dry:
@@ -774,7 +791,7 @@ class X3D:
             ft.scale = torch.tensor(scales, dtype=torch.float32).to(self.device)
             ft.partials = torch.empty(2 * ft.table.nchunk, dtype=torch.float64, device=self.device)
             ft.trust_ratios = torch.ones(ft.table.nseg, dtype=torch.float32, device=self.device)
-        self._ft = ft
+        self._ft, self.frozen_prefix = ft, k
         self.tuned_segments, self.lr_scales, self.frozen_names = tuned, {s.name: c for s, c in zip(tuned, scales)}, frozen
 
     def grads_finite(self) -> bool:
@@ -805,6 +822,22 @@ class X3D:
 
     def moving_stats_flat(self):
         return self.flat_params[self.n_trainable_flat:]
+
+    def trained_moving_stats_flat(self):
+        """`moving_stats_flat()` without the statistics of a frozen prefix in inference form, which no training step writes:
+        what data-parallel training averages over the ranks (x + x + x over three ranks, divided by three, need not give x
+        back; the prefix is to stay bit-identical).  The moving statistics lie in network order, so the prefix's are the
+        head of the block; without a prefix this is the whole block."""
+        if not self.frozen_prefix:
+            return self.moving_stats_flat()
+        from .finetune import depth_groups
+        group, _ = depth_groups(self.arch)
+        stats = [k for k in self.param_order if not self.specs[k].trainable]
+        cut = next((i for i, k in enumerate(stats) if group(k) >= self.frozen_prefix), len(stats))
+        if any(group(k) < self.frozen_prefix for k in stats[cut:]):
+            raise RuntimeError("the moving statistics are not laid out in network order")
+        lo = self._offsets[stats[cut]] if cut < len(stats) else self.flat_params.numel()
+        return self.flat_params[lo:]
 
     def precise_bn_layout(self):
         """Where precise BatchNorm (precise_bn.update_bn_stats) keeps and writes each layer's statistics: a PreciseBNLayout of

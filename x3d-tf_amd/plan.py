@@ -5,6 +5,9 @@ the backward list (``record_backward``) -- as pre-bound C calls; ``_Plan.run`` r
 network has one block shape, so the recorders are straight-line code: stem, one block (repeated), head.  The inference
 recorder and the training recorder share what is the same launch in both (stem, shortcut conv, SE, dense head) and keep
 apart what is not (the `a` conv with the deferred residual tail against the `c` conv with the tail in its epilogue).
+A CUT training plan (``record_training(..., frozen_prefix=k)``, SOLVER.FREEZE_EVAL) holds both forms: the frozen prefix -- the
+stem and the first k - 1 blocks -- as the inference recorder records it, everything above as the training recorder does, and
+a backward list that ends at the seam between the two (``record_backward(..., first_unit=k)``).
 
 fp64 accumulators are zeroed once per step in ONE flat buffer that exists only after recording, so a launch that takes the
 address of one records a deferred address instead (``_Plan.acc`` for a positional argument, ``_Plan.defer`` for struct
@@ -194,9 +197,17 @@ _Acc = collections.namedtuple("_Acc", "handle")
 class _Plan:
     """Buffers + recorded launches for one (N, T, H, W, training) configuration."""
 
-    def __init__(self, model, n, t, h, w, training):
+    def __init__(self, model, n, t, h, w, training, frozen_prefix=0):
         self.model = model
         self.n, self.t, self.h, self.w, self.training = n, t, h, w, bool(training)
+        # a cut training plan (SOLVER.FREEZE_EVAL): units u0..u(frozen_prefix - 1) -- the stem, then blocks -- are recorded in
+        # inference form, and the backward list ends at the seam, the first unit above them.  bn_eval: the form `bn` gives
+        # the NEXT layer it registers (the recorder flips it at the seam); prefix_bn: the layers registered in inference form
+        self.frozen_prefix = int(frozen_prefix) if training else 0
+        self.bn_eval = (not self.training) or self.frozen_prefix > 0
+        self.prefix_bn: List[str] = []
+        self.seam = None               # the output of the last prefix unit: a buffer of its own, read again by the backward pass
+        self.prefix_bufs: List = []    # the ping-pong / scratch buffers the prefix units share (nothing of them outlives the prefix)
         self.fwd: List = []
         self.bwd: List = []
         self.keep: List = []           # ctypes structs / tensors that must outlive the recording
@@ -248,10 +259,12 @@ class _Plan:
         return buf
 
     def bn(self, prefix, c):
-        """Buffers of a BatchNorm layer.  Inference: its coefficients come from the moving statistics, every layer's in ONE
-        launch at the head of the forward list (x3d_bn_eval_coef_batched over bn_eval_items)."""
+        """Buffers of a BatchNorm layer, in the form `bn_eval` names for it.  Inference form (every layer of an inference plan,
+        the frozen prefix of a cut training plan): its coefficients come from the moving statistics, every such layer's in
+        ONE launch at the head of the forward list (x3d_bn_eval_coef_batched over bn_eval_items); it keeps no statistics and
+        is not in bn_layers."""
         b = BNBuf(prefix, c, self.f32(c, 2), self.f32(c, 2))
-        if self.training:
+        if not self.bn_eval:
             # forward statistics: the library's replicated layout (x3d_stats_replicas copies, x3d_stats_stride apart)
             b.stats = self.acc64(self.model._stats_r * int(self.lib.x3d_stats_stride(c)))
             b.bsums = self.acc64(c, 2)
@@ -259,6 +272,8 @@ class _Plan:
             self.bn_layers.append(b)
         else:
             p = self.model.params
+            if self.training:
+                self.prefix_bn.append(prefix)
             self.bn_eval_items.append(hip.BnEvalItem(_p(p[f"{prefix}/gamma"]), _p(p[f"{prefix}/beta"]),
                                                      _p(p[f"{prefix}/moving_mean"]), _p(p[f"{prefix}/moving_variance"]),
                                                      _p(b.ss), _p(b.mi), c))
@@ -326,11 +341,19 @@ class _Plan:
             if b.prefix in by_prefix:
                 raise ValueError(f"precise_bn_table: BatchNorm layer {b.prefix} registered twice")
             by_prefix[b.prefix] = b
-        if sorted(by_prefix) != sorted(lay.prefixes):
-            odd = sorted(set(by_prefix) ^ set(lay.prefixes))
+        # (a cut plan: rows for the layers of the trained region only -- the prefix keeps no statistics and its moving
+        # statistics are not to be touched.  Row r's count slot is pooled[r], r < len(rows) <= layers, and every layer's sums
+        # lie at its layout offset >= layers: slots and sums cannot overlap, whichever subset a plan has)
+        want_layers = [q for q in lay.prefixes if q not in set(self.prefix_bn)]
+        if sorted(by_prefix) != sorted(want_layers) or len(want_layers) + len(self.prefix_bn) != len(lay.prefixes):
+            odd = sorted(set(by_prefix) ^ set(want_layers))
             raise ValueError(f"precise_bn_table: the plan's BatchNorm layers are not the model's: {odd}")
+        if not want_layers or min(lay.pooled_offsets) < len(lay.prefixes):
+            raise ValueError("precise_bn_table: no BatchNorm layer to recompute, or pooled sums that overlap the count slots")
         rows = []
         for l, prefix in enumerate(lay.prefixes):
+            if prefix not in by_prefix:
+                continue
             b = by_prefix[prefix]
             if b.stats is None or b.count is None:
                 raise ValueError(f"precise_bn_table: {prefix} has no {'stats' if b.stats is None else 'count'}")
@@ -416,15 +439,15 @@ def _geometry(arch, h, w):
 def _bind_stem_input(model, pl, dt):
     """Where the stem reads the batch from, and whether it runs as x3d_stem_fwd / x3d_stem_bwd (one launch each way): that
     needs the in-place channels-last input (pl.x_cl) and a shape the fused kernels take (x3d_stem_fused_supported: bit 0
-    forward, bit 1 backward -- a plan with a backward pass needs both, since the fused forward stores no conv_s output);
-    the two-kernel path otherwise."""
+    forward, bit 1 backward -- a plan whose backward pass reaches the stem needs both, since the fused forward stores no
+    conv_s output; a cut training plan's does not); the two-kernel path otherwise."""
     a, n, t, h, w = model.arch, pl.n, pl.t, pl.h, pl.w
     # 16-bit storage: the stem's matrix-core kernels read the caller's channels-last batch in place (x3d_hip.h K1)
     pl.x_cl = bool(pl.lib.x3d_stem_s_nthwc_supported(model.in_channels, w, a.c1, dt)) and model.opt["stem_nthwc"]
     pl.x = None if pl.x_cl else pl.act(n, model.in_channels, t, h, w)
     pl.stem_fused = False
     if pl.x_cl and model.opt["stem_fused"]:
-        need = 3 if pl.training else 1
+        need = 3 if pl.training and pl.frozen_prefix == 0 else 1
         have = pl.lib.x3d_stem_fused_supported(model.in_channels, a.c1, a.c1_temp_filter, n, t, h, w, dt, 1)
         pl.stem_fused = (have & need) == need
 
@@ -620,31 +643,34 @@ def _rec_infer_block(model, pl, B, dt):
 _Tail = collections.namedtuple("_Tail", "c_raw c_ss shortcut r_ss y cout p_out keep", defaults=(None,))
 
 
-def record_training(model, n, t, h, w) -> _Plan:
+def record_training(model, n, t, h, w, frozen_prefix=0) -> _Plan:
     """Forward list up to the loss, then the backward list.  Per block: a (raw + BN_a statistics) -> finalize -> b (BN_a + ReLU
     on load, BN_b statistics + SE squeeze in the epilogue) -> finalize -> [SE MLP] -> c (BN_b * gate -> swish on load) ->
-    finalize -> [shortcut conv -> finalize]; the residual tail is left to the first reader of the block output."""
+    finalize -> [shortcut conv -> finalize]; the residual tail is left to the first reader of the block output.
+
+    frozen_prefix = k > 0 (SOLVER.FREEZE_EVAL, finetune.frozen_prefix): a CUT plan.  Units u0..u(k-1) -- the stem, then the
+    first k - 1 blocks -- are recorded with the inference recorder's launches (_rec_frozen_prefix); the first trained unit
+    (block k - 1, or conv5 for k = blocks + 1) reads their output, the seam tensor, as a materialised, activated input;
+    everything above is recorded as always, and the backward list ends at that unit (record_backward first_unit = k)."""
     a = model.arch
-    pl = _Plan(model, n, t, h, w, True)
+    k = int(frozen_prefix)
+    if not 0 <= k <= len(a.blocks) + 1:
+        raise ValueError(f"frozen_prefix must lie in [0, {len(a.blocks) + 1}] (the stem and {len(a.blocks)} blocks), "
+                         f"not {frozen_prefix!r}")
+    pl = _Plan(model, n, t, h, w, True, k)
     dt = hip.dtype_code(model.dtype)
     F = pl.fwd
     # ---- input + stem --------------------------------------------------------------------
     _bind_stem_input(model, pl, dt)
     h1, w1, geo = _geometry(a, h, w)
-    # conv_s -> conv_t as one launch each way where the fused kernels take the shape: the conv_s output (616 MB at the
-    # headline's size) and its gradient never exist in HBM (reference model.py:202-206: nothing between the two convs)
-    pl.s_raw = None if pl.stem_fused else pl.act(n, a.c1, t, h1, w1)
-    pl.t_raw = pl.act(n, a.c1, t, h1, w1)
-    pl.y0 = pl.act(n, a.c1, t, h1, w1)
-    pl.bn1 = pl.bn("conv1/bn", a.c1)
-    _rec_stem(model, pl, pl.t_raw, pl.bn1.stats, None, ACT_NONE, dt)
-    _rec_bn_finalize(model, pl, pl.bn1, n * t * h1 * w1)
+    if k:
+        x_cur, tail = _rec_frozen_prefix(model, pl, k, h1, w1, geo, dt), None
+    else:
+        x_cur, tail = _rec_train_stem(model, pl, h1, w1, dt)
     # ---- residual stages -------------------------------------------------------------------
     # The residual tail of a block (y = relu(bn_c(c) + shortcut), reference model.py:381-392) is DEFERRED to the first
     # reader of y: the next block's `a` conv (or conv5) builds y on load and stores it (x3d_pw_fwd in_add / in_store) where
     # that form exists and does not cost the layer its weights-stationary kernel; otherwise x3d_tail_fwd runs first.
-    tail = _Tail(pl.t_raw, pl.bn1.ss, None, None, pl.y0, a.c1, t * h1 * w1)     # the stem's BatchNorm + ReLU (no Add)
-    x_cur = pl.y0
     # Stochastic depth (NETWORK.DROP_PATH_RATE): blocks with a rate > 0 scale bn_c's output by keep[l][n] -- 0, or 1 / (1 - rate_l)
     # -- in their residual tail.  The table [blocks][N] is drawn anew on the device before every replay (x3d_drop_path_draw,
     # model._draw_drop_path), so the lists themselves never change.  With every rate 0 nothing below differs from before.
@@ -654,6 +680,8 @@ def record_training(model, n, t, h, w) -> _Plan:
         if not model.dry:
             pl.dp_keep.fill_(1.0)
     for (l, b), (hh, ww, ho, wo) in zip(enumerate(a.blocks), geo):
+        if l + 1 < k:          # a block of the frozen prefix: recorded above, never dropped
+            continue
         B = Block(b, x_cur, hh, ww, ho, wo)
         if rates[l] > 0.0:
             B.dp_keep = pl.dp_keep.data_ptr() + 4 * n * l
@@ -664,7 +692,9 @@ def record_training(model, n, t, h, w) -> _Plan:
     hh, ww = geo[-1][2], geo[-1][3]
     pl.c5_raw = pl.act(n, a.conv5_out, t, hh, ww)
     pl.bn5 = pl.bn("conv5/layer_with_weights-1", a.conv5_out)
-    pl.s5 = _fold_pending_tail(model, pl, _conv5_args(model, pl, x_cur, hh, ww, dt), tail, dt)
+    pl.s5 = _conv5_args(model, pl, x_cur, hh, ww, dt)
+    if tail is not None:       # (None: conv5 reads the seam tensor of a cut plan)
+        pl.s5 = _fold_pending_tail(model, pl, pl.s5, tail, dt)
     pl.defer(pl.s5, stats=pl.bn5.stats)
     pl.rec(F, "x3d_pw_fwd", pl.s5)
     _rec_bn_finalize(model, pl, pl.bn5, n * pl.P5)
@@ -682,10 +712,71 @@ def record_training(model, n, t, h, w) -> _Plan:
         pl.targets = None                  # soft targets: allocated by the first call that brings some (use_soft_targets)
         pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
                a.num_classes)
-    pl.install_backward(record_backward(model, pl, model.opt))
+    pl.install_backward(record_backward(model, pl, model.opt, first_unit=k))
+    if k:
+        items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
+        pl.bn_eval_table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(model.device)
+        F[0] = ("x3d_bn_eval_coef_batched", pl.lib.x3d_bn_eval_coef_batched,
+                (pl.bn_eval_table.data_ptr(), len(pl.bn_eval_items), float(a.bn_eps)))
     pl.zero_buf = pl.carve()
     pl.resolve()
     return pl
+
+
+def _rec_train_stem(model, pl, h1, w1, dt):
+    """The stem in training form; returns (its output buffer, its pending BatchNorm + ReLU as a _Tail)."""
+    a, n, t = model.arch, pl.n, pl.t
+    # conv_s -> conv_t as one launch each way where the fused kernels take the shape: the conv_s output (616 MB at the
+    # headline's size) and its gradient never exist in HBM (reference model.py:202-206: nothing between the two convs)
+    pl.s_raw = None if pl.stem_fused else pl.act(n, a.c1, t, h1, w1)
+    pl.t_raw = pl.act(n, a.c1, t, h1, w1)
+    pl.y0 = pl.act(n, a.c1, t, h1, w1)
+    pl.bn1 = pl.bn("conv1/bn", a.c1)
+    _rec_stem(model, pl, pl.t_raw, pl.bn1.stats, None, ACT_NONE, dt)
+    _rec_bn_finalize(model, pl, pl.bn1, n * t * h1 * w1)
+    return pl.y0, _Tail(pl.t_raw, pl.bn1.ss, None, None, pl.y0, a.c1, t * h1 * w1)     # the stem's BatchNorm + ReLU (no Add)
+
+
+def _rec_frozen_prefix(model, pl, k, h1, w1, geo, dt):
+    """The frozen prefix of a cut training plan, units u0..u(k-1), as record_inference records them: the stem with BN + ReLU in
+    its epilogue, blocks through _rec_infer_block, every BatchNorm a per-channel affine from the moving statistics (one
+    x3d_bn_eval_coef_batched at slot 0 of the list, over these layers only: record_training fills it in), no statistics, no
+    c_raw, no residual-tail pass.  Unit outputs ping-pong between two buffers and the a / b / shortcut scratch is shared,
+    all sized for the prefix's largest user -- except the output of the LAST prefix unit, the seam tensor: the weight-gradient
+    launches of the first trained unit read it again during the backward pass, so it has a buffer of its own (pl.seam) that
+    nothing later writes.  Returns it, shaped."""
+    a, n, t, F = model.arch, pl.n, pl.t, pl.fwd
+    assert pl.bn_eval and not F
+    F.append(None)   # slot 0: x3d_bn_eval_coef_batched over the prefix layers
+    units = list(zip(a.blocks, geo))[:k - 1]
+    outs = [(a.c1, h1, w1)] + [(b.cout, g[2], g[3]) for b, g in units]          # (channels, h, w) of every prefix unit's output
+    pl.seam = pl.act(n, outs[-1][0], t, outs[-1][1], outs[-1][2])
+    numel_y = max([0] + [n * c * t * hh * ww for c, hh, ww in outs[:-1]])
+    ybuf = [pl.act(numel_y) for _ in range(min(len(outs) - 1, 2))]
+    numel_a = max([0 if pl.stem_fused else n * a.c1 * t * h1 * w1] + [n * b.inner * t * g[0] * g[1] for b, g in units])
+    numel_b = max([0] + [n * b.inner * t * g[2] * g[3] for b, g in units])
+    numel_r = max([0] + [n * b.cout * t * g[2] * g[3] for b, g in units if b.has_shortcut_conv])
+    abuf, bbuf, rbuf = (pl.act(m) if m else None for m in (numel_a, numel_b, numel_r))
+    pl.prefix_bufs = ybuf + [buf for buf in (abuf, bbuf, rbuf) if buf is not None]
+
+    def out_view(i):
+        c, hh, ww = outs[i]
+        return pl.seam if i == len(outs) - 1 else _view(ybuf[i % 2], n, c, t, hh, ww)
+
+    pl.t_raw = None      # (the stem's raw output is never stored: BN + ReLU in the epilogue)
+    pl.y0 = out_view(0)
+    pl.bn1 = pl.bn("conv1/bn", a.c1)
+    pl.s_raw = None if pl.stem_fused else _view(abuf, n, a.c1, t, h1, w1)   # conv_s output: dead once conv_t has run
+    _rec_stem(model, pl, pl.y0, None, pl.bn1.ss, ACT_RELU, dt)
+    x_cur = pl.y0
+    for i, (b, (hh, ww, ho, wo)) in enumerate(units):
+        B = Block(b, x_cur, hh, ww, ho, wo, a_raw=_view(abuf, n, b.inner, t, hh, ww), b_raw=_view(bbuf, n, b.inner, t, ho, wo),
+                  y=out_view(i + 1), r_raw=_view(rbuf, n, b.cout, t, ho, wo) if b.has_shortcut_conv else None)
+        _rec_infer_block(model, pl, B, dt)
+        pl.blocks.append(B)
+        x_cur = B.y
+    pl.bn_eval = False   # the seam: every layer registered from here on keeps batch statistics
+    return x_cur
 
 
 def _rec_bn_finalize(model, pl, b: BNBuf, count):
@@ -722,7 +813,8 @@ def _fold_pending_tail(model, pl, st, tl: _Tail, dt):
 
 
 def _rec_train_block(model, pl, B, tail: _Tail, dt) -> _Tail:
-    """Allocates and records one block; `tail`: the pending tail of the block below (or the stem).  Returns this block's."""
+    """Allocates and records one block; `tail`: the pending tail of the block below (or the stem), None where the block input
+    is already materialised and activated (the seam tensor of a cut plan).  Returns this block's."""
     b, p, F, n, t = B.spec, model.params, pl.fwd, pl.n, pl.t
     q = f"{block_prefix(b)}/bottleneck"
     P_in, P_out = t * B.hh * B.ww, t * B.ho * B.wo
@@ -736,7 +828,9 @@ def _rec_train_block(model, pl, B, tail: _Tail, dt) -> _Tail:
     B.hidden = pl.f32(n, b.se_width) if b.has_se else None
     # a: 1x1x1 on the block input -- materialised and already activated, or (16-bit storage, resident-panel kernel) built
     # on load from the raw `c` output + shortcut of the block below, whose residual tail is then not a pass of its own
-    B.sa = _fold_pending_tail(model, pl, _a_conv_args(model, pl, B, dt), tail, dt)
+    B.sa = _a_conv_args(model, pl, B, dt)
+    if tail is not None:       # (None: the block reads the seam tensor of a cut plan)
+        B.sa = _fold_pending_tail(model, pl, B.sa, tail, dt)
     pl.defer(B.sa, stats=B.bn_a.stats)
     pl.rec(F, "x3d_pw_fwd", B.sa)
     # b: channelwise 3x3x3, BN_a + ReLU folded into the load, BN_b statistics + SE squeeze in the epilogue
@@ -779,36 +873,57 @@ class _BwdState:
     slab_bufs: Dict = field(default_factory=dict)
 
 
-def record_backward(model, pl: _Plan, opt: dict) -> Backward:
+def record_backward(model, pl: _Plan, opt: dict, first_unit: int = 0) -> Backward:
     """Records the backward pass over the forward state of `pl` under the plan options `opt` and returns it; the plan and
-    its blocks are read, never written (new buffers and accumulators are allocated from the plan)."""
+    its blocks are read, never written (new buffers and accumulators are allocated from the plan).
+
+    first_unit = k > 0: the list ends at the SEAM, unit k (units: 0 the stem, 1..L the blocks, L + 1 conv5 and the head) -- the
+    first unit above a frozen prefix u0..u(k-1), though the plan need not be a cut one.  The seam unit's convs that read the
+    seam tensor -- a block's `a` and shortcut conv, or conv5 -- record their BatchNorm-backward finalize and x3d_pw_wgrad
+    only: nobody below wants a data gradient, so there is no x3d_pw_dgrad, no fused x3d_pw_bwd and no write to gbuf / rtmp
+    for them.  Nothing below the seam is recorded: no tail backward of the unit below, no stem backward; nothing is left
+    pending.  stage_marks keeps every key: the seam's stage, the stages wholly below it and the stem get len(launches)."""
     n, t, a = pl.n, pl.t, model.arch
+    k, L = int(first_unit), len(pl.blocks)
+    if not 0 <= k <= L + 1 or k < pl.frozen_prefix:
+        raise ValueError(f"record_backward: first_unit must lie in [{pl.frozen_prefix}, {L + 1}], not {first_unit!r}")
     out = Backward()
+    live = pl.blocks[max(k - 1, 0):]          # the blocks this list walks
     # scratch shared by all blocks (sized for the largest user)
-    max_out = max([pl.y0.numel()] + [B.y.numel() for B in pl.blocks])
-    max_inner_out = max(B.b_raw.numel() for B in pl.blocks)
-    max_inner_in = max(B.a_raw.numel() for B in pl.blocks)
-    max_r = max([1] + [n * B.spec.cin * t * B.ho * B.wo for B in pl.blocks if B.spec.has_shortcut_conv])
-    max_nc = max(n * B.spec.inner for B in pl.blocks)
+    max_out = max(([pl.y0.numel()] if k == 0 else [1]) + [B.y.numel() for B in live])
+    max_inner_out = max([1] + [B.b_raw.numel() for B in live])
+    max_inner_in = max([1] + [B.a_raw.numel() for B in live])
+    max_r = max([1] + [n * B.spec.cin * t * B.ho * B.wo for B in live[1 if k else 0:] if B.spec.has_shortcut_conv])
+    max_nc = max([1] + [n * B.spec.inner for B in live])
     out.gbuf = [pl.act(max_out), pl.act(max_out)]
     out.dv = pl.act(max_inner_out)
     out.ga = pl.act(max_inner_in)
     out.rtmp = pl.act(max_r)
-    max_dp = max([0] + [B.y.numel() for B in pl.blocks if B.dp_keep is not None])
+    max_dp = max([0] + [B.y.numel() for B in live if B.dp_keep is not None])
     out.gbr = pl.act(max_dp) if max_dp else None
     out.coef_nc = pl.f32(max_nc * 4)
-    out.se_scratch = pl.f32(max([1] + [n * (2 * B.spec.inner + B.spec.se_width) for B in pl.blocks if B.spec.has_se]))
+    out.se_scratch = pl.f32(max([1] + [n * (2 * B.spec.inner + B.spec.se_width) for B in live if B.spec.has_se]))
     out.g5 = pl.act(*pl.c5_raw.shape)
     out.dh1 = pl.f32(n, a.fc1_out)
     out.dpooled = pl.f32(n, a.conv5_out)
-    out.ds = None if pl.stem_fused else pl.act(*pl.s_raw.shape)
+    out.ds = None if pl.stem_fused or k else pl.act(*pl.s_raw.shape)
     out.blocks = [BlockBackward() for _ in pl.blocks]
     s = _BwdState(out, opt, hip.dtype_code(model.dtype))
-    _bwd_head(model, pl, s)
+    _bwd_head(model, pl, s, seam=k == L + 1)
     # ---- residual blocks, last to first ----------------------------------------------------
-    for bi in range(len(pl.blocks) - 1, -1, -1):
-        _bwd_block(model, pl, s, bi)
-    _bwd_stem(model, pl, s)
+    for bi in range(L - 1, max(k - 1, 0) - 1, -1):
+        _bwd_block(model, pl, s, bi, seam=bi == k - 1)
+    if k == 0:
+        _bwd_stem(model, pl, s)
+        return out
+    # the seam: nothing may wait for a launch that never comes (a slab for a "next block", a dW riding on a later finalize)
+    assert s.pending_fin is None and s.pending_mark is None and s.pending_reduce is None
+    # the seam's stage is final behind the seam's last launch (also where the seam block is not the first of its stage), and
+    # so -- trivially: their gradients stay at the step's zeros -- are the stages wholly inside the prefix and the stem.  The
+    # keys are set in backward order, which forward_backward's stable sort keeps: the hooks fire once per bucket, as always
+    seam_stage = pl.blocks[k - 1].spec.stage if k <= L else len(a.stages)
+    for st in list(range(min(seam_stage, len(a.stages) - 1), -1, -1)) + [-1]:
+        out.stage_marks.setdefault(st, len(out.launches))
     return out
 
 
@@ -883,7 +998,8 @@ def _dw_slab_job(pl, s, st, role, dw):
     return hip.DwReduceJob(_p(buf), _p(dw), parts, elems)
 
 
-def _bwd_head(model, pl, s):
+def _bwd_head(model, pl, s, seam=False):
+    """seam: conv5 is the seam unit -- its weight gradient only, behind a plain finalize launch"""
     a, p, g, n, t, dt = model.arch, model.params, model.grads, pl.n, pl.t, s.dt
     out, Bk, c5, b5 = s.out, s.out.launches, model.arch.conv5_out, pl.bn5
     pl.rec(Bk, "x3d_dense_bwd", pl.dlogits, None, ACT_NONE, pl.h1, pl.drop_mask, float(pl.drop_scale),
@@ -899,14 +1015,20 @@ def _bwd_head(model, pl, s):
     d5 = hip.PwDgradArgs(_p(out.g5), _p(pl.c5_raw), _p(b5.coef), _p(p["conv5/layer_with_weights-0/kernel"]),
                          _p(s.dy), EPI_STORE, None, None, None, None, None, n, c_last, c5, t, pl.h5, pl.w5, dt)
     d5.w_panel = model._wp("conv5/layer_with_weights-0/kernel", True)
-    _rec_bn_bwd_finalize(model, pl, s, b5, n * pl.P5, c5, consumers=[(w5, "wgrad"), (d5, "dgrad")])
-    pl.rec(Bk, "x3d_pw_wgrad", w5)
-    pl.rec(Bk, "x3d_pw_dgrad", d5)
+    if seam:
+        s.dy = None
+        _rec_bn_bwd_finalize(model, pl, s, b5, n * pl.P5, c5)
+        pl.rec(Bk, "x3d_pw_wgrad", w5)
+    else:
+        _rec_bn_bwd_finalize(model, pl, s, b5, n * pl.P5, c5, consumers=[(w5, "wgrad"), (d5, "dgrad")])
+        pl.rec(Bk, "x3d_pw_wgrad", w5)
+        pl.rec(Bk, "x3d_pw_dgrad", d5)
     out.stage_marks[len(a.stages)] = len(Bk)   # head finished
 
 
-def _bwd_block(model, pl, s, bi):
-    """One block: [tail] -> c -> SE / BN_b -> depthwise b -> [shortcut conv] -> a, which stores the gradient of the block input."""
+def _bwd_block(model, pl, s, bi, seam=False):
+    """One block: [tail] -> c -> SE / BN_b -> depthwise b -> [shortcut conv] -> a, which stores the gradient of the block input.
+    seam: the list ends with this block -- the shortcut conv and `a` record their weight gradients only (_bwd_seam_wgrads)."""
     B, R, Bk = pl.blocks[bi], s.out.blocks[bi], s.out.launches
     b = B.spec
     R.bwd_start, R.dy_view = len(Bk), s.dy.view(B.y.shape)
@@ -932,6 +1054,10 @@ def _bwd_block(model, pl, s, bi):
     _bwd_dw(model, pl, s, B, R, dvv, gaa)
     # (bn_a's backward finalize is recorded in _bwd_a, right in front of the `a` backward: whether it also builds that launch's
     # panel is known there; the shortcut launches in between do not depend on it)
+    if seam:
+        _bwd_seam_wgrads(model, pl, s, B, gaa)
+        R.bwd_stop, s.dy = len(Bk), None
+        return
     nxt = s.out.gbuf[1 - s.cur][:B.x.numel()]
     rt = _bwd_shortcut(model, pl, s, B, R) if b.has_shortcut_conv else None
     _bwd_a(model, pl, s, bi, gaa, nxt, rt)
@@ -950,6 +1076,26 @@ def _bwd_block(model, pl, s, bi):
             s.pending_mark = b.stage       # the mark is set there (_rec_bn_bwd_finalize)
         else:
             s.out.stage_marks[b.stage] = len(Bk)   # every gradient of stages >= b.stage is final
+
+
+def _bwd_seam_wgrads(model, pl, s, B, gaa):
+    """The two convs of the seam block that read the seam tensor B.x: the shortcut conv (on B.xs where the forward pass made
+    the even-pixel copy) and `a`.  Each: the plain BatchNorm-backward finalize and x3d_pw_wgrad.  The weight gradients are
+    flushed by the launches themselves (no slab: no later x3d_se_bnb_bwd would add it up) and nothing rides on a later finalize."""
+    b, g, n, t, dt, Bk = B.spec, model.grads, pl.n, pl.t, s.dt, s.out.launches
+    pre = block_prefix(b)
+    q = f"{pre}/bottleneck"
+    assert s.pending_fin is None          # (taken by bn_c's finalize of this block at the latest)
+    if b.has_shortcut_conv:
+        x_r, geom = (B.xs, (B.ho, B.wo, 1)) if B.xs is not None else (B.x, (B.hh, B.ww, b.stride))
+        wr = hip.PwWgradArgs(_p(s.dy), _p(B.r_raw), _p(B.bn_r.coef), _p(x_r), None, None, ACT_NONE,
+                             _p(g[f"{pre}/residual/kernel"]), n, b.cin, b.cout, t, *geom, dt)
+        _rec_bn_bwd_finalize(model, pl, s, B.bn_r, n * t * B.ho * B.wo, b.cout)
+        pl.rec(Bk, "x3d_pw_wgrad", wr)
+    wa = hip.PwWgradArgs(_p(gaa), _p(B.a_raw), _p(B.bn_a.coef), _p(B.x), None, None, ACT_NONE,
+                         _p(g[f"{q}/a/kernel"]), n, b.cin, b.inner, t, B.hh, B.ww, 1, dt)
+    _rec_bn_bwd_finalize(model, pl, s, B.bn_a, n * t * B.hh * B.ww, b.inner)
+    pl.rec(Bk, "x3d_pw_wgrad", wa)
 
 
 def _bwd_c(model, pl, s, B, R, dvv):

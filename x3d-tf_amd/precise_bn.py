@@ -31,11 +31,16 @@ def update_bn_stats(model, batches, num_batches, group=None) -> int:
     overwrites every element.  The stochastic-depth state (seed, step) is copied on the device before the passes and copied
     back after them, so the training random stream does not depend on whether this ran.  Launches and device copies only: no
     host synchronisation.  `batches` is not closed: it may be the training iterator.  ValueError for num_batches < 1 and for
-    no batch at all."""
+    no batch at all.
+
+    A model with a frozen prefix in inference form (X3D.set_finetune freeze_eval): its training plans keep no statistics for
+    the prefix layers, and their tables have rows for the layers of the trained region only -- the same rows on every plan and
+    every rank, since the prefix is the model's, so the two launches and the all-reduce see one subset.  The prefix's moving
+    statistics are neither read nor written."""
     if isinstance(num_batches, bool) or not isinstance(num_batches, int) or num_batches < 1:
         raise ValueError(f"num_batches must be an integer >= 1, not {num_batches!r}")
     lay = model.precise_bn_layout()
-    nlayers = len(lay.prefixes)
+    nlayers = None                            # rows of the plans' tables: the model's layers, less a frozen prefix in inference form
     pooled = torch.zeros(lay.pooled_size, dtype=torch.float64, device=model.device)
     dp_state = model._dp_state.clone() if getattr(model, "_dp_state", None) is not None else None
     used = 0
@@ -46,6 +51,9 @@ def update_bn_stats(model, batches, num_batches, group=None) -> int:
             model(clips, training=True)
             n, t, h, w, _ = clips.shape
             table = model._plan(n, t, h, w, True).precise_bn_table()
+            if nlayers is not None and table.shape[0] != nlayers:
+                raise ValueError("update_bn_stats: the model's frozen prefix changed between batches")
+            nlayers = int(table.shape[0])
             hip.call("x3d_precise_bn_accum", table.data_ptr(), nlayers, pooled.data_ptr())
             used += 1
     finally:

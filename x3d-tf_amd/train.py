@@ -12,7 +12,7 @@ import torch
 
 from . import dist as xdist
 from . import ops
-from .config import (OPTIMIZERS, distill_settings, finetune_settings, mix_settings, optim_settings, precise_bn_settings,
+from .config import (OPTIMIZERS, distill_settings, finetune_settings, freeze_eval_settings, mix_settings, optim_settings, precise_bn_settings,
                      solver_settings)
 from .mix import NO_MIX, draw_mix_params
 from .solver import RULES
@@ -152,9 +152,13 @@ class Trainer:
         self.last_grad_norm = None            # device scalar: global L2 norm of the unscaled gradient of the last update
         # fine-tuning (SOLVER.FREEZE / LR_MULT / LAYER_DECAY; off by default: the model is then not told anything).  The update,
         # the clip norm and the finite check then cover the tuned tensors only, at lr * scale per tensor (X3D.set_finetune)
+        # SOLVER.FREEZE_EVAL: the frozen prefix also runs in inference form and the backward pass ends above it.  The buckets
+        # and the hooks are what they were -- the prefix's buckets carry the zeros the step starts from
         self.finetune = finetune_settings(cfg)
-        if self.finetune != (1.0, (), ()):
-            model.set_finetune(freeze=self.finetune.freeze, lr_mult=self.finetune.lr_mult, layer_decay=self.finetune.layer_decay)
+        self.freeze_eval = freeze_eval_settings(cfg)
+        if self.finetune != (1.0, (), ()) or self.freeze_eval:
+            model.set_finetune(freeze=self.finetune.freeze, lr_mult=self.finetune.lr_mult, layer_decay=self.finetune.layer_decay,
+                               **(dict(freeze_eval=True) if self.freeze_eval else {}))
         # weight EMA: trainable block + moving statistics, laid out as flat_params; starts from the (broadcast) weights
         self.ema = model.flat_params.clone() if self.solver.ema_decay > 0.0 else None
         # stochastic depth (NETWORK.DROP_PATH_RATE): the tables are drawn on the device from (seed, step); rank r seeds with
@@ -239,7 +243,7 @@ class Trainer:
         if self._stats_work is not None:      # mirrored-variable MEAN aggregation of the BN moving statistics [TF-3p]
             self._stats_work.wait()
             self._stats_work = None
-            self.model.moving_stats_flat().div_(self.world)
+            self.model.trained_moving_stats_flat().div_(self.world)
 
     def _update(self, pl, lr):
         """Finite check (fp16 loss scaling), clip, optimizer, EMA on the all-reduced gradient in `flat_grads`."""
@@ -537,7 +541,8 @@ class Trainer:
         all-reduce overlaps the whole backward pass), else a stage whose gradients are final."""
         if stage == "fwd":
             if self.sync_moving_stats:
-                self._stats_work = torch.distributed.all_reduce(self.model.moving_stats_flat(), group=self.group,
+                # (with SOLVER.FREEZE_EVAL: not the frozen prefix's, which no step writes)
+                self._stats_work = torch.distributed.all_reduce(self.model.trained_moving_stats_flat(), group=self.group,
                                                                 async_op=True)
             return
         i = self._launch_at.get(stage)
