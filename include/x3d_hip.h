@@ -58,7 +58,9 @@ extern "C" {
  *   138 (additions only, no bump) x3d_precise_bn_accum / x3d_precise_bn_final (precise BatchNorm statistics);
  *   138 (additions only, no bump) x3d_seg_grad_sumsq / x3d_sgd_pt / x3d_adam_pt / x3d_lars_pt / x3d_adamw_pt / x3d_lamb_pt
  *       (fine-tuning: frozen tensors and per-tensor learning rates);
- *   138 (additions only, no bump) x3d_softmax_xent_kd / x3d_sigmoid_bce_kd (knowledge distillation). */
+ *   138 (additions only, no bump) x3d_softmax_xent_kd / x3d_sigmoid_bce_kd (knowledge distillation);
+ *   138 (additions only, no bump) x3d_loss_scale_apply / x3d_unscale_sumsq / x3d_seg_unscale_sumsq / x3d_loss_scale_update
+ *       (the fp16 loss scaler on the device). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -832,6 +834,45 @@ int x3d_lamb_pt(float* w, float* m, float* v, const float* g, const int* chunks,
 /* LossScaleOptimizer support (Keras mixed_float16, train.py:99-100): *flag (device int the caller set to 1) is cleared
  * when any of the n values is inf / nan -- the step is then skipped and the loss scale halved. */
 int x3d_all_finite(const float* g, long long n, int* flag, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * The fp16 loss scaler on the device (SOLVER.DEVICE_LOSS_SCALE of the config): Keras' dynamic LossScaleOptimizer
+ * without a host read in the training step.  Added under ABI 138 without a version bump: new symbols only.  Plain vector loads
+ * and stores, no atomics; nothing allocates or synchronises.
+ *
+ * STATE: X3D_LOSS_SCALE_STATE doubles of device memory, 8-byte aligned, the caller's:
+ *     [0] the scale S, a power of two >= 1        [1] 1 / S (kept equal to it by x3d_loss_scale_update)
+ *     [2] consecutive finite steps                [3] skipped steps, total
+ *     [4] applied steps, total                    [5] 1.0 if the last update was skipped, else 0.0
+ *     [6], [7] zero
+ *   The counters are whole numbers held as doubles: exact up to 2^53.
+ *
+ * x3d_loss_scale_apply: x[i] = x[i] * (float)state[0], one fp32 product.  Launched on the head's dlogits, with the head given
+ *     1 / global_batch instead of S / global_batch: the head kernels are linear in that factor and S is a power of two, so the
+ *     backward pass sees the bits it would have seen.
+ * x3d_unscale_sumsq: x3d_grad_sumsq with g[i] = g[i] * (float)state[1] written back in the same pass.  out[0] = the fp64 sum of
+ *     squares of the finite UNSCALED entries, out[1] = the number of non-finite ones (inf and nan stay inf and nan); every
+ *     `norm` above can be this out[2].  The grid, the scratch layout (x3d_grad_sumsq_scratch(n) doubles) and the fixed
+ *     summation order are x3d_grad_sumsq's -- the same walk, instantiated with the product.  Two launches.
+ * x3d_seg_unscale_sumsq: the same over a chunk table, with x3d_seg_grad_sumsq's walk and reduction (partials: 2 * nchunk
+ *     doubles).  Only elements inside the table's chunks are read or written: a frozen tensor's gradient and the padding keep
+ *     their bits and are in neither the sum nor the count.  Two launches.
+ *   Because S is a power of two, wherever no product falls below the smallest normal fp32:
+ *     S = 1:   g keeps its bits and out has the bits of x3d_grad_sumsq / x3d_seg_grad_sumsq over g.
+ *     S = 2^k: g becomes exactly g * 2^-k, and out[0] * S^2 equals, bit for bit, the out[0] of x3d_grad_sumsq /
+ *              x3d_seg_grad_sumsq over the scaled gradient; out[1] is the same count.
+ * x3d_loss_scale_update: one workgroup.  Keras' DynamicLossScale from norm = the out[2] the step's update launches have read:
+ *     norm[1] != 0: S = max(S / 2, 1), [2] = 0, [3] += 1, [5] = 1
+ *     norm[1] == 0: [4] += 1, [2] += 1, [5] = 0; then if [2] >= growth_steps and (float)(2 S) is finite: S = 2 S, [2] = 0
+ *     and [1] = 1 / S.
+ * Refused before any launch (X3D_ERR_INVALID): a null pointer, n <= 0, growth_steps < 1, a float pointer that is not 4-byte or
+ * a double pointer that is not 8-byte aligned, and what x3d_seg_grad_sumsq refuses of a table.
+ * ------------------------------------------------------------------------------------------ */
+#define X3D_LOSS_SCALE_STATE 8
+int x3d_loss_scale_apply(float* x, long long n, const double* state, void* stream);
+int x3d_unscale_sumsq(float* g, long long n, const double* state, double* scratch, double* out, void* stream);
+int x3d_seg_unscale_sumsq(float* g, const int* chunks, int nchunk, const int* segs, int nseg, const double* state,
+                          double* partials, double* out, void* stream);
+int x3d_loss_scale_update(double* state, const double* norm, long long growth_steps, void* stream);
 /* sum of squares of the masked entries (L2 regularisation loss term), out [1] double += */
 int x3d_l2_sumsq(const float* w, const unsigned char* l2_mask, double* out, long long n, void* stream);
 

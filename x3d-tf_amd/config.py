@@ -183,10 +183,11 @@ def get_default_config():
     # factor], ...] on top of it, the longest matching prefix wins; FREEZE: name prefixes of the tensors the solver step leaves
     # alone; FREEZE_EVAL (freeze_eval_settings): the frozen PREFIX of the network -- the stem and the residual blocks behind it,
     # as far as every trainable tensor is frozen -- runs in inference form during training (moving statistics, nothing kept)
-    # and the backward pass ends above it.  The section knows the four keys without holding them: its items stay the four
-    # above until one is set.
+    # and the backward pass ends above it.  DEVICE_LOSS_SCALE (device_loss_scale_settings): the dynamic fp16 loss scaler lives
+    # in device memory and the training step reads nothing back (inert with a fixed scale or none).  The section knows the
+    # five keys without holding them: its items stay the four above until one is set.
     c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True),
-                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[], FREEZE_EVAL=False))
+                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[], FREEZE_EVAL=False, DEVICE_LOSS_SCALE=False))
     # the layer-wise optimizers (TRAIN.OPTIMIZER = lars | adamw | lamb; inert for sgd / adam).  LARS (PySlowFast's SOLVER.LARS_ON):
     # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
     # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
@@ -221,6 +222,7 @@ def get_config(name, overrides=None, freeze=True):
     solver_settings(cfg)
     finetune_settings(cfg)
     freeze_eval_settings(cfg)
+    device_loss_scale_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
     precise_bn_settings(cfg)
@@ -449,6 +451,18 @@ def freeze_eval_settings(cfg) -> bool:
     on = False if sv is None else getattr(sv, "FREEZE_EVAL", False)
     if not isinstance(on, bool):
         raise ValueError(f"SOLVER.FREEZE_EVAL must be a bool, not {on!r}")
+    return on
+
+
+def device_loss_scale_settings(cfg) -> bool:
+    """cfg.SOLVER.DEVICE_LOSS_SCALE (False for a config tree without the key or the section): the trainer's DYNAMIC loss scaling
+    -- float16 storage with loss_scale="auto", or loss_scale="dynamic" -- keeps its state in device memory and decides, skips
+    and rescales there (train.Trainer, x3d_loss_scale_update).  Inert with a fixed scale or none.  ValueError for a value that
+    is not a bool."""
+    sv = getattr(cfg, "SOLVER", None)
+    on = False if sv is None else getattr(sv, "DEVICE_LOSS_SCALE", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"SOLVER.DEVICE_LOSS_SCALE must be a bool, not {on!r}")
     return on
 
 

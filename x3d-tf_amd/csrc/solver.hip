@@ -14,6 +14,9 @@
 //   x3d_*_pt                the gradient reduction and all five rules walk it, and the learning rate of a chunk is lr *
 //                           lr_scale[segment].  The same kernels: the learning rate is a policy (LrOne / LrSeg) they are
 //                           instantiated with
+//   x3d_unscale_sumsq       the fp16 loss scaler on the device: the two gradient reductions with g * (1 / scale) written back in
+//   x3d_seg_unscale_sumsq   the same pass (the same walks, instantiated with SumsqUnscale), the scale applied to dlogits, and
+//   x3d_loss_scale_apply / _update   Keras' DynamicLossScale on eight doubles of device memory (at the end of this file)
 //
 // Every streaming kernel is ONE BODY handed to one of two walkers.  A body is a generic lambda body(N, at): it loads N
 // elements at `at` (vec_load), applies the rule to each (solver_each) and stores N elements (vec_store); N is a
@@ -258,10 +261,25 @@ __device__ __forceinline__ void sumsq_add(float x, double& s, unsigned& bad) {
   bad += fin ? 0u : 1u;
 }
 
+// What the sum-of-squares walks (flat and chunk table) do to an element before they add it.  SumsqKeep: nothing, g is read-only
+// (x3d_grad_sumsq / x3d_seg_grad_sumsq).  SumsqUnscale: g = g * inv, ONE fp32 product, written back in the same pass; the sum
+// and the count are those of the product (x3d_unscale_sumsq / x3d_seg_unscale_sumsq; inv a power of two: exact, so the sum is
+// the plain walk's times inv^2 to the bit).  inf and nan stay what they are under a finite positive inv.
+struct SumsqKeep {
+  static constexpr bool writes = false;
+  using ptr = const float*;
+  __device__ __forceinline__ float at(float x) const { return x; }
+};
+struct SumsqUnscale {
+  static constexpr bool writes = true;
+  using ptr = float*;
+  float inv;
+  __device__ __forceinline__ float at(float x) const { return x * inv; }
+};
+
 // scratch [2][parts]: partial sums, then partial counts.  Every workgroup writes its slot (zero when it had no item).
-template <int VEC>
-__global__ __launch_bounds__(SOLVER_BLOCK) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
-                                                                  double* __restrict__ scratch) {
+template <int VEC, class OP>
+__device__ __forceinline__ void grad_sumsq_walk(typename OP::ptr __restrict__ g, long long n, double* __restrict__ scratch, OP op) {
   __shared__ double sh_s[SOLVER_BLOCK / 64];
   __shared__ unsigned sh_b[SOLVER_BLOCK / 64];
   double s = 0.0;
@@ -270,7 +288,11 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void grad_sumsq_kernel(const float* _
     constexpr int N = decltype(nc)::value;
     float x[N];
     vec_load<N>(g + i, x);
-    solver_each<N>([&](int e) { sumsq_add(x[e], s, bad); });
+    solver_each<N>([&](int e) {
+      x[e] = op.at(x[e]);
+      sumsq_add(x[e], s, bad);
+    });
+    if constexpr (OP::writes) vec_store<N>(g + i, x);
   });
   // lanes by xor butterfly, then the waves in ascending order: a fixed tree
   s = wave_sum_d(s);
@@ -286,6 +308,20 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void grad_sumsq_kernel(const float* _
     scratch[blockIdx.x] = t;
     scratch[gridDim.x + blockIdx.x] = (double)b;
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(SOLVER_BLOCK) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
+                                                                  double* __restrict__ scratch) {
+  grad_sumsq_walk<VEC>(g, n, scratch, SumsqKeep{});
+}
+
+// state: the X3D_LOSS_SCALE_STATE doubles of the loss scaler (further down); slot 1 = 1 / scale
+template <int VEC>
+__global__ __launch_bounds__(SOLVER_BLOCK) void unscale_sumsq_kernel(float* __restrict__ g, long long n,
+                                                                     const double* __restrict__ state,
+                                                                     double* __restrict__ scratch) {
+  grad_sumsq_walk<VEC>(g, n, scratch, SumsqUnscale{(float)state[1]});
 }
 
 // one wave: lane l adds partials [l*per, (l+1)*per) in ascending order, lane 0 then adds the 64 lane sums in ascending order
@@ -315,6 +351,18 @@ extern "C" int x3d_grad_sumsq(const float* g, long long n, double* scratch, doub
   solver_launch(solver_vec(nullptr, g) == 4, grad_sumsq_kernel<4>, grad_sumsq_kernel<1>, parts, stream, g, n, scratch);
   hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, (int)parts, out);
   X3D_LAUNCH_CHECK("grad_sumsq");
+  return X3D_OK;
+}
+
+// x3d_grad_sumsq's grid, partial layout and final launch; the walk multiplies by state[1] and writes g back
+extern "C" int x3d_unscale_sumsq(float* g, long long n, const double* state, double* scratch, double* out, void* stream) {
+  X3D_REQUIRE(g && state && scratch && out && n > 0, "unscale_sumsq: bad args");
+  X3D_REQUIRE((((uintptr_t)state | (uintptr_t)scratch | (uintptr_t)out) & 7) == 0 && ((uintptr_t)g & 3) == 0,
+              "unscale_sumsq: misaligned pointer");
+  const unsigned parts = (unsigned)sumsq_parts(n);
+  solver_launch(solver_vec(nullptr, g) == 4, unscale_sumsq_kernel<4>, unscale_sumsq_kernel<1>, parts, stream, g, n, state, scratch);
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, (int)parts, out);
+  X3D_LAUNCH_CHECK("unscale_sumsq");
   return X3D_OK;
 }
 
@@ -585,9 +633,10 @@ static inline AdamLrSeg adam_lr_seg(float lr, const float* lr_scale, float beta1
 
 // ---- partial sums: partials[ch] (and partials[nchunk + ch]) of chunk ch ----
 // FINITE (x3d_seg_grad_sumsq): x3d_grad_sumsq's rule -- a non-finite entry adds nothing to the sum and one to the chunk's count
-template <bool AL, bool FINITE>
-__global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __restrict__ a, const int* __restrict__ chunks,
-                                                                 int nchunk, double* __restrict__ partials) {
+// OP: SumsqKeep, or SumsqUnscale (x3d_seg_unscale_sumsq): the elements of the chunks are rewritten, nothing outside them is touched
+template <bool AL, bool FINITE, class OP>
+__device__ __forceinline__ void seg_sumsq_walk(typename OP::ptr __restrict__ a, const int* __restrict__ chunks, int nchunk,
+                                               double* __restrict__ partials, OP op) {
   SEG_FOR_CHUNKS(ch) {
     int seg, first, cnt;
     seg_chunk(chunks, ch, seg, first, cnt);
@@ -598,9 +647,11 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __
       float x[N];
       vec_load<N, AL>(a + at, x);
       solver_each<N>([&](int e) {
+        x[e] = op.at(x[e]);
         if constexpr (FINITE) sumsq_add(x[e], s, bad);
         else sq_add(x[e], s);
       });
+      if constexpr (OP::writes) vec_store<N, AL>(a + at, x);
     });
     s = wave_sum_d(s);
     if constexpr (FINITE) {
@@ -612,6 +663,19 @@ __global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __
       if constexpr (FINITE) partials[nchunk + ch] = (double)bad;
     }
   }
+}
+
+template <bool AL, bool FINITE>
+__global__ __launch_bounds__(SOLVER_BLOCK) void seg_sumsq_kernel(const float* __restrict__ a, const int* __restrict__ chunks,
+                                                                 int nchunk, double* __restrict__ partials) {
+  seg_sumsq_walk<AL, FINITE>(a, chunks, nchunk, partials, SumsqKeep{});
+}
+
+template <bool AL>
+__global__ __launch_bounds__(SOLVER_BLOCK) void seg_unscale_sumsq_kernel(float* __restrict__ g, const int* __restrict__ chunks,
+                                                                         int nchunk, const double* __restrict__ state,
+                                                                         double* __restrict__ partials) {
+  seg_sumsq_walk<AL, true>(g, chunks, nchunk, partials, SumsqUnscale{(float)state[1]});
 }
 
 template <bool AL>
@@ -1002,4 +1066,83 @@ extern "C" int x3d_lamb_pt(float* w, float* m, float* v, const float* g, const i
   SEG_REQUIRE_LR_SCALE("lamb_pt");
   return lamb_run("lamb_pt", w, m, v, g, chunks, nchunk, segs, nseg, LrSeg{lr, lr_scale}, beta1, beta2, eps, decay, grad_scale,
                   step, norm, max_norm, ema, ema_decay, partials, q, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fp16 loss scaler on the device: x3d_loss_scale_apply / x3d_seg_unscale_sumsq / x3d_loss_scale_update
+// (x3d_unscale_sumsq stands beside x3d_grad_sumsq above)
+// ------------------------------------------------------------------------------------------------
+// state = X3D_LOSS_SCALE_STATE doubles (include/x3d_hip.h): scale S, 1 / S, consecutive finite steps, skipped steps, applied
+// steps, 1.0 after a skipped update, two zeros.  S is a power of two, so every product with it or with 1 / S is exact.
+enum { LS_SCALE = 0, LS_INV = 1, LS_GOOD = 2, LS_SKIPPED = 3, LS_APPLIED = 4, LS_LAST_SKIPPED = 5 };
+
+template <int VEC>
+__global__ __launch_bounds__(SOLVER_BLOCK) void loss_scale_apply_kernel(float* __restrict__ x, long long n,
+                                                                        const double* __restrict__ state) {
+  const float s = (float)state[LS_SCALE];
+  solver_for_items<VEC>(n, [&](auto nc, long long i) {
+    constexpr int N = decltype(nc)::value;
+    float v[N];
+    vec_load<N>(x + i, v);
+    solver_each<N>([&](int e) { v[e] = v[e] * s; });
+    vec_store<N>(x + i, v);
+  });
+}
+
+extern "C" int x3d_loss_scale_apply(float* x, long long n, const double* state, void* stream) {
+  X3D_REQUIRE(x && state && n > 0, "loss_scale_apply: bad args");
+  X3D_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)state & 7) == 0, "loss_scale_apply: misaligned pointer");
+  const int vec = solver_vec(nullptr, x);
+  solver_launch(vec == 4, loss_scale_apply_kernel<4>, loss_scale_apply_kernel<1>, solver_grid(solver_items(n, vec)), stream, x, n,
+                state);
+  X3D_LAUNCH_CHECK("loss_scale_apply");
+  return X3D_OK;
+}
+
+extern "C" int x3d_seg_unscale_sumsq(float* g, const int* chunks, int nchunk, const int* segs, int nseg, const double* state,
+                                     double* partials, double* out, void* stream) {
+  X3D_REQUIRE(g && state && partials && out, "seg_unscale_sumsq: bad args");
+  SEG_REQUIRE_TABLE("seg_unscale_sumsq");
+  X3D_REQUIRE(((uintptr_t)g & 3) == 0 && (((uintptr_t)state | (uintptr_t)partials | (uintptr_t)out) & 7) == 0,
+              "seg_unscale_sumsq: misaligned pointer");
+  solver_launch(seg_aligned(g), seg_unscale_sumsq_kernel<true>, seg_unscale_sumsq_kernel<false>, seg_grid(nchunk), stream, g,
+                chunks, nchunk, state, partials);
+  // x3d_seg_grad_sumsq's reduction: all chunks in ascending order, sums and counts
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, nchunk, out);
+  X3D_LAUNCH_CHECK("seg_unscale_sumsq");
+  return X3D_OK;
+}
+
+// Keras' DynamicLossScale on the state, from the norm block the update launches of the same step have read.  One workgroup of
+// one wave, one lane of it: eight doubles.
+__global__ __launch_bounds__(64) void loss_scale_update_kernel(double* __restrict__ state, const double* __restrict__ norm,
+                                                               long long growth_steps) {
+  if (threadIdx.x != 0) return;
+  double s = state[LS_SCALE], good = state[LS_GOOD];
+  if (norm[1] != 0.0) {
+    s = fmax(s * 0.5, 1.0);
+    good = 0.0;
+    state[LS_SKIPPED] = state[LS_SKIPPED] + 1.0;
+    state[LS_LAST_SKIPPED] = 1.0;
+  } else {
+    state[LS_APPLIED] = state[LS_APPLIED] + 1.0;
+    good += 1.0;
+    state[LS_LAST_SKIPPED] = 0.0;
+    const float twice = (float)(2.0 * s);
+    if (good >= (double)growth_steps && (__float_as_uint(twice) & 0x7f800000u) != 0x7f800000u) {
+      s = 2.0 * s;
+      good = 0.0;
+    }
+  }
+  state[LS_SCALE] = s;
+  state[LS_INV] = 1.0 / s;
+  state[LS_GOOD] = good;
+}
+
+extern "C" int x3d_loss_scale_update(double* state, const double* norm, long long growth_steps, void* stream) {
+  X3D_REQUIRE(state && norm && growth_steps >= 1, "loss_scale_update: bad args (growth_steps counts from 1)");
+  X3D_REQUIRE((((uintptr_t)state | (uintptr_t)norm) & 7) == 0, "loss_scale_update: misaligned pointer");
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, norm, growth_steps);
+  X3D_LAUNCH_CHECK("loss_scale_update");
+  return X3D_OK;
 }

@@ -134,6 +134,7 @@ MIX_MIXUP, MIX_CUTMIX = _consts("MIX_MIXUP", "MIX_CUTMIX")
 EPI_STORE, EPI_ADD, EPI_ADD_STRIDED, EPI_SWISH_BWD = _consts("EPI_STORE", "EPI_ADD", "EPI_ADD_STRIDED", "EPI_SWISH_BWD")
 AP_MAX_POSITIVES = _consts("AP_MAX_POSITIVES")[0]
 SEG_CHUNK = _consts("SEG_CHUNK")[0]         # elements per chunk of the layer-wise optimizers' chunk table (segments.py)
+LOSS_SCALE_STATE = _consts("LOSS_SCALE_STATE")[0]   # doubles of the device loss-scaler state (ops.loss_scale_state)
 AUG_CROP_JITTER, AUG_CROP_RRC, AUG_ERASE_CONST, AUG_ERASE_PIXEL = _consts("AUG_CROP_JITTER", "AUG_CROP_RRC", "AUG_ERASE_CONST",
                                                                           "AUG_ERASE_PIXEL")
 AUG_MEAN_PARTS, AUG_GEOM_COLS, AUG_COLOR_COLS, AUG_C_K = _consts("AUG_MEAN_PARTS", "AUG_GEOM_COLS", "AUG_COLOR_COLS", "AUG_C_K")

@@ -551,6 +551,10 @@ class X3D:
         loss_scale: every gradient is multiplied by this factor (Keras LossScaleOptimizer, reference train.py:99-100:
             keeps fp16 activation gradients out of the denormal range); the optimizer step divides it out again
             (`apply_sgd(grad_scale=1 / loss_scale)`).  The backward kernels are linear in the upstream gradient.
+            Also the device state of the loss scaler (ops.loss_scale_state, a [8] fp64 device tensor): the head then takes
+            1 / global_batch and x3d_loss_scale_apply multiplies dlogits by the state's scale right behind it -- the scale is
+            a power of two, so the backward pass sees the bits a host number would have given it -- and `unscale_norm_sq`
+            divides it out again.
         on_stage_done(stage): called with "fwd" once the forward pass is on the stream, then as soon as every
             gradient of ``stage`` (4 = head, 3..0 = stages, -1 = stem) is final on the stream -- the hook gradient
             all-reduce buckets attach to.
@@ -596,12 +600,14 @@ class X3D:
         self._draw_dropout(pl)
         self._draw_drop_path(pl)
         gb = float(global_batch or n)
+        on_device = torch.is_tensor(loss_scale)          # the device state of the loss scaler: the head takes 1 / gb, the scale follows
+        head_scale = (1.0 if on_device else float(loss_scale)) / gb
         if kd and teacher_logits.data_ptr() != pl.teacher.data_ptr():
             pl.teacher.copy_(teacher_logits)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
         if kd:
             tail = (pl.probs.data_ptr(), pl.loss_rows.data_ptr(), pl.kd_rows.data_ptr(), pl.dlogits.data_ptr(),
-                    float(loss_scale) / gb, kd_alpha, kd_temp, n, self.num_classes)
+                    head_scale, kd_alpha, kd_temp, n, self.num_classes)
             if self.multi_label:
                 hip.call("x3d_sigmoid_bce_kd", pl.logits.data_ptr(), pl.teacher.data_ptr(), pl.targets.data_ptr(), *tail)
             else:
@@ -609,13 +615,15 @@ class X3D:
                          None if soft else pl.labels.data_ptr(), pl.targets.data_ptr() if soft else None, *tail)
         elif self.multi_label:
             hip.call("x3d_sigmoid_bce", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
         elif soft:
             hip.call("x3d_softmax_xent_soft", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
         else:
             hip.call("x3d_softmax_xent", pl.logits.data_ptr(), pl.labels.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), float(loss_scale) / gb, n, self.num_classes)
+                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
+        if on_device:
+            ops.loss_scale_apply(pl.dlogits.view(-1), loss_scale)
         if on_stage_done is None:
             pl.run(pl.bwd)
         else:
@@ -667,20 +675,35 @@ class X3D:
             return dict(mask=self.l2_mask, n=self.n_trainable_flat)
         return dict(table=self.seg_table, partials=self._seg_partials, q=self.trust_ratios)
 
-    def grad_norm_sq(self):
-        """x3d_grad_sumsq over `flat_grads` into buffers the model keeps: the device [2] fp64 tensor (sum of squares of the
-        raw gradient, number of non-finite entries) the `norm=` of the apply_* methods reads.  Two launches, no
-        synchronisation; the tensor is overwritten by the next call."""
+    def _norm_buffers(self):
+        """the scratch and the [2] fp64 result of the gradient reductions, allocated by the first of them"""
         if getattr(self, "_norm_out", None) is None:
             n_scratch = int(hip.load().x3d_grad_sumsq_scratch(self.n_trainable_flat))
             self._norm_scratch = torch.empty(n_scratch, dtype=torch.float64, device=self.device)
             self._norm_out = torch.zeros(2, dtype=torch.float64, device=self.device)
+
+    def grad_norm_sq(self):
+        """x3d_grad_sumsq over `flat_grads` into buffers the model keeps: the device [2] fp64 tensor (sum of squares of the
+        raw gradient, number of non-finite entries) the `norm=` of the apply_* methods reads.  Two launches, no
+        synchronisation; the tensor is overwritten by the next call."""
+        self._norm_buffers()
         form = self._solver_form()
         if "table" in form:                   # the tuned tensors only, as clip_grad_norm_ over the requires_grad parameters
             return ops.seg_grad_sumsq(self.flat_grads, form["table"], self._norm_out, form["partials"])
         hip.call("x3d_grad_sumsq", self.flat_grads.data_ptr(), form["n"], self._norm_scratch.data_ptr(),
                  self._norm_out.data_ptr())
         return self._norm_out
+
+    def unscale_norm_sq(self, state):
+        """`grad_norm_sq` for a gradient that carries the loss scale of the device state `state` (ops.loss_scale_state):
+        x3d_unscale_sumsq -- with set_finetune x3d_seg_unscale_sumsq over the tuned tensors -- divides the scale out of
+        `flat_grads` in place and leaves (sum of squares of the unscaled gradient, number of non-finite entries) in the same
+        device [2] fp64 tensor.  A frozen tensor's gradient keeps its (scaled) bits.  Two launches, no synchronisation."""
+        self._norm_buffers()
+        form = self._solver_form()
+        if "table" in form:
+            return ops.seg_unscale_sumsq(self.flat_grads, form["table"], state, self._norm_out, form["partials"])
+        return ops.unscale_sumsq(self.flat_grads[:form["n"]], state, self._norm_out, self._norm_scratch)
 
     def _apply(self, rule, norm, max_norm, ema, ema_decay, **scalars):
         """One update of solver.RULES[rule], for every apply_*: claims the slot buffers for the rule's slot kind (zeroed when the

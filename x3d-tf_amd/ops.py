@@ -825,6 +825,82 @@ def seg_grad_sumsq(g, table, out=None, partials=None):
     return out
 
 
+# ---- the fp16 loss scaler on the device (include/x3d_hip.h: X3D_LOSS_SCALE_STATE) ----------------------------------------------
+LOSS_SCALE_STATE = hip.LOSS_SCALE_STATE
+LS_SCALE, LS_INV, LS_GOOD, LS_SKIPPED, LS_APPLIED, LS_LAST_SKIPPED = range(6)     # the slots of the state
+
+
+def loss_scale_value(scale) -> float:
+    """`scale` as the float a loss-scaler state may hold: a power of two >= 1, ValueError else"""
+    import math
+    s = float(scale)
+    if not (s >= 1.0 and math.isfinite(s) and math.frexp(s)[0] == 0.5):
+        raise ValueError(f"the loss scale must be a power of two >= 1, not {scale!r}")
+    return s
+
+
+def loss_scale_state(scale, device, applied=0, skipped=0):
+    """The device state of the loss scaler: [LOSS_SCALE_STATE] fp64 = (scale, 1 / scale, 0 finite steps in a row, `skipped`,
+    `applied`, 0, 0, 0).  scale: a power of two >= 1 (what makes every product with it exact)."""
+    s = loss_scale_value(scale)
+    return torch.tensor([s, 1.0 / s, 0.0, float(skipped), float(applied), 0.0, 0.0, 0.0], dtype=torch.float64).to(device)
+
+
+def _ls_state(op, state):
+    if not torch.is_tensor(state) or state.dtype != torch.float64 or state.numel() != LOSS_SCALE_STATE or not state.is_cuda \
+            or not state.is_contiguous():
+        raise ValueError(f"{op}: state must be the device [{LOSS_SCALE_STATE}] float64 tensor of loss_scale_state")
+
+
+def loss_scale_apply(x, state):
+    """x *= scale in place, the scale read from the device state (x3d_loss_scale_apply).  One launch, does not synchronise."""
+    _ls_state("loss_scale_apply", state)
+    _chk(x, state)
+    _f32_flat("loss_scale_apply", "x", x)
+    hip.call("x3d_loss_scale_apply", ptr(x), x.numel(), ptr(state))
+    return x
+
+
+def unscale_sumsq(g, state, out=None, scratch=None):
+    """grad_sumsq with g *= 1 / scale written back in the same pass (x3d_unscale_sumsq): out [2] fp64 = (sum of squares of the
+    finite unscaled entries, number of non-finite ones).  Two launches, does not synchronise."""
+    _ls_state("unscale_sumsq", state)
+    _chk(g, state, out, scratch)
+    _f32_flat("unscale_sumsq", "g", g)
+    n = g.numel()
+    scratch = _f64_scratch("unscale_sumsq", "scratch", scratch, int(hip.load().x3d_grad_sumsq_scratch(n)), g.device)
+    out = _f64_scratch("unscale_sumsq", "out", out, 2, g.device, exact=True)
+    hip.call("x3d_unscale_sumsq", ptr(g), n, ptr(state), ptr(scratch), ptr(out))
+    return out
+
+
+def seg_unscale_sumsq(g, table, state, out=None, partials=None):
+    """seg_grad_sumsq with g *= 1 / scale written back inside the table's chunks, and nowhere else (x3d_seg_unscale_sumsq).  Two
+    launches, does not synchronise."""
+    _ls_state("seg_unscale_sumsq", state)
+    _seg_table("seg_unscale_sumsq", table, ("g", g))
+    partials = _f64_scratch("seg_unscale_sumsq", "partials", partials, 2 * table.nchunk, g.device)
+    out = _f64_scratch("seg_unscale_sumsq", "out", out, 2, g.device, exact=True)
+    _chk(g, state, partials, out)
+    hip.call("x3d_seg_unscale_sumsq", ptr(g), ptr(table.d_chunks), table.nchunk, ptr(table.d_segs), table.nseg, ptr(state),
+             ptr(partials), ptr(out))
+    return out
+
+
+def loss_scale_update(state, norm, growth_steps):
+    """Keras' DynamicLossScale on the device state, from norm = the [2] fp64 result the step's update launches read
+    (x3d_loss_scale_update): halve and count a skip when norm[1] != 0, else count an applied step and double after
+    `growth_steps` finite ones in a row.  One launch, does not synchronise."""
+    _ls_state("loss_scale_update", state)
+    if norm is None or norm.dtype != torch.float64 or norm.numel() != 2 or not norm.is_cuda:
+        raise ValueError("loss_scale_update: norm must be the device [2] float64 result of unscale_sumsq")
+    if int(growth_steps) < 1:
+        raise ValueError(f"loss_scale_update: growth_steps must be >= 1, not {growth_steps}")
+    _chk(state, norm)
+    hip.call("x3d_loss_scale_update", ptr(state), ptr(norm), int(growth_steps))
+    return state
+
+
 # ---- the update rules (solver.RULES): one assembler makes every launch, the public wrappers bind their arguments to it -------
 def solver_extras(op, norm, max_norm, ema, ema_decay, n):
     """The norm / max_norm / ema / ema_decay arguments of the _ex and the chunk-table launches: norm is grad_sumsq's device result

@@ -12,8 +12,8 @@ import torch
 
 from . import dist as xdist
 from . import ops
-from .config import (OPTIMIZERS, distill_settings, finetune_settings, freeze_eval_settings, mix_settings, optim_settings, precise_bn_settings,
-                     solver_settings)
+from .config import (OPTIMIZERS, device_loss_scale_settings, distill_settings, finetune_settings, freeze_eval_settings, mix_settings,
+                     optim_settings, precise_bn_settings, solver_settings)
 from .mix import NO_MIX, draw_mix_params
 from .solver import RULES
 
@@ -85,6 +85,54 @@ def _validation_source(validation_data, epochs_to_run: int):
     return lambda: validation_data
 
 
+NO_CLIP = 3.0e38      # a max_norm that cannot clip: the largest the update launches accept (they refuse what is not finite)
+
+
+class DeviceLossScale:
+    """The dynamic loss scaler of SOLVER.DEVICE_LOSS_SCALE: `state`, the [8] fp64 device tensor the launches read and
+    x3d_loss_scale_update writes (ops.loss_scale_state: scale, 1 / scale, finite steps in a row, skipped, applied, last-skipped),
+    and what the host knows of it -- ONE STEP LATE.  `publish` (behind a step's update) copies the state into one of two pinned
+    host slots and records an event; `previous` (in the next step) waits for that event, which belongs to a step whose launches
+    have long run, never for the step in flight.  `read` is the explicit, synchronising read behind the trainer's properties."""
+
+    def __init__(self, device, scale):
+        self.state = ops.loss_scale_state(scale, device)
+        self.host = torch.zeros(2, ops.LOSS_SCALE_STATE, dtype=torch.float64).pin_memory()
+        self.events = [torch.cuda.Event(), torch.cuda.Event()]
+        self.turn, self.pending = 0, None         # the slot the next copy goes to; the slot whose copy nobody has waited for
+        self.known = [float(scale), 1.0 / float(scale), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+        self.dirty = False                        # launches have written the state since `known` was read
+
+    def publish(self):
+        self.host[self.turn].copy_(self.state, non_blocking=True)
+        self.events[self.turn].record()
+        self.pending, self.turn, self.dirty = self.turn, self.turn ^ 1, True
+
+    def previous(self):
+        """the state as the last published step left it (the initial one before any)"""
+        if self.pending is not None:
+            self.events[self.pending].synchronize()
+            self.known = self.host[self.pending].tolist()
+            self.pending = None
+        return self.known
+
+    def read(self):
+        """the state now: drains the stream when a step has run since the last read"""
+        if self.dirty:
+            self.known = self.state.tolist()
+            self.dirty, self.pending = False, None
+        return self.known
+
+    def write(self, values: dict, sync: bool):
+        """state[slot] = value for slot, value in `values`, in stream order.  sync (the counters: the host derives Adam's step
+        from them): read first, so that `known` stays what the device holds.  Without it `known` is as current as it was"""
+        if sync:
+            self.read()
+        for slot, value in values.items():
+            self.state[slot:slot + 1].fill_(float(value))
+            self.known[slot] = float(value)
+
+
 class Trainer:
     """fwd + bwd + gradient all-reduce + optimizer for one replica.
 
@@ -103,6 +151,7 @@ class Trainer:
         self.slot_kind = self.rule.slot_kind
         self.optim = optim_settings(cfg)      # OPTIM.*: read by the lars / adamw / lamb branches only
         self.last_trust_ratios = None         # lars / lamb: device [nseg] fp32 trust ratios of the last update (model.segments order; fine-tuning: model.tuned_segments)
+        self._dls = None                      # DeviceLossScale with SOLVER.DEVICE_LOSS_SCALE and dynamic scaling (below)
         self.opt_step = 0                     # optimizer steps applied (Adam's bias correction counts them)
         # Loss scaling = tf.keras.mixed_precision.LossScaleOptimizer(opt) with its defaults (train.py:99-100): dynamic,
         # initial scale 2^15, doubled after 2000 consecutive finite steps, halved (and the step skipped) when a gradient
@@ -113,6 +162,11 @@ class Trainer:
         self.dynamic_scale = loss_scale == "dynamic"
         self.loss_scale = 2.0 ** 15 if self.dynamic_scale else (float(loss_scale) if loss_scale else 1.0)
         self.growth_steps, self._good_steps, self.skipped_steps = 2000, 0, 0
+        # SOLVER.DEVICE_LOSS_SCALE: the dynamic scaler's state lives in device memory, the step decides, skips and rescales
+        # there and reads nothing back (`_update`); `loss_scale`, `skipped_steps` and `opt_step` are then synchronising reads
+        # of it.  Inert with a fixed scale or none.  Not written to checkpoints (nor is the host's): a resumed run starts at 2^15.
+        if device_loss_scale_settings(cfg) and self.dynamic_scale:
+            self._dls = DeviceLossScale(model.device, self._loss_scale)
         self.momentum = cfg.TRAIN.MOMENTUM if momentum is None else momentum
         self.world = torch.distributed.get_world_size(group) if torch.distributed.is_initialized() else 1
         self.collectives = xdist._active(group)      # world > 1, or the one-rank rehearsal (X3D_DIST_REHEARSE=1)
@@ -233,11 +287,36 @@ class Trainer:
             return self._accum_step(clips, labels, lr, n)
         pl = m.forward_backward(clips, labels, global_batch=n * self.world,
                                 on_stage_done=self._on_stage_done if self.collectives else None,
-                                loss_scale=self.loss_scale, **self._teacher_kw(clips))
+                                loss_scale=self._fb_scale(), **self._teacher_kw(clips))
         self.reducer.mark_backward_done()     # (an event on the compute stream: finish() measures the exposed exchange from it)
         self.reducer.finish()
         self._finish_stats()
         return self._update(pl, lr)
+
+    # loss_scale / skipped_steps / opt_step: plain host numbers -- except in device mode, where reading one reads the device
+    # state (DeviceLossScale.read: an explicit synchronisation of the caller's) and setting one writes it in stream order
+    def _ls_get(slot, name, as_type):
+        def get(self):
+            return getattr(self, name) if self._dls is None else as_type(self._dls.read()[slot])
+
+        def put(self, value):
+            if self._dls is None:
+                setattr(self, name, value)
+            elif slot == ops.LS_SCALE:
+                value = ops.loss_scale_value(value)
+                self._dls.write({ops.LS_SCALE: value, ops.LS_INV: 1.0 / value}, sync=False)
+            else:
+                self._dls.write({slot: int(value)}, sync=True)
+        return property(get, put)
+
+    loss_scale = _ls_get(ops.LS_SCALE, "_loss_scale", float)
+    skipped_steps = _ls_get(ops.LS_SKIPPED, "_skipped_steps", int)
+    opt_step = _ls_get(ops.LS_APPLIED, "_opt_step", int)
+    del _ls_get
+
+    def _fb_scale(self):
+        """forward_backward's loss_scale: the host number, or the device state"""
+        return self._loss_scale if self._dls is None else self._dls.state
 
     def _finish_stats(self):
         if self._stats_work is not None:      # mirrored-variable MEAN aggregation of the BN moving statistics [TF-3p]
@@ -248,6 +327,8 @@ class Trainer:
     def _update(self, pl, lr):
         """Finite check (fp16 loss scaling), clip, optimizer, EMA on the all-reduced gradient in `flat_grads`."""
         m = self.model
+        if self._dls is not None:
+            return self._update_on_device(pl, lr)
         if self.dynamic_scale:                # after the all-reduce: every replica sees the same sums, takes the same branch
             if not m.grads_finite():
                 self.loss_scale = max(self.loss_scale / 2.0, 1.0)
@@ -265,10 +346,20 @@ class Trainer:
             norm = m.grad_norm_sq()
             self.last_grad_norm = norm[0].sqrt() * grad_scale
             extras.update(norm=norm, max_norm=self.solver.clip_grad_l2norm)
+        self._apply_rule(lr, grad_scale, self.opt_step, extras)
+        if self.dynamic_scale and self._good_steps >= self.growth_steps:
+            self.loss_scale *= 2.0
+            self._good_steps = 0
+        return pl
+
+    def _apply_rule(self, lr, grad_scale, step, extras):
+        """The optimizer launch and the EMA of the moving statistics behind it.  extras: norm + max_norm of the clip / skip
+        channel, if any; `step`: the bias-correction step of the rules that have one."""
+        m = self.model
         if self.ema is not None:
             extras.update(ema=self.ema, ema_decay=self.solver.ema_decay)
         # the rule's scalars (solver.RULES): the trainer's own state for those it has, OPTIM.* for those the record maps there
-        mine = dict(momentum=self.momentum, step=self.opt_step)
+        mine = dict(momentum=self.momentum, step=step)
         kw = {k: mine[k] for k in self.rule.scalars if k in mine}
         kw.update({k: getattr(self.optim, field) for k, field in self.rule.settings.items()})
         q = getattr(m, "apply_" + self.optimizer)(lr, grad_scale=grad_scale, **kw, **extras)
@@ -276,9 +367,24 @@ class Trainer:
             self.last_trust_ratios = q
         if self.ema is not None:              # the moving statistics behind the trainable block: skipped together with the step
             ops.ema_update(self.ema[m.n_trainable_flat:], m.moving_stats_flat(), self.solver.ema_decay, extras.get("norm"))
-        if self.dynamic_scale and self._good_steps >= self.growth_steps:
-            self.loss_scale *= 2.0
-            self._good_steps = 0
+
+    def _update_on_device(self, pl, lr):
+        """`_update` with SOLVER.DEVICE_LOSS_SCALE: launches only, in stream order --
+          1. x3d_unscale_sumsq (set_finetune: x3d_seg_unscale_sumsq) divides the scale out of `flat_grads`, which from here on
+             holds the UNSCALED gradient, and leaves its norm block: squared norm, number of non-finite entries;
+          2. the rule's launch with grad_scale = 1 and norm = that block -- the skip channel of the clipping launches decides on
+             the device; without CLIP_GRAD_L2NORM max_norm is NO_CLIP, which no gradient reaches;
+          3. the EMA of the moving statistics, skipped through the same block;
+          4. x3d_loss_scale_update halves or grows the scale and counts the step, and the state is published to the host.
+        The host waits, at most, for the copy the PREVIOUS step published: the rules with a bias correction take their step
+        from it, applied steps so far + 1, so a skipped step does not advance the correction."""
+        ds = self._dls
+        norm = self.model.unscale_norm_sq(ds.state)
+        self.last_grad_norm = norm[0].sqrt()
+        step = int(ds.previous()[ops.LS_APPLIED]) + 1 if "step" in self.rule.scalars else 0
+        self._apply_rule(lr, 1.0, step, dict(norm=norm, max_norm=self.solver.clip_grad_l2norm if self._clip else NO_CLIP))
+        ops.loss_scale_update(ds.state, norm, self.growth_steps)
+        ds.publish()
         return pl
 
     def _accum_step(self, clips, labels, lr, n):
@@ -294,7 +400,7 @@ class Trainer:
             self._grad_acc = torch.zeros_like(m.flat_grads)
         hook = (self._on_stage_done if last else self._on_stage_done_no_grads) if self.collectives else None
         pl = m.forward_backward(clips, labels, global_batch=n * self.world * self._accum, on_stage_done=hook,
-                                loss_scale=self.loss_scale, **self._teacher_kw(clips))
+                                loss_scale=self._fb_scale(), **self._teacher_kw(clips))
         if not last:
             ops.grad_accum(self._grad_acc, m.flat_grads, first=self._micro == 1)
             self._finish_stats()
@@ -385,6 +491,10 @@ class Trainer:
         DISTILL.ENABLE: `history["kd_loss"]` is the epoch mean of the unweighted KD term (`kd_loss`); `loss` stays the combined
         loss (+ L2).
 
+        SOLVER.DEVICE_LOSS_SCALE (dynamic fp16 loss scaling on the device): no step reads the scaler; `history["loss_scale"]` is the
+        scale at the end of the epoch and `history["skipped_steps"]` the epoch's skipped updates, from one read of the device
+        state per epoch; `grad_norm` is summed on the device over the applied updates only.
+
         SOLVER.* (INTEGRATION.md): with CLIP_GRAD_L2NORM `history["grad_norm"]` is the epoch's mean gradient norm before
         clipping; with ACCUM_STEPS = A every batch is a micro-batch, steps_per_epoch and an integer save_freq must be multiples
         of A (ValueError); with EMA_DECAY and EMA_EVAL validation runs on the EMA weights (`ema_scope`).
@@ -426,6 +536,10 @@ class Trainer:
         self.history.update({k: [] for k in metrics})
         if self._clip:
             self.history["grad_norm"] = []
+        ds = self._dls
+        if ds is not None:                    # device loss scaling: the scale at epoch end and the epoch's skipped steps
+            self.history.update(loss_scale=[], skipped_steps=[])
+            seen = list(ds.read())            # (no synchronisation unless a step has run since the last read)
         if self.teacher is not None:
             self.history["kd_loss"] = []
         if val_source is not None:
@@ -439,12 +553,15 @@ class Trainer:
             kd_tot = torch.zeros((), dtype=torch.float64, device=self.model.device) if self.teacher is not None else None
             for _ in range(steps):
                 clips, labels = next(it)
-                before = self.opt_step
+                before = self.opt_step if ds is None else None
                 pl = self.step(clips, labels, lr)
                 tot += self.loss(pl).double()
                 if kd_tot is not None:
                     kd_tot += self.kd_loss(pl).double()
-                if gn_tot is not None and self.opt_step != before:     # an update ran (not inside an accumulation / fp16 skip)
+                if gn_tot is not None and ds is not None:
+                    if self._micro == 0:      # an update was launched: it adds its norm unless the device skipped it
+                        gn_tot += self.last_grad_norm * (1.0 - ds.state[ops.LS_LAST_SKIPPED])
+                elif gn_tot is not None and self.opt_step != before:   # an update ran (not inside an accumulation / fp16 skip)
                     gn_tot += self.last_grad_norm
                     updates += 1
                 if train_m is not None:
@@ -461,6 +578,12 @@ class Trainer:
             self.history["lr"].append(lr)
             if kd_tot is not None:            # the epoch mean of the unweighted KD term; read once per epoch, like the loss
                 self.history["kd_loss"].append(float(kd_tot.item()) / steps)
+            if ds is not None:                # the one read of the scaler state per epoch
+                now = ds.read()
+                updates = int(now[ops.LS_APPLIED] - seen[ops.LS_APPLIED])
+                self.history["loss_scale"].append(now[ops.LS_SCALE])
+                self.history["skipped_steps"].append(int(now[ops.LS_SKIPPED] - seen[ops.LS_SKIPPED]))
+                seen = list(now)
             if gn_tot is not None:            # mean over the epoch's updates; read once per epoch, like the loss
                 self.history["grad_norm"].append(float(gn_tot.item()) / max(updates, 1))
             if train_m is not None:
