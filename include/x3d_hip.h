@@ -60,7 +60,8 @@ extern "C" {
  *       (fine-tuning: frozen tensors and per-tensor learning rates);
  *   138 (additions only, no bump) x3d_softmax_xent_kd / x3d_sigmoid_bce_kd (knowledge distillation);
  *   138 (additions only, no bump) x3d_loss_scale_apply / x3d_unscale_sumsq / x3d_seg_unscale_sumsq / x3d_loss_scale_update
- *       (the fp16 loss scaler on the device). */
+ *       (the fp16 loss scaler on the device);
+ *   138 (additions only, no bump) x3d_stem_kernel_name (dry-run dispatch of the six stem entry points). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -121,6 +122,21 @@ int x3d_stem_fwd(const void* x, const float* w_s, const float* w_t, void* y, dou
 int x3d_stem_bwd(const void* g, const void* yraw, const float* relu_scale_shift, const float* coef, const void* x,
                  const float* w_s, const float* w_t, float* dw_s, float* dw_t, int N, int Cin, int T, int H, int W, int Cout,
                  int KT, int dtype, int x_layout, void* stream);
+/* Name of the kernel instantiation one of the six stem entry points above would launch, every template argument included
+ * ("stem_s_fwd_bf16_kernel<f16,4,nhwc>", "dwt_bwd_kernel<bf16,2,7>"), without launching anything: the entry's own checks and path
+ * decisions in dry-run mode (works without a GPU, makes no HIP call).  entry = the entry point's name ("x3d_dwt_bwd").
+ * a .. d = the addresses of its tensor operands in its own argument order, inspected for alignment only:
+ *   x3d_stem_s_fwd (x, y)   x3d_stem_s_wgrad (x, dy)   x3d_dwt_fwd (x, y)   x3d_dwt_bwd (g, yraw, x, dx)
+ *   x3d_stem_fwd (x, y)     x3d_stem_bwd (g, yraw, x);  the rest NULL.
+ * flags = the launch form, X3D_STEM_NAME_*: statistics given, out_scale_shift given, out_act = ReLU (forward entries),
+ * relu_scale_shift given (backward entries).  Extents as the entry takes them; x3d_dwt_fwd / x3d_dwt_bwd read C = Cout and
+ * HW = H * W (H, W: the plane conv_t runs on).  Returns what the entry would: an error where it refuses the launch. */
+#define X3D_STEM_NAME_STATS 1
+#define X3D_STEM_NAME_OUT_SS 2
+#define X3D_STEM_NAME_OUT_RELU 4
+#define X3D_STEM_NAME_RELU_SS 8
+int x3d_stem_kernel_name(const char* entry, const void* a, const void* b, const void* c, const void* d, int flags, int N,
+                         int Cin, int T, int H, int W, int Cout, int KT, int dtype, int x_layout, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------
  * K3  BatchNormalization(axis=-1, eps, momentum)   reference model.py:89-92,196-199,254-257,

@@ -954,16 +954,21 @@ def test_stem(gpu, dtype, shape):
     ws = torch.randn((c1, 3, 3, 3), generator=g_) * 0.3
     wt = torch.randn((c1, 5), generator=g_) * 0.4
     ref_s = F.conv3d(F.pad(xd, (1, 1, 1, 1, 0, 0)), ws.double().unsqueeze(2), stride=(1, 2, 2))
-    ys = ops.stem_s_fwd(x.to(gpu), ws.to(gpu))
+    from x3d_tf_amd import hip
+    xg, wsg = x.to(gpu), ws.to(gpu)
+    ys = ops.stem_s_fwd(xg, wsg)
     torch.cuda.synchronize()
     # 16-bit storage: the matrix-core path (W % 8 == 0) rounds the weights to the storage type, the scalar path keeps them
-    # in fp32 -- the output must match the fp64 conv over ONE of the two weight sets to the output rounding
+    # in fp32 -- the output must match the fp64 conv over the weight set of the kernel that RAN (the dispatch's own name for this
+    # launch) to the output rounding
+    kernel = hip.stem_kernel_name("x3d_stem_s_fwd", xg.data_ptr(), wsg.data_ptr(), ys.data_ptr(), n, 3, t, h, w, c1,
+                                  hip.dtype_code(dtype), 0)
+    on_mx = kernel.startswith("stem_s_fwd_bf16_kernel<")
+    assert on_mx or kernel.startswith("stem_s_fwd_kernel<"), kernel
+    assert on_mx == (dtype != torch.float32 and w % 8 == 0), kernel
     ref_r = F.conv3d(F.pad(xd, (1, 1, 1, 1, 0, 0)), round_to(ws, dtype).unsqueeze(2), stride=(1, 2, 2))
     rt, at = tol_gemm(dtype)
-    try:
-        report("conv_s", ys, ref_r, rt, at * ref_s.abs().max().item())
-    except AssertionError:
-        report("conv_s", ys, ref_s, rt, at * ref_s.abs().max().item())
+    report("conv_s", ys, ref_r if on_mx else ref_s, rt, at * ref_s.abs().max().item())
     # conv_t on the stored conv_s output
     ysd = ys.float().cpu().double()
     ref_t = F.conv3d(F.pad(ysd, (0, 0, 0, 0, 2, 2)), wt.double().view(-1, 1, 5, 1, 1), groups=c1)
@@ -1026,7 +1031,6 @@ def test_stem(gpu, dtype, shape):
     report("stem_s_dw", dws, dws_ref, 2e-4, 2e-4 * dws_ref.abs().max().item())
     # the clip batch channels-last, as the reference's model takes it (X3D_LAYOUT_NTHWC): the matrix-core kernels read it in
     # place -- same products in the same order as the planar form, so the outputs are bit-identical
-    from x3d_tf_amd import hip
     if hip.load().x3d_stem_s_nthwc_supported(3, w, c1, hip.dtype_code(dtype)):
         xcl = x.to(gpu).permute(0, 2, 3, 4, 1).contiguous()
         ys_cl = ops.stem_s_fwd(xcl, ws.to(gpu), channels_last=True)
@@ -1044,7 +1048,8 @@ STEM_FUSED = [(2, 4, 16, 16, 24), (1, 16, 12, 224, 24), (1, 2, 10, 312, 24),    
               (3, 5, 10, 72, 24),                           # 15 segments: the last group is three segments, Wo = 36 of 64 columns
               (1, 7, 6, 312, 32), (2, 3, 5, 160, 32),       # X3D-XL: 32 channels (four rows per wave), Wo % 8 == 4, odd H
               (1, 1, 8, 24, 24), (2, 2, 9, 32, 8),          # T < KT; Cout = 8 (rows 8.. of every wave idle)
-              (5, 6, 40, 128, 24)]                          # 100 segments = 25 groups: several groups per workgroup on a small GPU grid
+              (5, 6, 40, 128, 24),                          # 100 segments = 25 groups: several groups per workgroup on a small GPU grid
+              (1, 3, 7, 40, 16)]                            # Cout = 16 (SCALE_RES2 with WIDTH_FACTOR 1.0): rows 16.. idle, Wo = 20
 
 
 @pytest.mark.parametrize("dtype", S.HALF_DTYPES)
@@ -1068,6 +1073,17 @@ def test_stem_fused(gpu, dtype, shape):
     yt = ops.stem_fwd(xcl, ws, wt, stats=st)
     torch.cuda.synchronize()
     assert torch.equal(yt, yt_ref), f"fused stem forward differs from conv_s + conv_t: {(yt.float() - yt_ref.float()).abs().max().item()}"
+    # ... and against fp64 directly (at these shapes the two-kernel path is compared with nothing else): conv_s over the weights
+    # rounded to storage, its output rounded to storage as the kernel rounds it on chip, conv_t in fp64 -- at tol_store plus the
+    # tie slack of that rounding, as test_stem_fused_forward_full_size
+    from tests.util import tie_slack_t
+    s64 = F.conv3d(F.pad(xd, (1, 1, 1, 1, 0, 0)), round_to(ws.cpu(), dtype).unsqueeze(2), stride=(1, 2, 2))
+    yt64 = F.conv3d(F.pad(round_to(s64, dtype), (0, 0, 0, 0, 2, 2)), wt.cpu().double().view(-1, 1, 5, 1, 1), groups=c1)
+    rs64, as64 = tol_store(dtype)
+    lim = as64 * yt64.abs().max().item() + rs64 * yt64.abs() + tie_slack_t(s64, dtype, wt.cpu().abs())
+    err = (yt.double().cpu() - yt64).abs()
+    assert torch.isfinite(yt).all() and not (err > lim).any(), \
+        f"fused stem forward vs fp64: {int((err > lim).sum())}/{err.numel()} out of tolerance, max err {err.max().item():.3e}"
     report("stats", st, st_ref, 1e-5, 1e-5 * max(1.0, st_ref.abs().max().item()))
     # inference epilogue
     oss = torch.stack([1 + 0.3 * torch.randn(c1, generator=g_), 0.3 * torch.randn(c1, generator=g_)], 1).to(gpu)

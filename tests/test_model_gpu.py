@@ -125,8 +125,29 @@ def test_inference_batch_must_be_multiple_of_views(gpu):
 @pytest.mark.parametrize("name,n,t,s", S.MODEL_TRAIN_FP32)
 def test_train_step_fp32(gpu, name, n, t, s):
     """fwd + bwd in training mode (batch statistics, fixed dropout mask) against oracle autograd."""
+    _train_step_fp32(gpu, name, n, t, s)
+
+
+STEM_KT_TRAIN = S.MODEL_TRAIN_FP32[0]      # the smallest X3D-XS case: 4 clips of 4 x 64 x 64 (T <= KT / 2 + 1 for KT = 7; W % 8 == 0)
+STEM_ENTRIES_TWO_KERNEL = ["x3d_stem_s_fwd", "x3d_dwt_fwd", "x3d_dwt_bwd", "x3d_stem_s_wgrad"]
+
+
+@pytest.mark.parametrize("kt", [3, 7])
+def test_train_step_fp32_other_temporal_filter(gpu, kt):
+    """test_train_step_fp32 with NETWORK.C1_TEMP_FILTER 3 and 7 (only the stem differs from X3D-XS: dwt_fwd_kernel / dwt_bwd_kernel
+    with KT != 5 inside the model; the oracle takes kt from the kernel's shape), same tolerances."""
+    name, n, t, s = STEM_KT_TRAIN
+    assert name == "XS"
+    pl = _train_step_fp32(gpu, name, n, t, s, ["NETWORK.C1_TEMP_FILTER", kt])
+    names = [item[0] for lst in (pl.fwd, pl.bwd) for item in lst if item is not None]
+    assert pl.stem_fused is False and all(e in names for e in STEM_ENTRIES_TWO_KERNEL)
+    from tests.stem_classes import plan_stem_classes
+    assert {k for _, k, _ in plan_stem_classes(pl)} >= {f"dwt_fwd_kernel<float,4,{kt}>", f"dwt_bwd_kernel<float,2,{kt}>"}
+
+
+def _train_step_fp32(gpu, name, n, t, s, overrides=None):
     from oracle import x3d_oracle as O
-    cfg, arch, params = _setup(name)
+    cfg, arch, params = _setup(name, overrides)
     torch.manual_seed(1)
     x = torch.randn(n, t, s, s, 3)
     labels = torch.randint(0, arch.num_classes, (n,))
@@ -179,6 +200,7 @@ def test_train_step_fp32(gpu, name, n, t, s):
         # dw = -lr * (1 + momentum) * g from a zero velocity: the gradient tolerance above (2e-3 of max |g|) carries over
         tol = 1e-4 * ref_p[k].abs().max().item() + 0.05 * 1.9 * 2e-3 * g_ref.abs().max().item()
         report("updated " + k, m.params[k], ref_p[k], 0, tol)
+    return pl
 
 
 def test_train_matches_committed_golden_vector(gpu):
@@ -216,8 +238,31 @@ def test_train_step_half_block_by_block(gpu, name, n, t, s, dtype):
     two exact implementations decorrelate to O(30 %) on gradients.  Per block the error is one bf16 ulp class:
     stated tolerance 2 % of each tensor's max for activations/gradients; weight gradients (whose GEMM operands
     are rounded to bf16 for the matrix cores) 6.5 % relative L2 worst case (8 % for the two SE biases), 1.5 % median."""
+    _train_step_half(gpu, name, n, t, s, dtype)
+
+
+@pytest.mark.parametrize("dtype", S.HALF_DTYPES)
+@pytest.mark.parametrize("kt", [3, 7])
+def test_train_step_half_other_temporal_filter(gpu, kt, dtype):
+    """test_train_step_half_block_by_block with NETWORK.C1_TEMP_FILTER 3 and 7: x3d_stem_fused_supported refuses KT != 5, so a
+    16-bit model falls back to x3d_stem_s_fwd + x3d_dwt_fwd / x3d_dwt_bwd + x3d_stem_s_wgrad in training form -- a combination
+    no other test runs.  The stem is replayed on the oracle like a block (teacher forcing: the device's own upstream gradient at
+    the stem output) and the conv1/* gradients are held to the block tensors' limits."""
+    name, n, t, s = STEM_KT_TRAIN
+    assert name == "XS"
+    pl = _train_step_half(gpu, name, n, t, s, dtype, ["NETWORK.C1_TEMP_FILTER", kt], stem=True)
+    names = [item[0] for lst in (pl.fwd, pl.bwd) for item in lst if item is not None]
+    assert pl.stem_fused is False and all(e in names for e in STEM_ENTRIES_TWO_KERNEL)
+    assert "x3d_stem_fwd" not in names and "x3d_stem_bwd" not in names
+    from tests.stem_classes import plan_stem_classes
+    half = "bf16" if dtype == torch.bfloat16 else "f16"
+    assert {k for _, k, _ in plan_stem_classes(pl)} == {f"stem_s_fwd_bf16_kernel<{half},4,nhwc>", f"dwt_fwd_kernel<{half},4,{kt}>",
+                                                        f"dwt_bwd_kernel<{half},4,{kt}>", f"stem_s_wgrad_bf16_kernel<{half},4,nhwc>"}
+
+
+def _train_step_half(gpu, name, n, t, s, dtype, overrides=None, stem=False):
     from oracle import x3d_oracle as O
-    cfg, arch, params = _setup(name)
+    cfg, arch, params = _setup(name, overrides)
     torch.manual_seed(int(os.environ.get("X3D_TEST_SEED", "2")))      # (the variable: spread of the per-tensor errors over inputs)
     x = torch.randn(n, t, s, s, 3).to(dtype).float()
     labels = torch.randint(0, arch.num_classes, (n,))
@@ -263,7 +308,7 @@ def test_train_step_half_block_by_block(gpu, name, n, t, s, dtype):
         pl.run(pl.bwd, B.bwd_start, B.bwd_stop)
         torch.cuda.synchronize()
         pos = B.bwd_stop
-        dx_dev = B.dx_view.float().cpu()
+        dx_dev = B.dx_view.float().cpu().clone()
         # oracle on the device's block input
         pre = O.block_prefix(B.spec)
         names = [k for k in params if k.startswith(pre + "/") and not k.endswith(("moving_mean", "moving_variance"))]
@@ -288,6 +333,17 @@ def test_train_step_half_block_by_block(gpu, name, n, t, s, dtype):
         rms = [g_ref.double().norm().item() / max(g_ref.numel(), 1) ** 0.5 for g_ref in grads[1:]]
         floor_rms = 0.05 * sorted(rms)[len(rms) // 2]
         pending.append((names, [g_.double() for g_ in grads[1:]], floor_rms))
+    if stem:
+        # the stem as one more block: the oracle's stem on the clip batch (already representable in the storage type), driven by the
+        # device's stored gradient at the stem output (masked or not: the oracle's ReLU backward re-applies the same mask)
+        names = [k for k in params if k.startswith("conv1/") and not k.endswith(("moving_mean", "moving_variance"))]
+        assert {"conv1/conv_s/kernel", "conv1/conv_t/kernel"} <= set(names)
+        leaf = {k: (v.clone().requires_grad_(True) if k in names else v) for k, v in params.items()}
+        y0_ref = O.stem(x.permute(0, 4, 1, 2, 3).contiguous(), leaf, arch, True, O.BNState(), masks, st)
+        worst["y"] = max(worst["y"], _scaled("conv1/out", pl.y0, y0_ref, 2e-2 if dtype == torch.bfloat16 else 3e-3))
+        grads = torch.autograd.grad(y0_ref, [leaf[k] for k in names], grad_outputs=dx_dev)
+        rms = [g_ref.double().norm().item() / max(g_ref.numel(), 1) ** 0.5 for g_ref in grads]
+        pending.append((names, [g_.double() for g_ in grads], 0.05 * sorted(rms)[len(rms) // 2]))
     # the weight gradients are read once the WHOLE list has run: a launch of a later block may finish an earlier block's
     # gradient (the dW of the recomputed-output `a` backward rides on the next BatchNorm-backward finalize launch)
     pl.run(pl.bwd, pos, len(pl.bwd))
@@ -315,6 +371,7 @@ def test_train_step_half_block_by_block(gpu, name, n, t, s, dtype):
     bad = {k: e for k, e in errs.items() if e > (lim_se if k.endswith(("/se_fc1/bias", "/se_fc2/bias")) else lim)}
     assert not bad, f"relative L2 error beyond {lim} ({lim_se} for the SE biases) (teacher-forced, {dtype}): {bad}"
     assert sorted(errs.values())[len(errs) // 2] < med        # median
+    return pl
 
 
 # Limits of the differential test below, per storage type: (tensors no recomputed-output launch can reach; every other tensor;

@@ -286,18 +286,20 @@ extern "C" int x3d_stem_s_fwd(const void* x, const float* w, void* y, int N, int
     const int nws = ceil_div(Wo, 64);
     const long long total_segs = (long long)N * T * Ho * nws;
     static int slots = 0;
-    if (slots == 0) {
+    if (slots == 0 && !x3d_describe.out) {      // (a dry run makes no HIP call: it sizes the grid with the fallback below)
       int nb = 0, dev = 0, cus = 256;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stem_s_fwd_bf16_kernel<bf16, SEGS, false>, 256, 0) != hipSuccess || nb < 1) nb = 2;
       slots = nb * cus;
     }
-    long long spb2 = ceil_div_ll(total_segs, slots);
+    const int nslots = slots ? slots : 2 * 256;
+    long long spb2 = ceil_div_ll(total_segs, nslots);
     if (spb2 < 4 * SEGS) spb2 = 4 * SEGS;
     spb2 = ceil_div_ll(spb2, SEGS) * SEGS;
     const long long gx2 = ceil_div_ll(total_segs, spb2);
     X3D_REQUIRE(total_segs + spb2 < (1ll << 31), "stem_s_fwd: too many row segments");
+    X3D_DESCRIBE("stem_s_fwd_bf16_kernel<%s,%d,%s>", dtype == X3D_F16 ? "f16" : "bf16", SEGS, nhwc ? "nhwc" : "ncthw");
 #define STEM_FWD(TT, NHWC_) hipLaunchKernelGGL((stem_s_fwd_bf16_kernel<TT, SEGS, NHWC_>), dim3((unsigned)gx2), dim3(256), 0, st, (const TT*)x, w, \
                                                (TT*)y, Cin, Cout, T, H, W, Ho, Wo, nws, (int)total_segs, (int)spb2)
     if (dtype == X3D_F16) { if (nhwc) STEM_FWD(f16, true); else STEM_FWD(f16, false); }
@@ -315,6 +317,8 @@ extern "C" int x3d_stem_s_fwd(const void* x, const float* w, void* y, int N, int
     case 24: LAUNCH(TT, 24); break;    \
     default: LAUNCH(TT, 32); break;    \
   }
+  X3D_DESCRIBE("stem_s_fwd_kernel<%s,3,%d>", dtype == X3D_F32 ? "float" : (dtype == X3D_F16 ? "f16" : "bf16"),
+               (Cout == 8 || Cout == 16 || Cout == 24) ? Cout : 32);
   if (dtype == X3D_F32) { BY_CO(float) } else if (dtype == X3D_F16) { BY_CO(f16) } else { BY_CO(bf16) }
 #undef BY_CO
 #undef LAUNCH
@@ -622,19 +626,21 @@ extern "C" int x3d_stem_s_wgrad(const void* x, const void* dy, float* dw, int N,
     const int nws = ceil_div(Wo, 64);
     const long long total_segs = (long long)N * T * Ho * nws;
     static int slots = 0;
-    if (slots == 0) {
+    if (slots == 0 && !x3d_describe.out) {      // (a dry run makes no HIP call: it sizes the grid with the fallback below)
       int nb = 0, dev = 0, cus = 256;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stem_s_wgrad_bf16_kernel<bf16, SEGS, false>, 256, 0) != hipSuccess || nb < 1) nb = 2;
       slots = nb * cus;
     }
-    long long spb2 = ceil_div_ll(total_segs, slots);
+    const int nslots = slots ? slots : 2 * 256;
+    long long spb2 = ceil_div_ll(total_segs, nslots);
     if (spb2 < 8 * SEGS) spb2 = 8 * SEGS;
     spb2 = ceil_div_ll(spb2, SEGS) * SEGS;
     const long long gx2 = ceil_div_ll(total_segs, spb2);
     X3D_REQUIRE(gx2 < (1ll << 31), "stem_s_wgrad: grid too large");
     X3D_REQUIRE(total_segs + spb2 < (1ll << 31), "stem_s_wgrad: too many row segments");
+    X3D_DESCRIBE("stem_s_wgrad_bf16_kernel<%s,%d,%s>", dtype == X3D_F16 ? "f16" : "bf16", SEGS, nhwc ? "nhwc" : "ncthw");
 #define STEM_WG(TT, NHWC_) hipLaunchKernelGGL((stem_s_wgrad_bf16_kernel<TT, SEGS, NHWC_>), dim3((unsigned)gx2), dim3(256), 0, st, (const TT*)x, \
                                               (const TT*)dy, dw, Cin, Cout, T, H, W, Ho, Wo, nws, (int)total_segs, (int)spb2)
     if (dtype == X3D_F16) { if (nhwc) STEM_WG(f16, true); else STEM_WG(f16, false); }
@@ -647,12 +653,13 @@ extern "C" int x3d_stem_s_wgrad(const void* x, const void* dy, float* dw, int N,
     // row segments (round 6): 2-3 workgroups per CU, an equal share of the segments each
     const int nws = ceil_div(Wo, 64);
     const long long total_segs = (long long)N * T * Ho * nws;
-    long long spb2 = ceil_div_ll(total_segs, 3ll * x3d_device_cus());
+    long long spb2 = ceil_div_ll(total_segs, 3ll * (x3d_describe.out ? 256 : x3d_device_cus()));     // (a dry run makes no HIP call)
     if (spb2 < 8) spb2 = 8;
     const long long gx2 = ceil_div_ll(total_segs, spb2);
     // the kernel forms blockIdx.x * spb2 + spb2 and reads ahead to seg + 1 in int: the sum must stay below 2^31 (as in the
     // 16-bit path above); past that, the flattened-point kernel below
     if (total_segs + spb2 < (1ll << 31) && gx2 < (1ll << 31) && x3d_env_int("X3D_STEM_WGRAD_ROWS", 1) != 0) {      // X3D_STEM_WGRAD_ROWS=0: A/B hook (the flattened-point kernel)
+      X3D_DESCRIBE("stem_s_wgrad_rows_kernel<%s>", dtype == X3D_F32 ? "float" : (dtype == X3D_F16 ? "f16" : "bf16"));
 #define STEM_WGR(TT) hipLaunchKernelGGL((stem_s_wgrad_rows_kernel<TT>), dim3((unsigned)gx2), dim3(256), 0, st, (const TT*)x, (const TT*)dy, dw, \
                                         Cin, Cout, T, H, W, Ho, Wo, nws, (int)total_segs, (int)spb2)
       if (dtype == X3D_F32) STEM_WGR(float); else if (dtype == X3D_F16) STEM_WGR(f16); else STEM_WGR(bf16);
@@ -661,6 +668,7 @@ extern "C" int x3d_stem_s_wgrad(const void* x, const void* dy, float* dw, int N,
       return X3D_OK;
     }
   }
+  X3D_DESCRIBE("stem_s_wgrad_kernel<%s>", dtype == X3D_F32 ? "float" : (dtype == X3D_F16 ? "f16" : "bf16"));
   if (dtype == X3D_F32)
     hipLaunchKernelGGL((stem_s_wgrad_kernel<float>), dim3((unsigned)gx), dim3(256), 0, st, (const float*)x,
                        (const float*)dy, dw, Cin, Cout, T, H, W, Ho, Wo, spb);
@@ -873,6 +881,7 @@ template <typename T, int VEC>
 static int dwt_fwd_kt(const void* x, const float* w, void* y, double* stats, const float* oss, int oact, int NC, int C, int T_,
                       long long HW, int KT, hipStream_t st) {
   dim3 grid((unsigned)ceil_div_ll(HW, 256ll * VEC), (unsigned)NC);
+  if (KT == 1 || KT == 3 || KT == 5 || KT == 7) X3D_DESCRIBE("dwt_fwd_kernel<%s,%d,%d>", TypeName<T>::v, VEC, KT);
   switch (KT) {
     case 1: hipLaunchKernelGGL((dwt_fwd_kernel<T, VEC, 1>), grid, dim3(256), 0, st, (const T*)x, w, (T*)y, stats, oss, oact, C, T_, HW); break;
     case 3: hipLaunchKernelGGL((dwt_fwd_kernel<T, VEC, 3>), grid, dim3(256), 0, st, (const T*)x, w, (T*)y, stats, oss, oact, C, T_, HW); break;
@@ -908,6 +917,7 @@ static int dwt_bwd_kt(const void* g, const void* yraw, const float* rss, const f
                       float* dw, int NC, int C, int T_, long long HW, int KT, hipStream_t st) {
   dim3 grid((unsigned)ceil_div_ll(HW, 256ll * VEC), (unsigned)NC);
 #define L(K) hipLaunchKernelGGL((dwt_bwd_kernel<T, VEC, K>), grid, dim3(256), 0, st, (const T*)g, (const T*)yraw, rss, coef, (const T*)x, w, (T*)dx, dw, C, T_, HW)
+  if (KT == 1 || KT == 3 || KT == 5 || KT == 7) X3D_DESCRIBE("dwt_bwd_kernel<%s,%d,%d>", TypeName<T>::v, VEC, KT);
   switch (KT) {
     case 1: L(1); break;
     case 3: L(3); break;

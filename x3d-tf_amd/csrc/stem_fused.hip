@@ -598,6 +598,7 @@ extern "C" int x3d_stem_fwd(const void* x, const float* w_s, const float* w_t, v
   X3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "stem_fwd: x must be 16-byte and y 8-byte aligned");
   X3D_REQUIRE(!(out_scale_shift && stats), "stem_fwd: the inference epilogue (out_scale_shift) takes no statistics");
   X3D_REQUIRE(out_act == X3D_ACT_NONE || out_act == X3D_ACT_RELU, "stem_fwd: out_act must be none or ReLU");
+  X3D_DESCRIBE("stem_fwd_fused_kernel<%s,%d,%s>", dtype == X3D_F16 ? "f16" : "bf16", Cout <= 24 ? 3 : 4, out_scale_shift ? "infer" : "train");
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, nws = ceil_div(Wo, 64);
   const long long total_segs = (long long)N * Ho * nws;
   const int ngroups = (int)ceil_div_ll(total_segs, SF_SEGS);
@@ -625,6 +626,7 @@ extern "C" int x3d_stem_bwd(const void* g, const void* yraw, const float* relu_s
               "under 2 GB (x3d_stem_fused_supported); run x3d_dwt_bwd + x3d_stem_s_wgrad otherwise");
   X3D_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)g % 8) == 0 && ((uintptr_t)yraw % 8) == 0,
               "stem_bwd: x must be 16-byte, g and yraw 8-byte aligned");
+  X3D_DESCRIBE("stem_bwd_fused_kernel<%s,%d>", dtype == X3D_F16 ? "f16" : "bf16", Cout <= 24 ? 3 : 4);
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, nws = ceil_div(Wo, 64);
   const long long total_segs = (long long)N * Ho * nws;
   const int ngroups = (int)ceil_div_ll(total_segs, SF_SEGS);
@@ -639,4 +641,38 @@ extern "C" int x3d_stem_bwd(const void* g, const void* yraw, const float* relu_s
 #undef SF_BWD
   X3D_LAUNCH_CHECK("stem_bwd");
   return X3D_OK;
+}
+
+// Dry-run dispatch of the six stem entry points (include/x3d_hip.h): the entry runs its own argument checks and path decisions over
+// the caller's extents and operand ADDRESSES and writes the instantiation's name at its X3D_DESCRIBE line.  Nothing is launched and
+// no HIP call is made; the parameters (weights, coefficients, gradients) are a non-NULL placeholder no dry run dereferences.
+extern "C" int x3d_stem_kernel_name(const char* entry, const void* a, const void* b, const void* c, const void* d, int flags, int N,
+                                    int Cin, int T, int H, int W, int Cout, int KT, int dtype, int x_layout, char* out, int cap) {
+  X3D_REQUIRE(entry && out && cap > 0, "stem_kernel_name: bad args");
+  X3D_REQUIRE((flags & ~15) == 0, "stem_kernel_name: unknown flags %d", flags);
+  static float param[4];
+  float* const fp = param;
+  double* const stats = (flags & X3D_STEM_NAME_STATS) ? (double*)param : nullptr;
+  const float* const oss = (flags & X3D_STEM_NAME_OUT_SS) ? fp : nullptr;
+  const float* const rss = (flags & X3D_STEM_NAME_RELU_SS) ? fp : nullptr;
+  const int oact = (flags & X3D_STEM_NAME_OUT_RELU) ? X3D_ACT_RELU : X3D_ACT_NONE;
+  const long long HW = (long long)H * W;
+  out[0] = 0;
+  int rc = X3D_ERR_INVALID;
+  x3d_describe = {out, cap};
+  if (!strcmp(entry, "x3d_stem_s_fwd")) rc = x3d_stem_s_fwd(a, fp, (void*)b, N, Cin, T, H, W, Cout, dtype, x_layout, nullptr);
+  else if (!strcmp(entry, "x3d_stem_s_wgrad")) rc = x3d_stem_s_wgrad(a, b, fp, N, Cin, T, H, W, Cout, dtype, x_layout, nullptr);
+  else if (!strcmp(entry, "x3d_dwt_fwd")) {
+    if (HW > 0 && HW < (1ll << 31)) rc = x3d_dwt_fwd(a, fp, (void*)b, stats, oss, oact, N, Cout, T, (int)HW, KT, dtype, nullptr);
+    else x3d_set_error("stem_kernel_name: H * W out of range");
+  } else if (!strcmp(entry, "x3d_dwt_bwd")) {
+    if (HW > 0 && HW < (1ll << 31)) rc = x3d_dwt_bwd(a, b, rss, fp, c, fp, (void*)d, fp, N, Cout, T, (int)HW, KT, dtype, nullptr);
+    else x3d_set_error("stem_kernel_name: H * W out of range");
+  } else if (!strcmp(entry, "x3d_stem_fwd"))
+    rc = x3d_stem_fwd(a, fp, fp, (void*)b, stats, oss, oact, N, Cin, T, H, W, Cout, KT, dtype, x_layout, nullptr);
+  else if (!strcmp(entry, "x3d_stem_bwd"))
+    rc = x3d_stem_bwd(a, b, rss, fp, c, fp, fp, fp, fp, N, Cin, T, H, W, Cout, KT, dtype, x_layout, nullptr);
+  else x3d_set_error("stem_kernel_name: unknown entry point %s", entry);
+  x3d_describe = {nullptr, 0};
+  return rc;
 }

@@ -244,6 +244,51 @@ def pw_kernel_name(args):
     return buf.value.decode()
 
 
+STEM_ENTRIES = ("x3d_stem_s_fwd", "x3d_stem_s_wgrad", "x3d_dwt_fwd", "x3d_dwt_bwd", "x3d_stem_fwd", "x3d_stem_bwd")
+STEM_NAME_STATS, STEM_NAME_OUT_SS, STEM_NAME_OUT_RELU, STEM_NAME_RELU_SS = _consts("STEM_NAME_STATS", "STEM_NAME_OUT_SS",
+                                                                                   "STEM_NAME_OUT_RELU", "STEM_NAME_RELU_SS")
+
+
+def stem_launch_query(entry, args):
+    """The arguments of x3d_stem_kernel_name (without `out`, `cap`) for a launch of a stem entry point given by its own
+    positional arguments `args` (C ABI order, the stream excluded: what a plan records): the tensor operands' addresses, the launch
+    form as X3D_STEM_NAME_* flags, the extents."""
+    a = list(args)
+    nz = lambda p, flag: flag if p else 0
+    if entry == "x3d_stem_s_fwd":          # x, w, y, N, Cin, T, H, W, Cout, dtype, x_layout
+        ops_, flags, (n, cin, t, h, w, cout, dt, lay), kt = (a[0], a[2]), 0, a[3:11], 0
+    elif entry == "x3d_stem_s_wgrad":      # x, dy, dw, N, Cin, T, H, W, Cout, dtype, x_layout
+        ops_, flags, (n, cin, t, h, w, cout, dt, lay), kt = (a[0], a[1]), 0, a[3:11], 0
+    elif entry == "x3d_dwt_fwd":           # x, w, y, stats, out_scale_shift, out_act, N, C, T, HW, KT, dtype
+        ops_ = (a[0], a[2])
+        flags = nz(a[3], STEM_NAME_STATS) | nz(a[4], STEM_NAME_OUT_SS) | nz(a[5] == ACT_RELU, STEM_NAME_OUT_RELU)
+        (n, cout, t, hw, kt, dt), cin, h, w, lay = a[6:12], 0, 1, a[9], 0
+    elif entry == "x3d_dwt_bwd":           # g, yraw, relu_scale_shift, coef, x, w, dx, dw, N, C, T, HW, KT, dtype
+        ops_, flags = (a[0], a[1], a[4], a[6]), nz(a[2], STEM_NAME_RELU_SS)
+        (n, cout, t, hw, kt, dt), cin, h, w, lay = a[8:14], 0, 1, a[11], 0
+    elif entry == "x3d_stem_fwd":          # x, w_s, w_t, y, stats, out_scale_shift, out_act, N, Cin, T, H, W, Cout, KT, dtype, x_layout
+        ops_ = (a[0], a[3])
+        flags = nz(a[4], STEM_NAME_STATS) | nz(a[5], STEM_NAME_OUT_SS) | nz(a[6] == ACT_RELU, STEM_NAME_OUT_RELU)
+        n, cin, t, h, w, cout, kt, dt, lay = a[7:16]
+    elif entry == "x3d_stem_bwd":          # g, yraw, relu_scale_shift, coef, x, w_s, w_t, dw_s, dw_t, N, Cin, T, H, W, Cout, KT, dtype, x_layout
+        ops_, flags = (a[0], a[1], a[4]), nz(a[2], STEM_NAME_RELU_SS)
+        n, cin, t, h, w, cout, kt, dt, lay = a[9:18]
+    else:
+        raise X3DHipError(f"{entry} is not a stem entry point")
+    ops_ = tuple(ops_) + (None,) * (4 - len(ops_))
+    return (entry.encode(),) + ops_ + (flags, n, cin, t, h, w, cout, kt, dt, lay)
+
+
+def stem_kernel_name(entry, *args):
+    """Instantiation the stem entry point `entry` would launch for its positional arguments `args` (C ABI order, the stream
+    excluded; no launch, no GPU needed).  Raises where the entry refuses the launch."""
+    buf = C.create_string_buffer(128)
+    rc = load().x3d_stem_kernel_name(*stem_launch_query(entry, args), buf, 128)
+    if rc != 0:
+        raise X3DHipError(load().x3d_last_error().decode())
+    return buf.value.decode()
+
+
 def kernel_name(args):
     """pw_kernel_name / dw3d_kernel_name by struct type."""
     return dw3d_kernel_name(args) if isinstance(args, (Dw3dFwdArgs, Dw3dBwdArgs)) else pw_kernel_name(args)
