@@ -61,7 +61,9 @@ extern "C" {
  *   138 (additions only, no bump) x3d_softmax_xent_kd / x3d_sigmoid_bce_kd (knowledge distillation);
  *   138 (additions only, no bump) x3d_loss_scale_apply / x3d_unscale_sumsq / x3d_seg_unscale_sumsq / x3d_loss_scale_update
  *       (the fp16 loss scaler on the device);
- *   138 (additions only, no bump) x3d_stem_kernel_name (dry-run dispatch of the six stem entry points). */
+ *   138 (additions only, no bump) x3d_stem_kernel_name (dry-run dispatch of the six stem entry points);
+ *   138 (additions only, no bump) frozen BatchNorm backward: a negative count in x3d_bn_bwd_finalize / _rc and
+ *       x3d_se_bnb_bwd_args.P (values every earlier version refused; no struct changes its layout). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -147,6 +149,14 @@ int x3d_stem_kernel_name(const char* entry, const void* a, const void* b, const 
  *   eval_coef (inference): same outputs from the moving statistics.
  *   bwd_finalize: sums [C][2] = (sum g, sum g*yraw) -> coef [C][4] = (A,B,C,0) such that
  *     dYraw = A*g + B*yraw + C ; dgamma [C] += , dbeta [C] += .
+ *   FROZEN statistics (SOLVER.FREEZE_BN: a trained layer normalised with its moving statistics): the forward pass takes
+ *     scale_shift / mean_invstd from eval_coef and runs no finalize; backward, mean and invstd are constants, so
+ *     dYraw = gamma*invstd*g.  A caller asks for that form with a NEGATIVE count -- the one rule of the launches that finalize a
+ *     BatchNorm's backward pass: `count` of x3d_bn_bwd_finalize / x3d_bn_bwd_finalize_rc, and P of x3d_se_bnb_bwd_args (whose
+ *     |P| is still the points per sample).  Then A = gamma*invstd, B = C = +0 exactly (a branch, not arithmetic on a large
+ *     count), and dgamma / dbeta are the same expressions -- the same bits -- as in the batch form: invstd*(sum g*yraw -
+ *     mean*sum g) and sum g with the moving mean / invstd in mean_invstd.  count = 0 stays an error.  x3d_bn_bwd_fold (the
+ *     finalize derived by a consumer) has NO frozen form and still refuses count <= 0: give a frozen layer the launch.
  * ------------------------------------------------------------------------------------------ */
 int x3d_bn_finalize(const double* stats, double count, const float* gamma, const float* beta,
                     float* moving_mean, float* moving_var, float eps, float momentum,
@@ -283,7 +293,7 @@ int x3d_pw_fwd_tail_supported(const x3d_pw_fwd_args* a);   /* 1: the in_add / in
  * entry points refuse the field otherwise). */
 typedef struct {
   const double* sums;          /* [C][2] as x3d_bn_bwd_finalize takes them */
-  double count;
+  double count;                /* > 0 (no frozen form here: K3) */
   const float* mean_invstd;    /* [C][2] */
   const float* gamma;          /* [C] */
   float* dgamma;               /* [C] += , or NULL */
@@ -497,11 +507,12 @@ int x3d_se_fwd(const double* pool_sums, double P, const float* b_scale_shift, co
  *   dgate = s_b*S2 + t_b*S1 -> sigmoid' -> fc2^T -> relu' -> fc1^T -> dpool [N][C]
  *   dw1,db1,dw2,db2 += ; then BN_b backward over du = dv*gate + dpool/P:
  *   coef_nc [N][C][4] = (A*gate, B, C + A*dpool/P, 0) ; dgamma_b, dbeta_b += .
- * Without SE (w1 == NULL): gate = 1, dpool = 0. */
+ * Without SE (w1 == NULL): gate = 1, dpool = 0.
+ * P < 0: BN_b with frozen statistics (K3), |P| points per sample: coef_nc = (A*gate, +0, A*dpool/|P|, 0); the rest unchanged. */
 typedef struct {
   const double* nc_sums;       /* [N][C][2] */
   const double* pool_sums;     /* [N][C] (forward) or NULL without SE */
-  double P;
+  double P;                    /* points per sample; negative: frozen statistics */
   const float* b_scale_shift;  /* [C][2] */
   const float* b_mean_invstd;  /* [C][2] */
   const float* gamma_b;        /* [C] */

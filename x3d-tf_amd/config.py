@@ -135,7 +135,7 @@ def get_default_config():
     """Defaults with the keys and values of reference configs/default.py:3-140, plus DATA.MULTI_LABEL and
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA;
-    LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL: fine-tuning),
+    LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL / FREEZE_BN: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
     DISTILL.* (knowledge distillation against a teacher's logits)."""
@@ -183,11 +183,12 @@ def get_default_config():
     # factor], ...] on top of it, the longest matching prefix wins; FREEZE: name prefixes of the tensors the solver step leaves
     # alone; FREEZE_EVAL (freeze_eval_settings): the frozen PREFIX of the network -- the stem and the residual blocks behind it,
     # as far as every trainable tensor is frozen -- runs in inference form during training (moving statistics, nothing kept)
-    # and the backward pass ends above it.  DEVICE_LOSS_SCALE (device_loss_scale_settings): the dynamic fp16 loss scaler lives
+    # and the backward pass ends above it.  FREEZE_BN (freeze_bn_settings): name prefixes of BatchNorm layers that normalise with
+    # their moving statistics while training, and leave them alone, though their layers still train.  DEVICE_LOSS_SCALE (device_loss_scale_settings): the dynamic fp16 loss scaler lives
     # in device memory and the training step reads nothing back (inert with a fixed scale or none).  The section knows the
-    # five keys without holding them: its items stay the four above until one is set.
+    # six keys without holding them: its items stay the four above until one is set.
     c.SOLVER = CfgNode(dict(CLIP_GRAD_L2NORM=0.0, ACCUM_STEPS=1, EMA_DECAY=0.0, EMA_EVAL=True),
-                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[], FREEZE_EVAL=False, DEVICE_LOSS_SCALE=False))
+                       optional=dict(LAYER_DECAY=1.0, LR_MULT=[], FREEZE=[], FREEZE_EVAL=False, FREEZE_BN=[], DEVICE_LOSS_SCALE=False))
     # the layer-wise optimizers (TRAIN.OPTIMIZER = lars | adamw | lamb; inert for sgd / adam).  LARS (PySlowFast's SOLVER.LARS_ON):
     # trust coefficient eta, the eps of its denominator, LARC clipping q <- min(q / lr, 1).  WEIGHT_DECAY: the DECOUPLED decay
     # of adamw / lamb (they ignore NETWORK.WEIGHT_DECAY); LAMB_EPS: the eps of LAMB's denominator
@@ -222,6 +223,7 @@ def get_config(name, overrides=None, freeze=True):
     solver_settings(cfg)
     finetune_settings(cfg)
     freeze_eval_settings(cfg)
+    freeze_bn_settings(cfg)
     device_loss_scale_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
@@ -452,6 +454,19 @@ def freeze_eval_settings(cfg) -> bool:
     if not isinstance(on, bool):
         raise ValueError(f"SOLVER.FREEZE_EVAL must be a bool, not {on!r}")
     return on
+
+
+def freeze_bn_settings(cfg) -> tuple:
+    """cfg.SOLVER.FREEZE_BN as a tuple of name prefixes (() for a config tree without the key or the section): the BatchNorm
+    layers whose name -- the part in front of `/gamma` -- starts with one of them normalise with their moving statistics in a
+    training step and do not update them (PySlowFast's MODEL.FROZEN_BN, detectron2's FrozenBatchNorm); [""] is every layer.
+    Whether gamma and beta are updated stays SOLVER.FREEZE's business.  ValueError for anything that is not a list of strings;
+    whether a prefix matches a layer is the model's to check (finetune.frozen_bn_layers): it needs the architecture."""
+    sv = getattr(cfg, "SOLVER", None)
+    names = [] if sv is None else getattr(sv, "FREEZE_BN", [])
+    if not isinstance(names, (list, tuple)) or not all(isinstance(f, str) for f in names):
+        raise ValueError(f"SOLVER.FREEZE_BN must be a list of BatchNorm name prefixes (str), not {names!r}")
+    return tuple(names)
 
 
 def device_loss_scale_settings(cfg) -> bool:

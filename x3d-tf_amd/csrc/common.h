@@ -337,6 +337,27 @@ __device__ __forceinline__ void bn_bwd_coefs(const double* __restrict__ sums, do
   B = (float)Bd;
   C = (float)(-k1 * dbe / count - Bd * mean);
 }
+// FROZEN statistics (include/x3d_hip.h K3): mean / invstd in `mi` are constants (the moving statistics), not functions of the
+// batch, so dY = k1*g -- A = k1, B = C = +0; dgamma / dbeta by the statements of bn_bwd_coefs (the same bits).  The finalize
+// LAUNCHES take it (bn_bwd_coefs_signed: count < 0); the consumers that derive their table themselves (bn_bwd_coef_load) do not
+// -- a plan records the launch for a frozen layer.
+__device__ __forceinline__ void bn_bwd_coefs_frozen(const double* __restrict__ sums, const float* __restrict__ mi,
+                                                    const float* __restrict__ gamma, int c, float& A, float& B, float& C, double& dga,
+                                                    double& dbe) {
+  const double mean = mi[c * 2], invstd = mi[c * 2 + 1];
+  dbe = sums[c * 2];
+  dga = (sums[c * 2 + 1] - mean * dbe) * invstd;
+  const double k1 = (double)gamma[c] * invstd;
+  A = (float)k1;
+  B = 0.f;
+  C = 0.f;
+}
+__device__ __forceinline__ void bn_bwd_coefs_signed(const double* __restrict__ sums, double count, const float* __restrict__ mi,
+                                                    const float* __restrict__ gamma, int c, float& A, float& B, float& C, double& dga,
+                                                    double& dbe) {
+  if (count < 0.0) bn_bwd_coefs_frozen(sums, mi, gamma, c, A, B, C, dga, dbe);
+  else bn_bwd_coefs(sums, count, mi, gamma, c, A, B, C, dga, dbe);
+}
 // by-value copy of x3d_bn_bwd_fold for kernel arguments (sums == NULL: off, the table `coef` is read)
 struct BnBwdFold { const double* sums; double count; const float* mi; const float* gamma; float* dgamma; float* dbeta; float* coef_out; };
 static inline BnBwdFold bn_bwd_fold_arg(const x3d_bn_bwd_fold* f) {

@@ -32,7 +32,7 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums, double c
   if (c >= C) return;
   float A, B, Cc;
   double dga, dbe;
-  bn_bwd_coefs(sums, count, mi, gamma, c, A, B, Cc, dga, dbe);     // (common.h: the one definition)
+  bn_bwd_coefs_signed(sums, count, mi, gamma, c, A, B, Cc, dga, dbe);     // (common.h: the one definition; count < 0: frozen statistics)
   coef[c * 4] = A;
   coef[c * 4 + 1] = B;
   coef[c * 4 + 2] = Cc;
@@ -80,7 +80,7 @@ extern "C" int x3d_bn_eval_coef_batched(const x3d_bn_eval_item* items, int n_ite
 extern "C" int x3d_bn_bwd_finalize(const double* sums, double count, const float* mean_invstd,
                                    const float* gamma, float* coef, float* dgamma, float* dbeta, int C,
                                    void* stream) {
-  X3D_REQUIRE(sums && mean_invstd && gamma && coef && dgamma && dbeta && C > 0 && count > 0, "bn_bwd_finalize: bad args");
+  X3D_REQUIRE(sums && mean_invstd && gamma && coef && dgamma && dbeta && C > 0 && count != 0, "bn_bwd_finalize: bad args");      // (count < 0: frozen statistics)
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, sums, count,
                      mean_invstd, gamma, coef, dgamma, dbeta, C);
   X3D_LAUNCH_CHECK("bn_bwd_finalize");

@@ -638,14 +638,11 @@ __global__ __launch_bounds__(256) void rc_finalize_kernel(const RcFinalizeArgs a
     a.f_dw[i] += (float)v;
     return;
   }
-  // the finalize (the arithmetic of bn_bwd_finalize_kernel, elem.hip), every prepare workgroup for itself
+  // the finalize (bn_bwd_coefs_signed, common.h: the one definition, or its frozen form), every prepare workgroup for itself
   for (int c = threadIdx.x; c < a.C; c += 256) {
-    const double mean = a.mi[c * 2], invstd = a.mi[c * 2 + 1];
-    const double dbe = a.sums[c * 2];
-    const double dga = (a.sums[c * 2 + 1] - mean * dbe) * invstd;
-    const double k1 = (double)a.gamma[c] * invstd;
-    const double B = -k1 * invstd * dga / a.count;
-    const float fA = (float)k1, fB = (float)B, fC = (float)(-k1 * dbe / a.count - B * mean);
+    float fA, fB, fC;
+    double dga, dbe;
+    bn_bwd_coefs_signed(a.sums, a.count, a.mi, a.gamma, c, fA, fB, fC, dga, dbe);
     if (a.w) { cf[c * 4] = fA; cf[c * 4 + 1] = fB; cf[c * 4 + 2] = fC; cf[c * 4 + 3] = 0.f; }
     if (blockIdx.x == 0) {
       a.coef[c * 4] = fA; a.coef[c * 4 + 1] = fB; a.coef[c * 4 + 2] = fC; a.coef[c * 4 + 3] = 0.f;
@@ -663,7 +660,7 @@ extern "C" int x3d_bn_bwd_finalize_rc(const double* sums, double count, const fl
                                       float* dgamma, float* dbeta, int C, const float* w, void* rc_panel, float* rc_c0, int Cin,
                                       const float* fin_sums, const float* fin_w, const float* fin_coef, float* fin_dw, int fin_Cout,
                                       int fin_Cin, int dtype, void* stream) {
-  X3D_REQUIRE(sums && mean_invstd && gamma && coef && dgamma && dbeta && C > 0 && count > 0, "bn_bwd_finalize_rc: bad args");
+  X3D_REQUIRE(sums && mean_invstd && gamma && coef && dgamma && dbeta && C > 0 && count != 0, "bn_bwd_finalize_rc: bad args");   // (count < 0: frozen statistics)
   X3D_REQUIRE(x3d_is_half(dtype), "bn_bwd_finalize_rc: 16-bit storage types only");
   RcFinalizeArgs a;
   memset(&a, 0, sizeof(a));

@@ -196,9 +196,11 @@ __global__ __launch_bounds__(256) void se_bwd_kernel(const x3d_se_bnb_bwd_args a
 //   dw2[c][j] += sum_n dz2[n][c]*hidden[n][j]    db2[c] += sum_n dz2[n][c]
 //   dw1[j][c] += sum_n dz1[n][j]*pooled[n][c]    db1[j]  += sum_n dz1[n][j]   (workgroup 0)
 // Each gradient element has exactly one writer, so the += are plain read-modify-writes.
+// frozen (x3d_se_bnb_bwd_args P < 0; a.P holds |P| here): BN_b normalised with constants, dYraw = k1 * du -- the per-(n, c) table is
+// (k1*gate, +0, k1*dpool/P, 0); dgamma_b / dbeta_b and the SE part are the same expressions.
 // With SE the workgroup has FOUR waves: wave 0 does the BatchNorm part, and all four split the sequential pass over the samples
 // of the SE weight gradients (64 dependent rounds of loads in one wave were ~12 of the kernel's ~16 us on the 432-channel layers)
-__global__ __launch_bounds__(256) void bnb_bwd_kernel(const x3d_se_bnb_bwd_args a, int has_se, int nb0) {
+__global__ __launch_bounds__(256) void bnb_bwd_kernel(const x3d_se_bnb_bwd_args a, int has_se, int nb0, int frozen) {
   __shared__ float part[4][3][64];
   if ((int)blockIdx.x >= a.C) {        // extra workgroups: the weight-gradient slabs of earlier launches (a.reduce)
     __shared__ float rpart[16][16][4];
@@ -225,8 +227,8 @@ __global__ __launch_bounds__(256) void bnb_bwd_kernel(const x3d_se_bnb_bwd_args 
     const double mean = a.b_mean_invstd[c * 2], invstd = a.b_mean_invstd[c * 2 + 1];
     const double dga = (sdub - mean * sdu) * invstd;
     const double k1 = (double)a.gamma_b[c] * invstd;
-    const double B = -k1 * invstd * dga / count;
-    const double Cc = -k1 * sdu / count - B * mean;
+    const double B = frozen ? 0.0 : -k1 * invstd * dga / count;
+    const double Cc = frozen ? 0.0 : -k1 * sdu / count - B * mean;
     if (lane == 0) {
       a.dgamma_b[c] += (float)dga;
       a.dbeta_b[c] += (float)sdu;
@@ -280,8 +282,13 @@ __global__ __launch_bounds__(256) void bnb_bwd_kernel(const x3d_se_bnb_bwd_args 
   }
 }
 
-extern "C" int x3d_se_bnb_bwd(const x3d_se_bnb_bwd_args* a, void* stream) {
-  X3D_REQUIRE(a && a->nc_sums && a->b_scale_shift && a->b_mean_invstd && a->gamma_b && a->dgamma_b &&
+extern "C" int x3d_se_bnb_bwd(const x3d_se_bnb_bwd_args* a_, void* stream) {
+  X3D_REQUIRE(a_ != nullptr, "se_bnb_bwd: null pointer");
+  x3d_se_bnb_bwd_args copy = *a_;
+  const int frozen = copy.P < 0;        // frozen statistics of BN_b (the sign of P says so; the kernels see |P|)
+  if (frozen) copy.P = -copy.P;
+  const x3d_se_bnb_bwd_args* a = &copy;
+  X3D_REQUIRE(a->nc_sums && a->b_scale_shift && a->b_mean_invstd && a->gamma_b && a->dgamma_b &&
                   a->dbeta_b && a->coef_nc, "se_bnb_bwd: null pointer");
   X3D_REQUIRE(a->N > 0 && a->C > 0 && a->C <= SE_MAXC && a->P > 0, "se_bnb_bwd: bad extents");
   const int has_se = a->w1 != nullptr;
@@ -295,7 +302,7 @@ extern "C" int x3d_se_bnb_bwd(const x3d_se_bnb_bwd_args* a, void* stream) {
   }
   X3D_REQUIRE(dw_reduce_job_ok(a->reduce[0]) && dw_reduce_job_ok(a->reduce[1]), "se_bnb_bwd: bad reduce job (elems % 4 == 0, 16-byte aligned slab, dw)");
   const int nb0 = dw_reduce_blocks(a->reduce[0]), nb1 = dw_reduce_blocks(a->reduce[1]);
-  hipLaunchKernelGGL(bnb_bwd_kernel, dim3(a->C + nb0 + nb1), dim3((has_se || nb0 + nb1) ? 256 : 64), 0, st, *a, has_se, nb0);
+  hipLaunchKernelGGL(bnb_bwd_kernel, dim3(a->C + nb0 + nb1), dim3((has_se || nb0 + nb1) ? 256 : 64), 0, st, *a, has_se, nb0, frozen);
   X3D_LAUNCH_CHECK("bnb_bwd");
   return X3D_OK;
 }

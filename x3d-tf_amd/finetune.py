@@ -23,7 +23,11 @@ dropped by NETWORK.DROP_PATH_RATE; nothing kept for a backward pass -- and the b
 above the prefix, with that unit's weight gradients: no gradient of a prefix tensor is computed, its slice of `flat_grads`
 stays at the zero the step starts from (data parallelism reduces those zeros: the buckets and their order do not change).
 conv5, bn5 and the dense head are never part of the prefix.  Frozen tensors OUTSIDE the prefix keep the behaviour above
-(gradient computed, batch statistics), and the regularisation loss is unchanged either way."""
+(gradient computed, batch statistics), and the regularisation loss is unchanged either way.
+
+SOLVER.FREEZE_BN (`frozen_bn_layers`) is about BatchNorm layers, trained or not, anywhere in the network: a named layer normalises
+with its moving statistics in a training step, does not update them, and its backward pass treats them as the constants they then
+are (dYraw = gamma * invstd * g).  gamma and beta still receive gradients; whether they move is FREEZE's."""
 import math
 
 import numpy as np
@@ -70,6 +74,17 @@ def frozen_prefix(arch, param_specs, frozen_names) -> int:
     `arch.blocks` -- in which every trainable tensor of every unit is in `frozen_names`.  0: the stem is not fully frozen;
     1: the stem only; L + 1: the stem and all blocks.  conv5, bn5 and the dense head are never part of it."""
     return _prefix_break(arch, param_specs, frozen_names)[0]
+
+
+def frozen_bn_layers(param_specs, prefixes):
+    """The BatchNorm layers SOLVER.FREEZE_BN names, in layout order: a layer is the part of its `gamma`'s name in front of
+    `/gamma` (`conv1/bn`, `stages/2/blocks/0/bottleneck/bn_a`, ...), matched when it starts with one of `prefixes`; "" matches
+    every layer.  ValueError for a prefix that matches no BatchNorm layer."""
+    layers = [s.name[:-len("/gamma")] for s in param_specs if s.name.endswith("/gamma")]
+    for p in prefixes:
+        if not any(q.startswith(p) for q in layers):
+            raise ValueError(f"SOLVER.FREEZE_BN: prefix {p!r} matches no BatchNorm layer")
+    return tuple(q for q in layers if any(q.startswith(p) for p in prefixes))
 
 
 def flat_segments(param_specs):

@@ -222,6 +222,7 @@ class X3D:
         self._ft = None
         self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
         self.frozen_prefix = 0     # units (stem, blocks) a training plan records in inference form (set_finetune freeze_eval)
+        self.frozen_bn = ()        # BatchNorm layers a training plan normalises with their moving statistics (set_finetune freeze_bn)
 
     def _build_panels(self):
         """bf16 LDS-image panels of every pointwise-conv weight (x3d_pw_pack_weights): refreshed by one launch
@@ -395,9 +396,12 @@ class X3D:
 
     def _plan(self, n, t, h, w, training, logits_only=False) -> _Plan:
         """logits_only: the inference list that ends with fc2 (`logits`), a plan of its own beside the `call` one"""
-        # (a training plan is recorded for one frozen prefix: changing it never reuses a stale plan)
+        # (a training plan is recorded for one frozen prefix and one set of frozen BatchNorm layers: changing either never reuses
+        # a stale plan)
         key = (n, t, h, w, False, "logits") if logits_only else ((n, t, h, w, True, self.frozen_prefix) if training and self.frozen_prefix
                                                                   else (n, t, h, w, bool(training)))
+        if training and self.frozen_bn and not logits_only:
+            key += (self.frozen_bn,)
         pl = self._plans.pop(key, None)
         if pl is None:
             self.release_plans(keep=self.MAX_PLANS - 1)
@@ -770,7 +774,7 @@ class X3D:
             self.trust_ratios = torch.ones(self._seg_table.nseg, dtype=torch.float32, device=self.device)
         return self._seg_table
 
-    def set_finetune(self, freeze=(), lr_mult=(), layer_decay=1.0, freeze_eval=False):
+    def set_finetune(self, freeze=(), lr_mult=(), layer_decay=1.0, freeze_eval=False, freeze_bn=()):
         """Fine-tuning (SOLVER.FREEZE / LR_MULT / LAYER_DECAY, finetune.py): freeze the trainable tensors whose names start with
         a prefix of `freeze`, and give every other ("tuned") tensor the learning rate lr * scale, scale = layer_decay ** (D -
         depth group) * factor of the longest `lr_mult` prefix ([(prefix, factor), ...]).  Builds and keeps the chunk table of
@@ -786,8 +790,16 @@ class X3D:
         those units as training=False runs them (moving statistics, not updated; never dropped by NETWORK.DROP_PATH_RATE;
         nothing kept) and end their backward list at the first unit above them: the prefix tensors' slices of `flat_grads`
         stay at the zero forward_backward writes.  Frozen tensors outside the prefix behave as described above.  ValueError
-        when the stem is not fully frozen (an empty prefix), naming the first tensor that breaks the run."""
-        from .finetune import _prefix_break, lr_scales
+        when the stem is not fully frozen (an empty prefix), naming the first tensor that breaks the run.
+        freeze_bn (SOLVER.FREEZE_BN): name prefixes of BatchNorm layers (finetune.frozen_bn_layers; "" = every layer) that training
+        plans recorded from now on normalise with their moving statistics, which the step then leaves bit-identical; their
+        backward pass is dYraw = gamma * invstd * g, gamma and beta still get their gradients.  Independent of
+        the other arguments: the layers it names may be trained or frozen, inside or outside a prefix (a prefix layer is in that
+        form anyway).  `frozen_bn`: the layers, in layout order.  ValueError for a prefix that matches no BatchNorm layer."""
+        from .finetune import _prefix_break, frozen_bn_layers, lr_scales
+        if isinstance(freeze_bn, str) or not all(isinstance(p, str) for p in freeze_bn):
+            raise ValueError(f"set_finetune: freeze_bn must be a sequence of name prefixes (str), not {freeze_bn!r}")
+        fbn = frozen_bn_layers([self.specs[n] for n in self.param_order], tuple(freeze_bn))
         st = FinetuneSettings(float(layer_decay), tuple((str(p), float(f)) for p, f in lr_mult), tuple(freeze))
         if not 0.0 < st.layer_decay <= 1.0 or not all(f > 0.0 and f < float("inf") for _, f in st.lr_mult):
             raise ValueError(f"set_finetune: layer_decay must lie in (0, 1] and every factor must be finite and > 0, not "
@@ -795,7 +807,7 @@ class X3D:
         if st == FinetuneSettings(1.0, (), ()):
             if freeze_eval:
                 raise ValueError("set_finetune: freeze_eval needs a `freeze` list that freezes the stem (conv1/) at least")
-            self._ft, self.frozen_prefix = None, 0
+            self._ft, self.frozen_prefix, self.frozen_bn = None, 0, fbn
             self.tuned_segments, self.lr_scales, self.frozen_names = list(self.segments), {s.name: 1.0 for s in self.segments}, []
             return
         tuned, scales, frozen = lr_scales(self.arch, [self.specs[n] for n in self.param_order], st)
@@ -814,7 +826,7 @@ class X3D:
             ft.scale = torch.tensor(scales, dtype=torch.float32).to(self.device)
             ft.partials = torch.empty(2 * ft.table.nchunk, dtype=torch.float64, device=self.device)
             ft.trust_ratios = torch.ones(ft.table.nseg, dtype=torch.float32, device=self.device)
-        self._ft, self.frozen_prefix = ft, k
+        self._ft, self.frozen_prefix, self.frozen_bn = ft, k, fbn
         self.tuned_segments, self.lr_scales, self.frozen_names = tuned, {s.name: c for s, c in zip(tuned, scales)}, frozen
 
     def grads_finite(self) -> bool:

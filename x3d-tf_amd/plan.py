@@ -8,6 +8,10 @@ apart what is not (the `a` conv with the deferred residual tail against the `c` 
 A CUT training plan (``record_training(..., frozen_prefix=k)``, SOLVER.FREEZE_EVAL) holds both forms: the frozen prefix -- the
 stem and the first k - 1 blocks -- as the inference recorder records it, everything above as the training recorder does, and
 a backward list that ends at the seam between the two (``record_backward(..., first_unit=k)``).
+A FROZEN BatchNorm layer of the trained region (SOLVER.FREEZE_BN, ``model.frozen_bn``) keeps the training
+recorder's launches around it but takes its coefficients from the moving statistics -- the same batched launch at slot 0 --
+has no finalize launch and no statistics accumulator, and its backward finalize is a launch in the frozen form (a negative
+count), never derived by its consumers.
 
 fp64 accumulators are zeroed once per step in ONE flat buffer that exists only after recording, so a launch that takes the
 address of one records a deferred address instead (``_Plan.acc`` for a positional argument, ``_Plan.defer`` for struct
@@ -110,7 +114,9 @@ class BNBuf:
     """The buffers of one BatchNorm layer.  ss / mi: scale-shift and mean-invstd tables [C][2]; training plans add the fp64
     statistics (`stats`: forward sums, the library's replicated layout; `bsums`: backward sums) as accumulator handles, the
     backward coefficient table `coef` [C][4] and `count`, the elements per channel behind `stats` (set where the layer's
-    finalize is recorded; read by precise_bn_table)."""
+    finalize is recorded; read by precise_bn_table).  frozen: a layer of the trained region that normalises with its moving
+    statistics (SOLVER.FREEZE_BN) -- ss / mi come from the batched eval-coefficient launch, `stats` stays None (its producer
+    accumulates nothing), and the backward sums and table are kept as for any trained layer."""
     prefix: str
     c: int
     ss: Any = None
@@ -119,6 +125,7 @@ class BNBuf:
     bsums: Optional[int] = None
     coef: Any = None
     count: Optional[int] = None
+    frozen: bool = False
 
 
 @dataclass(kw_only=True)
@@ -205,7 +212,9 @@ class _Plan:
         # the NEXT layer it registers (the recorder flips it at the seam); prefix_bn: the layers registered in inference form
         self.frozen_prefix = int(frozen_prefix) if training else 0
         self.bn_eval = (not self.training) or self.frozen_prefix > 0
-        self.prefix_bn: List[str] = []
+        # SOLVER.FREEZE_BN: layers registered in TRAINING form that take their coefficients from the moving statistics all the same
+        self.frozen_bn = frozenset(model.frozen_bn) if self.training else frozenset()
+        self.prefix_bn: List[str] = []     # (... and those: every layer of a training plan that keeps no batch statistics)
         self.seam = None               # the output of the last prefix unit: a buffer of its own, read again by the backward pass
         self.prefix_bufs: List = []    # the ping-pong / scratch buffers the prefix units share (nothing of them outlives the prefix)
         self.fwd: List = []
@@ -262,9 +271,14 @@ class _Plan:
         """Buffers of a BatchNorm layer, in the form `bn_eval` names for it.  Inference form (every layer of an inference plan,
         the frozen prefix of a cut training plan): its coefficients come from the moving statistics, every such layer's in
         ONE launch at the head of the forward list (x3d_bn_eval_coef_batched over bn_eval_items); it keeps no statistics and
-        is not in bn_layers."""
+        is not in bn_layers.  A frozen layer of the trained region (frozen_bn) is both: coefficients as in inference form, from
+        the same launch, and the backward sums and table of a trained layer -- but no forward statistics."""
         b = BNBuf(prefix, c, self.f32(c, 2), self.f32(c, 2))
-        if not self.bn_eval:
+        b.frozen = not self.bn_eval and prefix in self.frozen_bn
+        if b.frozen:
+            b.bsums = self.acc64(c, 2)
+            b.coef = self.f32(c, 4)
+        if not self.bn_eval and not b.frozen:
             # forward statistics: the library's replicated layout (x3d_stats_replicas copies, x3d_stats_stride apart)
             b.stats = self.acc64(self.model._stats_r * int(self.lib.x3d_stats_stride(c)))
             b.bsums = self.acc64(c, 2)
@@ -660,6 +674,8 @@ def record_training(model, n, t, h, w, frozen_prefix=0) -> _Plan:
     pl = _Plan(model, n, t, h, w, True, k)
     dt = hip.dtype_code(model.dtype)
     F = pl.fwd
+    if k or pl.frozen_bn:
+        F.append(None)   # slot 0: x3d_bn_eval_coef_batched over the prefix layers and the frozen layers above them, filled in below
     # ---- input + stem --------------------------------------------------------------------
     _bind_stem_input(model, pl, dt)
     h1, w1, geo = _geometry(a, h, w)
@@ -713,7 +729,7 @@ def record_training(model, n, t, h, w, frozen_prefix=0) -> _Plan:
         pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
                a.num_classes)
     pl.install_backward(record_backward(model, pl, model.opt, first_unit=k))
-    if k:
+    if F[0] is None:
         items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
         pl.bn_eval_table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(model.device)
         F[0] = ("x3d_bn_eval_coef_batched", pl.lib.x3d_bn_eval_coef_batched,
@@ -746,8 +762,7 @@ def _rec_frozen_prefix(model, pl, k, h1, w1, geo, dt):
     launches of the first trained unit read it again during the backward pass, so it has a buffer of its own (pl.seam) that
     nothing later writes.  Returns it, shaped."""
     a, n, t, F = model.arch, pl.n, pl.t, pl.fwd
-    assert pl.bn_eval and not F
-    F.append(None)   # slot 0: x3d_bn_eval_coef_batched over the prefix layers
+    assert pl.bn_eval and F == [None]   # slot 0: x3d_bn_eval_coef_batched over the prefix layers (record_training reserved it)
     units = list(zip(a.blocks, geo))[:k - 1]
     outs = [(a.c1, h1, w1)] + [(b.cout, g[2], g[3]) for b, g in units]          # (channels, h, w) of every prefix unit's output
     pl.seam = pl.act(n, outs[-1][0], t, outs[-1][1], outs[-1][2])
@@ -780,9 +795,12 @@ def _rec_frozen_prefix(model, pl, k, h1, w1, geo, dt):
 
 
 def _rec_bn_finalize(model, pl, b: BNBuf, count):
-    """after the producer kernel: turn the batch statistics into scale / shift (and update the moving statistics)"""
+    """after the producer kernel: turn the batch statistics into scale / shift (and update the moving statistics).  A frozen
+    layer: no launch -- its coefficients are in place since slot 0, its moving statistics are not to be touched"""
     p, a = model.params, model.arch
     b.count = int(count)
+    if b.frozen:
+        return
     pl.rec(pl.fwd, "x3d_bn_finalize", pl.acc(b.stats), float(count), p[f"{b.prefix}/gamma"], p[f"{b.prefix}/beta"],
            p[f"{b.prefix}/moving_mean"], p[f"{b.prefix}/moving_variance"], float(a.bn_eps), float(a.bn_momentum), 1,
            b.ss, b.mi, b.c)
@@ -960,6 +978,11 @@ def _rec_bn_bwd_finalize(model, pl, s, bn, count, c, prep=None, consumers=None):
     recomputed-output launch that follows."""
     Bk = s.out.launches
     gamma, dgamma, dbeta = model.params[f"{bn.prefix}/gamma"], model.grads[f"{bn.prefix}/gamma"], model.grads[f"{bn.prefix}/beta"]
+    if bn.frozen:
+        # a negative count asks the two finalize LAUNCHES for the frozen rule: A = gamma * invstd, B = C = +0 (x3d_hip.h K3).
+        # The consumers that derive their table themselves (coef_fold) have no such form: a frozen layer gets the launch.  The
+        # recomputed-output jobs take the table as data and hold for B = C = 0 (DESIGN section 22)
+        count, consumers = -count, None
     if prep is None and s.pending_fin is None and _fold_bn_bwd(pl, s, bn, count, gamma, dgamma, dbeta, consumers):
         return          # (derived by the consumers: no launch)
     fin, s.pending_fin = s.pending_fin, None
@@ -1134,7 +1157,7 @@ def _bwd_se_bnb(model, pl, s, B, R, c_job):
     b, p, g = B.spec, model.params, model.grads
     q = f"{block_prefix(b)}/bottleneck"
     se = hip.SeBnbBwdArgs(
-        None, None, float(pl.t * B.ho * B.wo), _p(B.bn_b.ss), _p(B.bn_b.mi), _p(p[f"{q}/bn_b/gamma"]),
+        None, None, float(pl.t * B.ho * B.wo) * (-1.0 if B.bn_b.frozen else 1.0), _p(B.bn_b.ss), _p(B.bn_b.mi), _p(p[f"{q}/bn_b/gamma"]),
         _p(p.get(f"{q}/se_fc1/kernel")), _p(p.get(f"{q}/se_fc1/bias")), _p(p.get(f"{q}/se_fc2/kernel")),
         _p(p.get(f"{q}/se_fc2/bias")), _p(B.gate), _p(B.hidden), _p(g.get(f"{q}/se_fc1/kernel")),
         _p(g.get(f"{q}/se_fc1/bias")), _p(g.get(f"{q}/se_fc2/kernel")), _p(g.get(f"{q}/se_fc2/bias")),

@@ -16,6 +16,16 @@ from . import dist as xdist
 from . import hip
 
 
+def recomputed_layers(model):
+    """The BatchNorm layers update_bn_stats recomputes: the model's, in layout order, less those of a frozen prefix in inference
+    form and the frozen layers (X3D.set_finetune freeze_eval / freeze_bn) -- the rows of every training plan's table."""
+    from .finetune import depth_groups
+    group, _ = depth_groups(model.arch)
+    held = set(getattr(model, "frozen_bn", ()))
+    k = getattr(model, "frozen_prefix", 0)
+    return [q for q in model.precise_bn_layout().prefixes if q not in held and group(q + "/gamma") >= k]
+
+
 def update_bn_stats(model, batches, num_batches, group=None) -> int:
     """Overwrites the moving statistics of every BatchNorm layer of `model` with the exact statistics of the first `num_batches`
     items of `batches`; returns how many were used (an iterable that ends early is allowed, an empty one is not).
@@ -36,10 +46,14 @@ def update_bn_stats(model, batches, num_batches, group=None) -> int:
     A model with a frozen prefix in inference form (X3D.set_finetune freeze_eval): its training plans keep no statistics for
     the prefix layers, and their tables have rows for the layers of the trained region only -- the same rows on every plan and
     every rank, since the prefix is the model's, so the two launches and the all-reduce see one subset.  The prefix's moving
-    statistics are neither read nor written."""
+    statistics are neither read nor written.  The same holds for frozen BatchNorm layers (set_finetune freeze_bn): no rows, their
+    moving statistics untouched.  With no layer left to recompute -- every layer frozen, or frozen or in the prefix -- nothing
+    runs, `batches` is not drawn from, and the result is 0."""
     if isinstance(num_batches, bool) or not isinstance(num_batches, int) or num_batches < 1:
         raise ValueError(f"num_batches must be an integer >= 1, not {num_batches!r}")
     lay = model.precise_bn_layout()
+    if len(recomputed_layers(model)) == 0:
+        return 0
     nlayers = None                            # rows of the plans' tables: the model's layers, less a frozen prefix in inference form
     pooled = torch.zeros(lay.pooled_size, dtype=torch.float64, device=model.device)
     dp_state = model._dp_state.clone() if getattr(model, "_dp_state", None) is not None else None

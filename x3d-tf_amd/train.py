@@ -12,8 +12,8 @@ import torch
 
 from . import dist as xdist
 from . import ops
-from .config import (OPTIMIZERS, device_loss_scale_settings, distill_settings, finetune_settings, freeze_eval_settings, mix_settings,
-                     optim_settings, precise_bn_settings, solver_settings)
+from .config import (OPTIMIZERS, device_loss_scale_settings, distill_settings, finetune_settings, freeze_bn_settings, freeze_eval_settings,
+                     mix_settings, optim_settings, precise_bn_settings, solver_settings)
 from .mix import NO_MIX, draw_mix_params
 from .solver import RULES
 
@@ -209,10 +209,13 @@ class Trainer:
         # SOLVER.FREEZE_EVAL: the frozen prefix also runs in inference form and the backward pass ends above it.  The buckets
         # and the hooks are what they were -- the prefix's buckets carry the zeros the step starts from
         self.finetune = finetune_settings(cfg)
+        # SOLVER.FREEZE_BN: the named BatchNorm layers normalise with their moving statistics, which no step then writes
         self.freeze_eval = freeze_eval_settings(cfg)
-        if self.finetune != (1.0, (), ()) or self.freeze_eval:
+        self.freeze_bn = freeze_bn_settings(cfg)
+        if self.finetune != (1.0, (), ()) or self.freeze_eval or self.freeze_bn:
             model.set_finetune(freeze=self.finetune.freeze, lr_mult=self.finetune.lr_mult, layer_decay=self.finetune.layer_decay,
-                               **(dict(freeze_eval=True) if self.freeze_eval else {}))
+                               **(dict(freeze_eval=True) if self.freeze_eval else {}),
+                               **(dict(freeze_bn=self.freeze_bn) if self.freeze_bn else {}))
         # weight EMA: trainable block + moving statistics, laid out as flat_params; starts from the (broadcast) weights
         self.ema = model.flat_params.clone() if self.solver.ema_decay > 0.0 else None
         # stochastic depth (NETWORK.DROP_PATH_RATE): the tables are drawn on the device from (seed, step); rank r seeds with
