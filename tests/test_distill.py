@@ -155,7 +155,7 @@ def test_a_distilled_call_swaps_only_the_head_slot_and_back(head):
     multi = head == "multi"
     pl = _dry_plan(x.get_config("XS", BASE + (["DATA.MULTI_LABEL", True, "NETWORK.NUM_CLASSES", 157] if multi else [])))
     slot = pl.grad_scale_slot
-    assert pl.teacher is None and pl.kd_rows is None and pl._head_kd == {}        # nothing for distillation yet
+    assert pl.teacher is None and pl.kd_rows is None and list(pl._heads) == [(False, False)]   # nothing for distillation yet
     soft = head == "targets"
     pl.use_soft_targets(soft)
     f0, b0 = _names(pl)

@@ -1,4 +1,4 @@
-// Classification head on pooled vectors (reference model.py:95-111,119-127; loss train.py:104) and the
+// Classification head on pooled vectors (reference model.py:95-111,119-127; the losses, train.py:104: loss.hip) and the
 // loss-scaling / L2-loss helpers of the train step (the optimizer itself: solver.hip).  All fp32; sizes are [N <= a few hundred] x [432..2048] x [400].
 #include "common.h"
 
@@ -219,165 +219,6 @@ extern "C" int x3d_dense_bwd(const float* dy, const float* y, int act, const flo
   }
   hipLaunchKernelGGL(dense_bwd_dw_kernel, dim3(ceil_div(K, 256), ceil_div(M, DENSE_BM)), dim3(256), dzs_bytes, st, dy, y, act, x, mask, mask_scale, dw, db, N, K, M);
   X3D_LAUNCH_CHECK("dense_bwd_dw");
-  return X3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// softmax + Keras sparse categorical cross-entropy on probabilities.  One block per sample.
-//   p = softmax(z);  q = clip(p, 1e-7, 1-1e-7);  L = -log q_y + log sum_j q_j          [TF-3p]
-//   dL/dp_j = [1e-7 <= p_j <= 1-1e-7] * (-[j==y]/q_y + 1/sum q);   dz = p * (dL/dp - sum_k p_k dL/dp_k)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits,
-                                                           const int* __restrict__ labels, float* probs,
-                                                           float* loss_rows, float* dlogits, float grad_scale, int M) {
-  __shared__ float scratch[8];
-  __shared__ float bc[2];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const float* z = logits + (long long)n * M;
-  float mx = -INFINITY;
-  for (int j = tid; j < M; j += 256) mx = fmaxf(mx, z[j]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if ((tid & 63) == 0) scratch[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
-  __syncthreads();
-  float red[1] = {0.f};
-  for (int j = tid; j < M; j += 256) red[0] += expf(z[j] - mx);
-  block_sum<1>(red, scratch);
-  if (tid == 0) bc[0] = red[0];
-  __syncthreads();
-  const float inv = 1.f / bc[0];
-  __syncthreads();
-  const int label = labels ? labels[n] : -1;
-  float r2[2] = {0.f, 0.f};  // sum q, sum_k p_k*[in range]  (for the dz formula)
-  for (int j = tid; j < M; j += 256) {
-    const float p = expf(z[j] - mx) * inv;
-    probs[(long long)n * M + j] = p;
-    const float q = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
-    r2[0] += q;
-    r2[1] += (p >= 1e-7f && p <= 1.f - 1e-7f) ? p : 0.f;
-  }
-  if (!labels) return;
-  block_sum<2>(r2, scratch);
-  if (tid == 0) { bc[0] = r2[0]; bc[1] = r2[1]; }
-  __syncthreads();
-  const float sumq = bc[0], sum_p_in = bc[1];
-  if (label < 0 || label >= M) {
-    // out-of-range label (TF raises InvalidArgument): never index with it -- the loss row is NaN (so the step's loss is
-    // visibly non-finite) and the sample contributes no gradient
-    if (tid == 0 && loss_rows) loss_rows[n] = __builtin_nanf("");
-    if (dlogits)
-      for (int j = tid; j < M; j += 256) dlogits[(long long)n * M + j] = 0.f;
-    return;
-  }
-  const float py = expf(z[label] - mx) * inv;
-  const float qy = fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f);
-  const bool y_in = (py >= 1e-7f && py <= 1.f - 1e-7f);
-  if (tid == 0 && loss_rows) loss_rows[n] = -logf(qy) + logf(sumq);
-  if (dlogits) {
-    // inner = sum_k p_k * dL/dp_k = sum_p_in / sumq - [y in range] * p_y / q_y
-    const float inner = sum_p_in / sumq - (y_in ? py / qy : 0.f);
-    for (int j = tid; j < M; j += 256) {
-      const float p = expf(z[j] - mx) * inv;
-      const bool in = (p >= 1e-7f && p <= 1.f - 1e-7f);
-      float dldp = in ? 1.f / sumq : 0.f;
-      if (j == label && in) dldp -= 1.f / qy;
-      dlogits[(long long)n * M + j] = grad_scale * p * (dldp - inner);
-    }
-  }
-}
-
-extern "C" int x3d_softmax_xent(const float* logits, const int* labels, float* probs, float* loss_rows,
-                                float* dlogits, float grad_scale, int N, int M, void* stream) {
-  X3D_REQUIRE(logits && probs && N > 0 && M > 0, "softmax_xent: bad args");
-  X3D_REQUIRE(labels || (!loss_rows && !dlogits), "softmax_xent: loss/grad need labels");
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, labels, probs,
-                     loss_rows, dlogits, grad_scale, M);
-  X3D_LAUNCH_CHECK("softmax_xent");
-  return X3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same loss on a dense target row y (label smoothing, mixup / CutMix): Keras CategoricalCrossentropy on probabilities.
-//   S = sum_j y_j;  L = sum_j y_j * (-log q_j) + S * log sum_k q_k                                     [TF-3p]
-//   dL/dp_j = [1e-7 <= p_j <= 1-1e-7] * (-y_j / q_j + S / sum q);   dz = p * (dL/dp - sum_k p_k dL/dp_k)
-// A one-hot row gives the expressions of softmax_xent_kernel.  One block per sample, no atomics.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_xent_soft_kernel(const float* __restrict__ logits,
-                                                                const float* __restrict__ targets, float* probs,
-                                                                float* loss_rows, float* dlogits, float grad_scale, int M) {
-  __shared__ float scratch[24];
-  __shared__ float bc[6];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const float* z = logits + (long long)n * M;
-  float mx = -INFINITY;
-  for (int j = tid; j < M; j += 256) mx = fmaxf(mx, z[j]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if ((tid & 63) == 0) scratch[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
-  __syncthreads();
-  float red[1] = {0.f};
-  for (int j = tid; j < M; j += 256) red[0] += expf(z[j] - mx);
-  block_sum<1>(red, scratch);
-  if (tid == 0) bc[0] = red[0];
-  __syncthreads();
-  const float inv = 1.f / bc[0];
-  __syncthreads();
-  const float* y = targets ? targets + (long long)n * M : nullptr;
-  // sum q, sum_k p_k*[in range], S, sum y*(-log q), sum [in range]*y*p/q, #NaN targets
-  float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int j = tid; j < M; j += 256) {
-    const float p = expf(z[j] - mx) * inv;
-    probs[(long long)n * M + j] = p;
-    if (!y) continue;
-    const float q = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
-    const bool in = (p >= 1e-7f && p <= 1.f - 1e-7f);
-    const float yj = y[j];
-    r6[0] += q;
-    r6[1] += in ? p : 0.f;
-    if (yj != yj) { r6[5] += 1.f; continue; }
-    r6[2] += yj;
-    r6[3] += yj * -logf(q);
-    r6[4] += in ? yj * p / q : 0.f;
-  }
-  if (!y) return;
-  block_sum<6>(r6, scratch);
-  if (tid == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) bc[i] = r6[i];
-  }
-  __syncthreads();
-  const float sumq = bc[0], sum_p_in = bc[1], S = bc[2];
-  if (bc[5] > 0.f) {
-    // a NaN target (x3d_mix_targets writes one for a label outside [0, M)): NaN loss row, no gradient from this sample
-    if (tid == 0 && loss_rows) loss_rows[n] = __builtin_nanf("");
-    if (dlogits)
-      for (int j = tid; j < M; j += 256) dlogits[(long long)n * M + j] = 0.f;
-    return;
-  }
-  if (tid == 0 && loss_rows) loss_rows[n] = bc[3] + S * logf(sumq);
-  if (dlogits) {
-    // inner = sum_k p_k * dL/dp_k = S * sum_p_in / sumq - sum_k [in range] * y_k * p_k / q_k
-    const float inner = S * sum_p_in / sumq - bc[4];
-    for (int j = tid; j < M; j += 256) {
-      const float p = expf(z[j] - mx) * inv;
-      const bool in = (p >= 1e-7f && p <= 1.f - 1e-7f);
-      const float q = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
-      const float dldp = in ? S / sumq - y[j] / q : 0.f;
-      dlogits[(long long)n * M + j] = grad_scale * p * (dldp - inner);
-    }
-  }
-}
-
-extern "C" int x3d_softmax_xent_soft(const float* logits, const float* targets, float* probs, float* loss_rows,
-                                     float* dlogits, float grad_scale, int N, int M, void* stream) {
-  X3D_REQUIRE(logits && probs && N > 0 && M > 0, "softmax_xent_soft: bad args (N=%d M=%d)", N, M);
-  X3D_REQUIRE(targets || (!loss_rows && !dlogits), "softmax_xent_soft: loss/grad need targets");
-  X3D_REQUIRE((long long)N * M < (1LL << 31), "softmax_xent_soft: N*M = %lld >= 2^31", (long long)N * M);
-  hipLaunchKernelGGL(softmax_xent_soft_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, targets, probs,
-                     loss_rows, dlogits, grad_scale, M);
-  X3D_LAUNCH_CHECK("softmax_xent_soft");
   return X3D_OK;
 }
 

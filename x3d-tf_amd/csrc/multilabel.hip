@@ -1,62 +1,7 @@
-// Multi-label head and metric (DATA.MULTI_LABEL, Charades-style training): a sigmoid / binary cross-entropy head, the
-// element-wise max over the views of a video, and per-class average precision over a whole evaluation set.  The exact
-// rules are in include/x3d_hip.h.
+// Multi-label evaluation (DATA.MULTI_LABEL, Charades-style training): the element-wise max over the views of a video and
+// per-class average precision over a whole evaluation set.  The exact rules are in include/x3d_hip.h.  (The sigmoid / binary
+// cross-entropy head: loss.hip.)
 #include "common.h"
-
-// ------------------------------------------------------------------------------------------------
-// sigmoid + Keras BinaryCrossentropy on the logits of Dense(activation="sigmoid") (TF 2.x evaluates it in the logits
-// form [TF-3p]).  One block per row; the element terms and the row sum in fp64, summed in a fixed order (no atomics):
-//   p = sigmoid(z);  loss_row = mean_j ( max(z,0) - z*y + log1p(exp(-|z|)) );  dz = grad_scale * (p - y) / M
-// ------------------------------------------------------------------------------------------------
-#define BCE_THREADS 256
-
-__device__ __forceinline__ double sigmoid_d(double z) {
-  // exp of a non-positive argument only: no overflow for any finite z, 0 / 1 at the far ends
-  if (z >= 0.0) return 1.0 / (1.0 + exp(-z));
-  const double e = exp(z);
-  return e / (1.0 + e);
-}
-
-__global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(const float* __restrict__ logits,
-                                                                  const float* __restrict__ targets, float* probs,
-                                                                  float* loss_rows, float* dlogits, float grad_scale,
-                                                                  int M) {
-  __shared__ double part[BCE_THREADS / WAVE];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const long long row = (long long)n * M;
-  const double gs = (double)grad_scale / (double)M;
-  double acc = 0.0;
-  for (int j = tid; j < M; j += BCE_THREADS) {
-    const double z = (double)logits[row + j];
-    const double p = sigmoid_d(z);      // NaN in, NaN out
-    probs[row + j] = (float)p;
-    if (!targets) continue;
-    const double y = (double)targets[row + j];
-    // max(z, 0) written as a select: NaN must not become 0 (the -z*y and log1p terms carry it anyway)
-    acc += (z > 0.0 ? z : 0.0) - z * y + log1p(exp(-fabs(z)));
-    if (dlogits) dlogits[row + j] = (float)(gs * (p - y));
-  }
-  if (!targets || !loss_rows) return;
-  acc = wave_sum_d(acc);
-  if ((tid & 63) == 0) part[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    for (int w = 0; w < BCE_THREADS / WAVE; w++) s += part[w];
-    loss_rows[n] = (float)(s / (double)M);
-  }
-}
-
-extern "C" int x3d_sigmoid_bce(const float* logits, const float* targets, float* probs, float* loss_rows,
-                               float* dlogits, float grad_scale, int N, int M, void* stream) {
-  X3D_REQUIRE(logits && probs && N > 0 && M > 0, "sigmoid_bce: bad args (N=%d M=%d)", N, M);
-  X3D_REQUIRE(targets || (!loss_rows && !dlogits), "sigmoid_bce: loss/grad need targets");
-  X3D_REQUIRE((long long)N * M < (1LL << 31), "sigmoid_bce: N*M = %lld >= 2^31", (long long)N * M);
-  hipLaunchKernelGGL(sigmoid_bce_kernel, dim3(N), dim3(BCE_THREADS), 0, (hipStream_t)stream, logits, targets, probs,
-                     loss_rows, dlogits, grad_scale, M);
-  X3D_LAUNCH_CHECK("sigmoid_bce");
-  return X3D_OK;
-}
 
 // ------------------------------------------------------------------------------------------------
 // out[v][m] = max over `views` consecutive rows; a NaN in any view makes the output NaN (torch.amax)

@@ -583,14 +583,12 @@ class X3D:
                 got = (tuple(teacher_logits.shape), teacher_logits.dtype, teacher_logits.device) \
                     if torch.is_tensor(teacher_logits) else type(teacher_logits)
                 raise ValueError(f"teacher_logits must be a device float32 [{n}, {self.num_classes}] tensor, got {got}")
+        pl.use_soft_targets(soft, distill=kd)
         if self.multi_label:
-            pl.use_soft_targets(False, distill=kd)
             self._bind_targets(pl, labels, n)
         elif soft:
-            pl.use_soft_targets(True, distill=kd)
             self._bind_targets(pl, labels, n, what="soft")
         else:
-            pl.use_soft_targets(False, distill=kd)
             if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
                 if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
                     raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
@@ -609,23 +607,8 @@ class X3D:
         if kd and teacher_logits.data_ptr() != pl.teacher.data_ptr():
             pl.teacher.copy_(teacher_logits)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
-        if kd:
-            tail = (pl.probs.data_ptr(), pl.loss_rows.data_ptr(), pl.kd_rows.data_ptr(), pl.dlogits.data_ptr(),
-                    head_scale, kd_alpha, kd_temp, n, self.num_classes)
-            if self.multi_label:
-                hip.call("x3d_sigmoid_bce_kd", pl.logits.data_ptr(), pl.teacher.data_ptr(), pl.targets.data_ptr(), *tail)
-            else:
-                hip.call("x3d_softmax_xent_kd", pl.logits.data_ptr(), pl.teacher.data_ptr(),
-                         None if soft else pl.labels.data_ptr(), pl.targets.data_ptr() if soft else None, *tail)
-        elif self.multi_label:
-            hip.call("x3d_sigmoid_bce", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
-        elif soft:
-            hip.call("x3d_softmax_xent_soft", pl.logits.data_ptr(), pl.targets.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
-        else:
-            hip.call("x3d_softmax_xent", pl.logits.data_ptr(), pl.labels.data_ptr(), pl.probs.data_ptr(),
-                     pl.loss_rows.data_ptr(), pl.dlogits.data_ptr(), head_scale, n, self.num_classes)
+        name, args = pl.head_launch(soft, kd, head_scale, *((kd_alpha, kd_temp) if kd else ()))
+        hip.call(name, *args)
         if on_device:
             ops.loss_scale_apply(pl.dlogits.view(-1), loss_scale)
         if on_stage_done is None:

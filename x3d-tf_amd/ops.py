@@ -543,22 +543,29 @@ def _f32_2d(name, what, t, shape=None):
         raise ValueError(f"{name}: {what} must be {want} float32, got {tuple(t.shape)} {t.dtype}")
 
 
+def _loss_args(name, logits, probs, mats, rows):
+    """the tensor checks of the loss wrappers (all but softmax_xent's): logits and probs [N, M] float32, every tensor given in
+    `mats` ({what: tensor or None}) the same, every one in `rows` N float32; returns (N, M)"""
+    _f32_2d(name, "logits", logits)
+    n, m = logits.shape
+    _f32_2d(name, "probs", probs, (n, m))
+    for what, t in mats.items():
+        if t is not None:
+            _f32_2d(name, what, t, (n, m))
+    for what, t in rows.items():
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n):
+            raise ValueError(f"{name}: {what} must be {n} float32, got {t.numel()} {t.dtype}")
+    return n, m
+
+
 def sigmoid_bce(logits, targets, probs, loss_rows=None, dlogits=None, grad_scale=1.0):
     """probs = sigmoid(logits); with targets [N, M] fp32 in [0, 1]: loss_rows [N] = Keras BinaryCrossentropy per row,
     dlogits = grad_scale * (probs - targets) / M (x3d_sigmoid_bce: the rules are in include/x3d_hip.h).  targets=None
     computes probs only.  One launch, does not synchronise."""
     _chk(logits, targets, probs, loss_rows, dlogits)
-    _f32_2d("sigmoid_bce", "logits", logits)
-    n, m = logits.shape
-    _f32_2d("sigmoid_bce", "probs", probs, (n, m))
-    if targets is not None:
-        _f32_2d("sigmoid_bce", "targets", targets, (n, m))
-    elif loss_rows is not None or dlogits is not None:
+    if targets is None and (loss_rows is not None or dlogits is not None):
         raise ValueError("sigmoid_bce: loss_rows / dlogits need targets")
-    if dlogits is not None:
-        _f32_2d("sigmoid_bce", "dlogits", dlogits, (n, m))
-    if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() != n):
-        raise ValueError(f"sigmoid_bce: loss_rows must be {n} float32, got {loss_rows.numel()} {loss_rows.dtype}")
+    n, m = _loss_args("sigmoid_bce", logits, probs, dict(targets=targets, dlogits=dlogits), dict(loss_rows=loss_rows))
     hip.call("x3d_sigmoid_bce", ptr(logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(dlogits),
              float(grad_scale), n, m)
     return probs
@@ -611,34 +618,12 @@ def softmax_xent_soft(logits, targets, probs, loss_rows=None, dlogits=None, grad
     include/x3d_hip.h; a one-hot row gives softmax_xent's result).  targets=None computes probs only.  One launch, does not
     synchronise."""
     _chk(logits, targets, probs, loss_rows, dlogits)
-    _f32_2d("softmax_xent_soft", "logits", logits)
-    n, m = logits.shape
-    _f32_2d("softmax_xent_soft", "probs", probs, (n, m))
-    if targets is not None:
-        _f32_2d("softmax_xent_soft", "targets", targets, (n, m))
-    elif loss_rows is not None or dlogits is not None:
+    if targets is None and (loss_rows is not None or dlogits is not None):
         raise ValueError("softmax_xent_soft: loss_rows / dlogits need targets")
-    if dlogits is not None:
-        _f32_2d("softmax_xent_soft", "dlogits", dlogits, (n, m))
-    if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() != n):
-        raise ValueError(f"softmax_xent_soft: loss_rows must be {n} float32, got {loss_rows.numel()} {loss_rows.dtype}")
+    n, m = _loss_args("softmax_xent_soft", logits, probs, dict(targets=targets, dlogits=dlogits), dict(loss_rows=loss_rows))
     hip.call("x3d_softmax_xent_soft", ptr(logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(dlogits),
              float(grad_scale), n, m)
     return probs
-
-
-def _kd_args(name, logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits):
-    """the tensor checks softmax_xent_kd and sigmoid_bce_kd share (those of softmax_xent_soft); returns (N, M)"""
-    _f32_2d(name, "logits", logits)
-    n, m = logits.shape
-    _f32_2d(name, "probs", probs, (n, m))
-    for what, t in (("teacher_logits", teacher_logits), ("targets", targets), ("dlogits", dlogits)):
-        if t is not None:
-            _f32_2d(name, what, t, (n, m))
-    for what, t in (("loss_rows", loss_rows), ("kd_rows", kd_rows)):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != n):
-            raise ValueError(f"{name}: {what} must be {n} float32, got {t.numel()} {t.dtype}")
-    return n, m
 
 
 def softmax_xent_kd(logits, teacher_logits, probs, labels=None, targets=None, loss_rows=None, kd_rows=None, dlogits=None,
@@ -649,7 +634,8 @@ def softmax_xent_kd(logits, teacher_logits, probs, labels=None, targets=None, lo
     and the gradient of the sum in dlogits.  probs is softmax(logits), as those kernels write it.  alpha = 0 does not read
     the teacher (teacher_logits may be None).  The scalars are the library's to check.  One launch, does not synchronise."""
     _chk(logits, teacher_logits, labels, targets, probs, loss_rows, kd_rows, dlogits)
-    n, m = _kd_args("softmax_xent_kd", logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
+    n, m = _loss_args("softmax_xent_kd", logits, probs, dict(teacher_logits=teacher_logits, targets=targets, dlogits=dlogits),
+                      dict(loss_rows=loss_rows, kd_rows=kd_rows))
     if (labels is None) == (targets is None):
         raise ValueError("softmax_xent_kd: exactly one of labels / targets must be given")
     if labels is not None and (labels.dtype != torch.int32 or labels.numel() != n):
@@ -668,7 +654,8 @@ def sigmoid_bce_kd(logits, teacher_logits, targets, probs, loss_rows=None, kd_ro
     _chk(logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
     if targets is None:
         raise ValueError("sigmoid_bce_kd: targets must be given")
-    n, m = _kd_args("sigmoid_bce_kd", logits, teacher_logits, targets, probs, loss_rows, kd_rows, dlogits)
+    n, m = _loss_args("sigmoid_bce_kd", logits, probs, dict(teacher_logits=teacher_logits, targets=targets, dlogits=dlogits),
+                      dict(loss_rows=loss_rows, kd_rows=kd_rows))
     hip.call("x3d_sigmoid_bce_kd", ptr(logits), ptr(teacher_logits), ptr(targets), ptr(probs), ptr(loss_rows), ptr(kd_rows),
              ptr(dlogits), float(grad_scale), float(alpha), float(temperature), n, m)
     return probs

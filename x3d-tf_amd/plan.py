@@ -233,8 +233,7 @@ class _Plan:
         self.blocks: List[Block] = []
         self.bn_eval_items: List = []
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
-        self._head_hard = self._head_soft = None   # the two loss launches of a single-label training plan (use_soft_targets)
-        self._head_kd: Dict = {}       # their distillation forms, and the multi-label head's: "labels" | "targets" | "multi" -> entry
+        self._heads: Dict = {}         # the loss launches of a training plan recorded so far: (soft, distill) -> entry (use_soft_targets)
         self.teacher = self.kd_rows = None   # distillation: the teacher's logits [N][classes] and the KD term per row (first distilled call)
         self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
         self.bn_layers: List[BNBuf] = []   # every BatchNorm layer of a training plan, as recorded (precise_bn_table)
@@ -398,35 +397,37 @@ class _Plan:
         x3d_sigmoid_bce_kd for a multi-label plan (whose one hard head takes no `soft`) -- reading the teacher's logits from
         `teacher` and writing the KD term per row to `kd_rows`; both buffers and the entries likewise come into being with
         the first distilled call.  The scalars of a recorded entry (grad_scale, alpha, temperature) are placeholders: the
-        model launches the slot's entry point with the step's own."""
-        slot, m = self.grad_scale_slot, self.model
+        model launches the slot's entry point with the step's own (head_launch)."""
+        m = self.model
+        key = (bool(soft) and not m.multi_label, bool(distill))
+        if key not in self._heads:
+            if key[0] and self.targets is None:
+                self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
+            if key[1] and self.teacher is None:
+                self.teacher, self.kd_rows = self.f32(self.n, m.num_classes), self.f32(self.n)
+            tmp = []
+            name, args = self.head_launch(*key, grad_scale=1.0 / self.n)
+            self.rec(tmp, name, *args)
+            self._heads[key] = tmp[0]
+        self.fwd[self.grad_scale_slot] = self._heads[key]
+
+    def head_launch(self, soft: bool, distill: bool, grad_scale, alpha=0.5, temperature=1.0):
+        """(entry point, its arguments without the stream) of the loss of a training plan: the one place that says which of
+        the five a step runs and in which order it takes the plan's buffers and the scalars.  `soft` counts for single-label
+        plans only; the buffers the choice needs exist (use_soft_targets)."""
+        m = self.model
         soft = bool(soft) and not m.multi_label
-        if (soft or distill) and self._head_hard is None:
-            self._head_hard = self.fwd[slot]
-        if soft and self._head_soft is None:
-            self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
-            tmp = []
-            self.rec(tmp, "x3d_softmax_xent_soft", self.logits, self.targets, self.probs, self.loss_rows, self.dlogits,
-                     1.0 / self.n, self.n, m.num_classes)
-            self._head_soft = tmp[0]
-        if not distill:
-            entry = self._head_soft if soft else self._head_hard
-            if entry is not None:
-                self.fwd[slot] = entry
-            return
-        if self.teacher is None:
-            self.teacher, self.kd_rows = self.f32(self.n, m.num_classes), self.f32(self.n)
-        key = "multi" if m.multi_label else ("targets" if soft else "labels")
-        if key not in self._head_kd:
-            tmp = []
-            tail = (self.probs, self.loss_rows, self.kd_rows, self.dlogits, 1.0 / self.n, 0.5, 1.0, self.n, m.num_classes)
-            if m.multi_label:
-                self.rec(tmp, "x3d_sigmoid_bce_kd", self.logits, self.teacher, self.targets, *tail)
-            else:
-                self.rec(tmp, "x3d_softmax_xent_kd", self.logits, self.teacher, None if soft else self.labels,
-                         self.targets if soft else None, *tail)
-            self._head_kd[key] = tmp[0]
-        self.fwd[slot] = self._head_kd[key]
+        ptr = hip.ptr
+        size = (self.n, m.num_classes)
+        labels, targets = (None, ptr(self.targets)) if soft or m.multi_label else (ptr(self.labels), None)
+        if distill:
+            given = (targets,) if m.multi_label else (labels, targets)
+            return "x3d_sigmoid_bce_kd" if m.multi_label else "x3d_softmax_xent_kd", (
+                ptr(self.logits), ptr(self.teacher), *given, ptr(self.probs), ptr(self.loss_rows), ptr(self.kd_rows),
+                ptr(self.dlogits), grad_scale, alpha, temperature, *size)
+        name = "x3d_sigmoid_bce" if m.multi_label else "x3d_softmax_xent_soft" if soft else "x3d_softmax_xent"
+        return name, (ptr(self.logits), targets if labels is None else labels, ptr(self.probs), ptr(self.loss_rows),
+                      ptr(self.dlogits), grad_scale, *size)
 
     def run(self, lst, start=0, stop=None):
         if self.model.dry:
@@ -721,13 +722,11 @@ def record_training(model, n, t, h, w, frozen_prefix=0) -> _Plan:
     if model.multi_label:
         pl.labels = None
         pl.targets = torch.zeros(n, a.num_classes, dtype=torch.float32, device=model.device)
-        pl.rec(F, "x3d_sigmoid_bce", pl.logits, pl.targets, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
-               a.num_classes)
     else:
         pl.labels = torch.zeros(n, dtype=torch.int32, device=model.device)
         pl.targets = None                  # soft targets: allocated by the first call that brings some (use_soft_targets)
-        pl.rec(F, "x3d_softmax_xent", pl.logits, pl.labels, pl.probs, pl.loss_rows, pl.dlogits, 1.0 / n, n,
-               a.num_classes)
+    F.append(None)
+    pl.use_soft_targets(False)             # x3d_sigmoid_bce on targets / x3d_softmax_xent on labels
     pl.install_backward(record_backward(model, pl, model.opt, first_unit=k))
     if F[0] is None:
         items = (hip.BnEvalItem * len(pl.bn_eval_items))(*pl.bn_eval_items)
