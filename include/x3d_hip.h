@@ -63,7 +63,9 @@ extern "C" {
  *       (the fp16 loss scaler on the device);
  *   138 (additions only, no bump) x3d_stem_kernel_name (dry-run dispatch of the six stem entry points);
  *   138 (additions only, no bump) frozen BatchNorm backward: a negative count in x3d_bn_bwd_finalize / _rc and
- *       x3d_se_bnb_bwd_args.P (values every earlier version refused; no struct changes its layout). */
+ *       x3d_se_bnb_bwd_args.P (values every earlier version refused; no struct changes its layout);
+ *   138 (additions only, no bump) x3d_softmax_xent_w / x3d_sigmoid_bce_w / x3d_class_hits (class and sample weights,
+ *       focal terms, per-class hit counters). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -675,6 +677,56 @@ int x3d_softmax_xent_kd(const float* logits, const float* teacher_logits, const 
 int x3d_sigmoid_bce_kd(const float* logits, const float* teacher_logits, const float* targets, float* probs,
                        float* loss_rows, float* kd_rows, float* dlogits, float grad_scale, float alpha, float temperature,
                        int N, int M, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Class-imbalance losses (LOSS.* of the config): class weights, a positive weight, sample weights and focal factors on the
+ * hard term of either head, one entry point per head; each covers labels, dense targets and distillation.
+ * class_w, pos_w [M] fp32 and row_w [N] fp32 may each be NULL = all ones; below c = class_w, w+ = pos_w, r = row_w.
+ *   loss_rows[n] = (1 - a) * hard + a * r_n * kd;   kd_rows[n] = kd, the unweighted KD term (0 with alpha == 0);
+ *   dlogits = grad_scale * d loss_rows / dz.   The class and positive weights and the focal factors act on `hard` only.
+ * alpha, temperature, teacher_logits, kd: the distillation block above, rule for rule (alpha == 0 does not read the teacher,
+ * which may then be NULL; a non-finite teacher logit makes the row unusable).  probs is bit-identical to the plain kernel's.
+ * p, the row maximum and the softmax sum are the fp32 values of the plain kernels; everything behind them is evaluated in
+ * fp64 and stored as fp32.
+ * Bit rule: with class_w, pos_w and row_w NULL and every gamma 0 the entry points launch the distillation kernels of the
+ * block above (whose alpha == 0 branch runs the plain kernels' statements): every output has the bits of x3d_softmax_xent_kd
+ * / x3d_sigmoid_bce_kd, and at alpha == 0 those of x3d_softmax_xent / x3d_softmax_xent_soft / x3d_sigmoid_bce.
+ * Unusable rows -- a label outside [0, M), a NaN target, a non-finite teacher logit (alpha > 0), a row_w[n] that is NaN,
+ * negative or infinite -- get a NaN loss row and a zero dlogits row.  row_w[n] == 0 is a valid row: loss 0, gradient 0.
+ * Refused before any launch (X3D_ERR_INVALID, the message names the argument): what the distillation block refuses; a gamma
+ * that is negative, NaN, infinite or above 8; class_w, pos_w or row_w sharing a byte with probs, loss_rows, kd_rows or
+ * dlogits.  The values of class_w and pos_w are the caller's to check (config.loss_settings does: finite, >= 0).
+ * One launch, one 256-thread workgroup per row, sums in a fixed order, no atomics.
+ * ------------------------------------------------------------------------------------------ */
+/* Softmax head.  Exactly one of labels ([N] int32, the one-hot row y) and targets ([N][M] fp32 dense rows y) is given.
+ * With q = clip(p, 1e-7, 1 - 1e-7), x_j = q_j / sum_k q_k and f(x) = (1 - x)^gamma * (-log x):
+ *   hard = r_n * sum_j c_j y_j f(x_j)
+ * -- Keras CategoricalFocalCrossentropy with a per-class alpha; gamma = 0 with labels: Keras class_weight, c_y * the plain
+ * loss; gamma = 0, c = r = 1: the loss of x3d_softmax_xent / _soft.  With a_j = r_n c_j y_j:
+ *   dL/dp_k = [1e-7 <= p_k <= 1 - 1e-7] * (a_k f'(x_k) - sum_j a_j f'(x_j) x_j) / sum q,
+ *   d hard / dz = p * (dL/dp - sum_k p_k dL/dp_k).
+ * x = 1 (possible only at M = 1): loss 0, gradient 0, never NaN. */
+int x3d_softmax_xent_w(const float* logits, const float* teacher_logits, const int* labels, const float* targets,
+                       const float* class_w, const float* row_w, float* probs, float* loss_rows, float* kd_rows,
+                       float* dlogits, float grad_scale, float gamma, float alpha, float temperature, int N, int M,
+                       void* stream);
+/* Sigmoid head (DATA.MULTI_LABEL); targets [N][M] fp32 (required).  With s = sigmoid(z):
+ *   hard = r_n * mean_j c_j [ y_j w+_j (1 - s_j)^gamma_pos softplus(-z_j) + (1 - y_j) s_j^gamma_neg softplus(z_j) ]
+ * -- torch BCEWithLogitsLoss(pos_weight) at gamma 0, Keras BinaryFocalCrossentropy at gamma_pos == gamma_neg, asymmetric
+ * focusing (without the probability margin) otherwise; linear in y, so soft targets are defined; everything off:
+ * softplus(z) - z y, the loss of x3d_sigmoid_bce.  dlogits is the exact derivative:
+ *   d/dz (1 - s)^g softplus(-z) = -(1 - s)^g (g s softplus(-z) + 1 - s),   d/dz s^g softplus(z) = s^g (g (1 - s) softplus(z) + s). */
+int x3d_sigmoid_bce_w(const float* logits, const float* teacher_logits, const float* targets, const float* class_w,
+                      const float* pos_w, const float* row_w, float* probs, float* loss_rows, float* kd_rows,
+                      float* dlogits, float grad_scale, float gamma_pos, float gamma_neg, float alpha, float temperature,
+                      int N, int M, void* stream);
+/* Per-class top-1 counters (mean per-class accuracy): for every row with a label in [0, M), counts[y] += 1, and hits[y] += 1
+ * where the row is a top-1 hit by x3d_topk_metrics's rule (first-index argmax, every p_j finite).  A label outside [0, M) is
+ * counted nowhere.  hits, counts: int64 [M] device counters that are added into (zero them first).  probs [N][M] fp32;
+ * labels [N] int32 (label_bytes 4) or int64 (8).  Integer atomics only: the same inputs give the same counters.
+ * N * M < 2^31; N = 0 is a no-op. */
+int x3d_class_hits(const float* probs, const void* labels, int label_bytes, long long* hits, long long* counts, int N,
+                   int M, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mixup / CutMix (ABI 137; MIXUP.* of the config): a batch mixed with its own reverse, clip i with clip N-1-i.

@@ -138,7 +138,7 @@ def get_default_config():
     LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL / FREEZE_BN: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
-    DISTILL.* (knowledge distillation against a teacher's logits)."""
+    DISTILL.* (knowledge distillation against a teacher's logits), LOSS.* (class / positive weights and focal terms)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -197,6 +197,12 @@ def get_default_config():
     # KL(teacher || student) on logits softened by TEMPERATURE.  TEACHER: a shipped config name (XS .. XL) or a yaml path,
     # TEACHER_CKPT its checkpoint prefix; both unused when the trainer is handed a teacher model
     c.DISTILL = CfgNode(dict(ENABLE=False, TEACHER="", TEACHER_CKPT="", ALPHA=0.5, TEMPERATURE=1.0))
+    # class-imbalance losses (loss_settings; all off by default).  CLASS_WEIGHTS: one weight per class on the hard term of either
+    # head (Keras class_weight; losses.class_weights_from_counts builds them); POS_WEIGHT: one weight per class on the positive
+    # term of the sigmoid head (torch BCEWithLogitsLoss(pos_weight)); FOCAL_GAMMA: the focusing exponent (Keras
+    # Categorical / BinaryFocalCrossentropy), on the sigmoid head that of the positive term; FOCAL_GAMMA_NEG: that of the
+    # sigmoid head's negative term (the symmetric focal loss sets both to one value, asymmetric focusing to two).  [] = all ones
+    c.LOSS = CfgNode(dict(CLASS_WEIGHTS=[], POS_WEIGHT=[], FOCAL_GAMMA=0.0, FOCAL_GAMMA_NEG=0.0))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -229,6 +235,7 @@ def get_config(name, overrides=None, freeze=True):
     drop_path_settings(cfg)
     precise_bn_settings(cfg)
     distill_settings(cfg, have_teacher=True)   # (whether a teacher exists is the trainer's to check)
+    loss_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -557,4 +564,46 @@ def distill_settings(cfg, have_teacher: bool = False) -> DistillSettings:
     if s.enable and not s.teacher and not have_teacher:
         raise ValueError("DISTILL.ENABLE needs DISTILL.TEACHER (a shipped config name or a yaml path) or a teacher model "
                          "handed to the trainer")
+    return s
+
+
+LossSettings = collections.namedtuple("LossSettings", "class_weights pos_weight focal_gamma focal_gamma_neg")
+_LOSS_OFF = LossSettings((), (), 0.0, 0.0)
+FOCAL_GAMMA_MAX = 8.0          # the bound x3d_softmax_xent_w / x3d_sigmoid_bce_w refuse above
+
+
+def loss_settings(cfg) -> LossSettings:
+    """cfg.LOSS.* as one tuple (a config tree without the section: off; an empty list: no table).  The weight lists come back
+    as tuples of floats.  ValueError for a weight that is not finite and >= 0 or a list of all zeros, a gamma outside
+    [0, 8] (NaN fails), POS_WEIGHT or FOCAL_GAMMA_NEG without DATA.MULTI_LABEL, and a list whose length is not
+    NETWORK.NUM_CLASSES."""
+    import math
+    lv = getattr(cfg, "LOSS", None)
+    if lv is None:
+        return _LOSS_OFF
+    multi, classes = multi_label(cfg), int(cfg.NETWORK.NUM_CLASSES)
+
+    def table(key):
+        w = tuple(float(v) for v in (getattr(lv, key, None) or ()))
+        if not w:
+            return ()
+        if len(w) != classes:
+            raise ValueError(f"LOSS.{key} has {len(w)} entries, NETWORK.NUM_CLASSES is {classes}")
+        if not all(math.isfinite(v) and v >= 0.0 for v in w):
+            raise ValueError(f"LOSS.{key} must be finite and >= 0")
+        if not any(v > 0.0 for v in w):
+            raise ValueError(f"LOSS.{key} is all zeros: nothing would be trained")
+        return w
+
+    def gamma(key):
+        g = float(getattr(lv, key, 0.0))
+        if not 0.0 <= g <= FOCAL_GAMMA_MAX:
+            raise ValueError(f"LOSS.{key} must lie in [0, {FOCAL_GAMMA_MAX:g}], not {g}")
+        return g
+
+    s = LossSettings(table("CLASS_WEIGHTS"), table("POS_WEIGHT"), gamma("FOCAL_GAMMA"), gamma("FOCAL_GAMMA_NEG"))
+    if not multi and s.pos_weight:
+        raise ValueError("LOSS.POS_WEIGHT weighs the positive term of the sigmoid head: it needs DATA.MULTI_LABEL")
+    if not multi and s.focal_gamma_neg != 0.0:
+        raise ValueError("LOSS.FOCAL_GAMMA_NEG focuses the negative term of the sigmoid head: it needs DATA.MULTI_LABEL")
     return s

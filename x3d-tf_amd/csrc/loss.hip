@@ -1,6 +1,7 @@
-// The training losses of the head, all five entry points: softmax cross-entropy on labels (x3d_softmax_xent) and on dense target
+// The training losses of the head, all seven entry points: softmax cross-entropy on labels (x3d_softmax_xent) and on dense target
 // rows (x3d_softmax_xent_soft: label smoothing, mixup / CutMix), sigmoid / binary cross-entropy (x3d_sigmoid_bce: DATA.MULTI_LABEL),
-// and the knowledge-distillation forms of the three (x3d_softmax_xent_kd, x3d_sigmoid_bce_kd: DISTILL.*).  The exact rules are in
+// the knowledge-distillation forms of the three (x3d_softmax_xent_kd, x3d_sigmoid_bce_kd: DISTILL.*), and the weighted / focal
+// form of each head (x3d_softmax_xent_w, x3d_sigmoid_bce_w: LOSS.*, sample weights).  The exact rules are in
 // include/x3d_hip.h.  One 256-thread workgroup per row, sums in a fixed order, no atomics.
 //
 // Every term is written once, as a device function, and the kernels are compositions of them:
@@ -15,6 +16,8 @@
 //   sigmoid_bce_row       the plain sigmoid row: sigmoid_bce_kernel and alpha == 0 of its KD kernel
 // A distillation kernel with alpha == 0 takes a uniform branch into hard_row / sigmoid_bce_row -- the statements the plain kernel
 // runs -- so its results are bit-identical to the plain kernel's and the teacher is never read.
+//   clip_d, in_range_d, focal_d, softmax_kd_row, bce_w_term_d, bce_w_grad_d      the fp64 pieces of the two _w kernels
+// A _w entry point with nothing set launches the distillation kernel of its head, so it inherits those bits.
 #include "common.h"
 
 #define LOSS_THREADS 256
@@ -370,6 +373,190 @@ __global__ __launch_bounds__(LOSS_THREADS) void sigmoid_bce_kd_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// Class-imbalance losses (LOSS.*): class weights c_j, a positive weight w+_j (sigmoid head), a sample weight r_n and focal
+// factors on the hard term; the formulas are in include/x3d_hip.h.  With nothing set the host launches the kernels above, so
+// these two only ever run with a modifier.  p, mx and inv come from the fp32 softmax_row / softmax_p (probs has the plain
+// kernel's bits); everything behind them is fp64, stored as fp32, like the KD term.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool bad_row_weight(float w) { return !(w >= 0.f) || nonfinite(w); }   // NaN, negative, inf
+__device__ __forceinline__ double clip_d(float p) { return fmin(fmax((double)p, 1e-7), 1.0 - 1e-7); }
+__device__ __forceinline__ bool in_range_d(float p) { return (double)p >= 1e-7 && (double)p <= 1.0 - 1e-7; }
+__device__ __forceinline__ double pow_g(double x, double g) { return g == 0.0 ? 1.0 : pow(x, g); }   // x >= 0; x^0 = 1 also at x = 0
+
+// f(x) = (1 - x)^g * (-log x) and f'(x) for x in (0, 1].  x = 1 (one class): f = 0 and f' = 0 -- its limit for g >= 1, and the
+// element is outside the clip range there, so its gradient is masked anyway: 0, not inf * 0
+struct Focal { double f, df; };
+__device__ __forceinline__ Focal focal_d(double x, double g) {
+  const double om = 1.0 - x;
+  if (om <= 0.0) return {0.0, 0.0};
+  const double L = -log(x), pw = pow_g(om, g);
+  return {pw * L, -(g == 0.0 ? 0.0 : g * pw / om * L) - pw / x};
+}
+
+// the KD term of a softmax row in log space (the arithmetic of softmax_xent_kd_kernel); kd is NaN with a non-finite teacher logit
+struct KdRow { double lse_u, lse_v, kd; bool bad; };
+__device__ __forceinline__ KdRow softmax_kd_row(const float* __restrict__ z, const float* __restrict__ t, SoftmaxRow r, double T,
+                                                int M, double* part) {
+  const int tid = threadIdx.x;
+  double mv = -INFINITY, bad = 0.0;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const float tj = t[j];
+    if (nonfinite(tj)) bad = 1.0;
+    else mv = fmax(mv, (double)tj / T);
+  }
+  KdRow k;
+  k.bad = block_max_d(bad, part) > 0.0;
+  mv = block_max_d(mv, part);
+  const double mu = (double)r.mx / T;
+  double su = 0.0, sv = 0.0;
+  if (!k.bad)
+    for (int j = tid; j < M; j += LOSS_THREADS) {
+      su += exp((double)z[j] / T - mu);
+      sv += exp((double)t[j] / T - mv);
+    }
+  k.lse_u = mu + log(block_sum_d(su, part));
+  k.lse_v = mv + log(block_sum_d(sv, part));
+  double acc = 0.0;
+  if (!k.bad)
+    for (int j = tid; j < M; j += LOSS_THREADS) {
+      const double lps = (double)z[j] / T - k.lse_u, lpt = (double)t[j] / T - k.lse_v;
+      acc += exp(lpt) * (lpt - lps);
+    }
+  const double s = block_sum_d(acc, part);
+  k.kd = k.bad ? (double)__builtin_nanf("") : T * T * s;
+  return k;
+}
+
+// hard = r * sum_j c_j y_j f(q_j / sum q);  loss_rows = (1 - a) * hard + a * r * kd.  SOFT = false: y is the one-hot row of labels[n]
+template <bool SOFT>
+__global__ __launch_bounds__(LOSS_THREADS) void softmax_xent_w_kernel(
+    const float* __restrict__ logits, const float* __restrict__ teacher, const int* __restrict__ labels,
+    const float* __restrict__ targets, const float* __restrict__ class_w, const float* __restrict__ row_w, float* probs,
+    float* loss_rows, float* kd_rows, float* dlogits, float grad_scale, float gamma, float alpha, float temperature, int M) {
+  __shared__ float scratch[8];
+  __shared__ float bc[2];
+  __shared__ double part[LOSS_WAVES];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const long long row = (long long)n * M;
+  const float* z = logits + row;
+  const SoftmaxRow r = softmax_row(z, M, scratch, bc);
+  const float* y = SOFT ? targets + row : nullptr;
+  const int label = SOFT ? -1 : labels[n];
+  const float rwf = row_w ? row_w[n] : 1.f;
+  const double rw = (double)rwf, g = (double)gamma;
+
+  // sum q, sum_k p_k * [in range], NaN targets
+  double sq = 0.0, spin = 0.0, nb = 0.0;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const float p = softmax_p(z, j, r);
+    probs[row + j] = p;
+    sq += clip_d(p);
+    spin += in_range_d(p) ? (double)p : 0.0;
+    if (SOFT && y[j] != y[j]) nb = 1.0;
+  }
+  const double sumq = block_sum_d(sq, part), sum_p_in = block_sum_d(spin, part);
+  const bool bad = block_max_d(nb, part) > 0.0 || (!SOFT && (label < 0 || label >= M)) || bad_row_weight(rwf);
+
+  const bool kd_on = alpha != 0.f;             // uniform; alpha == 0 never reads the teacher
+  const double T = (double)temperature, a = (double)alpha, b = 1.0 - (double)alpha;
+  const float* t = kd_on ? teacher + row : nullptr;
+  KdRow k = {0.0, 0.0, 0.0, false};
+  if (kd_on) k = softmax_kd_row(z, t, r, T, M, part);
+  if (tid == 0 && kd_rows) kd_rows[n] = (float)k.kd;
+  if (bad || k.bad) return void_row(loss_rows, dlogits, n, M);
+
+  // hard term; B = sum_j a_j f'(x_j) x_j; sum_k [in range] p_k a_k f'(x_k)      (x = q / sum q, a_j = r c_j y_j)
+  double hl = 0.0, Bs = 0.0, C1 = 0.0;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const double yj = SOFT ? (double)y[j] : (j == label ? 1.0 : 0.0);
+    const double aj = rw * (class_w ? (double)class_w[j] : 1.0) * yj;
+    if (aj == 0.0) continue;
+    const float p = softmax_p(z, j, r);
+    const double x = clip_d(p) / sumq;
+    const Focal F = focal_d(x, g);
+    hl += aj * F.f;
+    Bs += aj * F.df * x;
+    C1 += in_range_d(p) ? (double)p * aj * F.df : 0.0;
+  }
+  hl = block_sum_d(hl, part);
+  Bs = block_sum_d(Bs, part);
+  C1 = block_sum_d(C1, part);
+  if (tid == 0 && loss_rows) loss_rows[n] = (float)(kd_on ? b * hl + a * rw * k.kd : hl);
+  if (!dlogits) return;
+  const double inner = (C1 - Bs * sum_p_in) / sumq;      // sum_k p_k dL/dp_k
+  const double gs = (double)grad_scale;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const float p = softmax_p(z, j, r);
+    const double yj = SOFT ? (double)y[j] : (j == label ? 1.0 : 0.0);
+    const double aj = rw * (class_w ? (double)class_w[j] : 1.0) * yj;
+    double dldp = 0.0;
+    if (in_range_d(p)) dldp = ((aj == 0.0 ? 0.0 : aj * focal_d(clip_d(p) / sumq, g).df) - Bs) / sumq;
+    const double dh = (double)p * (dldp - inner);
+    double d = dh;
+    if (kd_on) {
+      const double ps = exp((double)z[j] / T - k.lse_u), pt = exp((double)t[j] / T - k.lse_v);
+      d = b * dh + a * rw * T * (ps - pt);
+    }
+    dlogits[row + j] = (float)(gs * d);
+  }
+}
+
+// hard = r * mean_j c_j [ y w+ (1 - s)^g+ softplus(-z) + (1 - y) s^g- softplus(z) ], s = sigmoid(z);  the derivative in closed form:
+//   d/dz (1 - s)^g softplus(-z) = -(1 - s)^g (g s softplus(-z) + (1 - s)),   d/dz s^g softplus(z) = s^g (g (1 - s) softplus(z) + s)
+__device__ __forceinline__ double bce_w_term_d(double z, double y, double c, double wp, double gp, double gn) {
+  const double s = sigmoid_d(z), oms = sigmoid_d(-z);
+  return c * (y * wp * pow_g(oms, gp) * softplus_d(-z) + (1.0 - y) * pow_g(s, gn) * softplus_d(z));
+}
+
+__device__ __forceinline__ double bce_w_grad_d(double z, double y, double c, double wp, double gp, double gn) {
+  const double s = sigmoid_d(z), oms = sigmoid_d(-z);
+  return c * ((1.0 - y) * pow_g(s, gn) * (gn * oms * softplus_d(z) + s) - y * wp * pow_g(oms, gp) * (gp * s * softplus_d(-z) + oms));
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void sigmoid_bce_w_kernel(
+    const float* __restrict__ logits, const float* __restrict__ teacher, const float* __restrict__ targets,
+    const float* __restrict__ class_w, const float* __restrict__ pos_w, const float* __restrict__ row_w, float* probs,
+    float* loss_rows, float* kd_rows, float* dlogits, float grad_scale, float gamma_pos, float gamma_neg, float alpha,
+    float temperature, int M) {
+  __shared__ double part[LOSS_WAVES];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const long long row = (long long)n * M;
+  const float rwf = row_w ? row_w[n] : 1.f;
+  const double rw = (double)rwf, gp = (double)gamma_pos, gn = (double)gamma_neg;
+  const bool kd_on = alpha != 0.f;             // uniform; alpha == 0 never reads the teacher
+  const double T = (double)temperature, a = (double)alpha, b = 1.0 - (double)alpha;
+  double acc = 0.0, kacc = 0.0, nb = 0.0, tb = 0.0;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const double z = (double)logits[row + j];
+    probs[row + j] = (float)sigmoid_d(z);
+    const double y = (double)targets[row + j];
+    if (y != y) nb = 1.0;
+    else acc += bce_w_term_d(z, y, class_w ? (double)class_w[j] : 1.0, pos_w ? (double)pos_w[j] : 1.0, gp, gn);
+    if (!kd_on) continue;
+    const float tj = teacher[row + j];
+    if (nonfinite(tj)) { tb = 1.0; continue; }
+    const double u = z / T, v = (double)tj / T, sv = sigmoid_d(v);
+    kacc += (softplus_d(u) - sv * u) - (softplus_d(v) - sv * v);
+  }
+  const bool bad = block_max_d(nb, part) > 0.0 || bad_row_weight(rwf);
+  const bool kd_bad = block_max_d(tb, part) > 0.0;
+  const double hard = rw * block_sum_d(acc, part) / (double)M;
+  const double ks = block_sum_d(kacc, part);
+  const double kd = kd_bad ? (double)__builtin_nanf("") : T * T * ks / (double)M;
+  if (tid == 0 && kd_rows) kd_rows[n] = (float)kd;     // (alpha == 0: 0)
+  if (bad || kd_bad) return void_row(loss_rows, dlogits, n, M);
+  if (tid == 0 && loss_rows) loss_rows[n] = (float)(kd_on ? b * hard + a * rw * kd : hard);
+  if (!dlogits) return;
+  const double gs = (double)grad_scale * rw / (double)M;
+  for (int j = tid; j < M; j += LOSS_THREADS) {
+    const double z = (double)logits[row + j];
+    double d = bce_w_grad_d(z, (double)targets[row + j], class_w ? (double)class_w[j] : 1.0, pos_w ? (double)pos_w[j] : 1.0, gp, gn);
+    if (kd_on) d = b * d + a * T * (sigmoid_d(z / T) - sigmoid_d((double)teacher[row + j] / T));
+    dlogits[row + j] = (float)(gs * d);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 extern "C" int x3d_softmax_xent(const float* logits, const int* labels, float* probs, float* loss_rows,
@@ -457,5 +644,75 @@ extern "C" int x3d_sigmoid_bce_kd(const float* logits, const float* teacher_logi
   hipLaunchKernelGGL(sigmoid_bce_kd_kernel, dim3(N), dim3(LOSS_THREADS), 0, (hipStream_t)stream, logits, teacher_logits, targets,
                      probs, loss_rows, kd_rows, dlogits, grad_scale, alpha, temperature, M);
   X3D_LAUNCH_CHECK("sigmoid_bce_kd");
+  return X3D_OK;
+}
+
+// a weight table / vector (`n` floats) that must not alias an output
+#define W_ALIAS_CHECK(fn, in, n, in_name)                                                                                  \
+  X3D_REQUIRE(!kd_overlap(in, (size_t)(n) * sizeof(float), probs, mat) && !kd_overlap(in, (size_t)(n) * sizeof(float), dlogits, mat) && \
+                  !kd_overlap(in, (size_t)(n) * sizeof(float), loss_rows, vec) &&                                          \
+                  !kd_overlap(in, (size_t)(n) * sizeof(float), kd_rows, vec),                                              \
+              fn ": " in_name " overlaps an output")
+
+#define W_GAMMA_CHECK(fn, g, g_name) \
+  X3D_REQUIRE(g >= 0.f && g <= 8.f, fn ": " g_name " = %g outside [0, 8]", (double)g)
+
+// Nothing set (no table, no row weights, every gamma 0): the launch of x3d_softmax_xent_kd / x3d_sigmoid_bce_kd itself, whose
+// alpha == 0 branch in turn runs the plain kernels' statements -- the bits of the five entry points above by construction.
+extern "C" int x3d_softmax_xent_w(const float* logits, const float* teacher_logits, const int* labels, const float* targets,
+                                  const float* class_w, const float* row_w, float* probs, float* loss_rows, float* kd_rows,
+                                  float* dlogits, float grad_scale, float gamma, float alpha, float temperature, int N, int M,
+                                  void* stream) {
+  KD_COMMON_CHECKS("softmax_xent_w");
+  W_GAMMA_CHECK("softmax_xent_w", gamma, "gamma");
+  X3D_REQUIRE((labels != nullptr) != (targets != nullptr), "softmax_xent_w: exactly one of labels / targets must be given (%s)",
+              labels ? "both are" : "neither is");
+  const size_t mat = (size_t)N * M * sizeof(float), vec = (size_t)N * sizeof(float);
+  KD_ALIAS_CHECK("softmax_xent_w", teacher_logits, "teacher_logits");
+  KD_ALIAS_CHECK("softmax_xent_w", targets, "targets");
+  W_ALIAS_CHECK("softmax_xent_w", class_w, M, "class_w");
+  W_ALIAS_CHECK("softmax_xent_w", row_w, N, "row_w");
+  const dim3 grid(N), block(LOSS_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  if (!class_w && !row_w && gamma == 0.f) {
+    if (targets)
+      hipLaunchKernelGGL(softmax_xent_kd_kernel<true>, grid, block, 0, s, logits, teacher_logits, labels, targets, probs,
+                         loss_rows, kd_rows, dlogits, grad_scale, alpha, temperature, M);
+    else
+      hipLaunchKernelGGL(softmax_xent_kd_kernel<false>, grid, block, 0, s, logits, teacher_logits, labels, targets, probs,
+                         loss_rows, kd_rows, dlogits, grad_scale, alpha, temperature, M);
+  } else if (targets) {
+    hipLaunchKernelGGL(softmax_xent_w_kernel<true>, grid, block, 0, s, logits, teacher_logits, labels, targets, class_w, row_w,
+                       probs, loss_rows, kd_rows, dlogits, grad_scale, gamma, alpha, temperature, M);
+  } else {
+    hipLaunchKernelGGL(softmax_xent_w_kernel<false>, grid, block, 0, s, logits, teacher_logits, labels, targets, class_w, row_w,
+                       probs, loss_rows, kd_rows, dlogits, grad_scale, gamma, alpha, temperature, M);
+  }
+  X3D_LAUNCH_CHECK("softmax_xent_w");
+  return X3D_OK;
+}
+
+extern "C" int x3d_sigmoid_bce_w(const float* logits, const float* teacher_logits, const float* targets, const float* class_w,
+                                 const float* pos_w, const float* row_w, float* probs, float* loss_rows, float* kd_rows,
+                                 float* dlogits, float grad_scale, float gamma_pos, float gamma_neg, float alpha,
+                                 float temperature, int N, int M, void* stream) {
+  KD_COMMON_CHECKS("sigmoid_bce_w");
+  W_GAMMA_CHECK("sigmoid_bce_w", gamma_pos, "gamma_pos");
+  W_GAMMA_CHECK("sigmoid_bce_w", gamma_neg, "gamma_neg");
+  X3D_REQUIRE(targets, "sigmoid_bce_w: targets is null");
+  const size_t mat = (size_t)N * M * sizeof(float), vec = (size_t)N * sizeof(float);
+  KD_ALIAS_CHECK("sigmoid_bce_w", teacher_logits, "teacher_logits");
+  KD_ALIAS_CHECK("sigmoid_bce_w", targets, "targets");
+  W_ALIAS_CHECK("sigmoid_bce_w", class_w, M, "class_w");
+  W_ALIAS_CHECK("sigmoid_bce_w", pos_w, M, "pos_w");
+  W_ALIAS_CHECK("sigmoid_bce_w", row_w, N, "row_w");
+  if (!class_w && !pos_w && !row_w && gamma_pos == 0.f && gamma_neg == 0.f)
+    hipLaunchKernelGGL(sigmoid_bce_kd_kernel, dim3(N), dim3(LOSS_THREADS), 0, (hipStream_t)stream, logits, teacher_logits,
+                       targets, probs, loss_rows, kd_rows, dlogits, grad_scale, alpha, temperature, M);
+  else
+    hipLaunchKernelGGL(sigmoid_bce_w_kernel, dim3(N), dim3(LOSS_THREADS), 0, (hipStream_t)stream, logits, teacher_logits,
+                       targets, class_w, pos_w, row_w, probs, loss_rows, kd_rows, dlogits, grad_scale, gamma_pos, gamma_neg,
+                       alpha, temperature, M);
+  X3D_LAUNCH_CHECK("sigmoid_bce_w");
   return X3D_OK;
 }

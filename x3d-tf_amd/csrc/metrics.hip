@@ -115,3 +115,57 @@ extern "C" int x3d_topk_metrics(const float* probs, const void* labels, int labe
   X3D_LAUNCH_CHECK("topk_metrics");
   return X3D_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Per-class hit counts (mean per-class accuracy): counts[y] += 1 for every row with a label in [0, M), hits[y] += 1 where the
+// row is a top-1 hit by the rule above (first-index argmax, every p_j finite).  One wave per row, the comparisons counted with
+// ballots; lane 0 adds into the int64 counters with integer atomics, so the counters do not depend on the order of the rows.
+// ------------------------------------------------------------------------------------------------
+#define HITS_THREADS 256
+#define HITS_WAVES (HITS_THREADS / WAVE)
+
+template <typename L>
+__global__ __launch_bounds__(HITS_THREADS) void class_hits_kernel(const float* __restrict__ probs, const L* __restrict__ labels,
+                                                                  unsigned long long* hits, unsigned long long* counts, int N,
+                                                                  int M) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * HITS_WAVES + (threadIdx.x >> 6);     // wave-uniform
+  if (n >= N) return;
+  const long long y = (long long)labels[n];
+  if (y < 0 || y >= M) return;                                    // counted nowhere, never used as an index
+  const float* row = probs + (long long)n * M;
+  const float py = row[y];
+  int above = 0, tie_before = 0;
+  unsigned long long nonfinite = 0;
+  for (int j0 = 0; j0 < M; j0 += WAVE) {
+    const int j = j0 + lane;
+    const bool in = j < M;
+    const float p = in ? row[j] : 0.f;
+    above += __popcll(__ballot(in && p > py));
+    tie_before += __popcll(__ballot(in && j < y && p == py));
+    nonfinite |= __ballot(in && !isfinite(p));
+  }
+  if (lane == 0) {
+    atomicAdd(counts + y, 1ULL);
+    if (nonfinite == 0 && above == 0 && tie_before == 0) atomicAdd(hits + y, 1ULL);
+  }
+}
+
+extern "C" int x3d_class_hits(const float* probs, const void* labels, int label_bytes, long long* hits, long long* counts, int N,
+                              int M, void* stream) {
+  X3D_REQUIRE(label_bytes == 4 || label_bytes == 8, "class_hits: label_bytes %d (int32 = 4 or int64 = 8)", label_bytes);
+  X3D_REQUIRE(N >= 0 && M > 0, "class_hits: bad sizes N=%d M=%d", N, M);
+  X3D_REQUIRE((long long)N * M < (1LL << 31), "class_hits: N*M = %lld >= 2^31", (long long)N * M);
+  if (N == 0) return X3D_OK;
+  X3D_REQUIRE(probs && labels && hits && counts, "class_hits: null pointer");
+  X3D_REQUIRE(((uintptr_t)hits | (uintptr_t)counts) % 8 == 0, "class_hits: hits / counts must be 8-byte aligned");
+  const dim3 grid((N + HITS_WAVES - 1) / HITS_WAVES), block(HITS_THREADS);
+  if (label_bytes == 8)
+    hipLaunchKernelGGL(class_hits_kernel<long long>, grid, block, 0, (hipStream_t)stream, probs, (const long long*)labels,
+                       (unsigned long long*)hits, (unsigned long long*)counts, N, M);
+  else
+    hipLaunchKernelGGL(class_hits_kernel<int>, grid, block, 0, (hipStream_t)stream, probs, (const int*)labels,
+                       (unsigned long long*)hits, (unsigned long long*)counts, N, M);
+  X3D_LAUNCH_CHECK("class_hits");
+  return X3D_OK;
+}

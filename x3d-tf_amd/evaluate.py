@@ -58,12 +58,18 @@ class DeviceMetrics:
     """`Metrics` with the counters on the device: `update` launches one x3d_topk_metrics (no host read, no ATen op), the
     host reads the four fp64 counters once, in `result()`.  For the training loop, where a per-batch `int(...)` would
     synchronise every step.  Top-1 is the first-index argmax and top-5 is tf.math.in_top_k, ties at the 5th place
-    counting as hits (include/x3d_hip.h); on tie-free rows both equal `Metrics`."""
+    counting as hits (include/x3d_hip.h); on tie-free rows both equal `Metrics`.
 
-    def __init__(self, reg_loss=0.0, k: int = 5):
+    per_class: also keeps int64 [classes] counters of the top-1 hits and the rows per class (one x3d_class_hits launch more
+    per `update`), and `result()` gains "mean_class_acc": the mean of hits / rows over the classes that occurred (NaN when
+    none did).  Off by default: launches and result are then what they were."""
+
+    def __init__(self, reg_loss=0.0, k: int = 5, per_class: bool = False):
         self.reg_loss = reg_loss      # float, or a device tensor (model.regularization_loss()): read in result()
         self.k = int(k)
         self.acc = None               # [loss sum, top-1 hits, top-k hits, rows] fp64, on the device of the first batch
+        self.per_class = bool(per_class)
+        self.class_hits = self.class_counts = None   # per_class: int64 [classes], with the first batch
 
     def _counters(self, device):
         if self.acc is None:
@@ -76,6 +82,11 @@ class DeviceMetrics:
         if labels.device != probs.device:
             labels = labels.to(probs.device, non_blocking=True)
         ops.topk_metrics(probs, labels, self._counters(probs.device), self.k)
+        if self.per_class:
+            if self.class_hits is None:
+                self.class_hits = torch.zeros(probs.shape[1], dtype=torch.int64, device=probs.device)
+                self.class_counts = torch.zeros_like(self.class_hits)
+            ops.class_hits(probs, labels, self.class_hits, self.class_counts)
 
     def all_reduce_(self, group=None, device=None):
         """Sums the four counters over the replicas, as `Metrics.all_reduce_` does (no-op without a multi-rank process
@@ -90,13 +101,29 @@ class DeviceMetrics:
         dist.all_reduce(t, group=group)
         if t is not acc:
             acc.copy_(t)
+        if self.per_class:
+            if self.class_hits is None:
+                raise ValueError("DeviceMetrics.all_reduce_: per_class counters need a batch on every rank")
+            for c in (self.class_hits, self.class_counts):
+                tc = c.to(device)
+                dist.all_reduce(tc, group=group)
+                if tc is not c:
+                    c.copy_(tc)
         return self
 
     def result(self) -> Dict[str, float]:
         loss, top1, topk, n = self.acc.tolist() if self.acc is not None else (0.0, 0.0, 0.0, 0.0)
         reg = float(self.reg_loss.item()) if torch.is_tensor(self.reg_loss) else float(self.reg_loss)
         d = max(n, 1.0)
-        return {"loss": loss / d + reg, "acc": top1 / d, "top_5_acc": topk / d, "videos": int(round(n))}
+        r = {"loss": loss / d + reg, "acc": top1 / d, "top_5_acc": topk / d, "videos": int(round(n))}
+        if self.per_class:
+            r["mean_class_acc"] = float("nan")
+            if self.class_hits is not None:
+                hits, counts = self.class_hits.cpu().double(), self.class_counts.cpu().double()
+                have = counts > 0
+                if bool(have.any()):
+                    r["mean_class_acc"] = float((hits[have] / counts[have]).mean())
+        return r
 
 
 class DeviceMAP:

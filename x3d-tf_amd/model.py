@@ -29,7 +29,7 @@ from .arch import Arch, ParamSpec, block_prefix, build_arch, drop_path_rates, pa
 from .params import init_params
 from .segments import Segment, SegTable
 from .solver import RULES
-from .plan import PLAN_DEFAULTS, _FakeBuf, _Plan, _experiment_options, record_inference, record_training  # noqa: F401  (PLAN_DEFAULTS, _FakeBuf: re-exported)
+from .plan import PLAN_DEFAULTS, LossMods, _FakeBuf, _Plan, _experiment_options, record_inference, record_training  # noqa: F401  (PLAN_DEFAULTS, _FakeBuf: re-exported)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -167,6 +167,7 @@ class X3D:
             self._dp_scale = (1.0 / (1.0 - r32)).to(self.device)         # fp32 arithmetic, as the draw kernel's
             self.set_drop_path_state(0)
         self.last_loss = None
+        self.loss_mods = None          # class / positive weights and focal exponents of the training loss (set_loss); None: off
         self._stats_r = int(hip.load().x3d_stats_replicas())
 
     # ---------------------------------------------------------------------------------------------
@@ -540,8 +541,52 @@ class X3D:
         pl.run(pl.fwd)
         return pl.logits
 
+    def set_loss(self, class_weights=None, pos_weight=None, focal_gamma: float = 0.0, focal_gamma_neg: float = 0.0):
+        """The class-imbalance modifiers of the training loss (LOSS.* of the config; x3d_softmax_xent_w / x3d_sigmoid_bce_w in
+        include/x3d_hip.h): class_weights [classes] on the hard term of either head, pos_weight [classes] on the positive
+        term of the sigmoid head, the focal exponent focal_gamma (sigmoid head: of the positive term) and focal_gamma_neg (of
+        the sigmoid head's negative term).  The tables (sequences, arrays or tensors) are checked here -- finite, >= 0, not
+        all zero, one entry per class -- and uploaded once; every later `forward_backward` then launches the _w entry point
+        of its head.  Everything at its default switches the modifiers off again: the plain entry points, launch for launch."""
+        import math
+
+        def table(what, w):
+            if w is None:
+                return None
+            t = torch.as_tensor(w, dtype=torch.float64).detach().cpu().flatten()
+            if t.numel() == 0:
+                return None
+            if t.numel() != self.num_classes:
+                raise ValueError(f"{what} has {t.numel()} entries, the model has {self.num_classes} classes")
+            if not bool(torch.isfinite(t).all()) or float(t.min()) < 0.0 or float(t.max()) <= 0.0:
+                raise ValueError(f"{what} must be finite and >= 0, and not all zeros")
+            return t.to(torch.float32).to(self.device)
+
+        cw, pw = table("class_weights", class_weights), table("pos_weight", pos_weight)
+        g, gneg = float(focal_gamma), float(focal_gamma_neg)
+        for what, v in (("focal_gamma", g), ("focal_gamma_neg", gneg)):
+            if not (0.0 <= v <= 8.0 and math.isfinite(v)):
+                raise ValueError(f"{what} must lie in [0, 8], not {v}")
+        if not self.multi_label and (pw is not None or gneg != 0.0):
+            raise ValueError("pos_weight and focal_gamma_neg belong to the sigmoid head (DATA.MULTI_LABEL)")
+        off = cw is None and pw is None and g == 0.0 and gneg == 0.0
+        self.loss_mods = None if off else LossMods(cw, pw, g, gneg)
+
+    def _bind_sample_weight(self, pl: _Plan, sample_weight, n):
+        """sample weights [n] (host or device, any real type) -> pl.row_w fp32.  Host weights are checked (finite, >= 0); device
+        weights by the kernel (a NaN, negative or infinite weight: NaN loss row, no gradient from the sample)."""
+        w = sample_weight if torch.is_tensor(sample_weight) else torch.as_tensor(sample_weight)
+        if w.numel() != n or w.dim() > 1 or w.dtype == torch.bool or w.is_complex():
+            raise ValueError(f"sample_weight must be {n} real numbers, got {tuple(w.shape)} {w.dtype}")
+        if not w.is_cuda:
+            wd = w.double()
+            if not bool(torch.isfinite(wd).all()) or float(wd.min()) < 0.0:
+                raise ValueError("sample_weight must be finite and >= 0")
+        if w.data_ptr() != pl.row_w.data_ptr():
+            pl.row_w.copy_(w.to(self.device, non_blocking=True).reshape(n))
+
     def forward_backward(self, input, labels, global_batch=None, on_stage_done=None, loss_scale=1.0, teacher_logits=None,
-                         distill=None):
+                         distill=None, sample_weight=None):
         """One training forward + backward.  Fills ``self.grads`` (data gradients only; the L2 term is
         applied by the optimizer), updates BN moving statistics, returns the plan (loss_rows, probs).
 
@@ -567,6 +612,10 @@ class X3D:
             alpha * T^2 * KL(teacher || student) at temperature T (x3d_softmax_xent_kd / x3d_sigmoid_bce_kd), `plan.kd_rows`
             holds the KD term per row and `plan.teacher` the logits.  The shape is checked here, the values by the kernel
             (a non-finite teacher logit: NaN loss row, no gradient from the sample).  Without teacher_logits nothing changes.
+        sample_weight: [N] weights of the samples (host or device), Keras' `(x, y, sample_weight)`: row n's loss and gradient
+            are multiplied by sample_weight[n] and still divided by global_batch (SUM_OVER_BATCH_SIZE).  0 is a valid weight;
+            `plan.row_w` holds them.  With it, or with `set_loss` modifiers, the head runs x3d_softmax_xent_w /
+            x3d_sigmoid_bce_w; with neither nothing changes.
         """
         n, t, h, w, _ = input.shape
         pl = self._plan(n, t, h, w, True)
@@ -583,7 +632,11 @@ class X3D:
                 got = (tuple(teacher_logits.shape), teacher_logits.dtype, teacher_logits.device) \
                     if torch.is_tensor(teacher_logits) else type(teacher_logits)
                 raise ValueError(f"teacher_logits must be a device float32 [{n}, {self.num_classes}] tensor, got {got}")
-        pl.use_soft_targets(soft, distill=kd)
+        rw = sample_weight is not None
+        weighted = rw or self.loss_mods is not None
+        pl.use_soft_targets(soft, distill=kd, weighted=weighted, row_w=rw)
+        if rw:
+            self._bind_sample_weight(pl, sample_weight, n)
         if self.multi_label:
             self._bind_targets(pl, labels, n)
         elif soft:
@@ -607,7 +660,8 @@ class X3D:
         if kd and teacher_logits.data_ptr() != pl.teacher.data_ptr():
             pl.teacher.copy_(teacher_logits)
         pl.run(pl.fwd, 0, pl.grad_scale_slot)
-        name, args = pl.head_launch(soft, kd, head_scale, *((kd_alpha, kd_temp) if kd else ()))
+        name, args = pl.head_launch(soft, kd, head_scale, *((kd_alpha, kd_temp) if kd else ()),
+                                    **(dict(weighted=True, row_w=rw) if weighted else {}))
         hip.call(name, *args)
         if on_device:
             ops.loss_scale_apply(pl.dlogits.view(-1), loss_scale)

@@ -661,6 +661,71 @@ def sigmoid_bce_kd(logits, teacher_logits, targets, probs, loss_rows=None, kd_ro
     return probs
 
 
+def _weight_args(name, n, m, tables, row_w):
+    """the weight tensors of the _w wrappers: every table in `tables` ({what: tensor or None}) M float32, row_w N float32"""
+    for what, t in list(tables.items()) + [("row_w", row_w)]:
+        want = n if what == "row_w" else m
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.numel() != want or not t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be {want} contiguous float32, got {tuple(t.shape)} {t.dtype}")
+
+
+def softmax_xent_w(logits, probs, labels=None, targets=None, class_w=None, row_w=None, teacher_logits=None, loss_rows=None,
+                   kd_rows=None, dlogits=None, grad_scale=1.0, gamma=0.0, alpha=0.0, temperature=1.0):
+    """The softmax head's loss with class weights class_w [M], sample weights row_w [N] (fp32; None = all ones) and the focal
+    exponent gamma on the hard term (x3d_softmax_xent_w: the rules are in include/x3d_hip.h), on `labels` [N] int32 or dense
+    `targets` [N, M] fp32 (exactly one of the two): loss_rows = (1 - alpha) * hard + alpha * row_w * kd, the gradient in dlogits.
+    alpha = 0 does not read the teacher (teacher_logits may be None).  With nothing set the results have the bits of
+    softmax_xent_kd.  The scalars are the library's to check.  One launch, does not synchronise."""
+    _chk(logits, teacher_logits, labels, targets, class_w, row_w, probs, loss_rows, kd_rows, dlogits)
+    n, m = _loss_args("softmax_xent_w", logits, probs, dict(teacher_logits=teacher_logits, targets=targets, dlogits=dlogits),
+                      dict(loss_rows=loss_rows, kd_rows=kd_rows))
+    if (labels is None) == (targets is None):
+        raise ValueError("softmax_xent_w: exactly one of labels / targets must be given")
+    if labels is not None and (labels.dtype != torch.int32 or labels.numel() != n):
+        raise ValueError(f"softmax_xent_w: labels must be {n} int32, got {labels.numel()} {labels.dtype}")
+    _weight_args("softmax_xent_w", n, m, dict(class_w=class_w), row_w)
+    hip.call("x3d_softmax_xent_w", ptr(logits), ptr(teacher_logits), ptr(labels), ptr(targets), ptr(class_w), ptr(row_w),
+             ptr(probs), ptr(loss_rows), ptr(kd_rows), ptr(dlogits), float(grad_scale), float(gamma), float(alpha),
+             float(temperature), n, m)
+    return probs
+
+
+def sigmoid_bce_w(logits, targets, probs, class_w=None, pos_w=None, row_w=None, teacher_logits=None, loss_rows=None,
+                  kd_rows=None, dlogits=None, grad_scale=1.0, gamma_pos=0.0, gamma_neg=0.0, alpha=0.0, temperature=1.0):
+    """The multi-label head's loss with class weights class_w [M], positive weights pos_w [M], sample weights row_w [N] (fp32;
+    None = all ones) and the focal exponents of the positive and the negative term (x3d_sigmoid_bce_w: the rules are in
+    include/x3d_hip.h): loss_rows = (1 - alpha) * hard + alpha * row_w * kd, the gradient in dlogits.  alpha = 0 does not read
+    the teacher.  With nothing set the results have the bits of sigmoid_bce_kd.  One launch, does not synchronise."""
+    _chk(logits, teacher_logits, targets, class_w, pos_w, row_w, probs, loss_rows, kd_rows, dlogits)
+    if targets is None:
+        raise ValueError("sigmoid_bce_w: targets must be given")
+    n, m = _loss_args("sigmoid_bce_w", logits, probs, dict(teacher_logits=teacher_logits, targets=targets, dlogits=dlogits),
+                      dict(loss_rows=loss_rows, kd_rows=kd_rows))
+    _weight_args("sigmoid_bce_w", n, m, dict(class_w=class_w, pos_w=pos_w), row_w)
+    hip.call("x3d_sigmoid_bce_w", ptr(logits), ptr(teacher_logits), ptr(targets), ptr(class_w), ptr(pos_w), ptr(row_w),
+             ptr(probs), ptr(loss_rows), ptr(kd_rows), ptr(dlogits), float(grad_scale), float(gamma_pos), float(gamma_neg),
+             float(alpha), float(temperature), n, m)
+    return probs
+
+
+def class_hits(probs, labels, hits, counts):
+    """counts[y] += rows with label y, hits[y] += those that are top-1 hits, for probs [N, M] fp32 against labels [N] int32 |
+    int64; hits, counts: int64 [M] device counters (x3d_class_hits: the rules are in include/x3d_hip.h).  One launch, does
+    not synchronise."""
+    _chk(probs, labels, hits, counts)
+    _f32_2d("class_hits", "probs", probs)
+    n, m = probs.shape
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError(f"class_hits: labels must be [{n}] int32 or int64, got {tuple(labels.shape)} {labels.dtype}")
+    for what, t in (("hits", hits), ("counts", counts)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"class_hits: {what} must be {m} contiguous int64 counters, got {tuple(t.shape)} {t.dtype}")
+    if not probs.device == labels.device == hits.device == counts.device:
+        raise ValueError("class_hits: probs, labels, hits and counts must be on one device")
+    hip.call("x3d_class_hits", ptr(probs), ptr(labels), labels.element_size(), ptr(hits), ptr(counts), n, m)
+    return hits, counts
+
+
 MIX_MODES = {"mixup": hip.MIX_MIXUP, "cutmix": hip.MIX_CUTMIX}
 
 

@@ -69,6 +69,11 @@ def _experiment_options():
     return {opt: val for var, (opt, trigger, val) in _ENV_OPTIONS.items() if os.environ.get(var) == trigger}
 
 
+# X3D.loss_mods: the modifiers of the head's loss (X3D.set_loss) -- device tables [classes] fp32 or None, the focal exponents
+LossMods = collections.namedtuple("LossMods", "class_w pos_w gamma gamma_neg")
+NO_LOSS_MODS = LossMods(None, None, 0.0, 0.0)
+
+
 class _FakeBuf:
     """Stand-in for a device buffer in a DRY plan (X3D(..., device="dry")): an address range that is never touched.
     Dry plans exist so that the launch list of a full-size configuration -- and, through x3d_pw_kernel_name /
@@ -235,6 +240,7 @@ class _Plan:
         self.stem_tail_folded = False  # the stem's BatchNorm + ReLU is built on load by the first block's `a` conv
         self._heads: Dict = {}         # the loss launches of a training plan recorded so far: (soft, distill) -> entry (use_soft_targets)
         self.teacher = self.kd_rows = None   # distillation: the teacher's logits [N][classes] and the KD term per row (first distilled call)
+        self.row_w = None              # sample weights [N] of the step (first call that brings some)
         self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
         self.bn_layers: List[BNBuf] = []   # every BatchNorm layer of a training plan, as recorded (precise_bn_table)
         self._pbn_table = None
@@ -389,37 +395,56 @@ class _Plan:
         for B, r in zip(self.blocks, bw.blocks):
             vars(B).update(vars(r))
 
-    def use_soft_targets(self, soft: bool, distill: bool = False):
+    def use_soft_targets(self, soft: bool, distill: bool = False, weighted=None, row_w: bool = False):
         """Which loss the head slot (fwd[grad_scale_slot]) of a training plan holds.  Single-label plans: x3d_softmax_xent on
         `labels`, as recorded, or x3d_softmax_xent_soft on the dense rows in `targets`.  The targets buffer and the second
         entry come into being with the first soft call, so a plan that never sees soft targets allocates nothing for them.
         distill: the knowledge-distillation form of that loss instead -- x3d_softmax_xent_kd on `labels` or on `targets`,
         x3d_sigmoid_bce_kd for a multi-label plan (whose one hard head takes no `soft`) -- reading the teacher's logits from
         `teacher` and writing the KD term per row to `kd_rows`; both buffers and the entries likewise come into being with
-        the first distilled call.  The scalars of a recorded entry (grad_scale, alpha, temperature) are placeholders: the
-        model launches the slot's entry point with the step's own (head_launch)."""
+        the first distilled call.  weighted (None: whether the model has loss modifiers, X3D.set_loss): the _w entry point of
+        the head -- x3d_softmax_xent_w / x3d_sigmoid_bce_w -- which covers all of the above; row_w: the step brings sample
+        weights, and `row_w` [N] comes into being with the first such call (it implies weighted).  The scalars of a recorded
+        entry (grad_scale, alpha, temperature, the gammas) are placeholders: the model launches the slot's entry point with
+        the step's own (head_launch)."""
         m = self.model
-        key = (bool(soft) and not m.multi_label, bool(distill))
+        if weighted is None:
+            weighted = m.loss_mods is not None
+        weighted = bool(weighted) or bool(row_w)
+        key = (bool(soft) and not m.multi_label, bool(distill)) + (("w",) if weighted else ())
+        if row_w and self.row_w is None:
+            self.row_w = self.f32(self.n)
         if key not in self._heads:
             if key[0] and self.targets is None:
                 self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
             if key[1] and self.teacher is None:
                 self.teacher, self.kd_rows = self.f32(self.n, m.num_classes), self.f32(self.n)
             tmp = []
-            name, args = self.head_launch(*key, grad_scale=1.0 / self.n)
+            name, args = self.head_launch(*key[:2], grad_scale=1.0 / self.n, weighted=weighted)
             self.rec(tmp, name, *args)
             self._heads[key] = tmp[0]
         self.fwd[self.grad_scale_slot] = self._heads[key]
 
-    def head_launch(self, soft: bool, distill: bool, grad_scale, alpha=0.5, temperature=1.0):
+    def head_launch(self, soft: bool, distill: bool, grad_scale, alpha=0.5, temperature=1.0, weighted=False, row_w=False):
         """(entry point, its arguments without the stream) of the loss of a training plan: the one place that says which of
-        the five a step runs and in which order it takes the plan's buffers and the scalars.  `soft` counts for single-label
-        plans only; the buffers the choice needs exist (use_soft_targets)."""
+        the seven a step runs and in which order it takes the plan's buffers and the scalars.  `soft` counts for single-label
+        plans only; the buffers the choice needs exist (use_soft_targets).  weighted: the _w entry point of the head with the
+        model's tables and gammas (X3D.set_loss; none: NULL tables, gamma 0) and, with row_w, the plan's sample weights."""
         m = self.model
         soft = bool(soft) and not m.multi_label
         ptr = hip.ptr
         size = (self.n, m.num_classes)
         labels, targets = (None, ptr(self.targets)) if soft or m.multi_label else (ptr(self.labels), None)
+        if weighted or row_w:
+            mods = m.loss_mods or NO_LOSS_MODS
+            kd = (ptr(self.teacher), ptr(self.kd_rows), alpha, temperature) if distill else (None, None, 0.0, 1.0)
+            rw = ptr(self.row_w) if row_w else None
+            outs = (ptr(self.probs), ptr(self.loss_rows), kd[1], ptr(self.dlogits), grad_scale)
+            if m.multi_label:
+                return "x3d_sigmoid_bce_w", (ptr(self.logits), kd[0], targets, ptr(mods.class_w), ptr(mods.pos_w), rw, *outs,
+                                             mods.gamma, mods.gamma_neg, kd[2], kd[3], *size)
+            return "x3d_softmax_xent_w", (ptr(self.logits), kd[0], labels, targets, ptr(mods.class_w), rw, *outs, mods.gamma,
+                                          kd[2], kd[3], *size)
         if distill:
             given = (targets,) if m.multi_label else (labels, targets)
             return "x3d_sigmoid_bce_kd" if m.multi_label else "x3d_softmax_xent_kd", (

@@ -13,6 +13,7 @@ import torch
 from . import dist as xdist
 from . import ops
 from .config import (OPTIMIZERS, device_loss_scale_settings, distill_settings, finetune_settings, freeze_bn_settings, freeze_eval_settings,
+                     loss_settings,
                      mix_settings, optim_settings, precise_bn_settings, solver_settings)
 from .mix import NO_MIX, draw_mix_params
 from .solver import RULES
@@ -69,6 +70,7 @@ def check_accum_schedule(steps_per_epoch: int, save_freq, accum_steps: int):
 
 TRAIN_METRICS = ("acc", "top_5_acc")
 MULTI_LABEL_METRICS = ("mAP",)
+OPT_IN_METRICS = ("mean_class_acc",)   # single-label models, only when asked for: per-class counters (x3d_class_hits)
 _DEFAULT_METRICS = object()      # fit(metrics=...) default: TRAIN_METRICS, or MULTI_LABEL_METRICS for a multi-label model
 
 
@@ -236,6 +238,12 @@ class Trainer:
         if self.distill.enable:
             self.teacher = teacher if teacher is not None else self._build_teacher()
         self._kd = (self.distill.alpha, self.distill.temperature)
+        # class-imbalance losses (LOSS.*; off by default: the model is then not told anything and `step` is what it was).  The
+        # tables go to the device once; sample weights come with the batches (`step`, `fit`)
+        self.loss_mods = loss_settings(cfg)
+        if self.loss_mods != ((), (), 0.0, 0.0):
+            model.set_loss(class_weights=self.loss_mods.class_weights or None, pos_weight=self.loss_mods.pos_weight or None,
+                           focal_gamma=self.loss_mods.focal_gamma, focal_gamma_neg=self.loss_mods.focal_gamma_neg)
 
     def _check_teacher(self, teacher):
         m = self.model
@@ -275,22 +283,30 @@ class Trainer:
             return {}
         return dict(teacher_logits=self.teacher.logits(clips), distill=self._kd)
 
-    def step(self, clips, labels, lr: Optional[float] = None):
+    def step(self, clips, labels, lr: Optional[float] = None, sample_weight=None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
         plan (loss_rows, probs).  With MIXUP.ENABLE or TRAIN.LABEL_SMOOTHING the batch is mixed and the targets are built
         first (`_mix_batch`; `last_mix` holds the parameters drawn).  With DISTILL.ENABLE the teacher's logits of the (mixed)
-        clips join the loss (`_teacher_kw`; `plan.kd_rows` holds the KD term per row)."""
+        clips join the loss (`_teacher_kw`; `plan.kd_rows` holds the KD term per row).  sample_weight: [B] weights of this
+        shard's samples (host or device), Keras' `(x, y, sample_weight)`; the weighted rows are still divided by the global batch
+        (SUM_OVER_BATCH_SIZE), so `loss` and the data-parallel reduction are what they were.  ValueError together with
+        MIXUP.ENABLE: mixing the weights of two samples is not defined here (class weights are fine, the loss is linear in y)."""
         m = self.model
         n = clips.shape[0]
         if lr is None:
             lr = lr_schedule(self.epoch, self.cfg)
+        sw = {}
+        if sample_weight is not None:
+            if self.mix.enable:
+                raise ValueError("sample_weight with MIXUP.ENABLE: the weight of a mixed sample is not defined")
+            sw = dict(sample_weight=sample_weight)
         if self._mix_active:
             clips, labels = self._mix_batch(clips, labels)
         if self._accum > 1:
-            return self._accum_step(clips, labels, lr, n)
+            return self._accum_step(clips, labels, lr, n, sw)
         pl = m.forward_backward(clips, labels, global_batch=n * self.world,
                                 on_stage_done=self._on_stage_done if self.collectives else None,
-                                loss_scale=self._fb_scale(), **self._teacher_kw(clips))
+                                loss_scale=self._fb_scale(), **self._teacher_kw(clips), **sw)
         self.reducer.mark_backward_done()     # (an event on the compute stream: finish() measures the exposed exchange from it)
         self.reducer.finish()
         self._finish_stats()
@@ -390,7 +406,7 @@ class Trainer:
         ds.publish()
         return pl
 
-    def _accum_step(self, clips, labels, lr, n):
+    def _accum_step(self, clips, labels, lr, n, sw):
         """One micro-batch of SOLVER.ACCUM_STEPS = A > 1.  Micro-batches 1..A-1 add their local gradient to the accumulator
         (no gradient all-reduce; weights, slots, EMA and `opt_step` untouched; the moving statistics are averaged as always).
         Micro-batch A adds the accumulator back -- under data parallelism bucket by bucket in the backward hook, in front of
@@ -403,7 +419,7 @@ class Trainer:
             self._grad_acc = torch.zeros_like(m.flat_grads)
         hook = (self._on_stage_done if last else self._on_stage_done_no_grads) if self.collectives else None
         pl = m.forward_backward(clips, labels, global_batch=n * self.world * self._accum, on_stage_done=hook,
-                                loss_scale=self._fb_scale(), **self._teacher_kw(clips))
+                                loss_scale=self._fb_scale(), **self._teacher_kw(clips), **sw)
         if not last:
             ops.grad_accum(self._grad_acc, m.flat_grads, first=self._micro == 1)
             self._finish_stats()
@@ -470,7 +486,8 @@ class Trainer:
         train.py:145-152, with the metrics it was compiled with (train.py:102-108), its LearningRateScheduler (per-epoch
         `lr_schedule`, train.py:114-125) and ModelCheckpoint (utils.py:128-132) callbacks -- nothing else of the Keras harness
         (TensorBoard / wandb callbacks are out of scope).  `dataset`: an iterator of (clips, labels) batches, e.g.
-        `dataloader.InputReader(cfg, True, True)(pattern, cfg.TRAIN.BATCH_SIZE)` (infinite in training mode, like
+        `dataloader.InputReader(cfg, True, True)(pattern, cfg.TRAIN.BATCH_SIZE)`, or of (clips, labels, sample_weight)
+        batches as Keras' `model.fit` takes them (`step`; infinite in training mode, like
         `dataset.repeat()`; under torchrun the reader shards the records by rank and yields BATCH_SIZE // world clips per
         step, so `steps_per_epoch` = DATASET_SIZE // BATCH_SIZE is one pass over the data on every world size, as with
         MirroredStrategy).  Returns the per-epoch mean losses.
@@ -482,6 +499,9 @@ class Trainer:
             validates its shard and the counters are summed once.  The training plan stays cached across it.
         metrics: any of "acc", "top_5_acc": the hits of the training batches' probabilities, one x3d_topk_metrics launch
             after every step (skipped fp16 steps too, as Keras updates compiled metrics), read once per epoch.
+            "mean_class_acc" (single-label models, never a default): the mean over the classes that occurred of the per-class
+            top-1 accuracy -- one x3d_class_hits launch more per step, and `val_mean_class_acc` when validating.  Validation
+            metrics and `val_loss` are unweighted, as in Keras.
         save_freq: "epoch" or a positive int (`SaveSchedule`); rank 0 writes the checkpoints into `model_dir`.
 
         Multi-label models (DATA.MULTI_LABEL): batches are (clips, targets [B, classes]); `metrics` defaults to ("mAP",) --
@@ -522,11 +542,12 @@ class Trainer:
         if metrics is _DEFAULT_METRICS:
             metrics = known
         metrics = tuple(metrics or ())
-        unknown = [k for k in metrics if k not in known]
+        unknown = [k for k in metrics if k not in known + (() if multi else OPT_IN_METRICS)]
         if unknown:
             kind = "a multi-label model" if multi else "fit"
             raise ValueError(f"unknown metrics {unknown}: {kind} computes {known}")
-        val_keys = ("loss",) + known
+        per_class = "mean_class_acc" in metrics
+        val_keys = ("loss",) + known + (("mean_class_acc",) if per_class else ())
         schedule = SaveSchedule(save_freq)
         if initial_epoch is not None:
             self.epoch = int(initial_epoch)
@@ -551,13 +572,13 @@ class Trainer:
         while self.epoch < epochs:
             lr = lr_schedule(self.epoch, self.cfg)
             tot = torch.zeros((), dtype=torch.float64, device=self.model.device)
-            train_m = (DeviceMAP() if multi else DeviceMetrics()) if metrics else None
+            train_m = (DeviceMAP() if multi else DeviceMetrics(**(dict(per_class=True) if per_class else {}))) if metrics else None
             gn_tot, updates = (torch.zeros((), dtype=torch.float64, device=self.model.device) if self._clip else None), 0
             kd_tot = torch.zeros((), dtype=torch.float64, device=self.model.device) if self.teacher is not None else None
             for _ in range(steps):
-                clips, labels = next(it)
+                clips, labels, *weights = next(it)
                 before = self.opt_step if ds is None else None
-                pl = self.step(clips, labels, lr)
+                pl = self.step(clips, labels, lr, *weights)
                 tot += self.loss(pl).double()
                 if kd_tot is not None:
                     kd_tot += self.kd_loss(pl).double()
@@ -600,7 +621,7 @@ class Trainer:
                     self._fit_precise_bn(iter(precise_bn_data()), close=True)
             if val_source is not None:
                 with (self.ema_scope() if self.ema is not None and self.solver.ema_eval else contextlib.nullcontext()):
-                    r = self.validate(val_source(), validation_steps)
+                    r = self.validate(val_source(), validation_steps, **(dict(per_class=True) if per_class else {}))
                 for k in val_keys:
                     self.history["val_" + k].append(r[k])
             if ckpt is not None and writer:
@@ -628,16 +649,20 @@ class Trainer:
             if close and getattr(src, "close", None) is not None:
                 src.close()   # a reader's generator: stops its prefetch thread
 
-    def validate(self, batches, steps: Optional[int] = None):
+    def validate(self, batches, steps: Optional[int] = None, per_class: bool = False):
         """`model.evaluate` inside `fit` (reference train.py:148-151): `model(clips, training=False)` over `batches` (the
         first `steps` of them when given) into a DeviceMetrics, counters summed over the ranks once.  Unlike
         `evaluate_dataset` this releases no plan, so the training plan is still cached in the next epoch.  Returns
         {"loss", "acc", "top_5_acc", "videos"}; for a multi-label model the DeviceMAP result {"loss", "mAP", "videos",
-        "classes"} (batches of (clips, targets))."""
+        "classes"} (batches of (clips, targets)).  per_class (single-label models): + "mean_class_acc".  The loss is
+        unweighted: LOSS.* and sample weights act on the training loss only."""
         import itertools
         from .evaluate import DeviceMAP, DeviceMetrics
         m = self.model
-        dm = (DeviceMAP if getattr(m, "multi_label", False) else DeviceMetrics)(m.regularization_loss())
+        if getattr(m, "multi_label", False):
+            dm = DeviceMAP(m.regularization_loss())
+        else:
+            dm = DeviceMetrics(m.regularization_loss(), **(dict(per_class=True) if per_class else {}))
         it = iter(batches)
         try:
             for clips, labels in itertools.islice(it, None if steps is None else int(steps)):
