@@ -122,8 +122,8 @@ def test_tail_fwd_dp(gpu, n, c, p, off, dtype, conv_shortcut):
 
 
 def _wg_elems(n, p, dtype, aligned):
-    """elements one workgroup of x3d_tail_bwd_dp sums in fp32 before its fp64 atomics (drop_path.hip: 256 threads x 4 iterations x
-    the vector width; small 16-bit planes: nb samples of one channel)"""
+    """elements one workgroup of x3d_tail_bwd_dp sums in fp32 before its fp64 atomics (elem.hip, the DP form of tail_bwd_kernel:
+    256 threads x 4 iterations x the vector width; small 16-bit planes: nb samples of one channel)"""
     full = 4 if dtype == torch.float32 else 8
     vec = full if aligned and p % full == 0 else 1
     if dtype != torch.float32 and vec == 8 and p // 8 < 256:
@@ -313,7 +313,8 @@ def test_half_gradients_no_further_from_fp32_than_without_drop_path(gpu, dtype):
     (pinned to the reference by test_train_step_fp32_with_drop_path), at DROP_PATH_RATE = 0.5 and -- in this same test -- at 0, the
     parent's code path.  Required: maximum over tensors <= 2x, median <= 1.5x the rate-0 figures (the margin is for the smaller
     effective batch of a dropped branch).
-    Not yet measured on an MI355X: the test prints the four figures and both ratios before it asserts."""
+    On an MI355X (profiles/tail_refactor_mi355x.txt): bf16 ratios max 0.599, median 0.671; fp16 max 1.532, median 0.574.  The test
+    prints the four figures and both ratios before it asserts."""
     dist = {}
     for rate in (0.0, 0.5):
         ref, got = _fp32_run(gpu, rate), _grads_of(gpu, dtype, rate)

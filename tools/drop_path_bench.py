@@ -1,4 +1,4 @@
-"""What stochastic depth costs on the device (writes profiles/drop_path_mi355x.txt; no run has been recorded yet).
+"""What stochastic depth costs on the device (writes profiles/drop_path_mi355x.txt, which holds the run on an MI355X).
 
     python tools/drop_path_bench.py [--out FILE] [--no-step]          (FILE defaults to profiles/drop_path_mi355x.txt)
 

@@ -118,25 +118,10 @@ __device__ __forceinline__ void aug_geom_px(const AugArgs& a, const AugClip& c, 
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter-based, no state.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-// three N(0, 1) values of pixel `pix` of clip `clip` (Philox key: the clip's own seed): Box-Muller on uniforms (w >> 8) + 1) * 2^-24 in (0, 1] (exact in fp32)
+// three N(0, 1) values of pixel `pix` of clip `clip` (philox4x32_10 of common.h, key: the clip's own seed): Box-Muller on uniforms (w >> 8) + 1) * 2^-24 in (0, 1] (exact in fp32)
 __device__ __forceinline__ void aug_noise3(const AugClip& c, int clip, long long pix, float (&z)[3]) {
-  unsigned r[4];
-  philox4x32_10((unsigned)pix, (unsigned)((unsigned long long)pix >> 32), (unsigned)clip, 0u, c.seed_lo, c.seed_hi, r);
+  const Philox4 w = philox4x32_10((uint32_t)pix, (uint32_t)((unsigned long long)pix >> 32), (uint32_t)clip, 0u, c.seed_lo, c.seed_hi);
+  const uint32_t (&r)[4] = w.v;
   const float u0 = (float)((r[0] >> 8) + 1u) * 5.9604644775390625e-8f, u1 = (float)((r[1] >> 8) + 1u) * 5.9604644775390625e-8f;
   const float u2 = (float)((r[2] >> 8) + 1u) * 5.9604644775390625e-8f, u3 = (float)((r[3] >> 8) + 1u) * 5.9604644775390625e-8f;
   // hardware log2 / sin / cos (v_log_f32, v_sin_f32, v_cos_f32: the angle in revolutions, absolute error ~1e-6): plenty for

@@ -610,3 +610,26 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* scratch) {
 }
 
 __device__ __forceinline__ void atomic_add_d(double* p, double v) { atomicAdd(p, v); }
+
+// ------------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (c0, c1, c2, c3),
+// key (k0, k1), no state.  The one generator of the library: the drop-path keep table (drop_path.hip) and the erase noise of
+// the augmentation (aug.hip) draw from it.
+// ------------------------------------------------------------------------------------------------
+struct Philox4 { uint32_t v[4]; };
+__host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                          uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  Philox4 o;
+  o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
+  return o;
+}
+// uniform in [0, 1) on a 2^-24 grid: exact in fp32
+__host__ __device__ __forceinline__ float philox_u24(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }

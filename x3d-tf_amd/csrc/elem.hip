@@ -2,6 +2,7 @@
 // BN finalize (train / eval / backward), residual tail (Add+ReLU) forward and backward, ReLU+BN
 // backward reduce (stem, conv5 after global pooling), pool5, NTHWC<->NCTHW at the module boundary.
 #include "common.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // BN finalize kernels: one thread per channel (C <= a few hundred)
@@ -98,34 +99,50 @@ static inline dim3 elem_grid(long long P, int vec, int NC) {
   return dim3((unsigned)ceil_div_ll(P, (long long)ELEM_BLOCK * vec * ELEM_ITERS), (unsigned)NC);
 }
 
-// FOLD: the BatchNorm finalize of bn_c / bn_r runs here (x3d_bn_fold); the first workgroup of each channel of
-// sample 0 publishes the coefficients and updates the moving statistics
-struct TailFold { x3d_bn_fold c, r; int has_r; };
-template <typename T, int VEC, bool FOLD>
-__global__ __launch_bounds__(ELEM_BLOCK) void tail_fwd_kernel(const T* __restrict__ craw,
-                                                             const float* __restrict__ ssc,
-                                                             const T* __restrict__ sh,
-                                                             const float* __restrict__ ssr, T* __restrict__ y,
-                                                             int C, long long P, const TailFold fold) {
-  const int nc = blockIdx.y, c = nc % C;
-  float sc, tc, sr = 1.f, tr = 0.f;
-  if constexpr (FOLD) {
-    const bool writer = (nc < C) && blockIdx.x == 0 && threadIdx.x == 0;
-    bn_fold_channel(fold.c, c, writer, sc, tc, C);
-    if (fold.has_r) bn_fold_channel(fold.r, c, writer, sr, tr, C);
+// The launch ladder of this file, once: fn(ElemType<T>, integral_constant<int, VEC>) for the storage type of `dtype` and
+// vec = norm_vec() of the result of pick_vec: the full 16-byte vector (4 fp32 / 8 16-bit elements), or scalars
+template <typename T> struct ElemType { typedef T type; };
+template <int VEC> using ElemVec = std::integral_constant<int, VEC>;
+static inline int norm_vec(int dtype, int vec) {
+  const int full = dtype == X3D_F32 ? 4 : 8;
+  return vec >= full ? full : 1;
+}
+template <typename F>
+static inline void elem_dispatch(int dtype, int vec, F&& fn) {
+  const bool full = vec > 1;
+  if (dtype == X3D_F32) {
+    if (full) fn(ElemType<float>(), ElemVec<4>()); else fn(ElemType<float>(), ElemVec<1>());
+  } else if (dtype == X3D_F16) {
+    if (full) fn(ElemType<f16>(), ElemVec<8>()); else fn(ElemType<f16>(), ElemVec<1>());
   } else {
-    sc = ssc[c * 2]; tc = ssc[c * 2 + 1];
-    if (ssr) { sr = ssr[c * 2]; tr = ssr[c * 2 + 1]; }
+    if (full) fn(ElemType<bf16>(), ElemVec<8>()); else fn(ElemType<bf16>(), ElemVec<1>());
   }
-  const long long base = (long long)nc * P;
+}
+#define ELEM_T(t) typename decltype(t)::type
+
+// Residual tail (Add + ReLU).  One forward body, one general and one small-plane backward body for the plain tail, the tail
+// with the BatchNorm finalize folded in (FOLD) and the tail with stochastic depth (DP: keep[n] scales the branch).
+// The chunk of one workgroup, ELEM_ITERS vectors per thread.  DP: y = relu(k * (sc*craw + tc) + (sr*sh + tr)); !KEPT (k == 0):
+// y = relu(sr*sh + tr), craw not loaded.  KEPT is a template argument so that the uniform branch on keep[n] stands in front of
+// the loop, one loop per side.  (The pointers are the kernel's __restrict__ arguments; repeating the qualifier on these inlined
+// functions costs up to 4 VGPRs in the backward.)
+template <typename T, int VEC, bool DP, bool KEPT>
+__device__ __forceinline__ void tail_fwd_chunk(const T* craw, const T* sh, T* y, long long base, long long P, float sc, float tc,
+                                               float sr, float tr, float k) {
   long long p = ((long long)blockIdx.x * ELEM_ITERS * ELEM_BLOCK + threadIdx.x) * VEC;
 #pragma unroll
   for (int it = 0; it < ELEM_ITERS; it++, p += (long long)ELEM_BLOCK * VEC) {
     if (p < P) {
       float a[VEC], b[VEC], o[VEC];
-      VecIO<T, VEC>::load(craw + base + p, a);
-      if (sh) {
-        VecIO<T, VEC>::load(sh + base + p, b);
+      if (KEPT) VecIO<T, VEC>::load(craw + base + p, a);
+      if (DP || sh) VecIO<T, VEC>::load(sh + base + p, b);   // (DP: the entry point requires the shortcut)
+      if (!KEPT) {
+#pragma unroll
+        for (int e = 0; e < VEC; e++) o[e] = fmaxf(sr * b[e] + tr, 0.f);
+      } else if (DP) {
+#pragma unroll
+        for (int e = 0; e < VEC; e++) o[e] = fmaxf(k * (sc * a[e] + tc) + (sr * b[e] + tr), 0.f);
+      } else if (sh) {
 #pragma unroll
         for (int e = 0; e < VEC; e++) o[e] = fmaxf(sc * a[e] + tc + (sr * b[e] + tr), 0.f);
       } else {  // plain BN + ReLU (stem output)
@@ -137,61 +154,138 @@ __global__ __launch_bounds__(ELEM_BLOCK) void tail_fwd_kernel(const T* __restric
   }
 }
 
-// g = dy*[y>0] in place; sums_c += (sum g, sum g*craw); sums_r += (sum g, sum g*rraw)
-template <typename T, int VEC>
-__global__ __launch_bounds__(ELEM_BLOCK) void tail_bwd_kernel(T* __restrict__ dyg, const T* __restrict__ y,
-                                                             const T* __restrict__ craw,
-                                                             const T* __restrict__ rraw, double* sums_c,
-                                                             double* sums_r, int C, long long P) {
-  __shared__ float scratch[3 * (ELEM_BLOCK / 64)];
+// FOLD: the BatchNorm finalize of bn_c / bn_r runs here (x3d_bn_fold); the first workgroup of each channel of
+// sample 0 publishes the coefficients and updates the moving statistics
+// DP: keep[n] is uniform per workgroup in the (n, c) grid, read through a scalar load, and so is the branch on it
+struct TailFold { x3d_bn_fold c, r; int has_r; };
+template <typename T, int VEC, bool FOLD, bool DP>
+__global__ __launch_bounds__(ELEM_BLOCK) void tail_fwd_kernel(const T* __restrict__ craw,
+                                                             const float* __restrict__ ssc,
+                                                             const T* __restrict__ sh,
+                                                             const float* __restrict__ ssr,
+                                                             const float* __restrict__ keep, T* __restrict__ y,
+                                                             int C, long long P, const TailFold fold) {
+  static_assert(!(FOLD && DP), "the plan never folds a drop-path tail");
   const int nc = blockIdx.y, c = nc % C;
+  float sc, tc, sr = 1.f, tr = 0.f;
+  if constexpr (FOLD) {
+    const bool writer = (nc < C) && blockIdx.x == 0 && threadIdx.x == 0;
+    bn_fold_channel(fold.c, c, writer, sc, tc, C);
+    if (fold.has_r) bn_fold_channel(fold.r, c, writer, sr, tr, C);
+  } else {
+    sc = ssc[c * 2]; tc = ssc[c * 2 + 1];
+    if (ssr) { sr = ssr[c * 2]; tr = ssr[c * 2 + 1]; }
+  }
   const long long base = (long long)nc * P;
-  float red[3] = {0.f, 0.f, 0.f};
+  if constexpr (DP) {
+    const float k = keep[nc / C];
+    if (k == 0.f) tail_fwd_chunk<T, VEC, true, false>(craw, sh, y, base, P, sc, tc, sr, tr, k);
+    else tail_fwd_chunk<T, VEC, true, true>(craw, sh, y, base, P, sc, tc, sr, tr, k);
+  } else {
+    tail_fwd_chunk<T, VEC, false, true>(craw, sh, y, base, P, sc, tc, sr, tr, 1.f);
+  }
+}
+
+// Tail backward: g = dy*[y>0] in place; gb = the gradient of the branch: g itself, or with DP round(keep[n]*g), stored to
+// gbr; sums_c += (sum gb, sum gb*craw); sums_r += (sum g, sum g*rraw).
+// One element into the partial sums of its thread: red = (sum gb, sum gb*craw, sum g*rraw[, sum g: DP, where gb is not g]).
+// !KEPT (a dropped sample of the general kernel): gb = 0, cr is not read and nothing is added for the branch
+template <typename T, bool DP, bool KEPT>
+__device__ __forceinline__ float tail_bwd_term(float g, float k, const float& cr, const float& rr, bool has_r,
+                                               float (&red)[DP ? 4 : 3]) {
+  float gb = 0.f;
+  if constexpr (KEPT) {
+    gb = g;
+    if constexpr (DP) gb = round_to<T>(k * g);
+    red[0] += gb;
+    red[1] += gb * cr;
+  }
+  if (has_r) {
+    if constexpr (DP) red[3] += g;
+    red[2] += g * rr;
+  }
+  return gb;
+}
+// ... the chunk of one workgroup of the general kernel
+template <typename T, int VEC, bool DP, bool KEPT>
+__device__ __forceinline__ void tail_bwd_chunk(T* dyg, T* gbr, const T* y, const T* craw, const T* rraw, long long base,
+                                               long long P, float k, float (&red)[DP ? 4 : 3]) {
   long long p = ((long long)blockIdx.x * ELEM_ITERS * ELEM_BLOCK + threadIdx.x) * VEC;
 #pragma unroll
   for (int it = 0; it < ELEM_ITERS; it++, p += (long long)ELEM_BLOCK * VEC) {
     if (p < P) {
-      float d[VEC], yy[VEC], cr[VEC], rr[VEC], g[VEC];
+      float d[VEC], yy[VEC], cr[VEC], rr[VEC], g[VEC], gb[VEC];
       VecIO<T, VEC>::load(dyg + base + p, d);
       VecIO<T, VEC>::load(y + base + p, yy);
-      VecIO<T, VEC>::load(craw + base + p, cr);
+      if (KEPT) VecIO<T, VEC>::load(craw + base + p, cr);
       if (rraw) VecIO<T, VEC>::load(rraw + base + p, rr);
 #pragma unroll
       for (int e = 0; e < VEC; e++) {
         g[e] = yy[e] > 0.f ? d[e] : 0.f;
-        red[0] += g[e];
-        red[1] += g[e] * cr[e];
-        if (rraw) red[2] += g[e] * rr[e];
+        gb[e] = tail_bwd_term<T, DP, KEPT>(g[e], k, cr[e], rr[e], rraw != nullptr, red);
       }
       VecIO<T, VEC>::store(dyg + base + p, g);
+      if constexpr (DP) VecIO<T, VEC>::store(gbr + base + p, gb);
     }
   }
-  block_sum<3>(red, scratch);
-  if (threadIdx.x == 0) {
+}
+// ... and the sums of a workgroup into the fp64 accumulators (any_kept false: a dropped workgroup adds nothing to sums_c)
+template <bool DP>
+__device__ __forceinline__ void tail_bwd_flush(const float (&red)[DP ? 4 : 3], bool any_kept, bool has_r, double* sums_c,
+                                               double* sums_r, int c) {
+  if (any_kept) {
     atomic_add_d(&sums_c[c * 2], (double)red[0]);
     atomic_add_d(&sums_c[c * 2 + 1], (double)red[1]);
-    if (rraw) {
-      atomic_add_d(&sums_r[c * 2], (double)red[0]);
-      atomic_add_d(&sums_r[c * 2 + 1], (double)red[2]);
-    }
   }
+  if (has_r) {
+    atomic_add_d(&sums_r[c * 2], (double)red[DP ? 3 : 0]);
+    atomic_add_d(&sums_r[c * 2 + 1], (double)red[2]);
+  }
+}
+
+// DP: keep[n] and the branch on it are uniform per workgroup, as in the forward
+template <typename T, int VEC, bool DP>
+__global__ __launch_bounds__(ELEM_BLOCK) void tail_bwd_kernel(T* __restrict__ dyg, T* __restrict__ gbr, const T* __restrict__ y,
+                                                             const T* __restrict__ craw, const T* __restrict__ rraw,
+                                                             const float* __restrict__ keep, double* sums_c,
+                                                             double* sums_r, int C, long long P) {
+  constexpr int NR = DP ? 4 : 3;
+  __shared__ float scratch[NR * (ELEM_BLOCK / 64)];
+  const int nc = blockIdx.y, c = nc % C;
+  const long long base = (long long)nc * P;
+  float red[NR] = {};
+  bool kept = true;
+  if constexpr (DP) {
+    const float k = keep[nc / C];
+    kept = k != 0.f;
+    if (kept) tail_bwd_chunk<T, VEC, true, true>(dyg, gbr, y, craw, rraw, base, P, k, red);
+    else tail_bwd_chunk<T, VEC, true, false>(dyg, gbr, y, craw, rraw, base, P, k, red);
+  } else {
+    tail_bwd_chunk<T, VEC, false, true>(dyg, gbr, y, craw, rraw, base, P, 1.f, red);
+  }
+  block_sum<NR>(red, scratch);
+  if (threadIdx.x == 0) tail_bwd_flush<DP>(red, kept, rraw != nullptr, sums_c, sums_r, c);
 }
 
 // ... small planes (P / VEC < 256: the 7 x 7 stage): one workgroup takes NB samples of ONE channel -- with a workgroup per (n, c)
 // 98 of 256 threads had a vector and N workgroups per channel met in the fp64 atomics (192 ch x 64 clips of 16x7x7: 28 us for
 // 77 MB).  grid = (C, ceil(N / NB)); the flat index runs over (sample in the group, vector of the plane).
-template <typename T, int VEC>
-__global__ __launch_bounds__(ELEM_BLOCK) void tail_bwd_small_kernel(T* __restrict__ dyg, const T* __restrict__ y,
+// DP: keep belongs to the sample, so here it is per lane: a dropped sample's lanes skip the craw load and, with craw = 0 and
+// gb = round(0 * g), add exact zeros to sums_c.
+template <typename T, int VEC, bool DP>
+__global__ __launch_bounds__(ELEM_BLOCK) void tail_bwd_small_kernel(T* __restrict__ dyg, T* __restrict__ gbr, const T* __restrict__ y,
                                                                    const T* __restrict__ craw, const T* __restrict__ rraw,
-                                                                   double* sums_c, double* sums_r, int N, int C, int P, int NB) {
-  __shared__ float scratch[3 * (ELEM_BLOCK / 64)];
+                                                                   const float* __restrict__ keep, double* sums_c,
+                                                                   double* sums_r, int N, int C, int P, int NB) {
+  constexpr int NR = DP ? 4 : 3;
+  __shared__ float scratch[NR * (ELEM_BLOCK / 64)];
   const int c = blockIdx.x, n0 = blockIdx.y * NB;
   const int nb = min(NB, N - n0);
   const int vpp = P / VEC, total = nb * vpp;
-  float red[3] = {0.f, 0.f, 0.f};
+  float red[NR] = {};
   for (int i0 = threadIdx.x; i0 < total; i0 += 2 * ELEM_BLOCK) {
     // two vectors per thread and round, their loads issued together
-    float d[2][VEC], yy[2][VEC], cr[2][VEC], rr[2][VEC];
+    float d[2][VEC], yy[2][VEC], cr[2][VEC], rr[2][VEC], k[2];
     long long off[2];
     bool ok[2];
 #pragma unroll
@@ -200,36 +294,34 @@ __global__ __launch_bounds__(ELEM_BLOCK) void tail_bwd_small_kernel(T* __restric
       ok[u] = i < total;
       const int nl = ok[u] ? i / vpp : 0, pv = ok[u] ? i - nl * vpp : 0;
       off[u] = ((long long)(n0 + nl) * C + c) * P + (long long)pv * VEC;
+      k[u] = 1.f;
+      if constexpr (DP) {
+        k[u] = ok[u] ? keep[n0 + nl] : 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; e++) cr[u][e] = 0.f;
+      }
       if (ok[u]) {
         VecIO<T, VEC>::load(dyg + off[u], d[u]);
         VecIO<T, VEC>::load(y + off[u], yy[u]);
-        VecIO<T, VEC>::load(craw + off[u], cr[u]);
+        if (!DP || k[u] != 0.f) VecIO<T, VEC>::load(craw + off[u], cr[u]);
         if (rraw) VecIO<T, VEC>::load(rraw + off[u], rr[u]);
       }
     }
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       if (!ok[u]) continue;
-      float g[VEC];
+      float g[VEC], gb[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; e++) {
         g[e] = yy[u][e] > 0.f ? d[u][e] : 0.f;
-        red[0] += g[e];
-        red[1] += g[e] * cr[u][e];
-        if (rraw) red[2] += g[e] * rr[u][e];
+        gb[e] = tail_bwd_term<T, DP, true>(g[e], k[u], cr[u][e], rr[u][e], rraw != nullptr, red);
       }
       VecIO<T, VEC>::store(dyg + off[u], g);
+      if constexpr (DP) VecIO<T, VEC>::store(gbr + off[u], gb);
     }
   }
-  block_sum<3>(red, scratch);
-  if (threadIdx.x == 0) {
-    atomic_add_d(&sums_c[c * 2], (double)red[0]);
-    atomic_add_d(&sums_c[c * 2 + 1], (double)red[1]);
-    if (rraw) {
-      atomic_add_d(&sums_r[c * 2], (double)red[0]);
-      atomic_add_d(&sums_r[c * 2 + 1], (double)red[2]);
-    }
-  }
+  block_sum<NR>(red, scratch);
+  if (threadIdx.x == 0) tail_bwd_flush<DP>(red, true, rraw != nullptr, sums_c, sums_r, c);
 }
 
 // z = s*yraw + t ; g = (dy ? dy : dpool[n][c]/P) * [z > 0]; sums += (sum g, sum g*yraw)
@@ -294,9 +386,16 @@ __global__ __launch_bounds__(ELEM_BLOCK) void pool_fwd_kernel(const T* __restric
   if (threadIdx.x == 0) pooled[nc] = red[0] / (float)P;
 }
 
-static inline int norm_vec(int dtype, int vec) {
-  const int full = dtype == X3D_F32 ? 4 : 8;
-  return vec >= full ? full : 1;
+template <bool FOLD, bool DP>
+static void tail_fwd_launch(const void* c_raw, const float* c_scale_shift, const void* shortcut, const float* r_scale_shift,
+                            const float* keep, void* y, int N, int C, long long P, int dtype, const TailFold& fold, void* stream) {
+  const int eb = dtype == X3D_F32 ? 4 : 2;
+  const int vec = norm_vec(dtype, pick_vec(eb, P, c_raw, shortcut, y));
+  elem_dispatch(dtype, vec, [&](auto t, auto v) {
+    typedef ELEM_T(t) T;
+    hipLaunchKernelGGL((tail_fwd_kernel<T, decltype(v)::value, FOLD, DP>), elem_grid(P, vec, N * C), dim3(ELEM_BLOCK), 0,
+                       (hipStream_t)stream, (const T*)c_raw, c_scale_shift, (const T*)shortcut, r_scale_shift, keep, (T*)y, C, P, fold);
+  });
 }
 
 extern "C" int x3d_tail_fwd(const void* c_raw, const float* c_scale_shift, const void* shortcut,
@@ -304,24 +403,9 @@ extern "C" int x3d_tail_fwd(const void* c_raw, const float* c_scale_shift, const
                             void* stream) {
   X3D_REQUIRE(c_raw && c_scale_shift && y && N > 0 && C > 0 && P > 0, "tail_fwd: bad args");
   X3D_REQUIRE(x3d_dtype_ok(dtype), "tail_fwd: bad dtype");
-  const int eb = dtype == X3D_F32 ? 4 : 2;
-  const int vec = norm_vec(dtype, pick_vec(eb, P, c_raw, shortcut, y));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid = elem_grid(P, vec, N * C);
   TailFold nofold;
   memset(&nofold, 0, sizeof(nofold));
-#define ARGS(T) (const T*)c_raw, c_scale_shift, (const T*)shortcut, r_scale_shift, (T*)y, C, P, nofold
-  if (dtype == X3D_F32) {
-    if (vec == 4) hipLaunchKernelGGL((tail_fwd_kernel<float, 4, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-    else hipLaunchKernelGGL((tail_fwd_kernel<float, 1, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-  } else if (dtype == X3D_F16) {
-    if (vec == 8) hipLaunchKernelGGL((tail_fwd_kernel<f16, 8, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-    else hipLaunchKernelGGL((tail_fwd_kernel<f16, 1, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-  } else {
-    if (vec == 8) hipLaunchKernelGGL((tail_fwd_kernel<bf16, 8, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-    else hipLaunchKernelGGL((tail_fwd_kernel<bf16, 1, false>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-  }
-#undef ARGS
+  tail_fwd_launch<false, false>(c_raw, c_scale_shift, shortcut, r_scale_shift, nullptr, y, N, C, P, dtype, nofold, stream);
   X3D_LAUNCH_CHECK("tail_fwd");
   return X3D_OK;
 }
@@ -332,28 +416,55 @@ extern "C" int x3d_tail_fwd_bn(const void* c_raw, const x3d_bn_fold* c_bn, const
   X3D_REQUIRE(bn_fold_valid(c_bn), "tail_fwd_bn: incomplete x3d_bn_fold for bn_c");
   X3D_REQUIRE(!r_bn || (shortcut && bn_fold_valid(r_bn)), "tail_fwd_bn: incomplete x3d_bn_fold for bn_r");
   X3D_REQUIRE(x3d_dtype_ok(dtype), "tail_fwd_bn: bad dtype");
-  const int eb = dtype == X3D_F32 ? 4 : 2;
-  const int vec = norm_vec(dtype, pick_vec(eb, P, c_raw, shortcut, y));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid = elem_grid(P, vec, N * C);
   TailFold fold;
   memset(&fold, 0, sizeof(fold));
   fold.c = *c_bn;
   if (r_bn) { fold.r = *r_bn; fold.has_r = 1; }
-#define ARGS(T) (const T*)c_raw, (const float*)nullptr, (const T*)shortcut, (const float*)nullptr, (T*)y, C, P, fold
-  if (dtype == X3D_F32) {
-    if (vec == 4) hipLaunchKernelGGL((tail_fwd_kernel<float, 4, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-    else hipLaunchKernelGGL((tail_fwd_kernel<float, 1, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-  } else if (dtype == X3D_F16) {
-    if (vec == 8) hipLaunchKernelGGL((tail_fwd_kernel<f16, 8, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-    else hipLaunchKernelGGL((tail_fwd_kernel<f16, 1, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-  } else {
-    if (vec == 8) hipLaunchKernelGGL((tail_fwd_kernel<bf16, 8, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-    else hipLaunchKernelGGL((tail_fwd_kernel<bf16, 1, true>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-  }
-#undef ARGS
+  tail_fwd_launch<true, false>(c_raw, nullptr, shortcut, nullptr, nullptr, y, N, C, P, dtype, fold, stream);
   X3D_LAUNCH_CHECK("tail_fwd_bn");
   return X3D_OK;
+}
+
+extern "C" int x3d_tail_fwd_dp(const void* c_raw, const float* c_scale_shift, const void* shortcut, const float* r_scale_shift,
+                               const float* keep, void* y, int N, int C, long long P, int dtype, void* stream) {
+  X3D_REQUIRE(c_raw && c_scale_shift && y && keep && N > 0 && C > 0 && P > 0, "tail_fwd_dp: bad args");
+  X3D_REQUIRE(shortcut, "tail_fwd_dp: shortcut required (the stem's BatchNorm + ReLU has no branch to drop)");
+  X3D_REQUIRE(x3d_dtype_ok(dtype), "tail_fwd_dp: bad dtype");
+  TailFold nofold;
+  memset(&nofold, 0, sizeof(nofold));
+  tail_fwd_launch<false, true>(c_raw, c_scale_shift, shortcut, r_scale_shift, keep, y, N, C, P, dtype, nofold, stream);
+  X3D_LAUNCH_CHECK("tail_fwd_dp");
+  return X3D_OK;
+}
+
+// small planes in 16-bit storage: the number of samples of one channel a workgroup of tail_bwd_small_kernel takes
+// (0: the plane is not small, the general kernel takes it)
+static inline int tail_small_nb(int dtype, int vec, int N, long long P) {
+  if (dtype == X3D_F32 || vec != 8 || P / 8 >= ELEM_BLOCK) return 0;
+  int nb = (int)(4 * ELEM_BLOCK / (P / 8));
+  if (nb > N) nb = N;
+  if (nb > 16) nb = 16;
+  return nb;
+}
+
+// nb: tail_small_nb(), or 0 for the general kernel whatever the plane
+template <bool DP>
+static void tail_bwd_launch(void* dy_g, void* g_branch, const void* y, const void* c_raw, const void* r_raw, const float* keep,
+                            double* sums_c, double* sums_r, int N, int C, long long P, int dtype, int vec, int nb, void* stream) {
+  elem_dispatch(dtype, vec, [&](auto t, auto v) {
+    typedef ELEM_T(t) T;
+    constexpr int VEC = decltype(v)::value;
+    if constexpr (VEC == 8) {
+      if (nb > 0) {
+        hipLaunchKernelGGL((tail_bwd_small_kernel<T, 8, DP>), dim3((unsigned)C, (unsigned)ceil_div(N, nb)), dim3(ELEM_BLOCK), 0,
+                           (hipStream_t)stream, (T*)dy_g, (T*)g_branch, (const T*)y, (const T*)c_raw, (const T*)r_raw, keep, sums_c,
+                           sums_r, N, C, (int)P, nb);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((tail_bwd_kernel<T, VEC, DP>), elem_grid(P, vec, N * C), dim3(ELEM_BLOCK), 0, (hipStream_t)stream, (T*)dy_g,
+                       (T*)g_branch, (const T*)y, (const T*)c_raw, (const T*)r_raw, keep, sums_c, sums_r, C, P);
+  });
 }
 
 extern "C" int x3d_tail_bwd(void* dy_g, const void* y, const void* c_raw, const void* r_raw, double* sums_c,
@@ -363,36 +474,26 @@ extern "C" int x3d_tail_bwd(void* dy_g, const void* y, const void* c_raw, const 
   X3D_REQUIRE(x3d_dtype_ok(dtype), "tail_bwd: bad dtype");
   const int eb = dtype == X3D_F32 ? 4 : 2;
   const int vec = norm_vec(dtype, pick_vec(eb, P, dy_g, y, c_raw, r_raw));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid = elem_grid(P, vec, N * C);
-  // small planes in 16-bit storage: NB samples of one channel per workgroup (X3D_TAIL_SMALL=0: A/B hook)
-  if (dtype != X3D_F32 && vec == 8 && P / 8 < ELEM_BLOCK && x3d_env_int("X3D_TAIL_SMALL", 1) != 0) {
-    int nb = (int)(4 * ELEM_BLOCK / (P / 8));
-    if (nb > N) nb = N;
-    if (nb > 16) nb = 16;
-    const dim3 g2((unsigned)C, (unsigned)ceil_div(N, nb));
-    if (dtype == X3D_F16)
-      hipLaunchKernelGGL((tail_bwd_small_kernel<f16, 8>), g2, dim3(ELEM_BLOCK), 0, st, (f16*)dy_g, (const f16*)y, (const f16*)c_raw,
-                         (const f16*)r_raw, sums_c, sums_r, N, C, (int)P, nb);
-    else
-      hipLaunchKernelGGL((tail_bwd_small_kernel<bf16, 8>), g2, dim3(ELEM_BLOCK), 0, st, (bf16*)dy_g, (const bf16*)y, (const bf16*)c_raw,
-                         (const bf16*)r_raw, sums_c, sums_r, N, C, (int)P, nb);
-    X3D_LAUNCH_CHECK("tail_bwd");
-    return X3D_OK;
-  }
-#define ARGS(T) (T*)dy_g, (const T*)y, (const T*)c_raw, (const T*)r_raw, sums_c, sums_r, C, P
-  if (dtype == X3D_F32) {
-    if (vec == 4) hipLaunchKernelGGL((tail_bwd_kernel<float, 4>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-    else hipLaunchKernelGGL((tail_bwd_kernel<float, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-  } else if (dtype == X3D_F16) {
-    if (vec == 8) hipLaunchKernelGGL((tail_bwd_kernel<f16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-    else hipLaunchKernelGGL((tail_bwd_kernel<f16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-  } else {
-    if (vec == 8) hipLaunchKernelGGL((tail_bwd_kernel<bf16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-    else hipLaunchKernelGGL((tail_bwd_kernel<bf16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-  }
-#undef ARGS
+  // (X3D_TAIL_SMALL=0: A/B hook of the small-plane kernel)
+  const int nb = x3d_env_int("X3D_TAIL_SMALL", 1) != 0 ? tail_small_nb(dtype, vec, N, P) : 0;
+  tail_bwd_launch<false>(dy_g, nullptr, y, c_raw, r_raw, nullptr, sums_c, sums_r, N, C, P, dtype, vec, nb, stream);
   X3D_LAUNCH_CHECK("tail_bwd");
+  return X3D_OK;
+}
+
+extern "C" int x3d_tail_bwd_dp(void* dy_g, void* g_branch, const void* y, const void* c_raw, const void* r_raw, const float* keep,
+                               double* sums_c, double* sums_r, int N, int C, long long P, int dtype, void* stream) {
+  X3D_REQUIRE(dy_g && g_branch && y && c_raw && keep && sums_c && N > 0 && C > 0 && P > 0, "tail_bwd_dp: bad args");
+  X3D_REQUIRE(dy_g != g_branch, "tail_bwd_dp: g_branch must not alias dy_g");
+  X3D_REQUIRE(!r_raw || sums_r, "tail_bwd_dp: sums_r required with r_raw");
+  X3D_REQUIRE(x3d_dtype_ok(dtype), "tail_bwd_dp: bad dtype");
+  const int eb = dtype == X3D_F32 ? 4 : 2;
+  int vec = pick_vec(eb, P, dy_g, y, c_raw, r_raw);
+  const int vec_g = pick_vec(eb, P, g_branch);      // (g_branch may be the one misaligned pointer)
+  vec = norm_vec(dtype, vec < vec_g ? vec : vec_g);
+  tail_bwd_launch<true>(dy_g, g_branch, y, c_raw, r_raw, keep, sums_c, sums_r, N, C, P, dtype, vec, tail_small_nb(dtype, vec, N, P),
+                        stream);
+  X3D_LAUNCH_CHECK("tail_bwd_dp");
   return X3D_OK;
 }
 
@@ -404,20 +505,11 @@ extern "C" int x3d_relu_bn_bwd_reduce(const void* dy, const float* dpool, const 
   X3D_REQUIRE(x3d_dtype_ok(dtype), "relu_bn_bwd_reduce: bad dtype");
   const int eb = dtype == X3D_F32 ? 4 : 2;
   const int vec = norm_vec(dtype, pick_vec(eb, P, dy, yraw, g));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid = elem_grid(P, vec, N * C);
-#define ARGS(T) (const T*)dy, dpool, (const T*)yraw, scale_shift, (T*)g, sums, C, P
-  if (dtype == X3D_F32) {
-    if (vec == 4) hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<float, 4>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-    else hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<float, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-  } else if (dtype == X3D_F16) {
-    if (vec == 8) hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<f16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-    else hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<f16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-  } else {
-    if (vec == 8) hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<bf16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-    else hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<bf16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-  }
-#undef ARGS
+  elem_dispatch(dtype, vec, [&](auto t, auto v) {
+    typedef ELEM_T(t) T;
+    hipLaunchKernelGGL((relu_bn_bwd_reduce_kernel<T, decltype(v)::value>), elem_grid(P, vec, N * C), dim3(ELEM_BLOCK), 0,
+                       (hipStream_t)stream, (const T*)dy, dpool, (const T*)yraw, scale_shift, (T*)g, sums, C, P);
+  });
   X3D_LAUNCH_CHECK("relu_bn_bwd_reduce");
   return X3D_OK;
 }
@@ -428,20 +520,11 @@ extern "C" int x3d_pool_fwd(const void* x_raw, const float* scale_shift, float* 
   X3D_REQUIRE(x3d_dtype_ok(dtype), "pool_fwd: bad dtype");
   const int eb = dtype == X3D_F32 ? 4 : 2;
   const int vec = norm_vec(dtype, pick_vec(eb, P, x_raw));
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((unsigned)(N * C));
-#define ARGS(T) (const T*)x_raw, scale_shift, pooled, C, P
-  if (dtype == X3D_F32) {
-    if (vec == 4) hipLaunchKernelGGL((pool_fwd_kernel<float, 4>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-    else hipLaunchKernelGGL((pool_fwd_kernel<float, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(float));
-  } else if (dtype == X3D_F16) {
-    if (vec == 8) hipLaunchKernelGGL((pool_fwd_kernel<f16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-    else hipLaunchKernelGGL((pool_fwd_kernel<f16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(f16));
-  } else {
-    if (vec == 8) hipLaunchKernelGGL((pool_fwd_kernel<bf16, 8>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-    else hipLaunchKernelGGL((pool_fwd_kernel<bf16, 1>), grid, dim3(ELEM_BLOCK), 0, st, ARGS(bf16));
-  }
-#undef ARGS
+  elem_dispatch(dtype, vec, [&](auto t, auto v) {
+    typedef ELEM_T(t) T;
+    hipLaunchKernelGGL((pool_fwd_kernel<T, decltype(v)::value>), dim3((unsigned)(N * C)), dim3(ELEM_BLOCK), 0, (hipStream_t)stream,
+                       (const T*)x_raw, scale_shift, pooled, C, P);
+  });
   X3D_LAUNCH_CHECK("pool_fwd");
   return X3D_OK;
 }
