@@ -65,7 +65,8 @@ extern "C" {
  *   138 (additions only, no bump) frozen BatchNorm backward: a negative count in x3d_bn_bwd_finalize / _rc and
  *       x3d_se_bnb_bwd_args.P (values every earlier version refused; no struct changes its layout);
  *   138 (additions only, no bump) x3d_softmax_xent_w / x3d_sigmoid_bce_w / x3d_class_hits (class and sample weights,
- *       focal terms, per-class hit counters). */
+ *       focal terms, per-class hit counters);
+ *   138 (additions only, no bump) x3d_roi_pool_fwd / x3d_roi_pool_bwd (ROI head for action detection). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -584,6 +585,39 @@ int x3d_subsample2(const void* src, void* dst, long long planes, int H, int W, i
  * ------------------------------------------------------------------------------------------ */
 int x3d_pool_fwd(const void* x_raw, const float* scale_shift, float* pooled /* [N][C] */, int N, int C,
                  long long P, int dtype, void* stream);
+/* K7r  ROI head for action detection (PySlowFast DETECTION.ENABLE / ResNetRoIHead): per person box, the temporal mean of
+ *     relu(bn(conv5)), ROIAlign and a spatial max -- detectron2 / torchvision roi_align(aligned=True) followed by MaxPool2d(R).
+ *     The two launches take the places of x3d_pool_fwd and of x3d_relu_bn_bwd_reduce(dy == NULL, dpool).
+ *   x_raw / yraw [N][C][T][H][W] in the storage dtype; scale_shift [C][2] fp32, as x3d_pool_fwd reads them.
+ *   boxes [N][K][4] fp32 (x1, y1, x2, y2) in pixels of the clip; num_boxes [N] int32: slots k >= num_boxes[n] are empty.  K is
+ *   a fixed capacity per clip: the boxes of sample n are rows n*K .. n*K+K-1 (no batch-index column; the backward is a gather).
+ *   pooled [N*K][C] fp32; argmax [N*K][C] bytes, may be NULL in the forward (inference).
+ * Forward:
+ *   M[h][w] = mean_t relu(s_c*x + t_c), accumulated in fp32 (t in order).
+ *   Box coordinates are multiplied by spatial_scale and clamped to [0, W] x [0, H] (x1', y1', x2', y2'), so the sample loops are
+ *   bounded whatever the box is.  bin_w = (x2' - x1') / R, bin_h = (y2' - y1') / R; samples per bin gw = sampling_ratio > 0 ?
+ *   sampling_ratio : ceil((x2' - x1') / R), gh likewise.  Sample (iy, ix) of bin (ph, pw) sits at
+ *   y = y1' - 0.5 + ph*bin_h + (iy + 0.5)*bin_h/gh, x likewise (this geometry is worked out in fp64).
+ *   Bilinear interpolation with border clamp: y <= 0 -> 0; y_low = floor(y) >= H-1 -> y_low = y_high = H-1, y = H-1.  After the
+ *   box clamp no sample lies outside [-0.5, H-0.5], so torchvision's "outside -> 0" rule never applies.
+ *   The bin value is the mean of its gh*gw samples; pooled = max over the R*R bins, argmax = the first maximal bin in row-major
+ *   order (ph*R + pw).
+ *   Treated as empty: an empty slot, a box with x2' <= x1' or y2' <= y1', any non-finite coordinate.  Such a slot gives
+ *   pooled = 0, argmax = 0 and no gradient; the plane of a sample with num_boxes[n] <= 0 is not read.
+ * Backward:
+ *   dM[h][w] = sum over the boxes of sample n, in order, of dpooled[n*K+k][c] * (sum over the samples of the argmax bin of the
+ *   bilinear weight of (h, w)) / (gh*gw);  g = round_to<T>(dM[h][w] / T * [s*yraw + t > 0]) for every t;
+ *   sums [C][2] += (sum g, sum g*yraw), exactly as x3d_relu_bn_bwd_reduce with dy == NULL accumulates them.  dM is built without
+ *   floating-point atomics (threads own pixels), so g is bit-reproducible; sums go through fp64 atomics like the sibling's.
+ *   An argmax byte >= R*R is ignored (no gradient from that row).
+ * Refused before any launch: H*W > 1024; R outside 1..15; K outside 1..64; N*K > 2048 (x3d_dense_bwd's limit on rows);
+ *   sampling_ratio < 0; spatial_scale <= 0 or not finite. */
+int x3d_roi_pool_fwd(const void* x_raw, const float* scale_shift, const float* boxes, const int* num_boxes,
+                     float* pooled, unsigned char* argmax, int N, int C, int T, int H, int W, int K, int R,
+                     int sampling_ratio, float spatial_scale, int dtype, void* stream);
+int x3d_roi_pool_bwd(const float* dpooled, const unsigned char* argmax, const float* boxes, const int* num_boxes,
+                     const void* yraw, const float* scale_shift, void* g, double* sums, int N, int C, int T, int H,
+                     int W, int K, int R, int sampling_ratio, float spatial_scale, int dtype, void* stream);
 /* y[n][m] = act( sum_k (x[n][k] * (mask ? mask[n][k]*mask_scale : 1)) * w[m][k] + b[m] ), all fp32 */
 int x3d_dense_fwd(const float* x, const float* mask, float mask_scale, const float* w, const float* b,
                   float* y, int act, int N, int K, int M, void* stream);

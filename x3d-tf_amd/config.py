@@ -138,7 +138,8 @@ def get_default_config():
     LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL / FREEZE_BN: fine-tuning),
     NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
-    DISTILL.* (knowledge distillation against a teacher's logits), LOSS.* (class / positive weights and focal terms)."""
+    DISTILL.* (knowledge distillation against a teacher's logits), LOSS.* (class / positive weights and focal terms),
+    DETECTION.* (the ROI head for action detection)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -203,6 +204,12 @@ def get_default_config():
     # Categorical / BinaryFocalCrossentropy), on the sigmoid head that of the positive term; FOCAL_GAMMA_NEG: that of the
     # sigmoid head's negative term (the symmetric focal loss sets both to one value, asymmetric focusing to two).  [] = all ones
     c.LOSS = CfgNode(dict(CLASS_WEIGHTS=[], POS_WEIGHT=[], FOCAL_GAMMA=0.0, FOCAL_GAMMA_NEG=0.0))
+    # the ROI head for action detection (detection_settings; off by default; names as PySlowFast's DETECTION section): per person
+    # box, the temporal mean of relu(bn5(conv5)), ROIAlign at ROI_XFORM_RESOLUTION^2 bins, a spatial max, fc1 / fc2 and the head's
+    # loss over the valid boxes (x3d_roi_pool_fwd / x3d_roi_pool_bwd).  MAX_BOXES: the fixed number of box slots K per clip;
+    # SPATIAL_SCALE_FACTOR: clip pixels per conv5 pixel (the network's stride, 32); ROI_SAMPLING_RATIO: samples per bin and axis,
+    # 0 = ceil(bin size)
+    c.DETECTION = CfgNode(dict(ENABLE=False, MAX_BOXES=8, ROI_XFORM_RESOLUTION=7, SPATIAL_SCALE_FACTOR=32, ROI_SAMPLING_RATIO=0))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -236,6 +243,7 @@ def get_config(name, overrides=None, freeze=True):
     precise_bn_settings(cfg)
     distill_settings(cfg, have_teacher=True)   # (whether a teacher exists is the trainer's to check)
     loss_settings(cfg)
+    detection_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -606,4 +614,51 @@ def loss_settings(cfg) -> LossSettings:
         raise ValueError("LOSS.POS_WEIGHT weighs the positive term of the sigmoid head: it needs DATA.MULTI_LABEL")
     if not multi and s.focal_gamma_neg != 0.0:
         raise ValueError("LOSS.FOCAL_GAMMA_NEG focuses the negative term of the sigmoid head: it needs DATA.MULTI_LABEL")
+    return s
+
+
+DetectionSettings = collections.namedtuple("DetectionSettings", "enable max_boxes resolution spatial_scale_factor sampling_ratio")
+_DETECTION_OFF = DetectionSettings(False, 8, 7, 32, 0)
+# the limits of x3d_roi_pool_fwd / x3d_roi_pool_bwd (include/x3d_hip.h)
+ROI_MAX_BOXES, ROI_MAX_RESOLUTION = 64, 15
+
+
+def detection_settings(cfg) -> DetectionSettings:
+    """cfg.DETECTION.* as one tuple (a config tree without the section: off).  ValueError -- whether the switch is on or not -- for
+    MAX_BOXES outside [1, 64], ROI_XFORM_RESOLUTION outside [1, 15], a SPATIAL_SCALE_FACTOR < 1 and a
+    negative ROI_SAMPLING_RATIO (the kernels' own limits); with ENABLE also for MIXUP.ENABLE (a mixed clip has no boxes),
+    DISTILL.ENABLE, and TEST.NUM_SPATIAL_CROPS * TEST.NUM_TEMPORAL_VIEWS > 1 (box rows are not views of one video)."""
+    dv = getattr(cfg, "DETECTION", None)
+    if dv is None:
+        return _DETECTION_OFF
+    d = _DETECTION_OFF
+
+    def whole(key, dflt):
+        v = getattr(dv, key, dflt)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"DETECTION.{key} must be an integer, not {v!r}")
+        return v
+
+    k = whole("MAX_BOXES", d.max_boxes)
+    if not 1 <= k <= ROI_MAX_BOXES:
+        raise ValueError(f"DETECTION.MAX_BOXES must lie in [1, {ROI_MAX_BOXES}], not {k}")
+    r = whole("ROI_XFORM_RESOLUTION", d.resolution)
+    if not 1 <= r <= ROI_MAX_RESOLUTION:
+        raise ValueError(f"DETECTION.ROI_XFORM_RESOLUTION must lie in [1, {ROI_MAX_RESOLUTION}], not {r}")
+    f = whole("SPATIAL_SCALE_FACTOR", d.spatial_scale_factor)
+    if f < 1:
+        raise ValueError(f"DETECTION.SPATIAL_SCALE_FACTOR must be >= 1, not {f}")
+    sr = whole("ROI_SAMPLING_RATIO", d.sampling_ratio)
+    if sr < 0:
+        raise ValueError(f"DETECTION.ROI_SAMPLING_RATIO must be >= 0, not {sr}")
+    s = DetectionSettings(bool(getattr(dv, "ENABLE", False)), k, r, f, sr)
+    if s.enable:
+        if bool(getattr(getattr(cfg, "MIXUP", None), "ENABLE", False)):
+            raise ValueError("DETECTION.ENABLE with MIXUP.ENABLE: a mixed clip has no boxes")
+        if bool(getattr(getattr(cfg, "DISTILL", None), "ENABLE", False)):
+            raise ValueError("DETECTION.ENABLE with DISTILL.ENABLE: a clip-level teacher has no logits per box")
+        views = int(getattr(cfg.TEST, "NUM_SPATIAL_CROPS", 1)) * int(getattr(cfg.TEST, "NUM_TEMPORAL_VIEWS", 1))
+        if views > 1:
+            raise ValueError(f"DETECTION.ENABLE with TEST.NUM_SPATIAL_CROPS * TEST.NUM_TEMPORAL_VIEWS = {views}: box rows are "
+                             "not views of one video, set both to 1")
     return s

@@ -158,6 +158,7 @@ _ARG_ACCESS = {
     "x3d_tail_bwd": {4: ("bsums", "W"), 5: ("bsums", "W")},
     "x3d_tail_bwd_dp": {6: ("bsums", "W"), 7: ("bsums", "W")},
     "x3d_relu_bn_bwd_reduce": {5: ("bsums", "W")},
+    "x3d_roi_pool_bwd": {7: ("bsums", "W")},
 }
 
 

@@ -24,7 +24,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip, ops
-from .config import FinetuneSettings, ensemble_method, multi_label
+from .config import FinetuneSettings, detection_settings, ensemble_method, multi_label
 from .arch import Arch, ParamSpec, block_prefix, build_arch, drop_path_rates, param_specs, summary_rows
 from .params import init_params
 from .segments import Segment, SegTable
@@ -139,6 +139,9 @@ class X3D:
         # TEST.ENSEMBLE_METHOD: mean (x3d_view_mean) or max (x3d_view_max) over the views x crops of a video
         self.multi_label = multi_label(cfg)
         self.ensemble_method = ensemble_method(cfg)
+        # DETECTION.ENABLE: the head classifies box slots instead of clips (x3d_roi_pool_fwd / _bwd; plan.py _rec_roi_pool); None: off
+        det = detection_settings(cfg)
+        self.det = det if det.enable else None
         self._bn_cfg = cfg.NETWORK.BN
         self.dtype = dtype
         self.in_channels = in_channels
@@ -505,16 +508,24 @@ class X3D:
             return None
         return ops.drop_path_step(self._dp_state)
 
-    def __call__(self, input, training=False):
-        return self.call(input, training)
+    def __call__(self, input, training=False, boxes=None, num_boxes=None):
+        return self.call(input, training, boxes, num_boxes)
 
-    def call(self, input, training=False):
+    def call(self, input, training=False, boxes=None, num_boxes=None):
         """Forward pass (reference model.py:113-127).  Returns fp32 probabilities: ``[N, classes]`` when
         training, ``[N / (views*crops), classes]`` (views combined by TEST.ENSEMBLE_METHOD) otherwise.  With
-        DATA.MULTI_LABEL the probabilities are per-class sigmoids instead of a softmax."""
+        DATA.MULTI_LABEL the probabilities are per-class sigmoids instead of a softmax.
+
+        DETECTION.ENABLE: boxes [N, K, 4] fp32 (x1, y1, x2, y2 in pixels of the clips as passed; K = DETECTION.MAX_BOXES) and
+        num_boxes [N] (a HOST sequence or tensor: the valid count is taken from it without a device read) are required, and the
+        result is ``[N, K, classes]`` with the rows of empty slots zeroed.  Boxes without the switch, or the switch without
+        boxes, raise ValueError before any launch."""
         n, t, h, w, _ = input.shape
+        nb = self._check_boxes(boxes, num_boxes, n)
         pl = self._plan(n, t, h, w, training)
         self._bind_input(pl, input)
+        if self.det:
+            self._bind_boxes(pl, boxes, nb)
         self._pack_panels()
         if training:
             pl.zero_buf.zero_()
@@ -522,11 +533,55 @@ class X3D:
             self._draw_drop_path(pl)
             # forward only: stop before the loss kernel (labels unknown); softmax (sigmoid) without labels
             pl.run(pl.fwd, 0, pl.grad_scale_slot)
-            self._head_probs_only(pl, n)
-            return pl.probs
+            self._head_probs_only(pl, pl.rows)
+            return self._box_rows(pl, pl.probs)
         pl.zero_buf.zero_()
         pl.run(pl.fwd)
-        return pl.out
+        return self._box_rows(pl, pl.out)
+
+    # -- DETECTION.ENABLE ----------------------------------------------------------------------------
+    def _check_boxes(self, boxes, num_boxes, n):
+        """The argument checks of the box head, before any plan is recorded or kernel launched; returns num_boxes as a host int64
+        tensor [n] (None with the switch off)."""
+        if self.det is None:
+            if boxes is not None or num_boxes is not None:
+                raise ValueError("boxes / num_boxes were given but DETECTION.ENABLE is off: this model classifies clips")
+            return None
+        k = self.det.max_boxes
+        if boxes is None or num_boxes is None:
+            raise ValueError(f"DETECTION.ENABLE: boxes [N, {k}, 4] and num_boxes [N] are required")
+        if not torch.is_tensor(boxes):
+            boxes = torch.as_tensor(boxes)
+        if tuple(boxes.shape) != (n, k, 4) or not boxes.dtype.is_floating_point:
+            raise ValueError(f"boxes must be a floating-point [{n}, {k}, 4] tensor (DETECTION.MAX_BOXES = {k}), got "
+                             f"{tuple(boxes.shape)} {boxes.dtype}")
+        if torch.is_tensor(num_boxes) and num_boxes.is_cuda:
+            raise ValueError("num_boxes must live on the host: the number of valid boxes is taken from it without a device read")
+        nb = torch.as_tensor(num_boxes).reshape(-1)
+        if nb.numel() != n or nb.dtype.is_floating_point or nb.dtype == torch.bool or int(nb.min()) < 0 or int(nb.max()) > k:
+            raise ValueError(f"num_boxes must be {n} integers in [0, {k}], got {nb.tolist() if nb.numel() <= 16 else tuple(nb.shape)}")
+        return nb.to(torch.int64)
+
+    def _bind_boxes(self, pl: _Plan, boxes, nb):
+        """boxes / num_boxes -> the plan's own device buffers; box_mask [rows] = 1 for a filled slot.  Returns the number of
+        filled slots (a host int)."""
+        k = self.det.max_boxes
+        if not torch.is_tensor(boxes):
+            boxes = torch.as_tensor(boxes)
+        if boxes.data_ptr() != pl.boxes.data_ptr():
+            pl.boxes.copy_(boxes.to(self.device, non_blocking=True))
+        pl.num_boxes.copy_(nb.to(torch.int32), non_blocking=True)
+        mask = (torch.arange(k).view(1, k) < nb.view(-1, 1)).to(torch.float32).reshape(-1)
+        pl.box_mask.copy_(mask, non_blocking=True)
+        pl._box_keepalive = mask
+        return int(nb.sum())
+
+    def _box_rows(self, pl: _Plan, probs):
+        """[rows, classes] -> [N, K, classes] with the rows of empty slots zeroed in place (switch off: `probs` as it is)"""
+        if self.det is None:
+            return probs
+        probs.mul_(pl.box_mask.view(-1, 1))
+        return probs.view(pl.n, self.det.max_boxes, -1)
 
     def logits(self, input):
         """Per-clip logits at training=False (moving statistics, no dropout): the launches of `call(input)` up to, but not
@@ -586,7 +641,7 @@ class X3D:
             pl.row_w.copy_(w.to(self.device, non_blocking=True).reshape(n))
 
     def forward_backward(self, input, labels, global_batch=None, on_stage_done=None, loss_scale=1.0, teacher_logits=None,
-                         distill=None, sample_weight=None):
+                         distill=None, sample_weight=None, boxes=None, num_boxes=None):
         """One training forward + backward.  Fills ``self.grads`` (data gradients only; the L2 term is
         applied by the optimizer), updates BN moving statistics, returns the plan (loss_rows, probs).
 
@@ -616,8 +671,26 @@ class X3D:
             are multiplied by sample_weight[n] and still divided by global_batch (SUM_OVER_BATCH_SIZE).  0 is a valid weight;
             `plan.row_w` holds them.  With it, or with `set_loss` modifiers, the head runs x3d_softmax_xent_w /
             x3d_sigmoid_bce_w; with neither nothing changes.
+        boxes [N, K, 4], num_boxes [N] (host): DETECTION.ENABLE, as `call` takes them.  labels are then [N, K] class indices (with
+            DATA.MULTI_LABEL: targets [N, K, classes]); those of empty slots are not used (indices are replaced by 0, targets must
+            be finite).  The head runs its _w entry point on N * K rows with `plan.row_w` = N * K / max(valid, 1) for a filled
+            slot and 0 for an empty one, and divides by global_batch * K: loss and gradient are the mean over this rank's valid
+            boxes, and data-parallel averaging stays what it is.  A filled slot whose box is degenerate or not finite pools
+            zeros and still counts.  sample_weight and teacher_logits are refused with boxes.
         """
         n, t, h, w, _ = input.shape
+        nb = self._check_boxes(boxes, num_boxes, n)
+        rows = n * self.det.max_boxes if self.det else n
+        if self.det:
+            if sample_weight is not None or teacher_logits is not None:
+                raise ValueError("DETECTION.ENABLE: sample_weight / teacher_logits cannot be combined with boxes (the row weights "
+                                 "carry the valid-box mean)")
+            if not torch.is_tensor(labels):
+                labels = torch.as_tensor(labels)
+            want = (n, self.det.max_boxes) + ((self.num_classes,) if self.multi_label or labels.dim() == 3 else ())
+            if tuple(labels.shape) != want:
+                raise ValueError(f"DETECTION.ENABLE: labels must be {list(want)}, got {list(labels.shape)}")
+            labels = labels.reshape((rows,) + want[2:])
         pl = self._plan(n, t, h, w, True)
         self._bind_input(pl, input)
         soft = (not self.multi_label and torch.is_tensor(labels) and labels.dim() == 2
@@ -632,20 +705,26 @@ class X3D:
                 got = (tuple(teacher_logits.shape), teacher_logits.dtype, teacher_logits.device) \
                     if torch.is_tensor(teacher_logits) else type(teacher_logits)
                 raise ValueError(f"teacher_logits must be a device float32 [{n}, {self.num_classes}] tensor, got {got}")
-        rw = sample_weight is not None
+        rw = sample_weight is not None or self.det is not None
         weighted = rw or self.loss_mods is not None
         pl.use_soft_targets(soft, distill=kd, weighted=weighted, row_w=rw)
-        if rw:
+        if self.det:
+            valid = self._bind_boxes(pl, boxes, nb)
+            torch.mul(pl.box_mask, float(rows) / max(valid, 1), out=pl.row_w)
+        elif rw:
             self._bind_sample_weight(pl, sample_weight, n)
         if self.multi_label:
-            self._bind_targets(pl, labels, n)
+            self._bind_targets(pl, labels, rows)
         elif soft:
-            self._bind_targets(pl, labels, n, what="soft")
+            self._bind_targets(pl, labels, rows, what="soft")
         else:
             if not labels.is_cuda:   # host labels are validated for free; device labels by the kernel (NaN loss row, zero gradient)
-                if labels.numel() != n or int(labels.min()) < 0 or int(labels.max()) >= self.num_classes:
-                    raise ValueError(f"labels must be {n} class indices in [0, {self.num_classes})")
+                used = labels.reshape(-1)[pl._box_keepalive.bool()] if self.det else labels
+                if labels.numel() != rows or (used.numel() and (int(used.min()) < 0 or int(used.max()) >= self.num_classes)):
+                    raise ValueError(f"labels must be {rows} class indices in [0, {self.num_classes})")
             pl.labels.copy_(labels.to(self.device, non_blocking=True).to(torch.int32))
+            if self.det:             # the label of an empty slot is never an index the kernel could refuse
+                pl.labels.mul_(pl.box_mask.to(torch.int32))
         # (round 4: the panel packing, the gradient-buffer zeroing and the dropout draw -- ~70 us the stem does not depend on -- on a
         # second stream beside the stem's two convolutions, joined in front of the first pointwise conv: 22.30 -> 22.63 ms per step,
         # three alternating runs on one box; the fork / join costs more than it hides.  Not kept.)
@@ -654,7 +733,7 @@ class X3D:
         self.flat_grads.zero_()
         self._draw_dropout(pl)
         self._draw_drop_path(pl)
-        gb = float(global_batch or n)
+        gb = float(global_batch or n) * (self.det.max_boxes if self.det else 1)
         on_device = torch.is_tensor(loss_scale)          # the device state of the loss scaler: the head takes 1 / gb, the scale follows
         head_scale = (1.0 if on_device else float(loss_scale)) / gb
         if kd and teacher_logits.data_ptr() != pl.teacher.data_ptr():

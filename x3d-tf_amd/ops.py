@@ -486,6 +486,75 @@ def pool_fwd(x_raw, ss, pooled):
     return pooled
 
 
+ROI_MAX_HW, ROI_MAX_R, ROI_MAX_K, ROI_MAX_ROWS = 1024, 15, 64, 2048   # the limits of x3d_roi_pool_fwd / _bwd (include/x3d_hip.h)
+
+
+def roi_limits(name, n, hw, k, r, sampling_ratio, spatial_scale):
+    """The refusals of x3d_roi_pool_fwd / x3d_roi_pool_bwd as ValueErrors that name the argument (config.py and the plan
+    recorder state them through this too, before anything is allocated or launched)."""
+    if not 1 <= int(r) <= ROI_MAX_R:
+        raise ValueError(f"{name}: resolution R = {r} must be in 1..{ROI_MAX_R}")
+    if not 1 <= int(k) <= ROI_MAX_K:
+        raise ValueError(f"{name}: boxes holds K = {k} slots per clip, must be in 1..{ROI_MAX_K}")
+    if int(n) * int(k) > ROI_MAX_ROWS:
+        raise ValueError(f"{name}: boxes gives N*K = {int(n) * int(k)} rows, at most {ROI_MAX_ROWS}")
+    if hw is not None and int(hw) > ROI_MAX_HW:
+        raise ValueError(f"{name}: the feature map has H*W = {hw} pixels, at most {ROI_MAX_HW}")
+    if int(sampling_ratio) < 0:
+        raise ValueError(f"{name}: sampling_ratio = {sampling_ratio} must be >= 0")
+    if not 0.0 < float(spatial_scale) < float("inf"):
+        raise ValueError(f"{name}: spatial_scale = {spatial_scale} must be positive and finite")
+
+
+def _roi_args(name, fmap, ss, boxes, num_boxes, rows, argmax, resolution, sampling_ratio, spatial_scale):
+    """the tensor checks both ROI wrappers make; rows: {what: fp32 [N*K, C] tensor}.  Returns (N, C, T, H, W, K)."""
+    if fmap.dim() != 5:
+        raise ValueError(f"{name}: the feature map must be [N, C, T, H, W], got {tuple(fmap.shape)}")
+    n, c, t, h, w = fmap.shape
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4:
+        raise ValueError(f"{name}: boxes must be [{n}, K, 4] float32, got {tuple(boxes.shape)} {boxes.dtype}")
+    k = boxes.shape[1]
+    if num_boxes.dtype != torch.int32 or tuple(num_boxes.shape) != (n,):
+        raise ValueError(f"{name}: num_boxes must be [{n}] int32, got {tuple(num_boxes.shape)} {num_boxes.dtype}")
+    roi_limits(name, n, h * w, k, resolution, sampling_ratio, spatial_scale)
+    if ss.dtype != torch.float32 or ss.numel() != 2 * c:
+        raise ValueError(f"{name}: scale_shift must be [{c}, 2] float32, got {tuple(ss.shape)} {ss.dtype}")
+    for what, r in rows.items():
+        _f32_2d(name, what, r, (n * k, c))
+    if argmax is not None and (argmax.dtype != torch.uint8 or tuple(argmax.shape) != (n * k, c)):
+        raise ValueError(f"{name}: argmax must be [{n * k}, {c}] uint8, got {tuple(argmax.shape)} {argmax.dtype}")
+    return n, c, t, h, w, k
+
+
+def roi_pool_fwd(x_raw, ss, boxes, num_boxes, pooled, argmax=None, resolution=7, sampling_ratio=0, spatial_scale=1.0 / 32):
+    """pooled [N*K, C] fp32 = per box, the spatial max over resolution^2 ROIAlign bins of mean_t relu(s*x_raw + t)
+    (x3d_roi_pool_fwd: the rules are in include/x3d_hip.h).  boxes [N, K, 4] fp32 in pixels of the clip, num_boxes [N] int32;
+    argmax [N*K, C] uint8 receives the winning bin (None: inference).  One launch, does not synchronise."""
+    n, c, t, h, w, k = _roi_args("roi_pool_fwd", x_raw, ss, boxes, num_boxes, dict(pooled=pooled), argmax, resolution,
+                                 sampling_ratio, spatial_scale)
+    _chk(x_raw, ss, boxes, num_boxes, pooled, argmax)
+    hip.call("x3d_roi_pool_fwd", ptr(x_raw), ptr(ss), ptr(boxes), ptr(num_boxes), ptr(pooled), ptr(argmax), n, c, t, h, w, k,
+             int(resolution), int(sampling_ratio), float(spatial_scale), hip.dtype_code(x_raw.dtype))
+    return pooled
+
+
+def roi_pool_bwd(dpooled, argmax, boxes, num_boxes, yraw, ss, g, sums, resolution=7, sampling_ratio=0,
+                 spatial_scale=1.0 / 32):
+    """g [N, C, T, H, W] = the gradient of roi_pool_fwd's input through the ReLU of s*yraw + t, given dpooled [N*K, C] and the
+    forward's argmax; sums [C, 2] fp64 += (sum g, sum g*yraw) (x3d_roi_pool_bwd).  One launch, does not synchronise."""
+    n, c, t, h, w, k = _roi_args("roi_pool_bwd", yraw, ss, boxes, num_boxes, dict(dpooled=dpooled), argmax, resolution,
+                                 sampling_ratio, spatial_scale)
+    if argmax is None:
+        raise ValueError("roi_pool_bwd: argmax is required")
+    if g.dtype != yraw.dtype or tuple(g.shape) != tuple(yraw.shape):
+        raise ValueError(f"roi_pool_bwd: g must be {tuple(yraw.shape)} {yraw.dtype}, got {tuple(g.shape)} {g.dtype}")
+    if sums.dtype != torch.float64 or sums.numel() != 2 * c:
+        raise ValueError(f"roi_pool_bwd: sums must be [{c}, 2] float64, got {tuple(sums.shape)} {sums.dtype}")
+    _chk(dpooled, argmax, boxes, num_boxes, yraw, ss, g, sums)
+    hip.call("x3d_roi_pool_bwd", ptr(dpooled), ptr(argmax), ptr(boxes), ptr(num_boxes), ptr(yraw), ptr(ss), ptr(g), ptr(sums),
+             n, c, t, h, w, k, int(resolution), int(sampling_ratio), float(spatial_scale), hip.dtype_code(yraw.dtype))
+
+
 # ---- head ---------------------------------------------------------------------------------------
 def dense_fwd(x, w, b, y, act=ACT_NONE, mask=None, mask_scale=1.0):
     _chk(x, w, b, y, mask)

@@ -244,6 +244,12 @@ class _Plan:
         self.dp_keep = None            # stochastic depth: the keep table [blocks][N] of the step (training plans with a rate > 0)
         self.bn_layers: List[BNBuf] = []   # every BatchNorm layer of a training plan, as recorded (precise_bn_table)
         self._pbn_table = None
+        # DETECTION.ENABLE: the head runs per box slot, K = MAX_BOXES slots per clip -- `rows` = n * K rows of
+        # pooled / h1 / logits / probs / dlogits, the boxes of clip i in rows i*K .. i*K+K-1.  boxes / num_boxes are plan-owned and
+        # copied into by every call; box_mask [rows] is 1 for a filled slot; roi_argmax belongs to training plans
+        self.det = model.det
+        self.rows = n * self.det.max_boxes if self.det else n
+        self.boxes = self.num_boxes = self.box_mask = self.roi_argmax = None
 
     # -- allocation ------------------------------------------------------------------------------
     def act(self, *shape):
@@ -413,10 +419,10 @@ class _Plan:
         weighted = bool(weighted) or bool(row_w)
         key = (bool(soft) and not m.multi_label, bool(distill)) + (("w",) if weighted else ())
         if row_w and self.row_w is None:
-            self.row_w = self.f32(self.n)
+            self.row_w = self.f32(self.rows)
         if key not in self._heads:
             if key[0] and self.targets is None:
-                self.targets = torch.zeros(self.n, m.num_classes, dtype=torch.float32, device=m.device)
+                self.targets = torch.zeros(self.rows, m.num_classes, dtype=torch.float32, device=m.device)
             if key[1] and self.teacher is None:
                 self.teacher, self.kd_rows = self.f32(self.n, m.num_classes), self.f32(self.n)
             tmp = []
@@ -433,7 +439,7 @@ class _Plan:
         m = self.model
         soft = bool(soft) and not m.multi_label
         ptr = hip.ptr
-        size = (self.n, m.num_classes)
+        size = (self.rows, m.num_classes)
         labels, targets = (None, ptr(self.targets)) if soft or m.multi_label else (ptr(self.labels), None)
         if weighted or row_w:
             mods = m.loss_mods or NO_LOSS_MODS
@@ -556,12 +562,16 @@ def _conv5_args(model, pl, x_cur, hh, ww, dt):
 
 def _rec_head_dense(model, pl, dt):
     """pool of relu(bn5(conv5)) -> fc1 -> [dropout] -> fc2: logits"""
-    a, p, F, n, c5 = model.arch, model.params, pl.fwd, pl.n, model.arch.conv5_out
+    a, p, F, c5 = model.arch, model.params, pl.fwd, model.arch.conv5_out
+    n = pl.rows                                  # (DETECTION.ENABLE: one row per box slot)
     pl.pooled = pl.f32(n, c5)
     pl.h1 = pl.f32(n, a.fc1_out)
     pl.logits = pl.f32(n, a.num_classes)
     pl.probs = pl.f32(n, a.num_classes)
-    pl.rec(F, "x3d_pool_fwd", pl.c5_raw, pl.bn5.ss, pl.pooled, n, c5, pl.P5, dt)
+    if pl.det:
+        _rec_roi_pool(model, pl, dt)
+    else:
+        pl.rec(F, "x3d_pool_fwd", pl.c5_raw, pl.bn5.ss, pl.pooled, n, c5, pl.P5, dt)
     pl.rec(F, "x3d_dense_fwd", pl.pooled, None, 1.0, p["fc1/kernel"], None, pl.h1, ACT_RELU, n, c5, a.fc1_out)
     use_drop = pl.training and a.dropout_rate > 0
     pl.drop_mask = pl.f32(n, a.fc1_out) if use_drop else None
@@ -570,10 +580,36 @@ def _rec_head_dense(model, pl, dt):
            pl.logits, ACT_NONE, n, a.fc1_out, a.num_classes)
 
 
+def _roi_args(pl):
+    """(N, C, T, H, W, K, R, sampling_ratio, spatial_scale) as both ROI entry points take them"""
+    d = pl.det
+    return (pl.n, pl.model.arch.conv5_out, pl.t, pl.h5, pl.w5, d.max_boxes, d.resolution, d.sampling_ratio,
+            1.0 / d.spatial_scale_factor)
+
+
+def _rec_roi_pool(model, pl, dt):
+    """x3d_roi_pool_fwd in the place of x3d_pool_fwd: pl.pooled [n * K, c5] from the plan's own boxes [n, K, 4] / num_boxes [n]
+    (the model copies the caller's into them; all slots empty until then).  The shape limits are the kernel's: stated here,
+    before anything is launched."""
+    from .ops import roi_limits
+    d, n = pl.det, pl.n
+    roi_limits("DETECTION", n, pl.h5 * pl.w5, d.max_boxes, d.resolution, d.sampling_ratio, 1.0 / d.spatial_scale_factor)
+    pl.boxes, pl.box_mask = pl.f32(n, d.max_boxes, 4), pl.f32(pl.rows)
+    if model.dry:
+        pl.num_boxes = _FakeBuf((n,), torch.int32)
+        pl.roi_argmax = _FakeBuf((pl.rows, model.arch.conv5_out), torch.uint8) if pl.training else None
+    else:
+        pl.boxes.zero_()
+        pl.box_mask.zero_()
+        pl.num_boxes = torch.zeros(n, dtype=torch.int32, device=model.device)
+        pl.roi_argmax = torch.zeros(pl.rows, model.arch.conv5_out, dtype=torch.uint8, device=model.device) if pl.training else None
+    pl.rec(pl.fwd, "x3d_roi_pool_fwd", pl.c5_raw, pl.bn5.ss, pl.boxes, pl.num_boxes, pl.pooled, pl.roi_argmax, *_roi_args(pl), dt)
+
+
 def _rec_infer_head(model, pl):
     """probabilities of the logits (softmax, or sigmoid with DATA.MULTI_LABEL), then the views x crops of every video
     combined by TEST.ENSEMBLE_METHOD (mean, or element-wise max) into pl.out [n / num_preds, classes]"""
-    a, F, n = model.arch, pl.fwd, pl.n
+    a, F, n = model.arch, pl.fwd, pl.rows        # (DETECTION.ENABLE: num_preds is 1, pl.out has a row per box slot)
     pl.rec(F, "x3d_sigmoid_bce" if model.multi_label else "x3d_softmax_xent", pl.logits, None, pl.probs, None, None, 1.0, n,
            a.num_classes)
     pl.out = pl.f32(n // a.num_preds, a.num_classes)
@@ -741,14 +777,14 @@ def record_training(model, n, t, h, w, frozen_prefix=0) -> _Plan:
     pl.rec(F, "x3d_pw_fwd", pl.s5)
     _rec_bn_finalize(model, pl, pl.bn5, n * pl.P5)
     _rec_head_dense(model, pl, dt)
-    pl.loss_rows = pl.f32(n)
-    pl.dlogits = pl.f32(n, a.num_classes)
+    pl.loss_rows = pl.f32(pl.rows)
+    pl.dlogits = pl.f32(pl.rows, a.num_classes)
     pl.grad_scale_slot = len(F)
     if model.multi_label:
         pl.labels = None
-        pl.targets = torch.zeros(n, a.num_classes, dtype=torch.float32, device=model.device)
+        pl.targets = torch.zeros(pl.rows, a.num_classes, dtype=torch.float32, device=model.device)
     else:
-        pl.labels = torch.zeros(n, dtype=torch.int32, device=model.device)
+        pl.labels = torch.zeros(pl.rows, dtype=torch.int32, device=model.device)
         pl.targets = None                  # soft targets: allocated by the first call that brings some (use_soft_targets)
     F.append(None)
     pl.use_soft_targets(False)             # x3d_sigmoid_bce on targets / x3d_softmax_xent on labels
@@ -946,8 +982,8 @@ def record_backward(model, pl: _Plan, opt: dict, first_unit: int = 0) -> Backwar
     out.coef_nc = pl.f32(max_nc * 4)
     out.se_scratch = pl.f32(max([1] + [n * (2 * B.spec.inner + B.spec.se_width) for B in live if B.spec.has_se]))
     out.g5 = pl.act(*pl.c5_raw.shape)
-    out.dh1 = pl.f32(n, a.fc1_out)
-    out.dpooled = pl.f32(n, a.conv5_out)
+    out.dh1 = pl.f32(pl.rows, a.fc1_out)
+    out.dpooled = pl.f32(pl.rows, a.conv5_out)
     out.ds = None if pl.stem_fused or k else pl.act(*pl.s_raw.shape)
     out.blocks = [BlockBackward() for _ in pl.blocks]
     s = _BwdState(out, opt, hip.dtype_code(model.dtype))
@@ -1050,11 +1086,15 @@ def _bwd_head(model, pl, s, seam=False):
     a, p, g, n, t, dt = model.arch, model.params, model.grads, pl.n, pl.t, s.dt
     out, Bk, c5, b5 = s.out, s.out.launches, model.arch.conv5_out, pl.bn5
     pl.rec(Bk, "x3d_dense_bwd", pl.dlogits, None, ACT_NONE, pl.h1, pl.drop_mask, float(pl.drop_scale),
-           p["fc2/kernel"], out.dh1, g["fc2/kernel"], g["fc2/bias"], n, a.fc1_out, a.num_classes)
+           p["fc2/kernel"], out.dh1, g["fc2/kernel"], g["fc2/bias"], pl.rows, a.fc1_out, a.num_classes)
     pl.rec(Bk, "x3d_dense_bwd", out.dh1, pl.h1, ACT_RELU, pl.pooled, None, 1.0, p["fc1/kernel"], out.dpooled,
-           g["fc1/kernel"], None, n, c5, a.fc1_out)
-    pl.rec(Bk, "x3d_relu_bn_bwd_reduce", None, out.dpooled, pl.c5_raw, b5.ss, out.g5, pl.acc(b5.bsums), n, c5,
-           pl.P5, dt)
+           g["fc1/kernel"], None, pl.rows, c5, a.fc1_out)
+    if pl.det:     # the same contract below it: g5 and bn5's backward sums
+        pl.rec(Bk, "x3d_roi_pool_bwd", out.dpooled, pl.roi_argmax, pl.boxes, pl.num_boxes, pl.c5_raw, b5.ss, out.g5,
+               pl.acc(b5.bsums), *_roi_args(pl), dt)
+    else:
+        pl.rec(Bk, "x3d_relu_bn_bwd_reduce", None, out.dpooled, pl.c5_raw, b5.ss, out.g5, pl.acc(b5.bsums), n, c5,
+               pl.P5, dt)
     c_last = a.stages[-1].cout
     w5 = hip.PwWgradArgs(_p(out.g5), _p(pl.c5_raw), _p(b5.coef), _p(pl.y_last), None, None, ACT_NONE,
                          _p(g["conv5/layer_with_weights-0/kernel"]), n, c_last, c5, t, pl.h5, pl.w5, 1, dt)

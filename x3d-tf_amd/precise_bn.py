@@ -62,8 +62,12 @@ def update_bn_stats(model, batches, num_batches, group=None) -> int:
     try:
         for item in itertools.islice(it, num_batches):
             clips = item[0] if isinstance(item, (tuple, list)) else item
-            model(clips, training=True)
             n, t, h, w, _ = clips.shape
+            if getattr(model, "det", None) is not None:
+                # DETECTION.ENABLE: trunk statistics do not depend on the head -- every box slot empty, the ROI launch reads no plane
+                model(clips, training=True, boxes=torch.zeros(n, model.det.max_boxes, 4), num_boxes=[0] * n)
+            else:
+                model(clips, training=True)
             table = model._plan(n, t, h, w, True).precise_bn_table()
             if nlayers is not None and table.shape[0] != nlayers:
                 raise ValueError("update_bn_stats: the model's frozen prefix changed between batches")

@@ -283,23 +283,27 @@ class Trainer:
             return {}
         return dict(teacher_logits=self.teacher.logits(clips), distill=self._kd)
 
-    def step(self, clips, labels, lr: Optional[float] = None, sample_weight=None):
+    def step(self, clips, labels, lr: Optional[float] = None, sample_weight=None, boxes=None, num_boxes=None):
         """clips: this replica's shard [B, T, H, W, 3]; labels [B] (multi-label models: targets [B, classes]).  Returns the
         plan (loss_rows, probs).  With MIXUP.ENABLE or TRAIN.LABEL_SMOOTHING the batch is mixed and the targets are built
         first (`_mix_batch`; `last_mix` holds the parameters drawn).  With DISTILL.ENABLE the teacher's logits of the (mixed)
         clips join the loss (`_teacher_kw`; `plan.kd_rows` holds the KD term per row).  sample_weight: [B] weights of this
         shard's samples (host or device), Keras' `(x, y, sample_weight)`; the weighted rows are still divided by the global batch
         (SUM_OVER_BATCH_SIZE), so `loss` and the data-parallel reduction are what they were.  ValueError together with
-        MIXUP.ENABLE: mixing the weights of two samples is not defined here (class weights are fine, the loss is linear in y)."""
+        MIXUP.ENABLE: mixing the weights of two samples is not defined here (class weights are fine, the loss is linear in y).
+        boxes [B, K, 4], num_boxes [B] (host): DETECTION.ENABLE -- labels are then [B, K] (targets [B, K, classes]) and the loss is
+        the mean over this shard's valid boxes (`forward_backward`); missing with the switch on, or given with it off: ValueError."""
         m = self.model
         n = clips.shape[0]
         if lr is None:
             lr = lr_schedule(self.epoch, self.cfg)
         sw = {}
+        if boxes is not None or num_boxes is not None or getattr(m, "det", None) is not None:
+            sw = dict(boxes=boxes, num_boxes=num_boxes)      # (checked by forward_backward, before any launch)
         if sample_weight is not None:
             if self.mix.enable:
                 raise ValueError("sample_weight with MIXUP.ENABLE: the weight of a mixed sample is not defined")
-            sw = dict(sample_weight=sample_weight)
+            sw = dict(sw, sample_weight=sample_weight)
         if self._mix_active:
             clips, labels = self._mix_batch(clips, labels)
         if self._accum > 1:
@@ -538,6 +542,7 @@ class Trainer:
             raise ValueError("steps_per_epoch must be positive (cfg.TRAIN.DATASET_SIZE // cfg.TRAIN.BATCH_SIZE)")
         check_accum_schedule(steps, save_freq, self.solver.accum_steps)
         multi = bool(getattr(self.model, "multi_label", False))
+        det = getattr(self.model, "det", None) is not None
         known = MULTI_LABEL_METRICS if multi else TRAIN_METRICS
         if metrics is _DEFAULT_METRICS:
             metrics = known
@@ -578,7 +583,10 @@ class Trainer:
             for _ in range(steps):
                 clips, labels, *weights = next(it)
                 before = self.opt_step if ds is None else None
-                pl = self.step(clips, labels, lr, *weights)
+                if det:                       # (clips, labels, boxes, num_boxes)
+                    pl = self.step(clips, labels, lr, **dict(zip(("boxes", "num_boxes"), weights)))
+                else:
+                    pl = self.step(clips, labels, lr, *weights)
                 tot += self.loss(pl).double()
                 if kd_tot is not None:
                     kd_tot += self.kd_loss(pl).double()
@@ -589,7 +597,7 @@ class Trainer:
                     gn_tot += self.last_grad_norm
                     updates += 1
                 if train_m is not None:
-                    train_m.update(pl.probs, pl.targets if multi else pl.labels)
+                    train_m.update(*self._valid_rows(pl, pl.probs, pl.targets if multi else pl.labels))
                 if on_step is not None:
                     on_step(self, pl)
                 ckpt = schedule.after_batch(self.epoch)
@@ -654,7 +662,8 @@ class Trainer:
         first `steps` of them when given) into a DeviceMetrics, counters summed over the ranks once.  Unlike
         `evaluate_dataset` this releases no plan, so the training plan is still cached in the next epoch.  Returns
         {"loss", "acc", "top_5_acc", "videos"}; for a multi-label model the DeviceMAP result {"loss", "mAP", "videos",
-        "classes"} (batches of (clips, targets)).  per_class (single-label models): + "mean_class_acc".  The loss is
+        "classes"} (batches of (clips, targets)).  DETECTION.ENABLE: batches of (clips, labels [B, K] | targets [B, K, classes],
+        boxes, num_boxes); loss and metrics are taken over the filled box slots only, "videos" counts them.  per_class (single-label models): + "mean_class_acc".  The loss is
         unweighted: LOSS.* and sample weights act on the training loss only."""
         import itertools
         from .evaluate import DeviceMAP, DeviceMetrics
@@ -665,13 +674,29 @@ class Trainer:
             dm = DeviceMetrics(m.regularization_loss(), **(dict(per_class=True) if per_class else {}))
         it = iter(batches)
         try:
-            for clips, labels in itertools.islice(it, None if steps is None else int(steps)):
-                dm.update(m(clips, training=False), labels)
+            for clips, labels, *box_args in itertools.islice(it, None if steps is None else int(steps)):
+                if getattr(m, "det", None) is not None or box_args:      # (clips, labels, boxes, num_boxes): the valid rows only
+                    probs = m(clips, training=False, **dict(zip(("boxes", "num_boxes"), box_args)))
+                    pl = m._plan(*clips.shape[:4], False)
+                    labels = torch.as_tensor(labels)
+                    dm.update(*self._valid_rows(pl, probs.reshape(pl.rows, -1), labels.reshape((pl.rows,) + tuple(labels.shape[2:]))))
+                else:
+                    dm.update(m(clips, training=False), labels)
         finally:
             close = getattr(it, "close", None)
             if close is not None:
                 close()       # a reader's generator: stops its prefetch thread
         return dm.all_reduce_(self.group).result()
+
+    @staticmethod
+    def _valid_rows(pl, probs, labels):
+        """(probs, labels) of a plan's filled box slots (DETECTION.ENABLE; the index comes from the host-side num_boxes: a device
+        gather, no read) -- both as they are for a clip-level plan"""
+        if getattr(pl, "det", None) is None:
+            return probs, labels
+        idx = pl._box_keepalive.nonzero().flatten()
+        return (probs.index_select(0, idx.to(probs.device, non_blocking=True)),
+                labels.index_select(0, idx.to(labels.device, non_blocking=True)))
 
     def collective_stats(self):
         """What the exchange step of this replica did so far (bench.py's `collectives` block)."""
@@ -821,7 +846,7 @@ class Trainer:
     def loss(self, pl):
         """global-batch mean cross-entropy + L2 term (what Keras reports as `loss`).  adamw / lamb decay the weights outside
         the loss (OPTIM.WEIGHT_DECAY) and ignore NETWORK.WEIGHT_DECAY: for them this is the cross-entropy alone."""
-        ce = pl.loss_rows.sum() / (pl.n * self.world)
+        ce = pl.loss_rows.sum() / (pl.rows * self.world)      # (DETECTION.ENABLE: rows = n * K, weighted to the mean over valid boxes)
         if self.collectives:
             torch.distributed.all_reduce(ce, group=self.group)
         if not self.rule.l2_in_loss:
