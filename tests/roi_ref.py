@@ -117,12 +117,16 @@ def backward(dpooled, argmax, boxes, num_boxes, yraw, ss, R, sampling_ratio, spa
 BOX_KINDS = ("inside", "touching", "beyond", "subpixel", "zero_width", "nan")
 
 
-def box_mix(n, k, height, width, seed, first_kind=0):
+def box_mix(n, k, height, width, seed, first_kind=0, grid=8.0):
     """boxes [n][k][4] float32 in pixels of a height x width clip, on the 1/8-pixel grid (so that a power-of-two spatial_scale
     keeps every coordinate, difference and bin count exact in fp32 and fp64 alike), cycling through BOX_KINDS from `first_kind`:
-    inside the frame, touching its borders, reaching beyond it, narrower than a feature-map pixel, zero width, a NaN coordinate."""
+    inside the frame, touching its borders, reaching beyond it, narrower than a feature-map pixel, zero width, a NaN coordinate.
+    grid = None: the coordinates as drawn, rounded to fp32 only (box_mix_offgrid)."""
     rng = np.random.default_rng(seed)
-    q = lambda v: np.round(np.asarray(v, dtype=np.float64) * 8.0) / 8.0
+    if grid is None:
+        q = lambda v: np.asarray(v, dtype=np.float64)
+    else:
+        q = lambda v: np.round(np.asarray(v, dtype=np.float64) * grid) / grid
     out = np.zeros((n, k, 4), dtype=np.float32)
     i = first_kind
     for a in range(n):
@@ -145,3 +149,10 @@ def box_mix(n, k, height, width, seed, first_kind=0):
                 box[int(rng.integers(4))] = np.nan
             out[a, b] = box
     return out
+
+
+def box_mix_offgrid(n, k, height, width, seed, first_kind=0):
+    """box_mix without the grid: coordinates drawn uniformly and kept as fp32 rounds them, for a spatial_scale that is not a power
+    of two.  Kernel and reference then see products and quotients that are inexact in fp64 -- the same ones, from the same fp32
+    inputs in the same order.  A zero-width box keeps x2 == x1 exactly (the same fp32 value twice)."""
+    return box_mix(n, k, height, width, seed, first_kind, grid=None)

@@ -848,6 +848,58 @@ AUX_EDGE = _aux_edge()
 aux_edge_id = aux_full_id          # (defined below AUX_FULL: the same id scheme)
 
 
+# ---- ROI head (csrc/roi.hip): one case per loop and dispatch class of x3d_roi_pool_fwd / x3d_roi_pool_bwd ------------------------
+# (label, (T, H, W), C, K, num_boxes of the two samples, R, sampling_ratio, 1 / spatial_scale, boxes, (x_raw, yraw, g) offsets in
+# elements off a 16-byte boundary, extra).  boxes: "grid" = roi_ref.box_mix (1/8-pixel grid), "offgrid" = roi_ref.box_mix_offgrid;
+# both cycle through BOX_KINDS over the slots, so every round of four boxes mixes valid, zero-width, NaN and empty ones.
+# extra: "poison" = the backward is run a second time with argmax bytes >= R*R in some valid rows.  tests/roi_classes.py restates
+# what the launchers and kernels make of a case, and tests/test_roi_head.py fails with the name of a class no case here runs.
+_Z = (0, 0, 0)
+ROI_EDGE = [
+    # the shipped default (MAX_BOXES 8, R 7, sampling_ratio 0) on X3D-M's conv5 plane: 784 elements, 16-bit vectors cross planes of 49
+    ("m-default", (16, 7, 7), 24, 8, (8, 5), 7, 0, 32, "grid", _Z, ""),
+    # X3D-S: 325 elements, scalar in every type; a sample without boxes next to one with two rounds
+    ("s-plane", (13, 5, 5), 3, 8, (8, 0), 7, 0, 32, "grid", _Z, ""),
+    # X3D-XS: 100 elements, fp32 vectors and 16-bit scalars; L / XL: planes of 100 pixels, every vector type with H*W % 8 = 4
+    ("xs-plane-sr0", (4, 5, 5), 3, 8, (8, 3), 7, 0, 32, "grid", _Z, ""),
+    ("xs-plane-sr2", (4, 5, 5), 3, 8, (7, 8), 7, 2, 32, "grid", _Z, ""),
+    ("l-plane-sr0", (16, 10, 10), 3, 8, (8, 6), 7, 0, 32, "grid", _Z, ""),
+    ("l-plane-sr2", (16, 10, 10), 3, 8, (3, 8), 7, 2, 32, "grid", _Z, ""),
+    # box rounds on their own: a second round with one wave at work next to exactly one full round; sixteen rounds, and nine with the
+    # count ending inside the last
+    ("round2-one-wave", (2, 8, 10), 3, 5, (5, 4), 7, 0, 32, "grid", _Z, "poison"),
+    ("rounds-16", (2, 8, 10), 2, 64, (64, 33), 2, 0, 32, "grid", _Z, ""),
+    # bins per lane: R*R = 64 fills the wave, 81 gives 17 lanes a second bin, 225 takes four trips
+    ("bins-64", (2, 8, 10), 3, 3, (3, 2), 8, 0, 32, "grid", _Z, ""),
+    ("bins-81", (2, 8, 10), 3, 3, (2, 3), 9, 2, 32, "grid", _Z, ""),
+    ("bins-225", (2, 8, 10), 3, 3, (3, 1), 15, 0, 32, "grid", _Z, ""),
+    ("bins-64-1024px", (1, 32, 32), 2, 3, (2, 3), 8, 2, 32, "grid", _Z, ""),
+    ("bins-81-1024px", (1, 32, 32), 2, 3, (3, 2), 9, 0, 32, "grid", _Z, ""),
+    ("bins-225-1024px", (1, 32, 32), 2, 3, (1, 3), 15, 0, 32, "grid", _Z, ""),
+    # staging chunks of the forward with a short last one: q = 1 (8 + 1 slices); H*W = 625 (fp32 q = 4: 12 + 4, 16-bit q = 8: 8 + 8);
+    # H*W = 900 (fp32 q = 1: 9 + 1, 16-bit q = 2: 8 + 2); 9207 elements, scalar (8 + 1)
+    ("chunks-q1", (9, 32, 32), 2, 2, (2, 1), 2, 2, 32, "grid", _Z, ""),
+    ("chunks-hw625", (16, 25, 25), 2, 2, (1, 2), 7, 0, 32, "grid", _Z, ""),
+    ("chunks-hw900", (10, 30, 30), 2, 2, (2, 2), 2, 2, 32, "grid", _Z, ""),
+    ("chunks-scalar", (9, 31, 33), 2, 2, (2, 1), 7, 0, 32, "grid", _Z, ""),
+    # pixels per thread: 289, 513 and 930 pixels give the last thread rows 2, 3 and 4 pixels with a ragged end, over two box rounds
+    ("pixels-2", (2, 17, 17), 2, 5, (5, 2), 2, 0, 32, "grid", _Z, ""),
+    ("pixels-3", (1, 19, 27), 2, 5, (3, 5), 7, 2, 32, "grid", _Z, ""),
+    ("pixels-4", (1, 30, 31), 2, 5, (5, 5), 2, 0, 32, "grid", _Z, ""),
+    # an extent that divides but a pointer one element off: the forward's x_raw (and with it the backward's yraw), then g alone
+    ("misaligned-x", (8, 4, 4), 3, 3, (3, 2), 2, 2, 32, "grid", (1, 1, 0), ""),
+    ("misaligned-g", (8, 4, 4), 3, 3, (2, 3), 7, 0, 32, "grid", (0, 0, 1), ""),
+    # geometry off the exact grid: boxes drawn uniformly, spatial_scale 1/16 (exact) and 1/24 (rounded to fp32)
+    ("geometry-16", (4, 7, 7), 3, 6, (6, 2), 7, 0, 16, "offgrid", _Z, ""),
+    ("geometry-24", (4, 7, 7), 3, 6, (2, 6), 7, 2, 24, "offgrid", _Z, ""),
+]
+
+
+def roi_edge_id(case):
+    label, (t, h, w), c, k, nb, r, sr = case[:7]
+    return f"{label}-{t}x{h}x{w}-C{c}-K{k}-nb{nb[0]}_{nb[1]}-R{r}-sr{sr}"
+
+
 # ---- whole-model cases (tests/test_model_gpu.py): variant, N, T, S --------------------------------------------------------
 MODEL_TRAIN_FP32 = [
     ("XS", 4, 4, 64), ("S", 2, 13, 64), ("M", 2, 4, 64), ("S", 3, 5, 96),

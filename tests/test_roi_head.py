@@ -275,3 +275,66 @@ def test_model_refuses_boxes_with_the_switch_off_and_the_switch_without_boxes():
         on.forward_backward(clips, torch.zeros(2, K, dtype=torch.int64), boxes=torch.zeros(2, K, 4), num_boxes=[1, 1],
                             sample_weight=torch.ones(2))
     assert not on._plans and not off._plans           # nothing was recorded, let alone launched
+
+
+# ---- the edge table of the GPU suite ----------------------------------------------------------------------------------------
+def test_roi_edge_table_runs_every_class():
+    """shapes.ROI_EDGE, over the three storage types, holds a case of every loop and dispatch class of roi.hip (roi_classes.CLASSES);
+    a class loses its cases -> its name is reported; and the constants the table was built for are still roi.hip's"""
+    import roi_classes as RC
+    from shapes import ROI_EDGE, roi_edge_id
+    assert RC.roi_defines() == RC.ROI
+    assert RC.ROI["ROI_STAGE"] // RC.ROI["ROI_MAX_HW"] >= 8            # (what keeps `if (tc < q) tc = q` out of reach)
+    ids = [roi_edge_id(c) for c in ROI_EDGE]
+    assert len(set(ids)) == len(ids)
+    cov = RC.covered(ROI_EDGE)
+    assert RC.missing(ROI_EDGE) == [], f"no case of ROI_EDGE runs: {RC.missing(ROI_EDGE)}"
+    for name, labels in cov.items():                                   # the check has teeth: without its cases a class is reported
+        rest = [c for c in ROI_EDGE if c[0] not in labels]
+        assert name in RC.missing(rest), name
+    assert all(any(c[0] in labels for labels in cov.values()) for c in ROI_EDGE), "a case that runs no class"
+    for c in ROI_EDGE:                                                 # what the library and the GPU test's timing accept
+        _, (t, h, w), ch, k, nb, r, sr, den, boxes, offs, extra = c
+        assert h * w <= RC.ROI["ROI_MAX_HW"] and 1 <= r <= 15 and 1 <= k <= 64 and len(nb) == 2 and all(0 <= v <= k for v in nb)
+        assert (ch <= 3 or (t, h, w) == (16, 7, 7)) and boxes in ("grid", "offgrid") and extra in ("", "poison")
+    assert sum(c[10] == "poison" and max(RC.form(c, "float32")["bwd_rounds"]) >= 2 for c in ROI_EDGE) == 1
+
+
+def test_roi_reference_is_quick_on_the_edge_table():
+    """the fp64 reference of every ROI_EDGE case, forward and backward, in under two seconds (the GPU test runs it three times)"""
+    import time
+    import roi_classes as RC
+    from shapes import ROI_EDGE
+    worst = 0.0
+    for i, c in enumerate(ROI_EDGE):
+        _, (t, h, w), ch, k, nb, r, sr, den, kind, _, _ = c
+        scale = float(np.float32(1.0 / den))
+        rng = np.random.default_rng(i)
+        xx = rng.standard_normal((2, ch, t, h, w))
+        ss = np.stack([np.full(ch, 0.7), np.full(ch, 0.5)], 1)
+        boxes = RC.case_boxes(i, c)
+        t0 = time.perf_counter()
+        pooled, bins, am, valid = R.forward(xx, ss, boxes, nb, r, sr, scale)
+        R.backward(rng.standard_normal((2 * k, ch)), am, boxes, nb, xx, ss, r, sr, scale)
+        worst = max(worst, time.perf_counter() - t0)
+        assert valid.any() and (k < 4 or not valid.all()), c[0]
+        per_sample = valid.reshape(2, k)
+        assert all(per_sample[a].any() for a in range(2) if nb[a] >= 3), c[0]
+        if c[10] == "poison":
+            assert per_sample[:, 4:].any(), "the poison case needs a valid box in its second round"
+        if r in (9, 15):
+            assert valid.any()
+    print(f"slowest case: {worst:.3f} s")
+    assert worst < 2.0
+
+
+def test_offgrid_boxes_keep_the_kinds_and_leave_the_grid():
+    b = R.box_mix_offgrid(2, 6, 168, 168, seed=3)
+    g = R.box_mix(2, 6, 168, 168, seed=3)
+    fin = np.isfinite(b).all(axis=2)
+    assert (fin == np.isfinite(g).all(axis=2)).all() and (~fin).sum() == 2          # the NaN slots are the same
+    assert b.dtype == np.float32 and np.abs(b[fin] - g[fin]).max() <= 1.0 / 16      # the grid version is this one rounded
+    assert (b[fin] * 8 != np.round(b[fin] * 8)).mean() > 0.5                        # most coordinates are off the 1/8 grid
+    assert (b[:, 4, 0] == b[:, 4, 2]).all()                                          # zero width stays exactly zero
+    valid = [R.box_geometry(b[0, k], True, float(np.float32(1 / 24)), 7, 7, 7, 0) is not None for k in range(6)]
+    assert valid == [True, True, True, True, False, False]
