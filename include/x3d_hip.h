@@ -66,7 +66,9 @@ extern "C" {
  *       x3d_se_bnb_bwd_args.P (values every earlier version refused; no struct changes its layout);
  *   138 (additions only, no bump) x3d_softmax_xent_w / x3d_sigmoid_bce_w / x3d_class_hits (class and sample weights,
  *       focal terms, per-class hit counters);
- *   138 (additions only, no bump) x3d_roi_pool_fwd / x3d_roi_pool_bwd (ROI head for action detection). */
+ *   138 (additions only, no bump) x3d_roi_pool_fwd / x3d_roi_pool_bwd (ROI head for action detection);
+ *   138 (additions only, no bump) x3d_dw3d_fwd_dil / x3d_dw3d_bwd_dil / x3d_dw3d_kernel_name_dil (dilated channelwise convs of
+ *       a stride-1 res5 for detection; no struct changes its layout). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -461,6 +463,10 @@ int x3d_pw_coef_fold_supported(const x3d_pw_dgrad_args* dgrad, const x3d_pw_wgra
  *     reference model.py:259-267.  TF-SAME (asymmetric) padding.  The HBM-bound headline kernel.
  *     Prologue on load: v = act(s*x + t) inside the image, 0 in the padding.
  *     Epilogue: stats [C][2] += ; pool [N][C] += sum over T,Ho,Wo of y (SE squeeze, model.py:277,312)
+ *     DILATED form (x3d_dw3d_fwd_dil / x3d_dw3d_bwd_dil below; added under ABI 138 without a version bump: new symbols only,
+ *     the argument structs are the dense ones): Conv3D(k=(3,3,3), strides 1, dilation_rate=(1,d,d), groups=C).  Padding d on
+ *     each spatial side and 1 in time -- TF-SAME for the effective kernel 1 + 2d at stride 1, symmetric -- so y has x's extents.
+ *     Prologue, epilogue and every backward output as in the dense form (csrc/dw_dil.hip).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const void* x;               /* [N][C][T][H][W] */
@@ -496,6 +502,14 @@ int x3d_dw3d_bwd(const x3d_dw3d_bwd_args* a, void* stream);
  * bench.py so that its roofline row names the same kernel as the rocprofv3 summary.  Exactly one of
  * fwd / bwd is non-NULL.  Returns X3D_OK and a NUL-terminated string in out[0..cap). */
 int x3d_dw3d_kernel_name(const x3d_dw3d_fwd_args* fwd, const x3d_dw3d_bwd_args* bwd, char* out, int cap);
+/* The dilated form of K6: the same argument structs, the dilation d as an argument of its own.  d = 0 and d = 1 ARE the dense
+ * conv: the call is handed to x3d_dw3d_fwd / x3d_dw3d_bwd as it stands.  d >= 2 needs stride == 1, d <= 4 and
+ * (H + 2d)(W + 2d) <= 4096 (the zero-haloed plane of one channel must fit the LDS ring; no tiling); anything else is refused
+ * with X3D_ERR_INVALID and a message naming the argument, before any launch.  x3d_dw3d_kernel_name_dil: the dry-run dispatch
+ * of the two, as x3d_dw3d_kernel_name. */
+int x3d_dw3d_fwd_dil(const x3d_dw3d_fwd_args* a, int dilation, void* stream);
+int x3d_dw3d_bwd_dil(const x3d_dw3d_bwd_args* a, int dilation, void* stream);
+int x3d_dw3d_kernel_name_dil(const x3d_dw3d_fwd_args* fwd, const x3d_dw3d_bwd_args* bwd, int dilation, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------
  * K7/K8  squeeze-excite MLP: se_pool -> se_fc1(+bias, ReLU) -> se_fc2(+bias, sigmoid)

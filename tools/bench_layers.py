@@ -42,10 +42,10 @@ def describe(name, st, eb):
     if name == "x3d_pw_wgrad":
         by = eb * n * t * ho * wo * (2 * f["Cout"] + f["Cin"])
         return f"{f['Cout']}x{f['Cin']} @{t}x{ho}x{wo}", by
-    if name == "x3d_dw3d_fwd":
+    if name in ("x3d_dw3d_fwd", "x3d_dw3d_fwd_dil"):
         by = eb * n * f["C"] * t * (h * w + ho * wo)
         return f"C{f['C']} @{t}x{h}x{w} s{s}", by
-    if name == "x3d_dw3d_bwd":
+    if name in ("x3d_dw3d_bwd", "x3d_dw3d_bwd_dil"):
         by = eb * n * f["C"] * t * (2 * h * w + 2 * ho * wo)
         return f"C{f['C']} @{t}x{h}x{w} s{s}", by
     return "", 0

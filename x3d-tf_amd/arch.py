@@ -8,7 +8,7 @@ import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .config import drop_path_settings
+from .config import drop_path_settings, res5_dilation_settings
 
 
 def round_width(width, multiplier, min_depth=8, divisor=8):
@@ -54,6 +54,7 @@ class BlockSpec:
     has_se: bool
     se_width: int
     has_shortcut_conv: bool
+    dilation: int = 1       # spatial dilation of the 3x3x3 `b` conv (NETWORK.RES5_DILATION: 2 in the last stage)
 
 
 @dataclass
@@ -80,6 +81,12 @@ class Arch:
     num_preds: int               # TEST.NUM_TEMPORAL_VIEWS * TEST.NUM_SPATIAL_CROPS (model.py:25)
     se_ratio: float = 0.0625
     drop_path_rate: float = 0.0  # NETWORK.DROP_PATH_RATE: stochastic depth of the bottleneck branches (drop_path_rates)
+    res5_dilation: int = 1       # NETWORK.RES5_DILATION: 2 = the last stage at stride 1, its `b` convs dilated by 2
+
+    @property
+    def spatial_stride(self) -> int:
+        """Clip pixels per pixel of the last stage's output (and of conv5): 32, or 16 with the dilated stride-1 res5."""
+        return 32 // self.res5_dilation
 
     @property
     def blocks(self) -> List[BlockSpec]:
@@ -90,8 +97,8 @@ class Arch:
         h = (h + 2 - 3) // 2 + 1
         w = (w + 2 - 3) // 2 + 1
         for s in self.stages:
-            h = same_pad(h, 3, 2)[0]
-            w = same_pad(w, 3, 2)[0]
+            h = same_pad(h, 3, s.blocks[0].stride)[0]
+            w = same_pad(w, 3, s.blocks[0].stride)[0]
         return t, h, w
 
 
@@ -114,6 +121,7 @@ def build_arch(cfg) -> Arch:
     basis = [(1, base), (2, round_width(base, 2)), (5, round_width(base, 4)),
              (3, round_width(base, 8))]
 
+    res5_dilation = res5_dilation_settings(cfg)
     stages: List[StageSpec] = []
     out_dim = c1
     counter = 0
@@ -126,13 +134,15 @@ def build_arch(cfg) -> Arch:
         for bi in range(depth):
             counter += 1
             bcin = in_dim if bi == 0 else out_dim
-            stride = 2 if bi == 0 else 1
+            # the dilated res5 (NETWORK.RES5_DILATION = 2): the last stage keeps the resolution and dilates its `b` convs
+            dilation = res5_dilation if si == len(basis) - 1 else 1
+            stride = 2 if bi == 0 and dilation == 1 else 1
             has_se = (counter + 1) % 2 == 0
             st.blocks.append(BlockSpec(
                 stage=si, index=bi, global_index=counter, cin=bcin, inner=inner, cout=out_dim,
                 stride=stride, has_se=has_se,
                 se_width=round_width(inner, 0.0625) if has_se else 0,
-                has_shortcut_conv=(bcin != out_dim or stride != 1)))
+                has_shortcut_conv=(bcin != out_dim or stride != 1), dilation=dilation))
         stages.append(st)
 
     return Arch(
@@ -141,7 +151,7 @@ def build_arch(cfg) -> Arch:
         bn_momentum=float(net.BN.MOMENTUM), dropout_rate=float(net.DROPOUT_RATE),
         weight_decay=float(net.WEIGHT_DECAY),
         num_preds=cfg.TEST.NUM_TEMPORAL_VIEWS * cfg.TEST.NUM_SPATIAL_CROPS,
-        drop_path_rate=drop_path_settings(cfg))
+        drop_path_rate=drop_path_settings(cfg), res5_dilation=res5_dilation)
 
 
 def drop_path_rates(arch: Arch) -> List[float]:
@@ -262,8 +272,8 @@ def summary_rows(arch: Arch, t: int, h: int, w: int, in_channels: int = 3):
     ww = (w + 2 - 3) // 2 + 1
     rows.append(("conv_1", (t, hh, ww, arch.c1), psum("conv1/")))
     for i, s in enumerate(arch.stages):
-        hh = same_pad(hh, 3, 2)[0]
-        ww = same_pad(ww, 3, 2)[0]
+        hh = same_pad(hh, 3, s.blocks[0].stride)[0]
+        ww = same_pad(ww, 3, s.blocks[0].stride)[0]
         rows.append((f"res_stage_{i + 2}", (t, hh, ww, s.cout), psum(f"stages/{i}/")))
     rows.append(("conv_5", (t, hh, ww, arch.conv5_out), psum("conv5/")))
     rows.append(("pool_5", (1, 1, 1, arch.conv5_out), 0))

@@ -136,7 +136,7 @@ def get_default_config():
     TEST.ENSEMBLE_METHOD (multi-label training), MIXUP.* and TRAIN.LABEL_SMOOTHING (soft-target training),
     AUG.* (batched training augmentation, AUG.AA_TYPE: RandAugment), SOLVER.* (gradient clipping, accumulation, weight EMA;
     LAYER_DECAY / LR_MULT / FREEZE / FREEZE_EVAL / FREEZE_BN: fine-tuning),
-    NETWORK.DROP_PATH_RATE (stochastic depth), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
+    NETWORK.DROP_PATH_RATE (stochastic depth), NETWORK.RES5_DILATION (dilated stride-1 res5 for detection), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
     DISTILL.* (knowledge distillation against a teacher's logits), LOSS.* (class / positive weights and focal terms),
     DETECTION.* (the ROI head for action detection)."""
@@ -149,7 +149,11 @@ def get_default_config():
         DROP_PATH_RATE=0.0,
         # USE_PRECISE_STATS (PySlowFast's BN section): Trainer.fit recomputes every layer's moving statistics exactly, from
         # NUM_BATCHES_PRECISE training batches, after each epoch's steps -- before its validation and its checkpoint
-        BN=dict(MOMENTUM=0.9, EPS=1e-5, USE_PRECISE_STATS=False, NUM_BATCHES_PRECISE=200)))
+        BN=dict(MOMENTUM=0.9, EPS=1e-5, USE_PRECISE_STATS=False, NUM_BATCHES_PRECISE=200)),
+        # RES5_DILATION (res5_dilation_settings; 1 = off): 2 runs the last stage at stride 1 with its 3x3x3 convs dilated by 2 in
+        # space -- PySlowFast's RESNET.SPATIAL_STRIDES [[1],[2],[2],[1]] / SPATIAL_DILATIONS [[1],[1],[1],[2]], the X3D detection
+        # setup: conv5 at stride 16.  The weights keep their shapes.  Known without being held, as the SOLVER keys below
+        optional=dict(RES5_DILATION=1))
     c.DATA = CfgNode(dict(
         FRAME_RATE=1, TEMP_DURATION=1, NUM_INPUT_CHANNELS=3, TRAIN_JITTER_SCALES=[182, 228],
         TRAIN_CROP_SIZE=112, TEST_CROP_SIZE=160, MEAN=[0.45, 0.45, 0.45],
@@ -240,6 +244,7 @@ def get_config(name, overrides=None, freeze=True):
     device_loss_scale_settings(cfg)
     optim_settings(cfg)
     drop_path_settings(cfg)
+    res5_dilation_settings(cfg)
     precise_bn_settings(cfg)
     distill_settings(cfg, have_teacher=True)   # (whether a teacher exists is the trainer's to check)
     loss_settings(cfg)
@@ -532,6 +537,25 @@ def drop_path_settings(cfg) -> float:
     if not 0.0 <= rate < 1.0:           # (NaN fails too)
         raise ValueError(f"NETWORK.DROP_PATH_RATE must lie in [0, 1), not {rate}")
     return rate
+
+
+RES5_DILATIONS = (1, 2)
+
+
+def res5_dilation_settings(cfg) -> int:
+    """cfg.NETWORK.RES5_DILATION (1 for a config tree without the key).  ValueError for anything but the integers 1 and 2, and --
+    only when the key is not 1 -- for DETECTION.ENABLE with a DETECTION.SPATIAL_SCALE_FACTOR that is not the network's stride,
+    32 // RES5_DILATION."""
+    d = getattr(cfg.NETWORK, "RES5_DILATION", 1)
+    if isinstance(d, bool) or not isinstance(d, int) or d not in RES5_DILATIONS:
+        raise ValueError(f"NETWORK.RES5_DILATION must be one of {RES5_DILATIONS}, not {d!r}")
+    dv = getattr(cfg, "DETECTION", None)
+    if d != 1 and dv is not None and bool(getattr(dv, "ENABLE", False)):
+        f = getattr(dv, "SPATIAL_SCALE_FACTOR", 32)
+        if f != 32 // d:
+            raise ValueError(f"DETECTION.SPATIAL_SCALE_FACTOR = {f} with NETWORK.RES5_DILATION = {d}: conv5 is at stride "
+                             f"{32 // d}, set DETECTION.SPATIAL_SCALE_FACTOR to {32 // d}")
+    return d
 
 
 PreciseBNSettings = collections.namedtuple("PreciseBNSettings", "enable num_batches")

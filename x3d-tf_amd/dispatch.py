@@ -15,7 +15,8 @@ from . import hip
 from .config import get_config
 from .model import X3D
 
-CONV_ENTRIES = ("x3d_pw_fwd", "x3d_pw_dgrad", "x3d_pw_wgrad", "x3d_pw_bwd", "x3d_dw3d_fwd", "x3d_dw3d_bwd")
+CONV_ENTRIES = ("x3d_pw_fwd", "x3d_pw_dgrad", "x3d_pw_wgrad", "x3d_pw_bwd", "x3d_dw3d_fwd", "x3d_dw3d_bwd", "x3d_dw3d_fwd_dil",
+                "x3d_dw3d_bwd_dil")
 
 # the five BASELINE.json configurations at full size: (variant, batch per GPU, T, S, dtype, training, cfg overrides)
 BASELINE_CONFIGS = {
@@ -30,7 +31,7 @@ BASELINE_CONFIGS = {
 def describe_struct(st) -> str:
     """Shape summary of an argument struct (for messages)."""
     if isinstance(st, (hip.Dw3dFwdArgs, hip.Dw3dBwdArgs)):
-        return f"N{st.N} C{st.C} T{st.T} {st.H}x{st.W} s{st.stride}"
+        return f"N{st.N} C{st.C} T{st.T} {st.H}x{st.W} s{st.stride}" + (f" d{hip.dw3d_dilation(st)}" if hip.dw3d_dilation(st) > 1 else "")
     s = f"N{st.N} {st.Cin}->{st.Cout} T{st.T} {st.H}x{st.W}"
     if hasattr(st, "stride"):
         s += f" s{st.stride}"

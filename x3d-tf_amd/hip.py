@@ -219,12 +219,31 @@ def load(path=None):
     return lib
 
 
+def dilated(args, dilation):
+    """`args` (a Dw3dFwdArgs / Dw3dBwdArgs) tagged with the dilation its launch passes to x3d_dw3d_fwd_dil / x3d_dw3d_bwd_dil.
+    The C structs have no such field (the dilation is an argument of the dilated entry points): the tag is an attribute of
+    the Python object, so that whoever holds the struct of a recorded launch -- dw3d_kernel_name, dispatch, the per-launch
+    tools -- names and describes the launch that was recorded.  Returns args."""
+    args.dilation = int(dilation)
+    return args
+
+
+def dw3d_dilation(args) -> int:
+    """The dilation a depthwise argument struct was tagged with (dilated); 1 for an untagged one."""
+    return int(getattr(args, "dilation", 1))
+
+
 def dw3d_kernel_name(args):
-    """Instantiation x3d_dw3d_fwd / x3d_dw3d_bwd would launch for this argument struct (no launch)."""
+    """Instantiation x3d_dw3d_fwd / x3d_dw3d_bwd -- or, for a struct tagged with a dilation >= 2 (dilated), x3d_dw3d_fwd_dil /
+    x3d_dw3d_bwd_dil -- would launch for this argument struct (no launch)."""
     buf = C.create_string_buffer(128)
     fwd = C.byref(args) if isinstance(args, Dw3dFwdArgs) else None
     bwd = C.byref(args) if isinstance(args, Dw3dBwdArgs) else None
-    rc = load().x3d_dw3d_kernel_name(fwd, bwd, buf, 128)
+    d = dw3d_dilation(args)
+    if d in (0, 1):
+        rc = load().x3d_dw3d_kernel_name(fwd, bwd, buf, 128)
+    else:
+        rc = load().x3d_dw3d_kernel_name_dil(fwd, bwd, d, buf, 128)
     if rc != 0:
         raise X3DHipError(load().x3d_last_error().decode())
     return buf.value.decode()
@@ -330,6 +349,12 @@ def call(name, *args):
 def call_struct(name, struct):
     lib = load()
     check(getattr(lib, name)(C.byref(struct), stream_ptr()), name)
+
+
+def call_struct_dil(name, struct, dilation):
+    """x3d_dw3d_fwd_dil / x3d_dw3d_bwd_dil on the current stream: the struct, then the dilation"""
+    lib = load()
+    check(getattr(lib, name)(C.byref(struct), int(dilation), stream_ptr()), name)
 
 
 def stats_layout(c: int):

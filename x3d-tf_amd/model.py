@@ -297,7 +297,7 @@ class X3D:
                 bt.bn_a = self._bn(f"{q}/bn_a")
                 bt.relu = Activation("relu")
                 bt.b = Conv3D("b", p[f"{q}/b/kernel"], kernel_size=(3, 3, 3), strides=(1, b.stride, b.stride),
-                              groups=b.inner)
+                              groups=b.inner, dilation_rate=(1, b.dilation, b.dilation))
                 bt.bn_b = self._bn(f"{q}/bn_b")
                 bt.swish = Activation("swish")
                 if b.has_se:

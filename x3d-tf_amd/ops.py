@@ -354,8 +354,9 @@ def pw_wgrad(g, yraw, coef, x, dw, in_ss=None, in_gate=None, in_act=ACT_NONE, st
 
 
 # ---- depthwise ----------------------------------------------------------------------------------
-def dw3d_fwd(x, w, stride, y=None, in_ss=None, in_act=ACT_NONE, stats=None, pool=None, in_bn=None):
-    """in_bn: an ops.bn_fold(...) struct -- the prologue's BatchNorm finalize runs inside the kernel (in_ss unused)."""
+def dw3d_fwd(x, w, stride, y=None, in_ss=None, in_act=ACT_NONE, stats=None, pool=None, in_bn=None, dilation=1):
+    """in_bn: an ops.bn_fold(...) struct -- the prologue's BatchNorm finalize runs inside the kernel (in_ss unused).
+    dilation >= 2: the dilated form, x3d_dw3d_fwd_dil (stride 1, padding `dilation`: y has x's extents)."""
     _chk(x, w, y, in_ss, stats, pool)
     n, c, t, h, ww = x.shape
     ho, wo = _out_hw(h, ww, stride)
@@ -364,17 +365,23 @@ def dw3d_fwd(x, w, stride, y=None, in_ss=None, in_act=ACT_NONE, stats=None, pool
     st = _Stats(stats, c)
     a = hip.Dw3dFwdArgs(ptr(x), ptr(w), ptr(y), ptr(in_ss), in_act, ptr(st.arg()), ptr(pool), n, c, t, h,
                         ww, stride, hip.dtype_code(x.dtype), None if in_bn is None else ctypes.pointer(in_bn))
-    hip.call_struct("x3d_dw3d_fwd", a)
+    if int(dilation) in (0, 1):
+        hip.call_struct("x3d_dw3d_fwd", a)
+    else:
+        hip.call_struct_dil("x3d_dw3d_fwd_dil", a, dilation)
     st.done()
     return y
 
 
-def dw3d_bwd(dv, braw, coef_nc, araw, a_ss, w, ga, a_sums, dw, stride):
+def dw3d_bwd(dv, braw, coef_nc, araw, a_ss, w, ga, a_sums, dw, stride, dilation=1):
     _chk(dv, braw, coef_nc, araw, a_ss, w, ga, a_sums, dw)
     n, c, t, h, ww = araw.shape
     a = hip.Dw3dBwdArgs(ptr(dv), ptr(braw), ptr(coef_nc), ptr(araw), ptr(a_ss), ptr(w), ptr(ga),
                         ptr(a_sums), ptr(dw), n, c, t, h, ww, stride, hip.dtype_code(araw.dtype))
-    hip.call_struct("x3d_dw3d_bwd", a)
+    if int(dilation) in (0, 1):
+        hip.call_struct("x3d_dw3d_bwd", a)
+    else:
+        hip.call_struct_dil("x3d_dw3d_bwd_dil", a, dilation)
 
 
 # ---- squeeze-excite -----------------------------------------------------------------------------

@@ -521,6 +521,16 @@ def _a_conv_args(model, pl, B, dt):
     return sa
 
 
+def _rec_dw(pl, lst, entry, st):
+    """One channelwise 3x3x3 launch: the entry point itself, or -- a struct tagged with a dilation >= 2 (NETWORK.RES5_DILATION) -- its
+    dilated form, which takes the dilation behind the struct.  An undilated block records what it always recorded."""
+    d = hip.dw3d_dilation(st)
+    if d > 1:
+        pl.rec(lst, entry + "_dil", st, d)
+    else:
+        pl.rec(lst, entry, st)
+
+
 def _rec_se(model, pl, B):
     b, p, q = B.spec, model.params, f"{block_prefix(B.spec)}/bottleneck"
     pl.rec(pl.fwd, "x3d_se_fwd", pl.acc(B.pool), float(pl.t * B.ho * B.wo), B.bn_b.ss, p[f"{q}/se_fc1/kernel"],
@@ -694,10 +704,10 @@ def _rec_infer_block(model, pl, B, dt):
     B.hidden = pl.f32(n, b.se_width) if b.has_se else None
     B.sa = _a_conv_args(model, pl, B, dt)
     pl.rec(F, "x3d_pw_fwd", B.sa)
-    B.sb = hip.Dw3dFwdArgs(_p(B.a_raw), _p(p[f"{q}/b/kernel"]), _p(B.b_raw), _p(B.bn_a.ss), ACT_RELU, None, None,
-                           n, b.inner, t, B.hh, B.ww, b.stride, dt)
+    B.sb = hip.dilated(hip.Dw3dFwdArgs(_p(B.a_raw), _p(p[f"{q}/b/kernel"]), _p(B.b_raw), _p(B.bn_a.ss), ACT_RELU, None, None,
+                                       n, b.inner, t, B.hh, B.ww, b.stride, dt), b.dilation)
     pl.defer(B.sb, pool=B.pool)
-    pl.rec(F, "x3d_dw3d_fwd", B.sb)
+    _rec_dw(pl, F, "x3d_dw3d_fwd", B.sb)
     if b.has_se:
         _rec_se(model, pl, B)
     if b.has_shortcut_conv:
@@ -913,10 +923,10 @@ def _rec_train_block(model, pl, B, tail: _Tail, dt) -> _Tail:
     pl.rec(F, "x3d_pw_fwd", B.sa)
     # b: channelwise 3x3x3, BN_a + ReLU folded into the load, BN_b statistics + SE squeeze in the epilogue
     _rec_bn_finalize(model, pl, B.bn_a, n * P_in)
-    B.sb = hip.Dw3dFwdArgs(_p(B.a_raw), _p(p[f"{q}/b/kernel"]), _p(B.b_raw), _p(B.bn_a.ss), ACT_RELU, None, None,
-                           n, b.inner, t, B.hh, B.ww, b.stride, dt)
+    B.sb = hip.dilated(hip.Dw3dFwdArgs(_p(B.a_raw), _p(p[f"{q}/b/kernel"]), _p(B.b_raw), _p(B.bn_a.ss), ACT_RELU, None, None,
+                                       n, b.inner, t, B.hh, B.ww, b.stride, dt), b.dilation)
     pl.defer(B.sb, stats=B.bn_b.stats, pool=B.pool)
-    pl.rec(F, "x3d_dw3d_fwd", B.sb)
+    _rec_dw(pl, F, "x3d_dw3d_fwd", B.sb)
     _rec_bn_finalize(model, pl, B.bn_b, n * P_out)
     if b.has_se:
         _rec_se(model, pl, B)
@@ -1238,11 +1248,11 @@ def _bwd_se_bnb(model, pl, s, B, R, c_job):
 def _bwd_dw(model, pl, s, B, R, dvv, gaa):
     """b (fused data + weight gradient), emits grad wrt BN_a output with the ReLU mask applied"""
     b, q = B.spec, f"{block_prefix(B.spec)}/bottleneck"
-    R.db = hip.Dw3dBwdArgs(_p(dvv), _p(B.b_raw), _p(s.out.coef_nc), _p(B.a_raw), _p(B.bn_a.ss),
-                           _p(model.params[f"{q}/b/kernel"]), _p(gaa), None, _p(model.grads[f"{q}/b/kernel"]), pl.n, b.inner,
-                           pl.t, B.hh, B.ww, b.stride, s.dt)
+    R.db = hip.dilated(hip.Dw3dBwdArgs(_p(dvv), _p(B.b_raw), _p(s.out.coef_nc), _p(B.a_raw), _p(B.bn_a.ss),
+                                       _p(model.params[f"{q}/b/kernel"]), _p(gaa), None, _p(model.grads[f"{q}/b/kernel"]), pl.n,
+                                       b.inner, pl.t, B.hh, B.ww, b.stride, s.dt), b.dilation)
     pl.defer(R.db, a_sums=B.bn_a.bsums)
-    pl.rec(s.out.launches, "x3d_dw3d_bwd", R.db)
+    _rec_dw(pl, s.out.launches, "x3d_dw3d_bwd", R.db)
 
 
 def _bwd_shortcut(model, pl, s, B, R):
