@@ -68,7 +68,8 @@ extern "C" {
  *       focal terms, per-class hit counters);
  *   138 (additions only, no bump) x3d_roi_pool_fwd / x3d_roi_pool_bwd (ROI head for action detection);
  *   138 (additions only, no bump) x3d_dw3d_fwd_dil / x3d_dw3d_bwd_dil / x3d_dw3d_kernel_name_dil (dilated channelwise convs of
- *       a stride-1 res5 for detection; no struct changes its layout). */
+ *       a stride-1 res5 for detection; no struct changes its layout);
+ *   138 (additions only, no bump) x3d_frame_match / x3d_frame_ap (frame-mAP for action detection). */
 #define X3D_ABI_VERSION 138
 int x3d_version(void);
 const char* x3d_last_error(void);
@@ -689,6 +690,49 @@ int x3d_view_max(const float* probs, float* out, int videos, int views, int M, v
  * never truncated: its ap is NaN and npos[c] = -P (only possible when N > X3D_AP_MAX_POSITIVES). */
 #define X3D_AP_MAX_POSITIVES 32768
 int x3d_multilabel_ap(const float* scores, const float* targets, int N, int M, double* ap, int* npos, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Frame-mAP for action detection (AVA; the PASCAL evaluator of the TensorFlow object-detection API, restated): the proposals
+ * of an image are matched against its annotated boxes per class, and the per-class AP is PASCAL VOC's area under the monotone
+ * precision envelope.  Where the original leaves something to chance (score ties) the rules below pin it.
+ *   Sizes: I images, K proposal slots and G ground-truth slots per image (1 <= K, G <= 64), C classes.
+ *   scores [I*K][C] fp32 (row i*K + k); boxes [I][K][4] fp32 (x1, y1, x2, y2), num_boxes [I] int32;
+ *   gt_boxes [I][G][4] fp32, num_gt [I] int32; gt_labels [I][G][C] bytes, non-zero = box g carries class c (several allowed).
+ * Validity: a proposal is a DETECTION iff k < num_boxes[i], its four coordinates are finite, x2 > x1 and y2 > y1 (the ROI
+ *   head's "treated as empty" rule, negated); a ground-truth box is VALID by the same rule with num_gt.  What an empty or invalid
+ *   slot holds -- box, score, labels -- is never used.
+ * IoU, in IEEE double from the fp32 coordinates, every operation rounded on its own (no fused multiply-add), the division
+ *   correctly rounded:  iw = max(0, min(ax2, bx2) - max(ax1, bx1)), ih likewise;  inter = iw * ih;
+ *   ua = (ax2 - ax1) * (ay2 - ay1), ub likewise;  iou = inter / (ua + ub - inter).  This is numpy's value bit for bit, so every
+ *   decision below is exact.
+ * Matching, per image i, class c and detection d:
+ *   1. among the valid ground-truth boxes with gt_labels[i][g][c] != 0 (none: d is a false positive), g*(d) is the one with the
+ *      largest iou(d, g), the lowest g among equals; d is a CANDIDATE iff iou(d, g*(d)) >= iou_threshold.  Only the arg-max box
+ *      is tried: a detection whose best box is claimed is a false positive even if another box of the class would pass.
+ *   2. the detections of the image are ordered by score descending, the lower slot k first among equal scores; d is a TRUE
+ *      POSITIVE iff it is a candidate and no detection before it in that order is a candidate with the same g*.
+ *   3. a detection whose score for c is NaN is never a candidate and claims nothing.
+ * x3d_frame_match writes tp [I*K][C] bytes (1 / 0; 0 for a non-detection) and det_scores [I*K][C] fp32 (the score of a
+ *   detection unchanged, NaN included; -inf for a non-detection), and INCREMENTS ngt [C] int32 by the number of valid
+ *   ground-truth boxes carrying c (integer atomics: the result does not depend on their order).  One workgroup per image, the
+ *   IoU table in LDS, one wave per class; no floating-point atomics, nothing else written that another workgroup writes.
+ *   Refused before the launch: a null pointer; I < 1; K or G outside 1..64; C < 1; I*K*C >= 2^31; iou_threshold NaN or outside
+ *   (0, 1].
+ * x3d_frame_ap, per class c over the N = I*K rows of a whole evaluation set: order [N][C] int64 holds the class's row
+ *   permutation by det_scores[:, c] descending, equal scores by row index ascending (a stable sort; the original's argsort is
+ *   unstable), NaN scores first -- what torch.sort(descending=True, stable=True) returns.  With the true positives t = 1..P in
+ *   that order and pos_t the 1-based position of the t-th:  prec_t = t / pos_t;  env_t = max over t' >= t of prec_t';
+ *   ap[c] = (sum over t of env_t) / ngt[c] in double;  ntp[c] = P.  Rows at -inf sort behind every detection and carry tp = 0.
+ *   ngt[c] <= 0: ap[c] = NaN (the class is dropped from the mean).  ngt[c] > 0 and P == 0: ap[c] = 0.  A NaN among the class's
+ *   scores (the class's first row in `order`): ap[c] = NaN.  An entry of `order` outside [0, N) is never followed (its
+ *   position counts as a false positive).  One workgroup per class; the flags stream from memory, so there is no cap on rows
+ *   or true positives per class; the sums are added in a fixed order: the same inputs give the same bits.
+ *   Refused before the launch: a null pointer; N < 1; C < 1; N*C >= 2^31. */
+int x3d_frame_match(const float* scores, const float* boxes, const int* num_boxes, const float* gt_boxes,
+                    const unsigned char* gt_labels, const int* num_gt, int I, int K, int G, int C, double iou_threshold,
+                    unsigned char* tp, float* det_scores, int* ngt, void* stream);
+int x3d_frame_ap(const unsigned char* tp, const float* det_scores, const long long* order, const int* ngt, int N, int C,
+                 double* ap, int* ntp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Knowledge distillation (DISTILL.* of the config): the three training losses with a second term against a teacher's

@@ -4,7 +4,8 @@ SparseCategoricalCrossentropy, SparseCategoricalAccuracy ('acc') and SparseTopKC
 ('top_5_acc') (eval.py:48-66).  Videos come as decoded uint8 tensors; the views are built on the GPU (views.py).
 
 With DATA.MULTI_LABEL the model's outputs are per-class sigmoids and the metrics are the binary cross-entropy and the mean
-average precision over the classes (`DeviceMAP`, x3d_multilabel_ap)."""
+average precision over the classes (`DeviceMAP`, x3d_multilabel_ap).  With DETECTION.ENABLE the detection score is AVA's
+frame-mAP (`DeviceFrameMAP`, x3d_frame_match / x3d_frame_ap), fed by `Trainer.validate`."""
 from typing import Dict, Iterable, Tuple
 
 import torch
@@ -188,6 +189,105 @@ class DeviceMAP:
         have = npos > 0
         m_ap = float(ap[have].mean()) if bool(have.any()) else float("nan")
         return {"loss": loss + reg, "mAP": m_ap, "videos": int(s.shape[0]), "classes": int(have.sum())}
+
+
+class DeviceFrameMAP:
+    """Frame-mAP of an action-detection evaluation (AVA): `update` matches a batch's proposals against its annotated boxes on
+    the device (one x3d_frame_match launch, no host read) and keeps only the per-row scores (fp32), the true-positive flags
+    (uint8) and the running ground-truth counts -- the boxes are not kept; `result()` sorts every class's column and runs
+    x3d_frame_ap once over everything seen.  The rules (IoU matching, VOC AP, ties) are in include/x3d_hip.h.
+
+    result(): {"frame_mAP", "classes", "detections", "gt_boxes", "ap"} -- frame_mAP = the mean of the per-class AP over the
+    `classes` classes with ground truth (a class without is dropped; a NaN score makes its class's AP and so the mean NaN);
+    detections = the valid proposal rows, gt_boxes = the valid annotated boxes, ap = the per-class list (NaN where dropped)."""
+
+    def __init__(self, iou_threshold: float = 0.5):
+        self.iou_threshold = float(iou_threshold)
+        if not 0.0 < self.iou_threshold <= 1.0:
+            raise ValueError(f"DeviceFrameMAP: iou_threshold = {iou_threshold} must be in (0, 1]")
+        self._scores = []
+        self._tp = []
+        self.ngt = None               # int32 [classes], on the device of the first batch
+        self.counts = None            # int64 [2]: valid proposals, valid annotated boxes
+        self._slots = None            # ((K, G), the slot index of every column of the two box sets side by side)
+
+    def _count_valid(self, boxes, num_boxes, gt_boxes, num_gt):
+        """counts += (valid proposals, valid annotated boxes) by x3d_frame_match's rule; both box sets in one chain of device
+        ops (the chain, not the launch, is what an `update` costs: DESIGN section 26), no host read"""
+        k, g = boxes.shape[1], gt_boxes.shape[1]
+        if self._slots is None or self._slots[0] != (k, g):
+            self._slots = ((k, g), torch.cat([torch.arange(k, device=boxes.device), torch.arange(g, device=boxes.device)]))
+        b = torch.cat([boxes, gt_boxes], 1)
+        filled = torch.cat([num_boxes[:, None].expand(-1, k), num_gt[:, None].expand(-1, g)], 1)
+        ok = (b[..., 2:] > b[..., :2]).all(-1) & torch.isfinite(b).all(-1) & (self._slots[1] < filled)
+        self.counts += torch.stack([ok[:, :k].sum(), ok[:, k:].sum()])
+
+    def update(self, probs: torch.Tensor, boxes, num_boxes, gt_boxes, gt_labels, num_gt):
+        """probs [B*K, C] fp32 on the GPU (the model's output rows); boxes [B, K, 4], num_boxes [B] (the proposals); gt_boxes
+        [B, G, 4], gt_labels [B, G, C] (non-zero = the box carries the class), num_gt [B].  The box arguments are tensors,
+        arrays or sequences on any device: they are moved to probs' device and to the kernel's types."""
+        from . import ops
+        dev = probs.device
+        conv = lambda t, dt: torch.as_tensor(t).to(dev, dt, non_blocking=True).contiguous()
+        boxes, gt_boxes = conv(boxes, torch.float32), conv(gt_boxes, torch.float32)
+        num_boxes, num_gt = conv(num_boxes, torch.int32), conv(num_gt, torch.int32)
+        gt_labels = torch.as_tensor(gt_labels)
+        gt_labels = conv(gt_labels if gt_labels.dtype == torch.uint8 else gt_labels != 0, torch.uint8)
+        if self.ngt is None:
+            self.ngt = torch.zeros(probs.shape[-1], dtype=torch.int32, device=dev)
+            self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        rows = probs.detach().reshape(-1, probs.shape[-1]).to(torch.float32).contiguous()      # ([B, K, C] as the model returns it too)
+        tp, det, _ = ops.frame_match(rows, boxes, num_boxes, gt_boxes, gt_labels, num_gt, self.iou_threshold, ngt=self.ngt)
+        self._scores.append(det)      # the kernel's own output buffers: nothing of the model's is kept
+        self._tp.append(tp)
+        self._count_valid(boxes, num_boxes, gt_boxes, num_gt)
+
+    def _cat(self):
+        if len(self._scores) > 1:
+            self._scores = [torch.cat(self._scores, 0)]
+            self._tp = [torch.cat(self._tp, 0)]
+        return (self._scores[0], self._tp[0]) if self._scores else (None, None)
+
+    def all_reduce_(self, group=None, device=None):
+        """All-gathers the scores and flags of every rank in rank order, as `DeviceMAP.all_reduce_` does, and sums the
+        ground-truth counts (no-op without a multi-rank process group).  Every rank must hold the same number of rows: the
+        gather receives into buffers of this rank's size.  A reader's shards are (InputReader._shard drops the trailing partial
+        global batch); a caller that feeds its own batches, a detector's proposals for instance, gives every rank equally many
+        images."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        s, t = self._cat()
+        if s is None:
+            raise ValueError("DeviceFrameMAP.all_reduce_: no batch on this rank")
+        if device is None:
+            device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+        world = dist.get_world_size(group)
+        out = []
+        for x in (s, t):
+            xs = x.to(device)
+            parts = [torch.empty_like(xs) for _ in range(world)]
+            dist.all_gather(parts, xs, group=group)
+            out.append(torch.cat(parts, 0).to(s.device))
+        self._scores, self._tp = [out[0]], [out[1]]
+        for c in (self.ngt, self.counts):
+            tc = c.to(device)
+            dist.all_reduce(tc, group=group)
+            if tc is not c:
+                c.copy_(tc)
+        return self
+
+    def result(self) -> Dict[str, float]:
+        from . import ops
+        s, t = self._cat()
+        if s is None:
+            return {"frame_mAP": float("nan"), "classes": 0, "detections": 0, "gt_boxes": 0, "ap": []}
+        ap, _ = ops.frame_ap(t, s, self.ngt)
+        ap, ngt, counts = ap.cpu(), self.ngt.cpu(), self.counts.cpu()
+        have = ngt > 0
+        m_ap = float(ap[have].mean()) if bool(have.any()) else float("nan")
+        return {"frame_mAP": m_ap, "classes": int(have.sum()), "detections": int(counts[0]), "gt_boxes": int(counts[1]),
+                "ap": ap.tolist()}
 
 
 def _targets_of(label, num_classes: int) -> torch.Tensor:

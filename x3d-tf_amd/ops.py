@@ -688,6 +688,110 @@ def multilabel_ap(scores, targets, ap=None, npos=None, check=True):
     return ap, npos
 
 
+FRAME_MAX_BOXES = 64   # K and G of x3d_frame_match (include/x3d_hip.h)
+
+
+def _frame_tensor(name, what, t, dtype, shape, device):
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{name}: {what} must be {list(shape)} {str(dtype).replace('torch.', '')}, got {got}")
+    if t.device != device:
+        raise ValueError(f"{name}: {what} is on {t.device}, scores on {device}: all tensors must be on one device")
+
+
+def frame_match(scores, boxes, num_boxes, gt_boxes, gt_labels, num_gt, iou_threshold=0.5, tp=None, det_scores=None, ngt=None):
+    """The frame-mAP matching of a batch of images (x3d_frame_match: the rules are in include/x3d_hip.h): scores [I*K, C] fp32,
+    boxes [I, K, 4] fp32 with num_boxes [I] int32 (the proposals), gt_boxes [I, G, 4] fp32 with num_gt [I] int32 and gt_labels
+    [I, G, C] uint8 (the annotated boxes and the classes each carries).  Returns (tp [I*K, C] uint8, det_scores [I*K, C] fp32,
+    ngt [C] int32); a given ngt is INCREMENTED, a missing one starts at zero.  One launch, does not synchronise."""
+    name = "frame_match"
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 2:
+        got = f"{tuple(scores.shape)} {scores.dtype}" if torch.is_tensor(scores) else type(scores).__name__
+        raise ValueError(f"{name}: scores must be [I*K, C] float32, got {got}")
+    rows, c = scores.shape
+    if not torch.is_tensor(boxes) or boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"{name}: boxes must be [I, K, 4] float32, got {tuple(boxes.shape) if torch.is_tensor(boxes) else boxes}")
+    i, k = int(boxes.shape[0]), int(boxes.shape[1])
+    if not torch.is_tensor(gt_boxes) or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise ValueError(f"{name}: gt_boxes must be [I, G, 4] float32, got "
+                         f"{tuple(gt_boxes.shape) if torch.is_tensor(gt_boxes) else gt_boxes}")
+    g = int(gt_boxes.shape[1])
+    if i < 1:
+        raise ValueError(f"{name}: boxes holds I = {i} images, must be >= 1")
+    if not 1 <= k <= FRAME_MAX_BOXES:
+        raise ValueError(f"{name}: boxes holds K = {k} slots per image, must be in 1..{FRAME_MAX_BOXES}")
+    if not 1 <= g <= FRAME_MAX_BOXES:
+        raise ValueError(f"{name}: gt_boxes holds G = {g} slots per image, must be in 1..{FRAME_MAX_BOXES}")
+    if c < 1:
+        raise ValueError(f"{name}: scores has C = {c} classes, must be >= 1")
+    if rows != i * k:
+        raise ValueError(f"{name}: scores has {rows} rows, boxes gives I*K = {i * k}")
+    if i * k * c >= 2 ** 31:
+        raise ValueError(f"{name}: scores has I*K*C = {i * k * c} elements, must be < 2^31")
+    thr = float(iou_threshold)
+    if not 0.0 < thr <= 1.0:     # (false for NaN)
+        raise ValueError(f"{name}: iou_threshold = {iou_threshold} must be in (0, 1]")
+    dev = scores.device
+    _frame_tensor(name, "boxes", boxes, torch.float32, (i, k, 4), dev)
+    _frame_tensor(name, "num_boxes", num_boxes, torch.int32, (i,), dev)
+    _frame_tensor(name, "gt_boxes", gt_boxes, torch.float32, (i, g, 4), dev)
+    _frame_tensor(name, "gt_labels", gt_labels, torch.uint8, (i, g, c), dev)
+    _frame_tensor(name, "num_gt", num_gt, torch.int32, (i,), dev)
+    if tp is not None:
+        _frame_tensor(name, "tp", tp, torch.uint8, (rows, c), dev)
+    if det_scores is not None:
+        _frame_tensor(name, "det_scores", det_scores, torch.float32, (rows, c), dev)
+    if ngt is not None:
+        _frame_tensor(name, "ngt", ngt, torch.int32, (c,), dev)
+    _chk(scores, boxes, num_boxes, gt_boxes, gt_labels, num_gt, tp, det_scores, ngt)
+    if tp is None:
+        tp = torch.empty((rows, c), dtype=torch.uint8, device=dev)
+    if det_scores is None:
+        det_scores = torch.empty((rows, c), dtype=torch.float32, device=dev)
+    if ngt is None:
+        ngt = torch.zeros(c, dtype=torch.int32, device=dev)
+    hip.call("x3d_frame_match", ptr(scores), ptr(boxes), ptr(num_boxes), ptr(gt_boxes), ptr(gt_labels), ptr(num_gt), i, k, g, c,
+             thr, ptr(tp), ptr(det_scores), ptr(ngt))
+    return tp, det_scores, ngt
+
+
+def frame_ap(tp, det_scores, ngt, order=None, ap=None, ntp=None):
+    """Per-class PASCAL VOC average precision over the N rows of an evaluation set (x3d_frame_ap: the rules are in
+    include/x3d_hip.h): tp [N, C] uint8 and det_scores [N, C] fp32 as frame_match wrote them, ngt [C] int32.  order [N, C] int64:
+    every class's rows by score descending, stable; None: torch.sort(det_scores, dim=0, descending=True, stable=True).
+    Returns (ap [C] float64, ntp [C] int32).  A class without ground truth or with a NaN score has ap NaN.  Does not
+    synchronise."""
+    name = "frame_ap"
+    if not torch.is_tensor(det_scores) or det_scores.dtype != torch.float32 or det_scores.dim() != 2:
+        got = f"{tuple(det_scores.shape)} {det_scores.dtype}" if torch.is_tensor(det_scores) else type(det_scores).__name__
+        raise ValueError(f"{name}: det_scores must be [N, C] float32, got {got}")
+    n, c = det_scores.shape
+    if n < 1:
+        raise ValueError(f"{name}: det_scores has N = {n} rows, must be >= 1")
+    if c < 1:
+        raise ValueError(f"{name}: det_scores has C = {c} classes, must be >= 1")
+    if n * c >= 2 ** 31:
+        raise ValueError(f"{name}: det_scores has N*C = {n * c} elements, must be < 2^31")
+    dev = det_scores.device
+    _frame_tensor(name, "tp", tp, torch.uint8, (n, c), dev)
+    _frame_tensor(name, "ngt", ngt, torch.int32, (c,), dev)
+    if order is not None:
+        _frame_tensor(name, "order", order, torch.int64, (n, c), dev)
+    if ap is not None:
+        _frame_tensor(name, "ap", ap, torch.float64, (c,), dev)
+    if ntp is not None:
+        _frame_tensor(name, "ntp", ntp, torch.int32, (c,), dev)
+    _chk(tp, det_scores, ngt, order, ap, ntp)
+    if order is None:
+        order = torch.sort(det_scores, dim=0, descending=True, stable=True).indices
+    if ap is None:
+        ap = torch.empty(c, dtype=torch.float64, device=dev)
+    if ntp is None:
+        ntp = torch.empty(c, dtype=torch.int32, device=dev)
+    hip.call("x3d_frame_ap", ptr(tp), ptr(det_scores), ptr(order), ptr(ngt), n, c, ptr(ap), ptr(ntp))
+    return ap, ntp
+
+
 def softmax_xent_soft(logits, targets, probs, loss_rows=None, dlogits=None, grad_scale=1.0):
     """probs = softmax(logits); with dense target rows [N, M] fp32 (label smoothing, mixup / CutMix): loss_rows [N] = Keras
     CategoricalCrossentropy on the probabilities and its gradient (x3d_softmax_xent_soft: the rules are in

@@ -513,7 +513,8 @@ class Trainer:
             refused -- and validation fills `val_loss` / `val_mAP`.
 
         self.history: per-epoch lists like keras.callbacks.History.history -- `loss` (= the returned list), `lr`, the
-        requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating.
+        requested `metrics`, and `val_loss` / `val_acc` / `val_top_5_acc` when validating; `val_frame_mAP` when the validation
+        batches of a detection model have seven items (`validate`), created at the first validation that returns it.
 
         DISTILL.ENABLE: `history["kd_loss"]` is the epoch mean of the unweighted KD term (`kd_loss`); `loss` stays the combined
         loss (+ L2).
@@ -632,6 +633,8 @@ class Trainer:
                     r = self.validate(val_source(), validation_steps, **(dict(per_class=True) if per_class else {}))
                 for k in val_keys:
                     self.history["val_" + k].append(r[k])
+                if "frame_mAP" in r:          # seven-item detection batches (validate): created at the first validation that has it
+                    self.history.setdefault("val_frame_mAP", []).append(r["frame_mAP"])
             if ckpt is not None and writer:
                 self.save_checkpoint(model_dir, ckpt)
         return history
@@ -657,36 +660,72 @@ class Trainer:
             if close and getattr(src, "close", None) is not None:
                 src.close()   # a reader's generator: stops its prefetch thread
 
-    def validate(self, batches, steps: Optional[int] = None, per_class: bool = False):
+    def validate(self, batches, steps: Optional[int] = None, per_class: bool = False, iou_threshold: float = 0.5):
         """`model.evaluate` inside `fit` (reference train.py:148-151): `model(clips, training=False)` over `batches` (the
         first `steps` of them when given) into a DeviceMetrics, counters summed over the ranks once.  Unlike
         `evaluate_dataset` this releases no plan, so the training plan is still cached in the next epoch.  Returns
         {"loss", "acc", "top_5_acc", "videos"}; for a multi-label model the DeviceMAP result {"loss", "mAP", "videos",
         "classes"} (batches of (clips, targets)).  DETECTION.ENABLE: batches of (clips, labels [B, K] | targets [B, K, classes],
         boxes, num_boxes); loss and metrics are taken over the filled box slots only, "videos" counts them.  per_class (single-label models): + "mean_class_acc".  The loss is
-        unweighted: LOSS.* and sample weights act on the training loss only."""
+        unweighted: LOSS.* and sample weights act on the training loss only.
+
+        Frame-mAP (DETECTION.ENABLE): batches of seven items (clips, labels, boxes, num_boxes, gt_boxes [B, G, 4], gt_labels
+        [B, G, classes], num_gt [B]) -- `boxes` are then the proposals the ROI head pools, e.g. a person detector's -- also feed an
+        `evaluate.DeviceFrameMAP(iou_threshold)` (one x3d_frame_match launch per batch behind the forward pass), and the result
+        gains "frame_mAP", "frame_classes", "detections" and "gt_boxes".  `labels` may be None in such a batch (proposals have
+        no labels of their own): "loss" and the row-wise metric are then NaN.  Every batch of the set has seven items or every
+        one four, and `labels` is None in every batch or in none: a mixture of either kind is a ValueError.  Four-item sets
+        return exactly the keys above.  Under data parallelism the ranks' sets are of one form (all labelled or all unlabelled:
+        an unlabelled rank skips the exchange of the row-wise metric) and of equal size (`DeviceFrameMAP.all_reduce_`), as the
+        reader's shards are."""
         import itertools
-        from .evaluate import DeviceMAP, DeviceMetrics
+        from .evaluate import DeviceFrameMAP, DeviceMAP, DeviceMetrics
         m = self.model
         if getattr(m, "multi_label", False):
             dm = DeviceMAP(m.regularization_loss())
         else:
             dm = DeviceMetrics(m.regularization_loss(), **(dict(per_class=True) if per_class else {}))
+        fm = None                     # the frame-mAP of seven-item batches, next to dm
+        forms, labelled = set(), set()          # the batch lengths seen; whether labels were given (True) or None (False)
         it = iter(batches)
         try:
             for clips, labels, *box_args in itertools.islice(it, None if steps is None else int(steps)):
                 if getattr(m, "det", None) is not None or box_args:      # (clips, labels, boxes, num_boxes): the valid rows only
+                    forms.add(2 + len(box_args))
+                    if len(forms) > 1 or (len(box_args) > 2 and len(box_args) != 5):
+                        raise ValueError("validate: every detection batch must have four items (clips, labels, boxes, num_boxes) "
+                                         "or every one seven (+ gt_boxes, gt_labels, num_gt); got batches of "
+                                         f"{sorted(forms)} items")
+                    labelled.add(labels is not None)
+                    if len(labelled) > 1:
+                        raise ValueError("validate: labels must be None in every batch of the set or in none")
+                    if labels is None and len(box_args) != 5:
+                        raise ValueError("validate: labels may be None only in a seven-item batch")
                     probs = m(clips, training=False, **dict(zip(("boxes", "num_boxes"), box_args)))
                     pl = m._plan(*clips.shape[:4], False)
+                    probs = probs.reshape(pl.rows, -1)
+                    if len(box_args) == 5:
+                        if fm is None:
+                            fm = DeviceFrameMAP(iou_threshold)
+                        fm.update(probs, *box_args)
+                    if labels is None:                # detector proposals carry no labels of their own: the frame keys only
+                        continue
                     labels = torch.as_tensor(labels)
-                    dm.update(*self._valid_rows(pl, probs.reshape(pl.rows, -1), labels.reshape((pl.rows,) + tuple(labels.shape[2:]))))
+                    dm.update(*self._valid_rows(pl, probs, labels.reshape((pl.rows,) + tuple(labels.shape[2:]))))
                 else:
                     dm.update(m(clips, training=False), labels)
         finally:
             close = getattr(it, "close", None)
             if close is not None:
                 close()       # a reader's generator: stops its prefetch thread
-        return dm.all_reduce_(self.group).result()
+        if False in labelled:         # no row-wise metric without labels: the keys stay, NaN and zero rows (no exchange: every
+            r = {k: (0 if k in ("videos", "classes") else float("nan")) for k in dm.result()}    # rank's set is unlabelled, below)
+        else:
+            r = dm.all_reduce_(self.group).result()
+        if fm is not None:
+            f = fm.all_reduce_(self.group).result()
+            r.update(frame_mAP=f["frame_mAP"], frame_classes=f["classes"], detections=f["detections"], gt_boxes=f["gt_boxes"])
+        return r
 
     @staticmethod
     def _valid_rows(pl, probs, labels):
