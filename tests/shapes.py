@@ -917,6 +917,9 @@ MODEL_TRAIN_HALF = [     # teacher-forced block by block, bf16 and fp16 storage
     ("M", 1, 4, 224),     # BASELINE config 3's own planes (112 / 56 / 28 / 14 / 7) with T % 4 == 0: the exact dw_mx variants, the
                           #   stage-2/3 forward tail fold on real rows, the stem fold at 112^2 -- what bench.py times
 ]
+# config overrides of the detection model on the dilated stride-16 map (test_dilated_res5_gpu, test_trajectory, test_trajectory_gpu)
+DILATED_DETECTION = ["NETWORK.RES5_DILATION", 2, "DETECTION.ENABLE", True, "DETECTION.MAX_BOXES", 2,
+                     "DETECTION.SPATIAL_SCALE_FACTOR", 16]
 MODEL_INFER = [           # variant, views, crops, T, S, dtype
     ("XS", 10, 1, 4, 160, F32), ("S", 2, 1, 13, 96, F32),
     ("XL", 10, 3, 2, 96, F32), ("XL", 10, 3, 2, 96, F16), ("XL", 10, 3, 2, 96, BF16),   # BASELINE config 5: 30 views per video

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import dilated_ref as R
+from tests import shapes as S
 from tests.aux_checks import _Bands, _frac
 from tests.util import report, rnd, round_to, tol_gemm, tol_store
 
@@ -349,24 +350,39 @@ def test_inference_against_the_dilated_oracle(gpu):
         report("probs", out, dense, 0, 1e-4)
 
 
+DET = S.DILATED_DETECTION
+
+
 def test_detection_step_on_the_stride_16_map(gpu):
     """DETECTION.ENABLE on the dilated model, SPATIAL_SCALE_FACTOR 16, a 64^2 clip (conv5 map 4 x 4), K = 2: the head restated in
     fp64 on the plan's own trunk output, as tests/test_roi_head_gpu.py test_model_step_matches_the_head_restated_in_fp64 does, at
     its limits (loss 1e-5, probabilities 1e-4, dlogits 1e-6 of their maximum, dpooled / gradients / g5 1e-3 relative L2)."""
-    import numpy as np
     from tests import roi_ref
     from tests import test_roi_head_gpu as H
-    kb, s, nb, scale = 2, 64, [2, 0], 1.0 / 16
-    cfg, arch, params = H._setup(["NETWORK.RES5_DILATION", 2, "DETECTION.ENABLE", True, "DETECTION.MAX_BOXES", kb,
-                                  "DETECTION.SPATIAL_SCALE_FACTOR", 16])
+    kb, s, nb = 2, 64, [2, 0]
+    cfg, arch, params = H._setup(DET)
     n, t, classes, rows = 2, 4, arch.num_classes, 2 * kb
     g = torch.Generator().manual_seed(1)
     clips = torch.randn(n, t, s, s, 3, generator=g)
     boxes = roi_ref.box_mix(n, kb, s, s, seed=2)
-    valid = (torch.arange(kb).view(1, kb) < torch.tensor(nb).view(n, 1)).reshape(-1)
     labels = torch.randint(0, classes, (n, kb), generator=g)
     mask = (torch.rand(rows, arch.fc1_out, generator=g) >= arch.dropout_rate).float()
     m = H._model(cfg, params, gpu)
+    _detection_step(m, clips, boxes, nb, labels, mask)
+
+
+def _detection_step(m, clips, boxes, nb, labels, mask, scale=1.0 / 16):
+    """one forward_backward of the live detection model `m` with the head restated in fp64 on the plan's own trunk output and on
+    the parameters the device holds at that moment; returns the plan"""
+    import numpy as np
+    from tests import roi_ref
+    from tests import test_roi_head_gpu as H
+    arch, gpu = m.arch, m.device
+    n, t, kb = clips.shape[0], clips.shape[1], m.det.max_boxes
+    classes, rows = arch.num_classes, n * kb
+    torch.cuda.synchronize()
+    params = {k: m.params[k].detach().cpu().clone() for k in ("fc1/kernel", "fc2/kernel", "fc2/bias")}
+    valid = (torch.arange(kb).view(1, kb) < torch.tensor(nb).view(n, 1)).reshape(-1)
     m.set_dropout_mask(mask)
     pl = m.forward_backward(clips.to(gpu), labels, boxes=torch.from_numpy(boxes), num_boxes=nb)
     torch.cuda.synchronize()
@@ -395,9 +411,12 @@ def test_detection_step_on_the_stride_16_map(gpu):
         assert H._rel_l2(m.grads[name].cpu().reshape(ref.shape), ref) < 1e-3, name
     g5_ref, _ = roi_ref.backward(pooled.grad.numpy(), am, boxes, nb, c5, ss, 7, 0, scale)
     g5 = pl.backward.g5.cpu().double()
-    assert H._rel_l2(g5, torch.from_numpy(g5_ref)) < 1e-3 and (g5[0] != 0).any() and (g5[1] == 0).all()
+    assert H._rel_l2(g5, torch.from_numpy(g5_ref)) < 1e-3
+    for i in range(n):        # an image without a box sends nothing into the trunk
+        assert (g5[i] != 0).any() if nb[i] else (g5[i] == 0).all(), f"g5 of image {i} with {nb[i]} boxes"
     # the trunk's gradients are alive down to the stem
     assert torch.isfinite(m.flat_grads).all() and m.grads["conv1/conv_s/kernel"].abs().sum().item() > 0
+    return pl
 
 
 def test_dilation_one_checkpoint_loads_into_the_dilated_model(gpu, tmp_path):

@@ -146,14 +146,49 @@ def test_train_step_fp32_other_temporal_filter(gpu, kt):
 
 
 def _train_step_fp32(gpu, name, n, t, s, overrides=None):
-    from oracle import x3d_oracle as O
     cfg, arch, params = _setup(name, overrides)
     torch.manual_seed(1)
     x = torch.randn(n, t, s, s, 3)
     labels = torch.randint(0, arch.num_classes, (n,))
     mask = (torch.rand(n, arch.fc1_out) >= arch.dropout_rate).float()
-
     m = _model(cfg, params, torch.float32, gpu)
+    return _check_step_fp32(m, x, labels, mask, 0.05, 0.9, overrides)
+
+
+def _ratio(got, ref, rtol, atol):
+    """worst error of `got` in units of the limit `report` holds it to"""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    return ((got - ref).abs() / (atol + rtol * ref.abs() + 1e-300)).max().item()
+
+
+def _device_state(m):
+    """the model's parameters (moving statistics included) and its velocity slots, read back from the device"""
+    torch.cuda.synchronize()
+    params = {k: v.detach().cpu().clone() for k, v in m.params.items()}
+    vel = {k: m.flat_velocity[m._offsets[k]:m._offsets[k] + v.numel()].view(v.shape).detach().cpu().clone()
+           for k, v in m.params.items() if m.specs[k].trainable}
+    return params, vel
+
+
+def _check_step_fp32(m, x, labels, mask, lr, momentum, overrides=None, storage=None, tag="step"):
+    """One device step (forward_backward + apply_sgd) of the LIVE fp32 model `m` against the oracle started from the state the
+    device holds at that moment: parameters, moving statistics and Nesterov velocity are read back first, so the limits are the
+    single-step limits whichever step of a run this is.  overrides: the config overrides `m` was built with (the printed line
+    names them); storage: the oracle Storage to run under (a DilatedStorage for NETWORK.RES5_DILATION).  Prints the worst error
+    / limit ratio per compared quantity and the ReLU sign mismatches; returns the plan."""
+    from oracle import x3d_oracle as O
+    arch = m.arch
+    params, vel0 = _device_state(m)
+    gpu = m.device
+    worst = {}
+
+    def note(kind, got, ref, rtol, atol):
+        worst[kind] = max(worst.get(kind, 0.0), _ratio(got, ref, rtol, atol))
+
+    def scaled(kind, name, got, ref, rel):
+        note(kind, got, ref, 0, rel * (ref.detach().abs().max().item() + 1e-30))
+        return _scaled(name, got, ref, rel)
+
     m.set_dropout_mask(mask)
     pl = m.forward_backward(x.to(gpu), labels.to(gpu))
     torch.cuda.synchronize()
@@ -163,16 +198,18 @@ def _train_step_fp32(gpu, name, n, t, s, overrides=None):
     st = O.BNState()
     free_masks = O.RecordMasks()
     probs_free = O.forward({k: v.clone() for k, v in params.items()}, x, arch, training=True, dropout_mask=mask,
-                           state=st, taps=taps, relu_masks=free_masks)
-    _scaled("conv1/out", pl.y0, taps["conv1/out"], 2e-5)
+                           state=st, taps=taps, relu_masks=free_masks, storage=storage)
+    scaled("act", "conv1/out", pl.y0, taps["conv1/out"], 2e-5)
     for B in pl.blocks:
         pre = O.block_prefix(B.spec)
-        _scaled(pre + "/a_raw", B.a_raw, taps[pre + "/a_raw"], 2e-4)
-        _scaled(pre + "/b_raw", B.b_raw, taps[pre + "/b_raw"], 2e-4)
-        _scaled(pre + "/out", B.y, taps[pre + "/out"], 2e-4)
-    _scaled("logits", pl.logits, taps["logits"], 1e-4)
+        scaled("act", pre + "/a_raw", B.a_raw, taps[pre + "/a_raw"], 2e-4)
+        scaled("act", pre + "/b_raw", B.b_raw, taps[pre + "/b_raw"], 2e-4)
+        scaled("act", pre + "/out", B.y, taps[pre + "/out"], 2e-4)
+    scaled("logits", "logits", pl.logits, taps["logits"], 1e-4)
+    note("probs", pl.probs, probs_free, 0, 1e-4)
     report("probs", pl.probs, probs_free, 0, 1e-4)
     for k, v in st.new_moving.items():
+        note("moving", m.params[k], v, 1e-4, 1e-5)
         report(k, m.params[k], v, 1e-4, 1e-5)
 
     # gradients and update with the device's ReLU sign patterns -- which may differ from the free-running oracle's only
@@ -183,23 +220,35 @@ def _train_step_fp32(gpu, name, n, t, s, overrides=None):
     assert set(free_masks) == set(dev_masks)
     assert frac <= 1e-5, f"{bad} of {tot} ReLU signs differ between the device and the free-running oracle"
     ref_p = {k: v.clone() for k, v in params.items()}
-    r = O.train_step(ref_p, x, labels, arch, lr=0.05, momentum=0.9, dropout_mask=mask, apply_update=True,
-                     relu_masks=dev_masks)
+    r = O.train_step(ref_p, x, labels, arch, velocity={k: v.clone() for k, v in vel0.items()}, lr=lr, momentum=momentum,
+                     dropout_mask=mask, apply_update=True, relu_masks=dev_masks, storage=storage)
     loss = pl.loss_rows.mean() + m.regularization_loss().float()
+    note("loss", loss.view(1), r["loss"].view(1), 1e-5, 1e-5)
     report("loss", loss.view(1), r["loss"].view(1), 1e-5, 1e-5)
     for k, g_ref in r["grads"].items():
         g = m.grads[k].cpu().double()
         if m.specs[k].l2:
             g = g + 2 * arch.weight_decay * params[k].double()
         e = rel_l2(g, g_ref)
+        worst["grad rel-L2"] = max(worst.get("grad rel-L2", 0.0), e / 1e-3)
         assert e < 1e-3, f"grad {k}: relative L2 error {e:.3e}"
-        _scaled("grad " + k, g, g_ref, 2e-3)
-    m.apply_sgd(0.05, 0.9)
-    torch.cuda.synchronize()
+        scaled("grad max", "grad " + k, g, g_ref, 2e-3)
+    m.apply_sgd(lr, momentum)
+    _, vel1 = _device_state(m)
     for k, g_ref in r["grads"].items():
-        # dw = -lr * (1 + momentum) * g from a zero velocity: the gradient tolerance above (2e-3 of max |g|) carries over
-        tol = 1e-4 * ref_p[k].abs().max().item() + 0.05 * 1.9 * 2e-3 * g_ref.abs().max().item()
+        # w' = w + m^2 v0 - lr (1 + m) g: the velocity term is common to both sides, so the gradient tolerance above (2e-3 of
+        # max |g|) carries over as it does from a zero velocity
+        gmax = g_ref.abs().max().item()
+        tol = 1e-4 * ref_p[k].abs().max().item() + lr * (1 + momentum) * 2e-3 * gmax
+        note("updated", m.params[k], ref_p[k], 0, tol)
         report("updated " + k, m.params[k], ref_p[k], 0, tol)
+        # v' = m v0 - lr g: the gradient limit plus two fp32 roundings
+        v_ref = r["velocity"][k]
+        vtol = lr * 2e-3 * gmax + 2.0 ** -22 * v_ref.abs().max().item()
+        note("velocity", vel1[k], v_ref, 0, vtol)
+        report("velocity " + k, vel1[k], v_ref, 0, vtol)
+    print(f"CHECKED fp32 {tag}{'' if not overrides else ' ' + str(overrides)} lr {lr} n {x.shape[0]}: ReLU sign mismatches {bad} of {tot}; "
+          "worst error / limit " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
     return pl
 
 
@@ -261,7 +310,6 @@ def test_train_step_half_other_temporal_filter(gpu, kt, dtype):
 
 
 def _train_step_half(gpu, name, n, t, s, dtype, overrides=None, stem=False):
-    from oracle import x3d_oracle as O
     cfg, arch, params = _setup(name, overrides)
     torch.manual_seed(int(os.environ.get("X3D_TEST_SEED", "2")))      # (the variable: spread of the per-tensor errors over inputs)
     x = torch.randn(n, t, s, s, 3).to(dtype).float()
@@ -269,6 +317,19 @@ def _train_step_half(gpu, name, n, t, s, dtype, overrides=None, stem=False):
     mask = (torch.rand(n, arch.fc1_out) >= arch.dropout_rate).float()
     # (X3D_TEST_RC=0: the same test over the stored-output backward -- the seed sweeps under profiles/ run both)
     m = _model(cfg, params, dtype, gpu, options={"pw_bwd_rc": False} if os.environ.get("X3D_TEST_RC") == "0" else None)
+    return _check_step_half(m, x, labels, mask, stem=stem, tag=name)
+
+
+def _check_step_half(m, x, labels, mask, stem=False, tag="step"):
+    """The teacher-forced block-by-block comparison of one forward_backward of the LIVE 16-bit model `m` (x representable in its
+    storage type): the oracle replays every block from the parameters the device holds at that moment, so the step need not be
+    the first one of the model or of its plan.  The parameters are not updated.  Returns the plan."""
+    from oracle import x3d_oracle as O
+    arch, dtype, gpu = m.arch, m.dtype, m.device
+    n, t, s = x.shape[0], x.shape[1], x.shape[2]
+    name = tag
+    torch.cuda.synchronize()
+    params = {k: v.detach().cpu().clone() for k, v in m.params.items()}
     m.set_dropout_mask(mask)
     # fp16 gradients get the reference's loss scaling (LossScaleOptimizer, train.py:99-100): a power of two, so the oracle
     # replay -- fed the device's own (scaled) upstream gradient per block -- rounds exactly as the device does
