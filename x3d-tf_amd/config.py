@@ -139,7 +139,7 @@ def get_default_config():
     NETWORK.DROP_PATH_RATE (stochastic depth), NETWORK.RES5_DILATION (dilated stride-1 res5 for detection), OPTIM.* (LARS / AdamW / LAMB: TRAIN.OPTIMIZER = lars | adamw | lamb),
     NETWORK.BN.USE_PRECISE_STATS / NUM_BATCHES_PRECISE (precise BatchNorm statistics before validation and save),
     DISTILL.* (knowledge distillation against a teacher's logits), LOSS.* (class / positive weights and focal terms),
-    DETECTION.* (the ROI head for action detection)."""
+    DETECTION.* (the ROI head for action detection), AVA.* (the frame-list dataset of ava.AvaReader)."""
     c = CfgNode()
     c.NETWORK = CfgNode(dict(
         C1_TEMP_FILTER=5, C1_CHANNELS=12, SCALE_RES2=False, WIDTH_FACTOR=1.0, DEPTH_FACTOR=1.0,
@@ -214,6 +214,17 @@ def get_default_config():
     # SPATIAL_SCALE_FACTOR: clip pixels per conv5 pixel (the network's stride, 32); ROI_SAMPLING_RATIO: samples per bin and axis,
     # 0 = ceil(bin size)
     c.DETECTION = CfgNode(dict(ENABLE=False, MAX_BOXES=8, ROI_XFORM_RESOLUTION=7, SPATIAL_SCALE_FACTOR=32, ROI_SAMPLING_RATIO=0))
+    # the AVA frame-list dataset (ava_settings, ava.AvaReader; names as PySlowFast's AVA section; inert unless that reader is
+    # constructed).  FRAME_DIR: root of the extracted frames; FRAME_LIST_DIR: where TRAIN_LISTS / TEST_LISTS (frame lists) live;
+    # ANNOTATION_DIR: where the box lists, GROUNDTRUTH_FILE and EXCLUSION_FILE live.  Training boxes are TRAIN_GT_BOX_LISTS plus
+    # the rows of TRAIN_PREDICT_BOX_LISTS scored at least DETECTION_SCORE_THRESH; evaluation proposals the thresholded
+    # TEST_PREDICT_BOX_LISTS.  Second `sec` of a video is frame (sec - START_SEC) * FPS of its list; only seconds inside
+    # VALID_SECS = [first, last] are keyframes
+    c.AVA = CfgNode(dict(FRAME_DIR="", FRAME_LIST_DIR="", ANNOTATION_DIR="", TRAIN_LISTS=["train.csv"], TEST_LISTS=["val.csv"],
+                         TRAIN_GT_BOX_LISTS=["ava_train_v2.2.csv"], TRAIN_PREDICT_BOX_LISTS=[],
+                         TEST_PREDICT_BOX_LISTS=["ava_val_predicted_boxes.csv"], DETECTION_SCORE_THRESH=0.9,
+                         GROUNDTRUTH_FILE="ava_val_v2.2.csv", EXCLUSION_FILE="ava_val_excluded_timestamps_v2.2.csv",
+                         FPS=30, START_SEC=900, VALID_SECS=[902, 1798]))
     # ENSEMBLE_METHOD: how the views x crops of a video are combined at inference, "mean" (the reference's) or "max"
     c.TEST = CfgNode(dict(NUM_SPATIAL_CROPS=3, NUM_TEMPORAL_VIEWS=1, BATCH_SIZE=1, ENSEMBLE_METHOD="mean"))
     c.WANDB = CfgNode(dict(
@@ -249,6 +260,7 @@ def get_config(name, overrides=None, freeze=True):
     distill_settings(cfg, have_teacher=True)   # (whether a teacher exists is the trainer's to check)
     loss_settings(cfg)
     detection_settings(cfg)
+    ava_settings(cfg)
     if freeze:
         cfg.freeze()
     return cfg
@@ -685,4 +697,77 @@ def detection_settings(cfg) -> DetectionSettings:
         if views > 1:
             raise ValueError(f"DETECTION.ENABLE with TEST.NUM_SPATIAL_CROPS * TEST.NUM_TEMPORAL_VIEWS = {views}: box rows are "
                              "not views of one video, set both to 1")
+    return s
+
+
+AvaSettings = collections.namedtuple("AvaSettings", "frame_dir frame_list_dir annotation_dir train_lists test_lists "
+                                     "train_gt_box_lists train_predict_box_lists test_predict_box_lists detection_score_thresh "
+                                     "groundtruth_file exclusion_file fps start_sec valid_secs")
+_AVA_DEFAULTS = AvaSettings("", "", "", ("train.csv",), ("val.csv",), ("ava_train_v2.2.csv",), (), ("ava_val_predicted_boxes.csv",),
+                            0.9, "ava_val_v2.2.csv", "ava_val_excluded_timestamps_v2.2.csv", 30, 900, (902, 1798))
+
+
+def ava_settings(cfg) -> AvaSettings:
+    """cfg.AVA.* as one tuple (a config tree without the section: the defaults; the lists come back as tuples).  ValueError for a
+    list key that is not a list of strings, a DETECTION_SCORE_THRESH outside [0, 1] (NaN fails), an FPS that is not an integer
+    >= 1, a START_SEC that is not an integer >= 0 and VALID_SECS that is not a pair of integers first <= last with first >=
+    START_SEC.  What only the reader needs of the other sections is `ava_reader_check`'s."""
+    av = getattr(cfg, "AVA", None)
+    d = _AVA_DEFAULTS
+    if av is None:
+        return d
+
+    def text(key, dflt):
+        v = getattr(av, key, dflt)
+        if not isinstance(v, str):
+            raise ValueError(f"AVA.{key} must be a string, not {v!r}")
+        return v
+
+    def names(key, dflt):
+        v = getattr(av, key, list(dflt))
+        if not isinstance(v, (list, tuple)) or not all(isinstance(f, str) for f in v):
+            raise ValueError(f"AVA.{key} must be a list of file names (str), not {v!r}")
+        return tuple(v)
+
+    def whole(key, dflt, lo):
+        v = getattr(av, key, dflt)
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+            raise ValueError(f"AVA.{key} must be an integer >= {lo}, not {v!r}")
+        return v
+
+    thresh = float(getattr(av, "DETECTION_SCORE_THRESH", d.detection_score_thresh))
+    if not 0.0 <= thresh <= 1.0:
+        raise ValueError(f"AVA.DETECTION_SCORE_THRESH must lie in [0, 1], not {thresh}")
+    start = whole("START_SEC", d.start_sec, 0)
+    secs = getattr(av, "VALID_SECS", list(d.valid_secs))
+    if not isinstance(secs, (list, tuple)) or len(secs) != 2 or any(isinstance(s, bool) or not isinstance(s, int) for s in secs) \
+            or not start <= secs[0] <= secs[1]:
+        raise ValueError(f"AVA.VALID_SECS must be [first, last] with AVA.START_SEC <= first <= last, not {secs!r}")
+    return AvaSettings(text("FRAME_DIR", d.frame_dir), text("FRAME_LIST_DIR", d.frame_list_dir),
+                       text("ANNOTATION_DIR", d.annotation_dir), names("TRAIN_LISTS", d.train_lists),
+                       names("TEST_LISTS", d.test_lists), names("TRAIN_GT_BOX_LISTS", d.train_gt_box_lists),
+                       names("TRAIN_PREDICT_BOX_LISTS", d.train_predict_box_lists),
+                       names("TEST_PREDICT_BOX_LISTS", d.test_predict_box_lists), thresh,
+                       text("GROUNDTRUTH_FILE", d.groundtruth_file), text("EXCLUSION_FILE", d.exclusion_file),
+                       whole("FPS", d.fps, 1), start, (int(secs[0]), int(secs[1])))
+
+
+def ava_reader_check(cfg) -> AvaSettings:
+    """What ava.AvaReader needs of the other sections, checked at its construction; returns ava_settings(cfg).  ValueError naming
+    the key for DETECTION.ENABLE off (the reader yields boxes), DATA.MULTI_LABEL off (an AVA box carries several actions: the
+    sigmoid head is the one that fits), AUG.AA_TYPE set (RandAugment draws Rotate / Shear / Translate, and a rotated box is not a
+    box) and TEST.NUM_SPATIAL_CROPS * TEST.NUM_TEMPORAL_VIEWS > 1 (one clip per keyframe; detection_settings refuses it too)."""
+    s = ava_settings(cfg)
+    views = int(getattr(cfg.TEST, "NUM_SPATIAL_CROPS", 1)) * int(getattr(cfg.TEST, "NUM_TEMPORAL_VIEWS", 1))
+    if views > 1:
+        raise ValueError(f"the AVA reader builds one clip per keyframe: TEST.NUM_SPATIAL_CROPS * TEST.NUM_TEMPORAL_VIEWS = {views}, "
+                         "set both to 1")
+    if not detection_settings(cfg).enable:
+        raise ValueError("the AVA reader yields boxes: it needs DETECTION.ENABLE")
+    if not multi_label(cfg):
+        raise ValueError("the AVA reader yields multi-hot targets per box: it needs DATA.MULTI_LABEL")
+    aa = getattr(getattr(cfg, "AUG", None), "AA_TYPE", "")
+    if aa != "":
+        raise ValueError(f"AUG.AA_TYPE = {aa!r} with the AVA reader: RandAugment rotates, shears and translates the frames, and "
+                         "boxes are not mapped through it")
     return s

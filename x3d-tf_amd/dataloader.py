@@ -579,6 +579,12 @@ class InputReader:
         """dataloader.py:126-197.  Iterate to get batches; a background thread keeps `prefetch` of them ready.
         `batch_size` is the GLOBAL batch; with world > 1 this rank yields its batch_size // world share (class docstring)."""
         batch_size = self.local_batch(batch_size)
+        yield from self._prefetched(lambda: self._batches(file_pattern, batch_size), 2)
+
+    def _prefetched(self, batches: Callable[[], Iterator[tuple]], n_out: int) -> Iterator[tuple]:
+        """The batches of `batches()` -- tuples (n_out items to yield..., params, randaug) -- made by a background thread that
+        keeps `prefetch` of them ready; the first n_out items of each are yielded, `last_params` / `last_randaug` set from the
+        other two.  Device mode: made on the reader's own stream and handed over with an event."""
         q: "queue.Queue" = queue.Queue(self._prefetch)
         stop = threading.Event()
         END = object()
@@ -592,7 +598,7 @@ class InputReader:
                 if device_mode:       # the batches are made on the reader's own stream, handed over by an event
                     stream = torch.cuda.Stream(self._device)
                     torch.cuda.set_stream(stream)
-                for b in self._batches(file_pattern, batch_size):
+                for b in batches():
                     if device_mode:
                         ev = torch.cuda.Event()
                         ev.record(stream)
@@ -620,13 +626,14 @@ class InputReader:
                     return
                 if isinstance(item, BaseException):
                     raise item
-                self.last_params = item[2]      # the draws of THIS batch (the producer thread runs `prefetch` batches ahead)
-                self.last_randaug = item[3]
+                self.last_params = item[n_out]  # the draws of THIS batch (the producer thread runs `prefetch` batches ahead)
+                self.last_randaug = item[n_out + 1]
                 if device_mode:
                     consumer = torch.cuda.current_stream(self._device)
-                    consumer.wait_event(item[4])
-                    item[0].record_stream(consumer)     # made on the reader's stream: not reused before the consumer is done
-                    item[1].record_stream(consumer)
-                yield item[0], item[1]
+                    consumer.wait_event(item[n_out + 2])
+                    for t in item[:n_out]:              # made on the reader's stream: not reused before the consumer is done
+                        if torch.is_tensor(t) and t.is_cuda:
+                            t.record_stream(consumer)
+                yield item[:n_out]
         finally:
             stop.set()
