@@ -1256,14 +1256,24 @@ int x3d_randaug_clips(const long long* videos, const int* clips, const int* ops,
  *     `data_off` / `data_len` (where image i sits in the packed device copy of the bytes) and `out` (NULL: skip).
  * x3d_jpeg_decode: three launches on `stream` (entropy decode, dequantise + IDCT, upsample + colour convert);
  *     writes status[i] (device) per image: X3D_JPEG_OK, the parse status, X3D_JPEG_SKIPPED, or X3D_JPEG_CORRUPT
- *     for an entropy segment that ends early or holds an invalid code or restart marker (that image's slot is
- *     then not written).  Reads only bytes [data_off + ecs_off, data_off + ecs_end) and the tables of image i,
- *     writes only its scratch range and out[0 .. height * width * 3).
+ *     (that image's slot is then not written).  X3D_JPEG_OK means that out holds what the host decoder makes of
+ *     the same bytes, whether they are a legal stream or a damaged one.  X3D_JPEG_CORRUPT is reported for
+ *       - an entropy segment that ends before the last MCU, an invalid Huffman code, a restart interval that
+ *         is not followed at once by its RSTn;
+ *       - a marker among the bytes left over after the last MCU (the host decoder acts on it);
+ *       - a block with a dequantised coefficient beyond +-4095, a value between the two IDCT passes beyond
+ *         +-16383 or a sample before the level shift outside [-512, 511].  Up to there libjpeg's C and SIMD
+ *         IDCTs give the same integers (the range-limit table is the clamp on [-512, 511] and wraps beyond;
+ *         the SIMD code works in 16 and 32 bits and saturates); past it the result depends on the libjpeg
+ *         build, so the frame is the host's to decode.  No legal stream tried (q1 to q100, 0 / 255 noise
+ *         included) is refused; one whose quantisation error alone passed the sample limit would be.
+ *     A frame that lacks only its EOI is decoded.  Reads only bytes [data_off + ecs_off, data_off + ecs_end)
+ *     and the tables of image i, writes only its scratch range and out[0 .. height * width * 3).
  * ------------------------------------------------------------------------------------------ */
 #define X3D_JPEG_OK 0
 #define X3D_JPEG_UNSUPPORTED 1   /* valid JPEG outside the device decoder's scope (progressive, arithmetic, 12-bit, CMYK, ...) */
 #define X3D_JPEG_MALFORMED 2     /* header that cannot be parsed */
-#define X3D_JPEG_CORRUPT 3       /* (device) entropy-coded data ends early or is invalid */
+#define X3D_JPEG_CORRUPT 3       /* (device) entropy-coded data ends early, is invalid or decodes to values outside the IDCT range above */
 #define X3D_JPEG_SKIPPED 4       /* (device) supported, but `out` was NULL */
 typedef struct {
   unsigned char* out;          /* device [height][width][3] uint8 (caller) */

@@ -3,7 +3,12 @@
 Every <name>.jpg is written by Pillow (libjpeg-turbo) from a seeded synthetic frame -- a smooth gradient, sharp edges
 (IDCT overshoot, clamping) and noise -- and <name>.npy is its decode by Pillow on the same host (dataloader.decode_jpeg,
 the host path the device decoder must reproduce bit for bit).  manifest.json lists each file's extents, components,
-sampling factors (of the first component), restart interval and whether the device decoder takes it."""
+sampling factors (of the first component), restart interval and whether the device decoder takes it.
+
+The small 4:2:2 / 4:2:0 frames pin the chroma upsampling edges whatever Pillow the test machine has: widths 4 | 5, 6 are
+downsampled chroma widths 2 | 3, where replication gives way to the triangle filter, and heights 3 and 2 are chroma heights
+2 and 1, where both vertical neighbours are the edge row.  The `_rst1` frames restart after every MCU (12 MCUs: the marker
+numbers wrap past RST7); `_flat` is one colour (DC coefficients only), `_noise` is 0 / 255 per sample (the largest ones)."""
 import io
 import json
 import os
@@ -53,15 +58,25 @@ def main():
     cases += [dict(h=45, w=70, kind="420", q=90, opt=True, restart=dict(restart_marker_blocks=3)),
               dict(h=40, w=33, kind="444", q=75, opt=False, restart=dict(restart_marker_rows=1))]
     cases += [dict(h=33, w=17, kind="420", q=90, opt=True, progressive=True)]
+    for kind in ["422", "420"]:
+        cases += [dict(h=h, w=w, kind=kind, q=90, opt=True) for (h, w) in [(3, 4), (3, 5), (2, 6)]]
+    cases += [dict(h=17, w=49, kind="422", q=75, opt=False, restart=dict(restart_marker_blocks=1), tag="_rst1"),
+              dict(h=17, w=25, kind="gray", q=75, opt=False, restart=dict(restart_marker_blocks=1), tag="_rst1"),
+              dict(h=16, w=17, kind="420", q=90, opt=False, content="flat", tag="_flat"),
+              dict(h=9, w=15, kind="444", q=100, opt=False, content="noise", tag="_noise")]
     manifest = []
     for i, c in enumerate(cases):
         img = frame(c["h"], c["w"], seed=100 + i)
+        if c.get("content") == "flat":
+            img[:] = [201, 37, 118]
+        elif c.get("content") == "noise":
+            img = (np.random.default_rng(100 + i).integers(0, 2, img.shape) * 255).astype(np.uint8)
         kw = dict(c.get("restart", {}))
         if c.get("progressive"):
             kw["progressive"] = True
         data = encode(img, c["kind"], c["q"], c["opt"], **kw)
-        name = (f"{c['kind']}_{c['h']}x{c['w']}_q{c['q']}{'_opt' if c['opt'] else ''}"
-                f"{'_rst' if 'restart' in c else ''}{'_prog' if c.get('progressive') else ''}")
+        suffix = c.get("tag") or ("_rst" if "restart" in c else "") + ("_prog" if c.get("progressive") else "")
+        name = f"{c['kind']}_{c['h']}x{c['w']}_q{c['q']}{'_opt' if c['opt'] else ''}{suffix}"
         with open(os.path.join(HERE, name + ".jpg"), "wb") as f:
             f.write(data)
         np.save(os.path.join(HERE, name + ".npy"), decode(data))

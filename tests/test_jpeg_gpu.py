@@ -1,6 +1,9 @@
 """The device JPEG decoder (jpeg.decode_jpeg_batch -> x3d_jpeg_decode) against Pillow: every fixture of
 tests/golden/jpeg/ bit-identical to its host decode, alone and in one mixed batch; the out-of-scope fixture through the
-host fall-back; a cut entropy segment reported for its frame only; a batch of >= 1,024 frames equal to one at a time."""
+host fall-back; a cut entropy segment reported for its frame only; a batch of >= 1,024 frames equal to one at a time;
+the small-size sweep (every chroma width and height at which the upsampling changes its rule, every MCU edge, all samplings
+and encodings, flat and saturated frames) against a live Pillow decode; the damaged corpus of tests/golden/jpeg_damaged/
+against the statuses and pixels its manifest records."""
 import io
 import json
 import os
@@ -9,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import jpeg_replay_util as U
+from tests.aux_checks import _Bands
 from x3d_tf_amd import hip
 from x3d_tf_amd.dataloader import decode_jpeg, encode_jpeg
 from x3d_tf_amd.jpeg import JpegDecodeError, decode_jpeg_batch
@@ -104,3 +109,65 @@ def test_frames_of_different_sizes_need_slots(gpu):
         decode_jpeg_batch([a, b], gpu)
     with pytest.raises(ValueError, match="does not fit"):
         decode_jpeg_batch([a], gpu, out=[torch.empty((33, 17, 3), dtype=torch.uint8, device=gpu)])
+
+
+# widths 1-6: downsampled chroma widths 1, 2 | 3 (replication | triangle filter); heights 1-5: chroma heights 1, 2, 3 (both
+# vertical neighbours clamped, one, none); 8 | 9 and 16 | 17: the MCU edges of 4:4:4 / grey and of 4:2:0; 15, 31 | 33
+SWEEP_SIZES = [1, 2, 3, 4, 5, 6, 8, 9, 15, 16, 17, 31, 33]
+_SWEEP = []
+
+
+def _sweep():
+    """[(label, jpeg bytes, Pillow's decode)], made once: every height x width x sampling with the five encodings in turn,
+    and all five on the frames of at most 5 x 6; every 7th frame is 0 / 255 noise, every 11th flat"""
+    if not _SWEEP:
+        index = 0
+        for h in SWEEP_SIZES:
+            for w in SWEEP_SIZES:
+                for kind in U.KINDS:
+                    small = h <= 5 and w <= 6
+                    for enc in (list(U.ENCODINGS) if small else [list(U.ENCODINGS)[index % 5]]):
+                        data = U.legal_stream(h, w, kind, enc, index)
+                        _SWEEP.append((f"{kind}_{h}x{w}_{enc}#{index}", data, U.golden.decode(data)))
+                        index += 1
+    return _SWEEP
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("part,off", [(0, 0), (1, 5)])
+def test_small_size_sweep_equals_the_host_decode(gpu, part, off):
+    """one mixed batch per half of the sweep, every frame into its own slot: a view (16-byte aligned in one half, not in
+    the other) between bands of a sentinel that must still stand afterwards"""
+    sweep = _sweep()
+    assert len(sweep) >= 1000
+    kinds = {(n.split("_")[0], n.split("#")[0].split("_", 2)[2]) for n, _, _ in sweep}
+    assert len(kinds) == len(U.KINDS) * len(U.ENCODINGS)                    # every sampling with every encoding
+    mine = sweep[part::2]
+    bands = _Bands(gpu, off)
+    slots = [bands(want.shape, torch.uint8) for _, _, want in mine]
+    decode_jpeg_batch([d for _, d, _ in mine], gpu, out=slots)
+    bands.check()
+    got = [s.cpu().numpy() for s in slots]
+    wrong = [n for (n, _, want), g in zip(mine, got) if not np.array_equal(g, want)]
+    assert not wrong, (len(wrong), wrong[:8])
+
+
+@pytest.mark.gpu
+def test_damaged_corpus_matches_its_manifest(gpu):
+    """tests/golden/jpeg_damaged/ in one batch: the statuses and the accepted frames are what the host replay of the
+    decoder recorded (and verified against Pillow where it accepted), the slot of every corrupt frame keeps its sentinel"""
+    manifest = json.load(open(os.path.join(U.DAMAGED, "manifest.json")))
+    datas = [open(os.path.join(U.DAMAGED, m["name"] + ".jpg"), "rb").read() for m in manifest]
+    bands = _Bands(gpu)
+    slots = [bands((m["height"], m["width"], 3), torch.uint8) for m in manifest]
+    sentinel = int(slots[0].flatten()[0])
+    with pytest.raises(JpegDecodeError) as ei:
+        decode_jpeg_batch(datas, gpu, out=slots)
+    bands.check()
+    assert ei.value.status == [m["status"] for m in manifest]
+    assert ei.value.frames == [i for i, m in enumerate(manifest) if m["status"] == hip.JPEG_CORRUPT]
+    for m, s in zip(manifest, slots):
+        if m["status"] == hip.JPEG_OK:
+            assert np.array_equal(s.cpu().numpy(), np.load(os.path.join(U.DAMAGED, m["name"] + ".npy"))), m["name"]
+        else:
+            assert bool((s == sentinel).all()), m["name"]

@@ -17,8 +17,10 @@
 //   1. entropy: one wave per image.  The wave builds the image's Huffman lookup tables in LDS from the raw DHT bytes,
 //      then lane 0 decodes the (inherently sequential) scan: byte stuffing removed while reading, DC prediction,
 //      restart intervals.  Quantised coefficients go to an int16 scratch in natural order.  A stream that runs out
-//      early, an invalid code or a wrong restart marker sets the image's status word and stops that image.
-//   2. idct: one thread per 8x8 block: dequantise + ISLOW IDCT into uint8 component planes.
+//      early, an invalid code, a wrong restart marker or a marker behind the last MCU sets the image's status word
+//      and stops that image.
+//   2. idct: one thread per 8x8 block: dequantise + ISLOW IDCT into uint8 component planes.  A block outside the
+//      range in which the host decoders agree (kCoefLimit ...) sets the status word too.
 //   3. color: one thread per output pixel: upsample + convert, straight into the caller's [H][W][3] slot.
 #include "common.h"
 
@@ -407,6 +409,10 @@ __host__ __device__ inline int entropy_decode(const unsigned char* base, const x
         }
     }
   }
+  // what the scan left over must hold no marker: the host decoder skips other bytes on its way to EOI, but acts on a
+  // marker (and fails on one it does not know).  br.p: the first byte not loaded, or the marker that stopped fill().
+  for (const unsigned char* q = br.p; q + 1 < br.end; q++)
+    if (q[0] == 0xFF && q[1] != 0x00 && q[1] != 0xFF) return X3D_JPEG_CORRUPT;
   return X3D_JPEG_OK;
 }
 
@@ -448,11 +454,27 @@ constexpr int kConstBits = 13, kPass1Bits = 2;
 
 __host__ __device__ inline long long descale(long long x, int n) { return (x + (1ll << (n - 1))) >> n; }
 
+// The range in which every build of the host decoder computes the same sample, and this file with them.  libjpeg limits
+// the IDCT result v (before the + 128) through a table that holds the clamp for v in [-512, 511] and wraps beyond it; the
+// SIMD builds of libjpeg-turbo dequantise and add in 16 bits, accumulate in 32 and saturate where they narrow.  Samples
+// within [-512, 511] are the transform of coefficients within 6.6 x 512 (the largest 2-D basis sum, (5.13 / 2)^2) and of
+// pass-1 values within 4 x 2.6 x 512 (the 1-D sum, scaled by 2^kPass1Bits): with 4095 and 16383 as the limits no legal
+// block is refused that the sample range would not refuse, no 16-bit sum of two inputs wraps, and no sum of four
+// products with the 15-bit constants leaves 32 bits.  A block outside them is damaged data: X3D_JPEG_CORRUPT.
+constexpr int kCoefLimit = 4095, kPass1Limit = 16383, kSampleLo = -512, kSampleHi = 511;
+
 // one 1-D 8-point pass over x[0], x[s], ..., x[7s]; results descaled by `sh` into y[0], y[t], ..., y[7t] (64-bit
-// arithmetic: the garbage coefficients of a corrupt stream cannot overflow)
+// arithmetic: the garbage coefficients of a corrupt stream cannot overflow).  false: an input beyond +-in_lim or a
+// descaled result outside [out_lo, out_hi] (see above).
 template <typename In, typename Out>
-__host__ __device__ inline void idct_1d(const In* x, int s, Out* y, int t, int sh, const unsigned short* q, int add) {
-  auto in = [&](int k) { return q ? (long long)x[k * s] * q[k * s] : (long long)x[k * s]; };
+__host__ __device__ inline bool idct_1d(const In* x, int s, Out* y, int t, int sh, const unsigned short* q, int add,
+                                        int in_lim, int out_lo, int out_hi) {
+  bool ok = true;
+  auto in = [&](int k) {
+    const long long v = q ? (long long)x[k * s] * q[k * s] : (long long)x[k * s];
+    ok &= v >= -in_lim && v <= in_lim;
+    return v;
+  };
   long long z2 = in(2), z3 = in(6);
   long long z1 = (z2 + z3) * FIX_0_541196100;
   long long tmp2 = z1 + z3 * (-FIX_1_847759065);
@@ -486,7 +508,9 @@ __host__ __device__ inline void idct_1d(const In* x, int s, Out* y, int t, int s
   tmp2 += z2 + z3;
   tmp3 += z1 + z4;
   auto out = [&](int k, long long v) {
-    v = descale(v, sh) + add;
+    v = descale(v, sh);
+    ok &= v >= out_lo && v <= out_hi;
+    v += add;
     if (add) v = v < 0 ? 0 : (v > 255 ? 255 : v);
     y[k * t] = (Out)v;
   };
@@ -498,10 +522,12 @@ __host__ __device__ inline void idct_1d(const In* x, int s, Out* y, int t, int s
   out(5, tmp12 - tmp1);
   out(3, tmp13 + tmp0);
   out(4, tmp13 - tmp0);
+  return ok;
 }
 
-// block b (over all components of the image, component-major) -> its 8x8 pixels in the component plane
-__host__ __device__ inline void idct_block(const x3d_jpeg_image& d, unsigned char* scratch, long long b) {
+// block b (over all components of the image, component-major) -> its 8x8 pixels in the component plane; false: the
+// block's values leave the range in which the host decoders agree (the plane is written all the same)
+__host__ __device__ inline bool idct_block(const x3d_jpeg_image& d, unsigned char* scratch, long long b) {
   int c = 0;
   long long cb = 0, pb = 0;                 // coefficient blocks / plane bytes of the components before c
   for (; c < d.ncomp; c++) {
@@ -511,7 +537,7 @@ __host__ __device__ inline void idct_block(const x3d_jpeg_image& d, unsigned cha
     cb += nb;
     pb += nb * 64;
   }
-  if (c >= d.ncomp) return;
+  if (c >= d.ncomp) return true;
   const short* blk = (const short*)(scratch + d.coef_off) + (cb + b) * 64;
   const int stride = d.bw[c] * 8;
   const int by = (int)(b / d.bw[c]), bx = (int)(b % d.bw[c]);
@@ -520,21 +546,30 @@ __host__ __device__ inline void idct_block(const x3d_jpeg_image& d, unsigned cha
   unsigned short q[64];
   for (int k = 0; k < 64; k++) { in[k] = blk[k]; q[k] = d.qt[c][k]; }
   int ws[64];
-  for (int col = 0; col < 8; col++) idct_1d(in + col, 8, ws + col, 8, kConstBits - kPass1Bits, q + col, 0);
+  bool ok = true;
+  for (int col = 0; col < 8; col++)
+    ok &= idct_1d(in + col, 8, ws + col, 8, kConstBits - kPass1Bits, q + col, 0, kCoefLimit, -kPass1Limit, kPass1Limit);
   unsigned char px[64];
   for (int row = 0; row < 8; row++)
-    idct_1d(ws + row * 8, 1, px + row * 8, 1, kConstBits + kPass1Bits + 3, (const unsigned short*)nullptr, 128);
+    ok &= idct_1d(ws + row * 8, 1, px + row * 8, 1, kConstBits + kPass1Bits + 3, (const unsigned short*)nullptr, 128,
+                  kPass1Limit, kSampleLo, kSampleHi);
   for (int row = 0; row < 8; row++) {
     unsigned long long v = 0;
     for (int k = 0; k < 8; k++) v |= (unsigned long long)px[row * 8 + k] << (8 * k);
     *(unsigned long long*)(o + (long long)row * stride) = v;
   }
+  return ok;
 }
 
+// (a thread that finds its block out of range reports the image; the threads that race with the store read OK or
+// CORRUPT there and do their block or not, and the colour launch, which comes after, sees CORRUPT.  Relaxed atomic
+// accesses: the word is read and written by different threads of one launch on purpose.)
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const x3d_jpeg_image* __restrict__ imgs, unsigned char* scratch,
-                                                       const int* __restrict__ status) {
-  if (status[blockIdx.y] != X3D_JPEG_OK) return;
-  idct_block(imgs[blockIdx.y], scratch, (long long)blockIdx.x * 256 + threadIdx.x);
+                                                       int* status) {
+  int* st = status + blockIdx.y;
+  if (__hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != X3D_JPEG_OK) return;
+  if (!idct_block(imgs[blockIdx.y], scratch, (long long)blockIdx.x * 256 + threadIdx.x))
+    __hip_atomic_store(st, X3D_JPEG_CORRUPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,8 +7,14 @@ headers on the host, then three launches decode every supported frame straight i
 
 Frames the device decoder does not take (progressive or arithmetic coding, 12-bit samples, CMYK / RGB colour, other
 sampling factors, malformed headers) are decoded by `decode_jpeg` on the host, so the result never differs from the
-host decode.  A frame whose entropy-coded data is cut short or invalid raises `JpegDecodeError` naming it (or, with
-`on_corrupt="host"`, goes to the host decoder as well, which then reports it as the host path would)."""
+host decode.  That holds for damaged frames too: the device reports X3D_JPEG_CORRUPT, and writes nothing, for
+entropy-coded data that is cut short or holds an invalid code or a misplaced restart marker, for a marker left over
+behind the last MCU, and for a block whose values leave the IDCT range (dequantised coefficients beyond +-4095, values
+between the IDCT passes beyond +-16383, samples before the + 128 outside [-512, 511]), where libjpeg's C and SIMD builds
+stop agreeing with each other.  Such a frame raises `JpegDecodeError` naming it (or, with `on_corrupt="host"`, goes to
+the host decoder as well, which decodes it its way or reports it as the host path would).  Whatever the device accepts
+is what the host decodes from the same bytes.  One difference remains: a frame complete but for its EOI marker decodes
+here, while Pillow calls the file truncated."""
 import ctypes as C
 from typing import List, Sequence, Tuple, Union
 
